@@ -21,10 +21,14 @@ owns --utts utterances); value = frames of all ranks / max-over-ranks time.
 utterances (hmmlearn-compatible kernels, 10 word models) + ONE all-reduce of the sufficient statistics
 (RCCL) + the M-step on every rank; the all-reduce time is reported separately.
 
-The JSON line also carries `roofline` (dominant kernel: algorithmic bytes / HIP-event time vs the 8 TB/s HBM
+A plain run sets up, warms up, times --steps steps and prints one JSON line (metric, value, unit, ms_per_step, ...).
+With `--full` the line also carries `roofline` (dominant kernel: algorithmic bytes / HIP-event time vs the 8 TB/s HBM
 peak, plus its flop rate vs the float32 vector peak, and what actually limits it), `cpu_baseline` (the oracle
 on one host core), `cpu_baseline_all_cores` (the same sample over every core this process may use) and `extra`
 (the other BASELINE configs on one GPU, each with a parity flag), rank 0 / N=1 only.
+
+`--dump-outputs DIR` (default mode) writes what the last timed step returned to its caller as DIR/<name>.npy
+(see dump_outputs); the inputs are seeded, so two builds run with the same arguments can be compared file by file.
 """
 import os
 
@@ -509,6 +513,48 @@ def extra_stream_1m(torch, dev, pcm, n_utts, n_chunks=10):
             "kernel_ms_per_chunk": float(np.mean(rep.chunk_kernel_ms))}
 
 
+# ------------------------------------------------------------------------------------------- outputs
+DUMP_UTTS = 100000       # utterances whose results --dump-outputs writes (a fixed sample of them beyond that)
+DUMP_FEAT_UTTS = 1024    # utterances whose MFCC features it writes
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, pipe):
+    """--dump-outputs: what RecognizerPipeline.run hands its caller after the last timed step — best word, its Viterbi
+    score and the state path per utterance (`--decode full`: every word's score as well) — plus the MFCC features the
+    step computed for a sample of utterances.  Integers are written as float32 (exact: states and words < 2^24), scores
+    as float64.  Batches above DUMP_UTTS utterances are sampled with a fixed seed, the same utterances every run, so
+    the files stay under 64 MB; sampled utterances are listed in utterances.npy / mfcc_utterances.npy."""
+    n = pipe.n_utts
+    fo = np.concatenate([[0], np.cumsum(pipe.frames)])
+
+    def sample(k, seed):
+        return None if n <= k else np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+
+    def rows(utts):
+        return np.concatenate([np.arange(fo[u], fo[u + 1]) for u in utts])
+    utts, feat_utts = sample(DUMP_UTTS, 0), sample(DUMP_FEAT_UTTS, 1)
+    pick = (lambda a: a) if utts is None else (lambda a: a[utts])
+    out = {"best_word": pick(pipe.best_word.cpu().numpy()).astype(np.float32),
+           "best_score": pick(pipe.best_score.cpu().numpy()).astype(np.float64)}
+    path = pipe.path.cpu().numpy()
+    out["path"] = (path if utts is None else path[rows(utts)]).astype(np.float32)
+    if pipe.scores is not None:
+        out["scores"] = pick(pipe.scores.cpu().numpy()).astype(np.float64)
+    feats = pipe.feats if feat_utts is None else pipe.feats[pipe.torch.from_numpy(rows(feat_utts)).to(pipe.feats.device)]
+    out["mfcc"] = feats.cpu().numpy().astype(np.float32)
+    if utts is not None:
+        out["utterances"] = utts.astype(np.float64)
+    if feat_utts is not None:
+        out["mfcc_utterances"] = feat_utts.astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 # ------------------------------------------------------------------------------------------- modes
 def run_em_mode(args, torch, dist, dev, rank, world):
     """configs[3]: utterance-sharded Baum-Welch.  Per iteration: E-step kernels over this rank's shard,
@@ -711,7 +757,15 @@ def main():
     ap.add_argument("--mode", choices=["pipeline", "em", "stream"], default="pipeline")
     ap.add_argument("--total-utts", type=int, default=1000000, help="--mode stream: utterances of the whole corpus")
     ap.add_argument("--decode", choices=["pruned", "full"], default="pruned")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: roofline, CPU baselines, extras")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's results as DIR/<name>.npy (default mode only)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.mode != "pipeline":
+        ap.error("--dump-outputs is implemented for the default mode (--mode pipeline) only")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves, as a CHILD process (this one has
@@ -786,15 +840,19 @@ def main():
 
     for _ in range(args.warmup):
         pipe.run(pcm)
-    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)]
+    # per-launch-sequence HIP events only feed --full's roofline
+    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)] if args.full else None
     barrier()
     t0 = time.perf_counter()
     for k in range(args.steps):
-        ev[k][0].record()
+        if ev:
+            ev[k][0].record()
         pipe.launch_mfcc(pcm, stream)
-        ev[k][1].record()
+        if ev:
+            ev[k][1].record()
         pipe.launch_decode(stream)
-        ev[k][2].record()
+        if ev:
+            ev[k][2].record()
     barrier()
     elapsed = time.perf_counter() - t0
 
@@ -805,8 +863,22 @@ def main():
     pipe_frames = pipe.total_frames
     frames_per_step = pipe.total_frames * world
     value = frames_per_step * args.steps / elapsed
+    line = {"metric": "frames/sec MFCC+Viterbi (16kHz, 13-MFCC, 8-state HMM)", "value": value,
+            "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32 (MFCC) + f64 (trellis)", "data": "synthetic",
+            "config": {"workload": "configs[1]+[2]: 16 kHz 1 s utterances -> 13 MFCC (25 ms/10 ms, "
+                                   "n_fft 512, 40 mels) -> Viterbi vs 11 word models x 8 emitting "
+                                   "states (decoder.py API), features materialised in HBM",
+                       "utterances_per_gpu": n_utts, "frames_per_utterance": T_FRAMES,
+                       "word_models": W, "states": N_STATES + 2, "parallelism": f"utterance-shard x{world}",
+                       "decoder": args.decode}}
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, pipe)
 
-    if rank == 0:
+    if rank == 0 and not args.full:
+        print(json.dumps(line), flush=True)
+    elif rank == 0:
         kt = {name: float(np.mean([ev[k][i].elapsed_time(ev[k][i + 1]) for k in range(args.steps)]))
               for i, name in enumerate(("mfcc", "decode"))}  # ms per launch (sequence)
         dom = max(kt, key=kt.get)
@@ -914,18 +986,8 @@ def main():
             ms_all = kt["mfcc"] + extra["decode_sensitivity"]["all_vocabulary_ms"]
             both = {"ms_per_step": ms_all, "value": pipe_frames / (ms_all * 1e-3), "unit": "frames/s",
                     "what": "MFCC launch sequence as timed + all-vocabulary Viterbi and back-trace (HIP events, 1 GPU)"}
-        line = {"metric": "frames/sec MFCC+Viterbi (16kHz, 13-MFCC, 8-state HMM)", "value": value,
-                "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-                "vs_baseline": None, "dtype": "f32 (MFCC) + f64 (trellis)", "data": "synthetic",
-                "config": {"workload": "configs[1]+[2]: 16 kHz 1 s utterances -> 13 MFCC (25 ms/10 ms, "
-                                       "n_fft 512, 40 mels) -> Viterbi vs 11 word models x 8 emitting "
-                                       "states (decoder.py API), features materialised in HBM",
-                           "utterances_per_gpu": n_utts, "frames_per_utterance": T_FRAMES,
-                           "word_models": W, "states": N_STATES + 2, "parallelism": f"utterance-shard x{world}",
-                           "decoder": args.decode},
-                "roofline": roofline, "cpu_baseline": cpu, "cpu_baseline_all_cores": cpu_all,
-                "all_vocabulary_decode_equivalent": both, "extra": extra}
+        line.update({"roofline": roofline, "cpu_baseline": cpu, "cpu_baseline_all_cores": cpu_all,
+                     "all_vocabulary_decode_equivalent": both, "extra": extra})
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.destroy_process_group()

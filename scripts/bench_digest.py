@@ -1,4 +1,4 @@
-"""Print the key numbers of a bench.py JSON line (dev tool): python scripts/bench_digest.py <log>"""
+"""Print the key numbers of a `bench.py --full` JSON line (dev tool): python scripts/bench_digest.py <log>"""
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 r = d["roofline"]

@@ -370,6 +370,21 @@ def test_bench_without_a_launcher_starts_n_ranks_as_a_child(monkeypatch):
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+@pytest.mark.parametrize("argv", [["--steps", "0"], ["--warmup", "-1"], ["--mode", "em", "--dump-outputs", "x"],
+                                  ["--mode", "stream", "--dump-outputs", "x"]])
+def test_bench_refuses_arguments_it_cannot_honour_before_touching_the_gpu(monkeypatch, argv):
+    """--steps sets the number of timed steps (at least one: ms_per_step divides by it) and --dump-outputs writes the
+    default mode's results only: anything else is an argument error, raised before torch is imported."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("sapr_bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", *argv])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2
+
+
 def test_vectorised_m_step_is_the_per_model_m_step_bit_for_bit():
     """hmmlearn_hmm.m_step_batch (one numpy pass over the whole vocabulary's statistics, what fit_models runs) against W
     calls of m_step on split_stats' dictionaries: padded state counts and feature widths, a state that was never
