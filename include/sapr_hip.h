@@ -315,6 +315,14 @@ int sapr_custom_global_cov(const float *feats, int64_t total_frames, int32_t D, 
  *          the call cannot return an error for a mismatch.  The 512-point wave-private core checks it on the
  *          device: offsets that describe MORE frames than total_frames make it write nothing but NaN into all
  *          of `out` (tests/test_capi_errors_gpu.py) instead of running past the buffers.
+ *   slices The 512-point wave-private core cuts a large batch into slices of whole utterances and runs the finish
+ *          pass of slice k on a low-priority stream the plan owns, under the spectral kernel of slice k + 1
+ *          (same bits as the single launch sequence; SAPR_MFCC_SLICES at plan creation: 1 = never, n = always n).
+ *          The caller's stream waits for that work before sapr_mfcc_batch returns, so whatever is enqueued on
+ *          `stream` afterwards sees complete features; nothing is created per call.  Forced grids
+ *          (grid_blocks > 0), a capturing stream and small batches keep the single launch sequence.  The plan's
+ *          stream and events are guarded by a mutex: concurrent calls on one plan from several host threads are
+ *          serialised at the launch, not undefined.
  * ---------------------------------------------------------------------------------- */
 int sapr_mfcc_plan_create(double sr, int32_t n_fft, int32_t win_length, int32_t hop,
                           int32_t n_mels, int32_t n_mfcc, double fmin, double fmax /* <=0: sr/2 */,

@@ -32,6 +32,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <mutex>
 #include <type_traits>
 #include <vector>
 
@@ -179,6 +180,16 @@ struct MfccDev {
   const int *wave_blk;     // [16][4] per block: first bin, head mel or -1, next block continues, next but one
 };
 
+constexpr int kMaxSlices = 32;  // utterance slices of one batch (SAPR_MFCC_SLICES is clamped to it)
+#ifndef SAPR_MFCC_DEFAULT_SLICES
+#define SAPR_MFCC_DEFAULT_SLICES 2
+#endif
+#ifndef SAPR_MFCC_SLICE_MIN_SETS
+#define SAPR_MFCC_SLICE_MIN_SETS 64
+#endif
+constexpr int kDefaultSlices = SAPR_MFCC_DEFAULT_SLICES;  // power of two (halved until a batch is large enough)
+constexpr int kSliceMinSets = SAPR_MFCC_SLICE_MIN_SETS;   // 4-frame sets per spectral wavefront and slice
+
 struct MfccPlan {
   MfccDev dev;
   int R;
@@ -187,6 +198,14 @@ struct MfccPlan {
   int wave_rlo = 0, wave_rhi = 16;  // wave-private core: window support rows as template arguments
   size_t wave_lds = 0;
   int wave_blocks_per_cu = 0;       // resident workgroups per CU (occupancy query at plan creation)
+  // slice pipeline of the wave-private core (sapr_mfcc_batch): finish(slice k) on `side` under spectral(slice k + 1)
+  int slices_env = 0;               // SAPR_MFCC_SLICES at plan creation: 0 = unset (default), 1 = single launch, n = forced
+  int finish_beside = 1;            // finish workgroups per CU that fit next to the resident spectral grid
+  mutable std::mutex side_mu;       // the stream and the events below serve one sapr_mfcc_batch call at a time
+  mutable bool side_tried = false;  // created on the first call that cuts a batch
+  mutable hipStream_t side = nullptr;
+  mutable hipEvent_t ev_spec[kMaxSlices - 1] = {};
+  mutable hipEvent_t ev_side = nullptr;
 };
 
 __host__ __device__ inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
@@ -1048,22 +1067,25 @@ hipError_t wave_prepare(size_t lds, int *blocks_per_cu) {
 }
 template <bool PRE, int RLO, int RHI, int S4>
 hipError_t wave_launch_one(const MfccPlan &pl, const float *pcm, const int64_t *so, const int64_t *fo, int64_t n_utts,
-                           int grid, int64_t span, hipStream_t st, float *lm, unsigned *gmax, int64_t total_cap) {
+                           int grid, int64_t span, hipStream_t st, float *lm, unsigned *gmax, int64_t total_cap,
+                           const int64_t *fo_end) {
   SAPR_LAUNCH((mfcc_wave_kernel<PRE, RLO, RHI, S4>), dim3(grid), dim3(kThreads), pl.wave_lds, st, pcm, so, fo, n_utts,
-              pl.dev, lm, gmax, span, total_cap);
+              pl.dev, lm, gmax, span, total_cap, fo_end);
   return hipGetLastError();
 }
 // dispatch over the instantiated (pre-emphasis, window rows, step quads) combinations; `prepare` != nullptr runs the
-// occupancy query instead of a launch
+// occupancy query instead of a launch.  so / fo / gmax start at the launch's first utterance, fo_end points at the
+// batch's last offset; span == 0: the kernel derives the run length of its slice (mfcc_wave.h)
 template <bool PRE, int RLO, int RHI>
 hipError_t wave_dispatch_s4(const MfccPlan &pl, int *prepare, const float *pcm, const int64_t *so, const int64_t *fo,
                             int64_t n_utts, int grid, int64_t span, hipStream_t st, float *lm, unsigned *gmax,
-                            int64_t total_cap) {
+                            int64_t total_cap, const int64_t *fo_end) {
   switch (pl.dev.wave_s4) {
 #define SAPR_WAVE_CASE(S4)                                                                                        \
   case S4:                                                                                                        \
     return prepare ? wave_prepare<PRE, RLO, RHI, S4>(pl.wave_lds, prepare)                                        \
-                   : wave_launch_one<PRE, RLO, RHI, S4>(pl, pcm, so, fo, n_utts, grid, span, st, lm, gmax, total_cap);
+                   : wave_launch_one<PRE, RLO, RHI, S4>(pl, pcm, so, fo, n_utts, grid, span, st, lm, gmax, total_cap, \
+                                                        fo_end);
     SAPR_WAVE_CASE(6)
     SAPR_WAVE_CASE(7)
     SAPR_WAVE_CASE(8)
@@ -1074,12 +1096,24 @@ hipError_t wave_dispatch_s4(const MfccPlan &pl, int *prepare, const float *pcm, 
 }
 hipError_t wave_dispatch(const MfccPlan &pl, int *prepare, const float *pcm, const int64_t *so, const int64_t *fo,
                          int64_t n_utts, int grid, int64_t span, hipStream_t st, float *lm, unsigned *gmax,
-                         int64_t total_cap) {
+                         int64_t total_cap, const int64_t *fo_end) {
   const bool pre = pl.dev.preemph != 0.f, tight = pl.wave_rlo == 1 && pl.wave_rhi == 15;
-  if (pre && tight) return wave_dispatch_s4<true, 1, 15>(pl, prepare, pcm, so, fo, n_utts, grid, span, st, lm, gmax, total_cap);
-  if (pre) return wave_dispatch_s4<true, 0, 16>(pl, prepare, pcm, so, fo, n_utts, grid, span, st, lm, gmax, total_cap);
-  if (tight) return wave_dispatch_s4<false, 1, 15>(pl, prepare, pcm, so, fo, n_utts, grid, span, st, lm, gmax, total_cap);
-  return wave_dispatch_s4<false, 0, 16>(pl, prepare, pcm, so, fo, n_utts, grid, span, st, lm, gmax, total_cap);
+#define SAPR_WAVE_ARGS pl, prepare, pcm, so, fo, n_utts, grid, span, st, lm, gmax, total_cap, fo_end
+  if (pre && tight) return wave_dispatch_s4<true, 1, 15>(SAPR_WAVE_ARGS);
+  if (pre) return wave_dispatch_s4<true, 0, 16>(SAPR_WAVE_ARGS);
+  if (tight) return wave_dispatch_s4<false, 1, 15>(SAPR_WAVE_ARGS);
+  return wave_dispatch_s4<false, 0, 16>(SAPR_WAVE_ARGS);
+#undef SAPR_WAVE_ARGS
+}
+
+// the slice pipeline's stream and events (`s`: a stream not yet stored in the plan)
+void plan_side_destroy(const MfccPlan &pl, hipStream_t s) {
+  for (int k = 0; k < kMaxSlices - 1; ++k)
+    if (pl.ev_spec[k]) (void)hipEventDestroy(pl.ev_spec[k]), pl.ev_spec[k] = nullptr;
+  if (pl.ev_side) (void)hipEventDestroy(pl.ev_side), pl.ev_side = nullptr;
+  if (s) (void)hipStreamDestroy(s);
+  if (pl.side && pl.side != s) (void)hipStreamDestroy(pl.side);
+  pl.side = nullptr;
 }
 
 size_t finish_lds_bytes(const MfccDev &d) {
@@ -1421,11 +1455,31 @@ extern "C" int sapr_mfcc_plan_create(double sr, int32_t n_fft, int32_t win_lengt
     pl->wave_lds = static_cast<size_t>(wave_lds(d.wave_s4, wave_region_floats(d.n_mels, d.deltas)).total);
     pl->lds_bytes = pl->wave_lds;
     hipError_t oe = wave_dispatch(*pl, &pl->wave_blocks_per_cu, nullptr, nullptr, nullptr, 0, 0, 1, nullptr, nullptr,
-                                  nullptr, 0);
+                                  nullptr, 0, nullptr);
     if (oe != hipSuccess || pl->wave_blocks_per_cu < 1) {
       (void)hipFree(devbuf);
       delete pl;
       return hip_fail(oe, "occupancy query (mfcc_wave_kernel)");
+    }
+    // SAPR_MFCC_SLICES: 1 = single launch, n > 1 = n utterance slices whatever the batch size, unset = default
+    if (const char *sl = std::getenv("SAPR_MFCC_SLICES")) {
+      const int v = std::atoi(sl);
+      pl->slices_env = v < 1 ? 0 : (v > kMaxSlices ? kMaxSlices : v);
+    }
+    // finish workgroups per CU that fit into the LDS the resident spectral workgroups leave free (both rounded up to
+    // the allocation granule, 320 dwords on gfx950), at least 1 (it then waits for a slot), at most the finish pass's
+    // own occupancy.  Registers and wave slots do not bind before that: 4 x 64 + 2 x 88 of 512 VGPRs per SIMD lane.
+    {
+      int dev = 0, lds_cu = 0;
+      if (hipGetDevice(&dev) != hipSuccess ||
+          hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) != hipSuccess ||
+          lds_cu < 64 * 1024)
+        lds_cu = 160 * 1024;
+      constexpr int kGranule = 320 * 4;
+      const int spec = align_up(static_cast<int>(pl->wave_lds), kGranule) * pl->wave_blocks_per_cu;
+      const int fin = align_up(static_cast<int>(wave_finish_lds(d.n_mels, d.deltas)), kGranule);
+      const int fit = spec < lds_cu ? (lds_cu - spec) / fin : 0;
+      pl->finish_beside = fit < 1 ? 1 : (fit > SAPR_FINISH_OCC ? SAPR_FINISH_OCC : fit);
     }
   }
   *plan_out = pl;
@@ -1435,6 +1489,7 @@ extern "C" int sapr_mfcc_plan_create(double sr, int32_t n_fft, int32_t win_lengt
 extern "C" int sapr_mfcc_plan_destroy(void *plan) {
   if (!plan) return 0;
   MfccPlan *pl = static_cast<MfccPlan *>(plan);
+  plan_side_destroy(*pl, nullptr);
   if (pl->buffer) (void)hipFree(pl->buffer);
   delete pl;
   return 0;
@@ -1523,7 +1578,95 @@ extern "C" int sapr_mfcc_batch(const void *plan, const float *pcm, const int64_t
   if (pl->dev.wave_s4) {
     // persistent wavefronts; each takes an equal run of `span` consecutive frames of the batch (whole 4-frame sets,
     // across utterance boundaries), so the grid is balanced to +- one set for any batch size and length mix
-    int wgrid = grid_blocks > 0 ? grid_blocks : cus * pl->wave_blocks_per_cu;
+    const int full_grid = cus * pl->wave_blocks_per_cu;
+    const int64_t n_waves_full = static_cast<int64_t>(full_grid) * kWaves;
+    // second half: a wavefront per utterance again (16 resident wavefronts per CU keep ~48 log-mel tiles in flight)
+    const size_t flds = wave_finish_lds(pl->dev.n_mels, pl->dev.deltas);
+    const int64_t *fo_end = frame_offsets + n_utts;
+    auto finish = [&](hipStream_t s, int64_t u0, int64_t n, int fgrid, int fill) -> hipError_t {
+      const int64_t fwaves = static_cast<int64_t>(fgrid) * kWaves;
+      int fsplit = 1;
+      if (n < fwaves) {
+        fsplit = static_cast<int>(std::min<int64_t>(8, fwaves / n));
+        const int64_t need_blocks = (n * fsplit + kWaves - 1) / kWaves;
+        if (need_blocks < fgrid) fgrid = static_cast<int>(need_blocks);
+      }
+      SAPR_LAUNCH(mfcc_wave_finish_kernel, dim3(fgrid), dim3(kThreads), flds, s, lm, gmax + u0, frame_offsets + u0, n,
+                  pl->dev, out, fsplit, total_frames, fo_end, fill);
+      return hipGetLastError();
+    };
+
+    // ---- slice pipeline: the spectral kernel is bound by VALU issue and leaves ~70 % of the HBM bandwidth idle, the
+    // finish pass is almost pure HBM traffic.  The batch is cut into slices of whole utterances; finish(slice k) runs
+    // on the plan's low-priority side stream while spectral(slice k + 1) runs on the caller's.  Both kernels compute
+    // per frame / per tile exactly what the single launch computes (mfcc_wave.h).  The single launch stays for forced
+    // grids, during stream capture, without a side stream, and for batches too small to cut.
+    int n_slices = 1;
+    if (grid_blocks <= 0 && pl->slices_env != 1) {
+      if (pl->slices_env > 1) {
+        n_slices = pl->slices_env;
+      } else {
+        // default: every slice keeps the finish pass at one wavefront per utterance (fsplit == 1, as in the single
+        // launch of a batch this size) and gives each spectral wavefront at least kSliceMinSets sets per launch
+        n_slices = kDefaultSlices;
+        const int64_t fwaves = static_cast<int64_t>(cus) * SAPR_FINISH_OCC * kWaves;
+        while (n_slices > 1 && (n_utts / n_slices < fwaves || total_frames / n_slices < 4 * kSliceMinSets * n_waves_full))
+          n_slices >>= 1;
+      }
+      if (n_slices > n_utts) n_slices = static_cast<int>(n_utts);
+      if (n_slices > 1) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
+          (void)hipGetLastError();
+          n_slices = 1;
+        }
+      }
+    }
+    if (n_slices > 1) {
+      std::lock_guard<std::mutex> lock(pl->side_mu);
+      if (!pl->side_tried) {
+        pl->side_tried = true;
+        // lowest priority: the exactly-resident spectral grid is placed first, the finish workgroups take what is left
+        int least = 0, greatest = 0;
+        hipStream_t s = nullptr;
+        bool ok = hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess &&
+                  hipStreamCreateWithPriority(&s, hipStreamNonBlocking, least) == hipSuccess;
+        for (int k = 0; ok && k < kMaxSlices; ++k) {
+          hipEvent_t *e = k < kMaxSlices - 1 ? &pl->ev_spec[k] : &pl->ev_side;
+          ok = hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+        }
+        if (ok) {
+          pl->side = s;
+        } else {
+          (void)hipGetLastError();
+          plan_side_destroy(*pl, s);
+        }
+      }
+      if (pl->side) {
+        SAPR_HIP_TRY(hipMemsetAsync(gmax, 0, static_cast<size_t>(n_utts) * sizeof(unsigned), st));
+        const int beside_grid = cus * pl->finish_beside;
+        for (int k = 0; k < n_slices; ++k) {  // n_slices <= n_utts: no slice is empty
+          const int64_t u0 = n_utts * k / n_slices, n = n_utts * (k + 1) / n_slices - u0;
+          SAPR_HIP_TRY(wave_dispatch(*pl, nullptr, pcm, sample_offsets + u0, frame_offsets + u0, n, full_grid, 0, st, lm,
+                                     gmax + u0, total_frames, fo_end));
+          if (k + 1 < n_slices) {
+            SAPR_HIP_TRY(hipEventRecord(pl->ev_spec[k], st));
+            SAPR_HIP_TRY(hipStreamWaitEvent(pl->side, pl->ev_spec[k], 0));
+            SAPR_HIP_TRY(finish(pl->side, u0, n, beside_grid, 0));
+          } else {
+            // nothing runs beside the last slice's finish: the full grid, on the caller's stream; it is also the one
+            // launch that marks the output when the frame-count guard fires
+            SAPR_HIP_TRY(finish(st, u0, n, cus * SAPR_FINISH_OCC, 1));
+          }
+        }
+        // the side stream is in order: its last finish done = all of them done.  Whatever the caller enqueues next
+        // (and the next call's memset of the maxima) waits for it.
+        SAPR_HIP_TRY(hipEventRecord(pl->ev_side, pl->side));
+        SAPR_HIP_TRY(hipStreamWaitEvent(st, pl->ev_side, 0));
+        return 0;
+      }
+    }
+    int wgrid = grid_blocks > 0 ? grid_blocks : full_grid;
     const int64_t n_waves = static_cast<int64_t>(wgrid) * kWaves;
     int64_t span = (total_frames + n_waves - 1) / n_waves;
     span = span < 4 ? 4 : (span + 3) / 4 * 4;
@@ -1531,19 +1674,8 @@ extern "C" int sapr_mfcc_batch(const void *plan, const float *pcm, const int64_t
     if (need_blocks < wgrid) wgrid = static_cast<int>(need_blocks < 1 ? 1 : need_blocks);
     SAPR_HIP_TRY(hipMemsetAsync(gmax, 0, static_cast<size_t>(n_utts) * sizeof(unsigned), st));
     SAPR_HIP_TRY(wave_dispatch(*pl, nullptr, pcm, sample_offsets, frame_offsets, n_utts, wgrid, span, st, lm, gmax,
-                               total_frames));
-    // second half: a wavefront per utterance again (16 resident wavefronts per CU keep ~48 log-mel tiles in flight)
-    int fgrid = cus * SAPR_FINISH_OCC;
-    const int64_t fwaves = static_cast<int64_t>(fgrid) * kWaves;
-    int fsplit = 1;
-    if (n_utts < fwaves) {
-      fsplit = static_cast<int>(std::min<int64_t>(8, fwaves / n_utts));
-      const int64_t need_blocks = (n_utts * fsplit + kWaves - 1) / kWaves;
-      if (need_blocks < fgrid) fgrid = static_cast<int>(need_blocks);
-    }
-    SAPR_LAUNCH(mfcc_wave_finish_kernel, dim3(fgrid), dim3(kThreads), wave_finish_lds(pl->dev.n_mels, pl->dev.deltas), st,
-                lm, gmax, frame_offsets, n_utts, pl->dev, out, fsplit, total_frames);
-    SAPR_HIP_TRY(hipGetLastError());
+                               total_frames, fo_end));
+    SAPR_HIP_TRY(finish(st, 0, n_utts, cus * SAPR_FINISH_OCC, 1));
     return 0;
   } else if (pl->R == 16)
     SAPR_HIP_TRY((launch<16, true>(*pl, pcm, sample_offsets, frame_offsets, n_utts, out, grid, st, lm, gmax)));

@@ -285,11 +285,25 @@ __device__ __forceinline__ void wave_finish(const float *__restrict__ lm, int T,
 // The finish pass as its own launch: a wavefront per utterance (long utterances: `split` wavefronts take contiguous
 // runs of its tiles), wave-private LDS, no workgroup barrier after the table load.  gmax_enc holds the utterance
 // maxima the spectral kernel found.
+//
+// Slices: a launch serves the `n_utts` utterances whose offsets start at `frame_offsets` and whose maxima start at
+// `gmax_enc` — the whole batch, or a range [u0, u1) of it (the caller passes frame_offsets + u0, gmax + u0).  The offsets
+// themselves stay absolute, so `lm` and `out` are the batch's buffers either way.  `batch_end` points at the batch's
+// last offset (the frame-count guard is about the whole batch); of the launches of one batch exactly one has
+// `fill_on_mismatch` set and writes the NaN marker.
+//
+// A tile's result does NOT depend on `split`, on the grid or on the slice it is launched with: its 16 cepstra rows
+// come from its own 16 log-mel rows (rows past the utterance repeat the last one and are never stored), the clip
+// floor is the utterance's, and with deltas the wavefront that emits tile e transforms tiles e - 1 and e + 1 itself
+// — the same values whichever wavefront, in whatever launch, holds them.  The K-steps past n_mels multiply finite LDS
+// contents (zeroed below, later clipped log-mel values and cepstra) by a zero fragment.
 __global__ __launch_bounds__(kThreads, SAPR_FINISH_OCC) void mfcc_wave_finish_kernel(const float *__restrict__ lm,
                                                                        const unsigned *__restrict__ gmax_enc,
                                                                        const int64_t *__restrict__ frame_offsets,
                                                                        int64_t n_utts, MfccDev P, float *__restrict__ out,
-                                                                       int split, int64_t total_cap) {
+                                                                       int split, int64_t total_cap,
+                                                                       const int64_t *__restrict__ batch_end,
+                                                                       int fill_on_mismatch) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float *s_dtab = reinterpret_cast<float *>(smem);
   const int per_wave = 16 * (P.n_mels + 4) + (P.deltas ? 3 : 1) * 256;
@@ -302,10 +316,11 @@ __global__ __launch_bounds__(kThreads, SAPR_FINISH_OCC) void mfcc_wave_finish_ke
   float *s_tile = s_dtab + 168 + wave * per_wave;
   const int n_waves = gridDim.x * kWaves;
   const int wid = blockIdx.x * kWaves + wave;
-  if (frame_offsets[n_utts] > total_cap) {
+  if (*batch_end > total_cap) {
     // the offsets on the device describe MORE frames than the caller sized `out` and the workspace for (sapr_hip.h:
-    // frame_offsets[n_utts] == total_frames is a hard precondition): nothing was computed (mfcc_wave_kernel
-    // returned) — the whole output becomes NaN so that the mismatch cannot pass for features
+    // frame_offsets[n_utts] == total_frames is a hard precondition): nothing was computed (every mfcc_wave_kernel
+    // of the batch returned) — the whole output becomes NaN so that the mismatch cannot pass for features
+    if (!fill_on_mismatch) return;
     const int64_t n = total_cap * P.d_out;
     for (int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + tid; i < n; i += static_cast<int64_t>(gridDim.x) * kThreads)
       out[i] = __builtin_nanf("");
@@ -335,7 +350,7 @@ template <bool PREEMPH, int RLO, int RHI, int S4>
 __global__ __launch_bounds__(kThreads, SAPR_WAVE_OCC) void mfcc_wave_kernel(
     const float *__restrict__ pcm, const int64_t *__restrict__ sample_offsets,
     const int64_t *__restrict__ frame_offsets, int64_t n_utts, MfccDev P, float *__restrict__ lm_out,
-    unsigned *__restrict__ gmax_enc, int64_t span, int64_t total_cap) {
+    unsigned *__restrict__ gmax_enc, int64_t span, int64_t total_cap, const int64_t *__restrict__ batch_end) {
   constexpr int R = 16, kNc = 256, kBits = 4, NR = RHI - RLO;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int region_floats = wave_region_floats(P.n_mels, P.deltas);
@@ -395,16 +410,27 @@ __global__ __launch_bounds__(kThreads, SAPR_WAVE_OCC) void mfcc_wave_kernel(
   // boundaries (a wavefront finishes the tail of one utterance, takes whole ones, starts the head of another), so
   // every wavefront does the same number of sets +- 1 whatever the batch size and the utterance lengths; an
   // utterance shared by several wavefronts gets its maximum by atomicMax (gmax_enc is zeroed before the launch).
-  const int64_t total = frame_offsets[n_utts];
+  //
+  // Slices: sample_offsets, frame_offsets and gmax_enc start at the launch's first utterance (the whole batch, or a
+  // range of it); the offsets are absolute, so frames are numbered from frame_offsets[0] on and pcm / lm_out are the
+  // batch's buffers.  The host does not know a slice's frame count (the offsets live on the device): with span == 0
+  // the run length comes from the offsets and the grid, by the formula sapr_mfcc_batch uses for the whole batch.
+  const int64_t base = frame_offsets[0], total = frame_offsets[n_utts];
   const int64_t wid = static_cast<int64_t>(blockIdx.x) * kWaves + wave;
-  // the caller sized the log-mel workspace (and the maxima placed behind it) and the grid for `total_cap` frames: when
-  // the offsets on the device describe more, nothing is written (mfcc_wave_finish_kernel then marks the output)
-  if (total > total_cap) return;
-  const int64_t run_lo = wid * span;
+  // the caller sized the log-mel workspace (and the maxima placed behind it) and the grid for `total_cap` frames of the
+  // WHOLE batch: when the offsets on the device describe more, nothing is written by any of the batch's launches
+  // (mfcc_wave_finish_kernel then marks the output)
+  if (*batch_end > total_cap) return;
+  if (span == 0) {
+    const int64_t n_waves = static_cast<int64_t>(gridDim.x) * kWaves;
+    span = (total - base + n_waves - 1) / n_waves;
+    span = span < 4 ? 4 : (span + 3) / 4 * 4;
+  }
+  const int64_t run_lo = base + wid * span;
   if (run_lo >= total) return;
   const int64_t run_hi = run_lo + span < total ? run_lo + span : total;
   int64_t u_first = 0;
-  {  // the last utterance that starts at or before frame run_lo (frame_offsets[0] = 0 <= run_lo < total = frame_offsets[n_utts])
+  {  // the last utterance that starts at or before frame run_lo (frame_offsets[0] = base <= run_lo < total = frame_offsets[n_utts])
     int64_t hi = n_utts;
     while (hi - u_first > 1) {
       const int64_t mid = (u_first + hi) >> 1;

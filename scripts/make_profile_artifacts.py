@@ -2,7 +2,9 @@
 for the bench command, profiles/pmc_traffic.json (HBM bytes per launch of the bench's kernels from the FETCH_SIZE /
 WRITE_SIZE passes, corrected as MI355X_MICROARCH.md §HBM prescribes: FETCH_SIZE x2 for wide coalesced reads on
 gfx950, WRITE_SIZE as is).
-    python scripts/make_profile_artifacts.py <rocprof out dir> <tag> "<command that was profiled>" [utts]"""
+    python scripts/make_profile_artifacts.py <rocprof out dir> <tag> "<command that was profiled>" [utts] [mfcc slices]
+`mfcc slices`: launches of each MFCC kernel per launch sequence (the slice pipeline of sapr_mfcc_batch cuts the bench's
+batch in two): pmc_traffic.json holds bytes and instructions per launch SEQUENCE = mean per launch x that count."""
 import csv, glob, json, os, subprocess, sys
 from collections import defaultdict
 
@@ -12,6 +14,7 @@ from sapr_amd.build import source_hash  # noqa: E402
 src, tag = sys.argv[1], sys.argv[2]
 cmd = sys.argv[3] if len(sys.argv) > 3 else "bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras"
 utts = int(sys.argv[4]) if len(sys.argv) > 4 else 100000
+per_seq = {"mfcc": int(sys.argv[5]) if len(sys.argv) > 5 else 1, "decode": 1}
 os.makedirs("profiles", exist_ok=True)
 txt = subprocess.run([sys.executable, "scripts/prof_summary.py", src], capture_output=True, text=True).stdout
 out, skip = [], False
@@ -61,13 +64,13 @@ if "bench.py" in cmd and "--mode" not in cmd:
             if not f and not w:
                 continue
             found = True
-            fkb = sum(f) / len(f) if f else 0.0
-            wkb = sum(w) / len(w) if w else 0.0
+            fkb = per_seq[key] * sum(f) / len(f) if f else 0.0
+            wkb = per_seq[key] * sum(w) / len(w) if w else 0.0
             per[pat] = fkb * 2048 + wkb * 1024
             tot_f += fkb
             tot_w += wkb
         if found:
-            vi = {pat: sum(v) / len(v) for pat in pats for k, vs in valu.items() if pat + "<" in k or pat + "(" in k
+            vi = {pat: per_seq[key] * sum(v) / len(v) for pat in pats for k, vs in valu.items() if pat + "<" in k or pat + "(" in k
                   for v in [vs]}
             res[key] = {"utts": utts, "source_hash": source_hash(key), "fetch_size_kb_raw": tot_f, "write_size_kb_raw": tot_w,
                         "hbm_bytes_per_launch": tot_f * 1024 * 2 + tot_w * 1024, "per_kernel_bytes": per,
