@@ -187,6 +187,25 @@ int sapr_estep_diag(const float *feats, const int64_t *offsets, const int32_t *s
                     int32_t topology, int32_t fast_div, void *workspace, size_t workspace_bytes,
                     double *loglik, double *stats, void *stream);
 
+/* Forward scoring over the vocabulary: GaussianHMM.score (hmmlearn_hmm.py:104; hmmlearn _hmmc.cpp forward_log)
+ * extended over the model loop of decoder.py:42 — every utterance under EVERY word model in one launch, where
+ * sapr_forward_diag scores an utterance under the one model of its tile.  No tile layout and no workspace: `order`
+ * (optional, may be NULL) is the length-sorted permutation of the Viterbi entry points.  Only the exact-kernel
+ * operands of the pack are read (SAPR_PACK_EXACT_ONLY packs work).
+ *   loglik[n_utts][W]     log P(utterance | word model w); -inf for an utterance without frames
+ *   best_word[n_utts]     optional: first strict maximum of the row in model order, starting from -inf
+ *                         (decoder.py:42-47's rule on forward scores); -1 when no score beats -inf
+ *   word_post[n_utts][W]  optional: exp(loglik - logsumexp_w loglik), the posterior over the words under a uniform
+ *                         prior; NaN where the row's maximum is -inf or a score is NaN (nothing is repaired)
+ * Log-densities are evaluated in the E-step's quick form ((x - mean)^2 * RN(1/var) accumulated by FMA): scores agree
+ * with the float64 CPU evaluation to ~1e-13 relative, not bit for bit.  n_utts == 0 returns 0 at once.  max_T (the
+ * longest utterance, as in the Viterbi entry points) is checked to be >= 0 and sizes nothing: there is no workspace. */
+int sapr_forward_vocab(const float *feats, const int64_t *offsets, const int32_t *order /* may be NULL */,
+                       int64_t n_utts, int32_t D, int32_t max_T, const void *pack, int32_t W, int32_t S,
+                       int32_t topology, double *loglik /* [n_utts][W] */,
+                       int32_t *best_word /* [n_utts], may be NULL */,
+                       double *word_post /* [n_utts][W], may be NULL */, void *stream);
+
 /* Flat start of HMMLearnModel (hmmlearn_hmm.py:83-94: np.mean / np.var over axis 0 of the concatenated float32
  * features): numpy adds row after row in float32, so each column is one sequential float32 chain — reproduced
  * bit for bit.  center == NULL: out[d] = sum_r x[r][d]; else out[d] = sum_r RN32(RN32(x[r][d] - center[d])^2).

@@ -6,6 +6,11 @@ models go through ``sapr_viterbi_decode_pruned`` (bounding pass over the vocabul
 words that can still win; same bits as scoring every word) whenever the model pack allows it, and through
 ``sapr_viterbi_diag_scores`` + ``sapr_viterbi_backtrace`` otherwise; the reference's from-scratch models use
 ``sapr_custom_decode``.
+
+Beyond the reference's API the hmmlearn models can be scored by total (forward) likelihood, ``GaussianHMM.score``
+(hmmlearn_hmm.py:104) under every word model in one launch of ``sapr_forward_vocab``: ``score_batch`` returns the
+[N, W] matrix, ``nbest`` the best words of each utterance with their posteriors, and ``scoring="forward"`` makes
+``decode_batch`` classify by forward likelihood instead of by the Viterbi score.
 """
 from __future__ import annotations
 
@@ -21,9 +26,21 @@ from .mfcc_extract import load_mfccs_by_word
 
 
 class Decoder:
-    def __init__(self, models_dir: str = "trained_models", implementation: str = "hmmlearn", n_iter: int = 15):
+    def __init__(self, models_dir: str = "trained_models", implementation: str = "hmmlearn", n_iter: int = 15,
+                 scoring: str = "viterbi"):
+        """``scoring="viterbi"`` (default): decoder.py:35-49 — the word whose best state path scores highest, that
+        score, that path.  ``scoring="forward"``: the word with the highest forward log-likelihood (first strict maximum
+        in load order), that log-likelihood, and the Viterbi path of that word; the path costs one all-vocabulary exact
+        Viterbi pass (scores + back-pointers for every word, back-trace of the chosen one) on top of the forward launch,
+        not the pruned decoder's pass over the surviving words."""
+        if scoring not in ("viterbi", "forward"):
+            raise ValueError(f"scoring must be 'viterbi' or 'forward', got {scoring!r}")
+        if scoring == "forward" and implementation == "custom":
+            raise ValueError("scoring='forward' needs implementation='hmmlearn': the from-scratch model has no forward "
+                             "scorer over a vocabulary")
         self.models_dir = Path(models_dir)
         self.implementation = implementation
+        self.scoring = scoring
         self.n_iter = n_iter
         self.models: Dict = {}
         self.vocab: List[str] = []
@@ -78,6 +95,8 @@ class Decoder:
         if self._pack is None:
             self._pack = DiagModelPack.from_models(self._model_list())
         tie = _lib.TIE_HIGH if getattr(self._model_list()[0], "tie_break", "high") == "high" else _lib.TIE_LOW
+        if self.scoring == "forward":
+            return self._decode_forward(batch, tie)
         # decoder.py:59 hands hmmlearn the transposed VIEW of the (D,T) array → numpy's left-to-right sum.
         # Pruned decoder when the pack is prunable, all-vocabulary evaluation otherwise: identical outputs.
         best_word, best_score, best_path = viterbi_decode_best(batch, self._pack, tie=tie, sum_order=_lib.SUM_TVIEW)
@@ -87,6 +106,58 @@ class Decoder:
         bw_l, bs_l = bw.tolist(), bs.tolist()
         return [(words[w], sc, path[lo:hi]) if w >= 0 else (None, float("-inf"), None)
                 for w, sc, lo, hi in zip(bw_l, bs_l, offs[:-1], offs[1:])]
+
+    def _decode_forward(self, batch, tie) -> List[Tuple[str, float, object]]:
+        """Forward arg-max word, its forward log-likelihood, and the Viterbi path of that word."""
+        from .trellis import forward_scores, viterbi_decode
+        words = list(self.models)
+        fs = forward_scores(batch, self._pack, want_post=False)
+        # an utterance no model scores above -inf has no word (-1): model 0's path is walked and then dropped
+        vit = viterbi_decode(batch, self._pack, tie=tie, sum_order=_lib.SUM_TVIEW,
+                             word_sel=fs.best_word.clamp(min=0))
+        ll, bw, path = _lib.to_host(fs.loglik, fs.best_word, vit.path)
+        offs = np.r_[0, np.cumsum(batch.lengths)].tolist()
+        path = path.astype(np.int64)
+        return [(words[w], float(ll[u, w]), path[lo:hi]) if w >= 0 else (None, float("-inf"), None)
+                for u, (w, lo, hi) in enumerate(zip(bw.tolist(), offs[:-1], offs[1:]))]
+
+    # ---- forward scoring over the vocabulary --------------------------------------------------
+    def _forward_scores(self, feature_list, want_post):
+        if self.implementation == "custom":
+            raise ValueError("forward scoring over the vocabulary needs implementation='hmmlearn': the from-scratch "
+                             "model has no forward scorer over a vocabulary")
+        from .trellis import DiagModelPack, FeatureBatch, forward_scores
+        if self._pack is None:
+            self._pack = DiagModelPack.from_models(self._model_list())
+        return forward_scores(FeatureBatch.from_arrays(feature_list, layout="DT"), self._pack, want_post=want_post)
+
+    def score_batch(self, feature_list: List[np.ndarray]) -> np.ndarray:
+        """Forward log-likelihood (``GaussianHMM.score``) of every utterance of ``feature_list`` ((D, T) arrays as
+        in ``decode_batch``) under every word model: float64 [N, W], columns in ``self.vocab`` order."""
+        return _lib.to_host(self._forward_scores(feature_list, False).loglik)[0].copy()  # (out of the pinned buffer)
+
+    @staticmethod
+    def _nbest_rows(loglik: np.ndarray, word_post: np.ndarray, vocab: List[str],
+                    n: int) -> List[List[Tuple[str, float, float]]]:
+        """Host ordering of a score matrix [N, W] (columns in ``vocab`` order): per utterance the ``n`` best
+        ``(word, log_likelihood, posterior)``, best first; equal scores stay in load order, NaN scores sort last."""
+        loglik = np.asarray(loglik, dtype=np.float64)
+        word_post = np.asarray(word_post, dtype=np.float64)
+        W = loglik.shape[1]
+        n = max(0, min(int(n), W))
+        nan = np.isnan(loglik)
+        with np.errstate(invalid="ignore"):
+            key = np.where(nan, 0.0, -loglik)
+        idx = np.lexsort((key, nan), axis=-1)[:, :n]  # stable: by NaN-ness, then descending score, then column
+        return [[(vocab[w], float(loglik[u, w]), float(word_post[u, w])) for w in row] for u, row in enumerate(idx)]
+
+    def nbest(self, feature_list: List[np.ndarray], n: int = 3) -> List[List[Tuple[str, float, float]]]:
+        """The ``n`` most likely words of every utterance by forward log-likelihood: lists of ``(word,
+        log_likelihood, posterior)``, best first, the posterior over the vocabulary under a uniform prior.  ``n`` is
+        clipped to the vocabulary size.  The device returns the [N, W] matrices; the ordering is host work."""
+        fs = self._forward_scores(feature_list, True)
+        ll, post = _lib.to_host(fs.loglik, fs.word_post)
+        return self._nbest_rows(ll, post, list(self.models), n)
 
     # ---- the reference's API ------------------------------------------------------------------
     def decode_sequence(self, features: np.ndarray) -> Tuple[str, float, List[int]]:

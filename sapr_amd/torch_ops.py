@@ -10,13 +10,16 @@ on the current stream; there is no CPU implementation (calling an op on CPU tens
                                                           max_T, tie, sum_order, pack.flags)
     loglik, stats = torch.ops.sapr.hmm_estep(feat, offsets, slot_utt, tile_model, model_tile_off, pack.blob,
                                              W, S, D, max_T, topology, fast_div)
+    loglik_nw, word, post = torch.ops.sapr.hmm_forward_scores(feat, frame_offsets, order, pack.blob, W, S, D, max_T,
+                                                              topology)
     # the reference's from-scratch HMM (custom_hmm.py), model arrays as custom_hmm.model_arrays() prepares them
     gamma, utt = torch.ops.sapr.custom_estep(feat, offsets, means, inv, cterm, A, logA)
     scores, paths, word, best, best_path = torch.ops.sapr.custom_decode(feat, offsets, means, inv, cterm, A, logA,
                                                                         num_states, Tq)
 
 Reference call sites replaced: ``librosa.feature.mfcc`` (mfcc_extract.py:15-23), ``GaussianHMM.decode`` over the
-vocabulary + arg-max (decoder.py:35-49), the E-step of ``GaussianHMM.fit`` (hmmlearn_hmm.py:103), the E-step of
+vocabulary + arg-max (decoder.py:35-49), the E-step of ``GaussianHMM.fit`` (hmmlearn_hmm.py:103), ``GaussianHMM.score``
+(hmmlearn_hmm.py:104) over the model loop of decoder.py:42, the E-step of
 ``HMM.baum_welch`` (custom_hmm.py:422-439) and ``HMM.decode`` over the vocabulary (custom_hmm.py:462-514,
 decoder.py:42-47).
 """
@@ -35,6 +38,8 @@ _LIB.define("viterbi_decode_best(Tensor feats, Tensor offsets, Tensor order, Ten
             "int max_T, int tie, int sum_order, int pack_flags) -> (Tensor, Tensor, Tensor)")
 _LIB.define("hmm_estep(Tensor feats, Tensor offsets, Tensor slot_utt, Tensor tile_model, Tensor model_tile_off, "
             "Tensor pack, int W, int S, int D, int max_T, int topology, int fast_div) -> (Tensor, Tensor)")
+_LIB.define("hmm_forward_scores(Tensor feats, Tensor offsets, Tensor order, Tensor pack, int W, int S, int D, int max_T, "
+            "int topology) -> (Tensor, Tensor, Tensor)")
 _LIB.define("custom_estep(Tensor feats, Tensor offsets, Tensor means, Tensor inv, Tensor cterm, Tensor A, Tensor logA) "
             "-> (Tensor, Tensor)")
 _LIB.define("custom_decode(Tensor feats, Tensor offsets, Tensor means, Tensor inv, Tensor cterm, Tensor A, Tensor logA, "
@@ -112,6 +117,19 @@ def _hmm_estep(feats, offsets, slot_utt, tile_model, model_tile_off, pack, W, S,
     return loglik, stats
 
 
+def _hmm_forward_scores(feats, offsets, order, pack, W, S, D, max_T, topology):
+    """loglik[n][W] of every utterance under every word model, best_word[n] (-1: none) and word_post[n][W]."""
+    _check_dev(feats, offsets, order, pack)
+    n, dev = offsets.numel() - 1, feats.device
+    loglik = torch.empty((n, W), dtype=torch.float64, device=dev)
+    bw = torch.empty(n, dtype=torch.int32, device=dev)
+    post = torch.empty((n, W), dtype=torch.float64, device=dev)
+    _lib.check(_lib.load().sapr_forward_vocab(_lib.ptr(feats), _lib.ptr(offsets), _lib.ptr(order), n, D, max_T,
+                                              _lib.ptr(pack), W, S, topology, _lib.ptr(loglik), _lib.ptr(bw),
+                                              _lib.ptr(post), _lib.current_stream()), "sapr_forward_vocab")
+    return loglik, bw, post
+
+
 def _custom_shapes(feats, means, inv, cterm, A, logA):
     W, S, D = means.shape
     if feats.dim() != 2 or feats.shape[1] != D or feats.dtype != torch.float32:
@@ -164,5 +182,6 @@ def _custom_decode(feats, offsets, means, inv, cterm, A, logA, num_states, Tq):
 
 for _name, _fn in (("pcm16_to_f32", _pcm16_to_f32), ("mfcc_batch", _mfcc_batch),
                    ("viterbi_decode_best", _viterbi_decode_best), ("hmm_estep", _hmm_estep),
+                   ("hmm_forward_scores", _hmm_forward_scores),
                    ("custom_estep", _custom_estep), ("custom_decode", _custom_decode)):
     _LIB.impl(_name, _fn, "CUDA")

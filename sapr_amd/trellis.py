@@ -9,6 +9,8 @@
   the kernels, with every host-side constant evaluated by numpy exactly as hmmlearn
   evaluates it (``np.log(transmat)``, ``nf*log(2*pi) + log(covars).sum(-1)``).
 * :func:`viterbi_decode` – two launches (scores + back-trace) through the C ABI.
+* :func:`forward_scores` – forward log-likelihoods of every utterance under every word model, the arg-max
+  word and the posterior over the words, in one launch.
 
 PyTorch is used for device memory and streams only.
 """
@@ -442,6 +444,32 @@ def forward_loglik(batch: FeatureBatch, pack: DiagModelPack, utt_model, layout: 
                                      pack.W, pack.S, pack.topology, pack.fast_div, _lib.ptr(loglik),
                                      _lib.current_stream()), "sapr_forward_diag")
     return loglik
+
+
+@dataclass
+class ForwardScores:
+    loglik: "object"     # [N,W] f64 — GaussianHMM.score of every utterance under every word model
+    best_word: "object"  # [N] i32 (first strict maximum in model order; -1 if no score beats -inf)
+    word_post: "object"  # [N,W] f64 posterior over the words under a uniform prior, or None
+
+
+def forward_scores(batch: FeatureBatch, pack: DiagModelPack, want_post: bool = True) -> ForwardScores:
+    """Forward log-likelihood of every utterance under EVERY word model in one launch (``sapr_forward_vocab``), the
+    arg-max word and, with ``want_post``, ``exp(loglik - logsumexp_w loglik)``.  Device tensors; no workspace.
+    Padded models (``kernel_states`` / ``kernel_dims``) and ``exact_only`` packs are served as they are."""
+    torch = _torch()
+    lib = _lib.load()
+    _check_dims(batch, pack)
+    dev = batch.feats.device
+    N, W = batch.n_utts, pack.W
+    loglik = torch.empty((N, W), dtype=torch.float64, device=dev)
+    best_word = torch.empty(N, dtype=torch.int32, device=dev)
+    word_post = torch.empty((N, W), dtype=torch.float64, device=dev) if want_post else None
+    _lib.check(lib.sapr_forward_vocab(_lib.ptr(batch.feats), _lib.ptr(batch.offsets), _lib.ptr(batch.order), N,
+                                      batch.D, batch.max_T, _lib.ptr(pack.blob), W, pack.S, pack.topology,
+                                      _lib.ptr(loglik), _lib.ptr(best_word), _lib.ptr(word_post),
+                                      _lib.current_stream()), "sapr_forward_vocab")
+    return ForwardScores(loglik, best_word, word_post)
 
 
 class EStep:
