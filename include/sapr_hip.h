@@ -334,6 +334,9 @@ int sapr_custom_global_cov(const float *feats, int64_t total_frames, int32_t D, 
  *          the call cannot return an error for a mismatch.  The 512-point wave-private core checks it on the
  *          device: offsets that describe MORE frames than total_frames make it write nothing but NaN into all
  *          of `out` (tests/test_capi_errors_gpu.py) instead of running past the buffers.
+ *          That core counts frames and utterances in 32 bits: total_frames or n_utts of 2^31 - 16 or more
+ *          return SAPR_ERR_ARG before anything is launched (the log-mel workspace of such a batch exceeds the
+ *          device's memory by itself).
  *   slices The 512-point wave-private core cuts a large batch into slices of whole utterances and runs the finish
  *          pass of slice k on a low-priority stream the plan owns, under the spectral kernel of slice k + 1
  *          (same bits as the single launch sequence; SAPR_MFCC_SLICES at plan creation: 1 = never, n = always n).

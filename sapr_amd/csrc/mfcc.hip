@@ -1570,14 +1570,21 @@ extern "C" int sapr_mfcc_batch(const void *plan, const float *pcm, const int64_t
       SAPR_HIP_TRY((launch<32, false>(*pl, pcm, sample_offsets, frame_offsets, n_utts, out, grid, st, nullptr, nullptr)));
     return 0;
   }
+  // the wave-private core counts a launch's frames and utterances in 32 bits (mfcc_wave.h); the log-mel rows of 2^31
+  // frames would not fit the device anyway
+  if (pl->dev.wave_s4)
+    SAPR_REQUIRE(total_frames < (int64_t{1} << 31) - 16 && n_utts < (int64_t{1} << 31) - 16,
+                 "2^31 - 16 frames or utterances or more in one batch");
   const size_t need = (static_cast<size_t>(total_frames) * pl->dev.n_mels + static_cast<size_t>(n_utts)) * sizeof(float) + 256;
   if (!workspace || workspace_size < need)
     return fail(SAPR_ERR_WORKSPACE, "two-pass MFCC plan needs a %zu-byte workspace (sapr_mfcc_workspace_bytes)", need);
   float *lm = static_cast<float *>(workspace);
   unsigned *gmax = reinterpret_cast<unsigned *>(lm + static_cast<size_t>(total_frames) * pl->dev.n_mels);
   if (pl->dev.wave_s4) {
-    // persistent wavefronts; each takes an equal run of `span` consecutive frames of the batch (whole 4-frame sets,
-    // across utterance boundaries), so the grid is balanced to +- one set for any batch size and length mix
+    // persistent wavefronts; each takes an equal run of `span` consecutive frames of the batch = span / 4 whole sets of
+    // four frames on the batch's (or slice's) frame numbering through all utterances, so the grid is balanced to
+    // +- one set for any batch size and length mix and a set holds four real frames wherever utterances end
+    // (mfcc_wave.h)
     const int full_grid = cus * pl->wave_blocks_per_cu;
     const int64_t n_waves_full = static_cast<int64_t>(full_grid) * kWaves;
     // second half: a wavefront per utterance again (16 resident wavefronts per CU keep ~48 log-mel tiles in flight)

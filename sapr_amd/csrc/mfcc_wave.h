@@ -4,14 +4,19 @@
 // centre padding -> Hamming window -> rFFT -> |X|^2 -> Slaney mel filterbank -> 10 log10; the utterance-global
 // top_db clip, the DCT-II and the deltas run in mfcc_finish_kernel over the log-mel workspace.
 //
-// One WAVEFRONT owns four consecutive frames of one utterance from their PCM samples to their log-mel rows and
-// shares nothing with the other wavefronts of its workgroup but read-only tables: after the table load there is no
-// workgroup barrier, so co-resident wavefronts drift apart and cover each other's LDS round trips.
+// One WAVEFRONT owns a SET of four consecutive frames from their PCM samples to their log-mel rows and shares nothing
+// with the other wavefronts of its workgroup but read-only tables: after the table load there is no workgroup
+// barrier, so co-resident wavefronts drift apart and cover each other's LDS round trips.  Sets are cut on the
+// launch's frame numbering through ALL utterances (frames base + 4k ... base + 4k + 3, base = frame_offsets[0]), not
+// per utterance: where an utterance ends inside a set, the set's remaining 16-lane groups take the first frames of the
+// next utterance(s) instead of computing frames that do not exist (T = 101: 26 sets per utterance became 25.25).
 //
 //   samples  raw buffer loads straight into the FFT's register layout (lane l of a frame's 16-lane group holds the
 //            complex points z[l + 16 r] = y[2n] + i y[2n+1]); a descriptor of the utterance's own samples makes
 //            every offset outside the signal read as 0 = librosa's centre padding.  They are issued one set
-//            ahead, into the registers the FFT has just vacated, under the filterbank phase.
+//            ahead, across utterance boundaries, into the registers the FFT has just vacated, under the filterbank
+//            phase.  A set under which an utterance ends issues one batch of loads per utterance, each through that
+//            utterance's descriptor under the execution mask of its groups.
 //   FFT      256-point complex = 16 lanes x 16 register points: in-lane radix-2 DIF, twiddle, 16 x 16 transpose
 //            through the wavefront's own LDS scratch (real and imaginary plane in turn; rows of 18 floats make
 //            the ds_write_b32 columns and the ds_read_b64 rows conflict-free), in-lane DIF again.
@@ -23,8 +28,12 @@
 //            to four parts on neighbouring blocks, summed by two DPP row shifts): 4*S4 steps instead of 257, no
 //            16-frame tile, no cross-wavefront exchange.
 //   log      on the accumulators, one 16-byte store per lane into log_mel[frame][mel]; running maximum per
-//            utterance for the top_db clip.
-//   split    equal runs of consecutive frames per wavefront, across utterance boundaries (see the kernel).
+//            utterance for the top_db clip (atomicMax when the wavefront leaves the utterance).
+//   split    equal runs of whole sets per wavefront, across utterance boundaries (see the kernel).
+//
+// A frame's row is the same instruction sequence on the same samples whichever group, set or wavefront holds it (the
+// odd groups' LDS row rotation only moves data, MFMA columns are independent, the maximum is order-independent), so
+// the features do not depend on where the sets fall: tests/test_mfcc_packed_sets_gpu.py.
 #pragma once
 
 constexpr int kWRowPad = 18;              // floats per transpose row
@@ -405,16 +414,21 @@ __global__ __launch_bounds__(kThreads, SAPR_WAVE_OCC) void mfcc_wave_kernel(
   const int mel0 = bi.y;  // first mel of the block's group if it is the group's head part, else -1
   const float f1 = bi.z ? 1.f : 0.f, f2 = bi.w ? 1.f : 0.f;
 
-  // Work split: the batch's frames, numbered through all utterances, are cut into equal runs of `span` frames, one
-  // run per wavefront; a wavefront owns every 4-frame set whose FIRST frame lies in its run.  Runs ignore utterance
-  // boundaries (a wavefront finishes the tail of one utterance, takes whole ones, starts the head of another), so
-  // every wavefront does the same number of sets +- 1 whatever the batch size and the utterance lengths; an
-  // utterance shared by several wavefronts gets its maximum by atomicMax (gmax_enc is zeroed before the launch).
+  // Work split: the launch's frames, numbered through all utterances from base = frame_offsets[0] on, are cut into
+  // 4-frame SETS on that numbering (set k = frames base + 4k ... base + 4k + 3) and into equal runs of `span` frames
+  // (a multiple of four), one run per wavefront: a wavefront owns exactly the sets inside its run, so every wavefront
+  // does the same number of sets +- 1 whatever the batch size and the utterance lengths, and no frame slot is spent
+  // on a frame that does not exist except in the launch's last set.  A set whose four frames lie in one utterance
+  // takes the FAST path (one wave-uniform buffer descriptor, scalar bookkeeping); a set that reaches over the end of
+  // an utterance (or of the launch) takes the BOUNDARY path: its 16-lane groups belong to up to four utterances, each
+  // loaded through its own descriptor under the execution mask of its groups.  The arithmetic of a frame is the same
+  // instruction sequence whichever group holds it, so a row does not depend on where the sets fall.  An utterance
+  // shared by several wavefronts gets its maximum by atomicMax (gmax_enc is zeroed before the launch).
   //
   // Slices: sample_offsets, frame_offsets and gmax_enc start at the launch's first utterance (the whole batch, or a
-  // range of it); the offsets are absolute, so frames are numbered from frame_offsets[0] on and pcm / lm_out are the
-  // batch's buffers.  The host does not know a slice's frame count (the offsets live on the device): with span == 0
-  // the run length comes from the offsets and the grid, by the formula sapr_mfcc_batch uses for the whole batch.
+  // range of it); the offsets are absolute, so pcm / lm_out are the batch's buffers.  The host does not know a
+  // slice's frame count (the offsets live on the device): with span == 0 the run length comes from the offsets and
+  // the grid, by the formula sapr_mfcc_batch uses for the whole batch.
   const int64_t base = frame_offsets[0], total = frame_offsets[n_utts];
   const int64_t wid = static_cast<int64_t>(blockIdx.x) * kWaves + wave;
   // the caller sized the log-mel workspace (and the maxima placed behind it) and the grid for `total_cap` frames of the
@@ -426,281 +440,398 @@ __global__ __launch_bounds__(kThreads, SAPR_WAVE_OCC) void mfcc_wave_kernel(
     span = (total - base + n_waves - 1) / n_waves;
     span = span < 4 ? 4 : (span + 3) / 4 * 4;
   }
-  const int64_t run_lo = base + wid * span;
-  if (run_lo >= total) return;
-  const int64_t run_hi = run_lo + span < total ? run_lo + span : total;
-  int64_t u_first = 0;
-  {  // the last utterance that starts at or before frame run_lo (frame_offsets[0] = base <= run_lo < total = frame_offsets[n_utts])
-    int64_t hi = n_utts;
+  if (wid * span >= total - base) return;
+  // From here on frames are counted from `base`, in 32 bits (sapr_mfcc_batch admits no batch of 2^31 frames: their
+  // log-mel rows alone would not fit the device's memory), and everything about the sets is wave-uniform scalar work.
+  const int n_fr = static_cast<int>(total - base);
+  const int run_lo = static_cast<int>(wid * span);
+  const int run_hi = wid * span + span < n_fr ? run_lo + static_cast<int>(span) : n_fr;
+  const int n_u = static_cast<int>(n_utts);
+  // The offsets are read at utterance boundaries only.  Behind the kernel's stores the compiler no longer takes them
+  // for scalar loads and would keep what depends on them (the ends of the utterances the sets are compared with) in
+  // vector registers: readfirstlane puts every value back into scalar registers.
+  auto fo_rel = [&](int u) {
+    return __builtin_amdgcn_readfirstlane(static_cast<int>(frame_offsets[u] - base));
+  };
+  auto so_at = [&](int u) {
+    const int64_t v = sample_offsets[u];
+    const unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<int>(v));
+    const int hi = __builtin_amdgcn_readfirstlane(static_cast<int>(v >> 32));
+    return (static_cast<int64_t>(hi) << 32) | lo;
+  };
+  int u_first = 0;
+  {  // the last utterance that starts at or before frame run_lo (fo_rel(0) = 0 <= run_lo < n_fr = fo_rel(n_utts))
+    int hi = n_u;
     while (hi - u_first > 1) {
-      const int64_t mid = (u_first + hi) >> 1;
-      if (frame_offsets[mid] <= run_lo)
+      const int mid = (u_first + hi) >> 1;
+      if (fo_rel(mid) <= run_lo)
         u_first = mid;
       else
         hi = mid;
     }
   }
+  auto utt_rsrc = [&](int64_t s_beg, int64_t s_end) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(pcm + s_beg), 0, static_cast<int>(s_end - s_beg) * 4,
+                                             0x00020000 /* raw dword buffer */);
+  };
 
-  for (int64_t u = u_first; u < n_utts; ++u) {
-    const int64_t f_beg = frame_offsets[u];
-    if (f_beg >= run_hi) break;
-    const int T = static_cast<int>(frame_offsets[u + 1] - f_beg);
-    const int n_sets = (T + 3) >> 2;
-    const int s_lo = f_beg >= run_lo ? 0 : static_cast<int>((run_lo - f_beg + 3) >> 2);
-    const int s_hi_raw = static_cast<int>((run_hi - f_beg + 3) >> 2);
-    const int s_hi = s_hi_raw < n_sets ? s_hi_raw : n_sets;
-    if (s_lo >= s_hi) continue;
-    const int64_t s_beg = sample_offsets[u];
-    const int n_samp = static_cast<int>(sample_offsets[u + 1] - s_beg);
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(pcm + s_beg), 0, n_samp * 4, 0x00020000 /* raw dword buffer */);
-    float run_max = -3.0e38f;
+  // Two views of the utterances, both changed at utterance boundaries only (nothing is copied from set to set):
+  //   cu_*   the FETCH cursor: the utterance whose samples are being fetched for the next set, its descriptor, and
+  //          (nx_*) the ends of the utterance behind it, read one utterance ahead so that stepping over a boundary
+  //          waits for no load of an offset;
+  //   run_*  the utterance of the running maximum: the one the set in hand starts in, then each one under it in turn.
+  int cu = u_first;
+  int cu_fb = fo_rel(cu), cu_fe = fo_rel(cu + 1);
+  int64_t cu_se = so_at(cu + 1);
+  __amdgpu_buffer_rsrc_t cu_rsrc = utt_rsrc(so_at(cu), cu_se);
+  int nx = cu + 1 < n_u ? cu + 1 : cu;
+  int nx_fe = fo_rel(nx + 1);
+  int64_t nx_se = so_at(nx + 1);
+  auto seek = [&](int f) {  // f < n_fr: ends at the utterance that holds frame f (empty utterances are passed over)
+    while (cu_fe <= f && cu + 1 < n_u) {
+      cu = nx;
+      cu_fb = cu_fe;
+      cu_fe = nx_fe;
+      cu_rsrc = utt_rsrc(cu_se, nx_se);
+      cu_se = nx_se;
+      nx = cu + 1 < n_u ? cu + 1 : cu;
+      nx_fe = fo_rel(nx + 1);
+      nx_se = so_at(nx + 1);
+    }
+  };
+  // Boundary sets with pre-emphasis: the distinct utterances under the frames [f0, f0 + 4) of the launch, from utterance
+  // u0 (which holds f0) on: fn(first group, one past the last group, utterance, its first frame, one past its last).
+  auto for_each_utt = [&](int u0, int f0, auto fn) {
+    const int g_end = n_fr - f0 < 4 ? n_fr - f0 : 4;
+    int uu = u0;
+    for (int g = 0; g < g_end;) {
+      while (uu + 1 < n_u && fo_rel(uu + 1) <= f0 + g) ++uu;
+      const int fe = fo_rel(uu + 1);
+      const int g_hi = fe - f0 < g_end ? fe - f0 : g_end;
+      fn(g, g_hi, uu, fo_rel(uu), fe);
+      g = g_hi > g ? g_hi : g + 1;  // (offsets that do not ascend: never stall)
+    }
+  };
 
-    // samples of set s -> registers.  Offsets before sample 0 are negative = huge unsigned = out of range = 0; the
-    // hardware adds the instruction's immediate offset (128 r bytes, folded by the compiler) to the vector offset
-    // modulo 2^32 before the range check (scripts/ubench/bufoff_probe.hip), so a negative base with an in-range
-    // sum still reads the sample.
-    WaveSet<PREEMPH, NR> nxt;
-    auto issue = [&](int s) {
-      const int vo = ((4 * s + grp) * P.hop - kNc + 2 * l) * 4;
-      static_for<RLO, RHI>([&](auto r_c) {
-        constexpr int r = decltype(r_c)::value;
-        nxt.y[r - RLO] = __builtin_bit_cast(f2u, __builtin_amdgcn_raw_buffer_load_b64(rsrc, vo + 8 * R * r, 0, 0));
-      });
-      if constexpr (PREEMPH)
-        nxt.m0 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, vo + 8 * R * RLO - 4, 0, 0));
-    };
-    issue(s_lo);
-
-    for (int s = s_lo; s < s_hi; ++s) {
-      // ============================ window, FFT pass A ============================
-      float re[R], im[R];
-      {
-        v2f w[NR];
-        static_for<RLO, RHI>([&](auto r_c) {
-          constexpr int r = decltype(r_c)::value;
-          w[r - RLO] = ds_rd64<8 * R * r>(a_win);
-        });
-        const int n0 = (4 * s + grp) * P.hop - kNc + 2 * l;
-        // does the set's last sample lie inside the signal?  (pre-emphasis must not leak the last real sample
-        // into the first padded one)
-        const bool inside = (4 * s + 3) * P.hop + kNc <= n_samp;
-        lds_wait();
-        lds_dep(w);
-        static_for<0, R>([&](auto r_c) {
-          constexpr int r = decltype(r_c)::value;
-          if constexpr (r < RLO || r >= RHI) {
-            re[r] = 0.f;
-            im[r] = 0.f;
-          } else {
-            f2u y = nxt.y[r - RLO];
-            if constexpr (PREEMPH) {
-              // y[2n - 1] is the second sample of lane l - 1's pair of this row (row_shr:1; lane 0 has no source and
-              // keeps `old`) or, for lane 0, of lane 15's pair of the previous row (row_ror:1)
-              float m = nxt.m0;
-              if constexpr (r > RLO) {
-                const int wrap = __builtin_amdgcn_mov_dpp(__float_as_int(nxt.y[r - 1 - RLO].y), 0x121, 0xf, 0xf, true);
-                m = __int_as_float(__builtin_amdgcn_update_dpp(wrap, __float_as_int(y.y), 0x111, 0xf, 0xf, false));
-              }
-              const float ya = y.x - P.preemph * m;
-              const float yb = y.y - P.preemph * y.x;
-              y.x = ya;
-              y.y = yb;
-              if (!inside) {
-                const int idx = n0 + 2 * R * r;
-                y.x = idx < n_samp ? y.x : 0.f;
-                y.y = idx + 1 < n_samp ? y.y : 0.f;
-              }
-            }
-            re[r] = y.x * w[r - RLO].x;
-            im[r] = y.y * w[r - RLO].y;
-          }
-        });
-      }
-      {
-        v2f tw[R - 1];  // in flight under the in-lane FFT
-        static_for<1, R>([&](auto k1_c) {
-          constexpr int k1 = decltype(k1_c)::value;
-          tw[k1 - 1] = ds_rd64<8 * R * k1>(a_twab);
-        });
-        fft_inlane<R>(re, im);
-        lds_wait();
-        lds_dep(tw);
-        static_for<1, R>([&](auto k1_c) {
-          constexpr int k1 = decltype(k1_c)::value;
-          constexpr int p = bitrev(k1, kBits);
-          const float tr = re[p] * tw[k1 - 1].x - im[p] * tw[k1 - 1].y;
-          const float ti = re[p] * tw[k1 - 1].y + im[p] * tw[k1 - 1].x;
-          re[p] = tr;
-          im[p] = ti;
-        });
-      }
-      // ================= 16 x 16 transpose through the wavefront's scratch =================
-      // DS instructions of one wavefront execute in order: the stores need no wait before the reads
-      {
-        v2f t[R / 2];
-        static_for<0, R>([&](auto k1_c) {
-          constexpr int k1 = decltype(k1_c)::value;
-          (k1 < 8 ? wlo : whi)[k1 * kWRowPad] = re[bitrev(k1, kBits)];
-        });
-        static_for<0, R / 2>([&](auto c_c) {
-          constexpr int c = decltype(c_c)::value;
-          t[c] = ds_rd64_mem<8 * c>(a_rrow);
-        });
-        lds_wait();
-        lds_dep(t);
-        static_for<0, R / 2>([&](auto c_c) {
-          constexpr int c = decltype(c_c)::value;
-          re[2 * c] = t[c].x;
-          re[2 * c + 1] = t[c].y;
-        });
-        static_for<0, R>([&](auto k1_c) {
-          constexpr int k1 = decltype(k1_c)::value;
-          (k1 < 8 ? wlo : whi)[k1 * kWRowPad] = im[bitrev(k1, kBits)];
-        });
-        static_for<0, R / 2>([&](auto c_c) {
-          constexpr int c = decltype(c_c)::value;
-          t[c] = ds_rd64_mem<8 * c>(a_rrow);
-        });
-        lds_wait();
-        lds_dep(t);
-        static_for<0, R / 2>([&](auto c_c) {
-          constexpr int c = decltype(c_c)::value;
-          im[2 * c] = t[c].x;
-          im[2 * c + 1] = t[c].y;
-        });
-      }
-      // ============================ FFT pass B ============================
-      v2f tu[R / 2];  // untangle twiddles, in flight under the in-lane FFT
-      static_for<0, R / 2>([&](auto k2_c) {
-        constexpr int k2 = decltype(k2_c)::value;
-        tu[k2] = ds_rd64<8 * R * k2>(a_twu);
-      });
-      fft_inlane<R>(re, im);  // Z[sigma + 16 k2] at bitrev(k2)
-      lds_wait();
-      lds_dep(tu);
-
-      // ============== untangle to the real spectrum, power -> the wavefront's four rows ==============
-      // X[k] = E + W_k O and X[Nc - k] = conj(E - W_k O), E = Z[k] + conj Z[Nc - k], O = (Z[k] - conj Z[Nc - k]) / i
-      // (the window carries the 1/2).  Z[Nc - k] is register 15 - k2 of the mirrored lane; lane 0 (residue 0) pairs
-      // its own registers k2 and 16 - k2, lane 15 (residue 8) its own k2 and 15 - k2.
-      static_for<0, R / 2>([&](auto k2_c) {
-        constexpr int k2 = decltype(k2_c)::value;
-        constexpr int pz = bitrev(k2, kBits);
-        constexpr int po = bitrev(R - 1 - k2, kBits);
-        constexpr int ps = bitrev((R - k2) % R, kBits);
-#if SAPR_WAVE_CNDDPP == 2
-        float tr_, ti_;
-        mirror_unless2_e64(re[po], im[po], special_mask, tr_, ti_);
-        const float prr = is0 ? re[ps] : tr_, pii = is0 ? im[ps] : ti_;
-#elif SAPR_WAVE_CNDDPP
-        // fetch and select in one instruction: v_cndmask_b32 with a DPP source takes the mirrored lane's value except
-        // where vcc (lanes 0 and 15 of every row) keeps the lane's own; lane 0 then swaps in its register 16 - k2
-        float tr_, ti_;
-        mirror_unless2(re[po], im[po], special_mask, tr_, ti_);
-        const float prr = is0 ? re[ps] : tr_, pii = is0 ? im[ps] : ti_;
-#else
-        const float selfr = is0 ? re[ps] : re[po], selfi = is0 ? im[ps] : im[po];
-        const float mr = dpp_mov<0x140>(re[po]), mi = dpp_mov<0x140>(im[po]);  // row_mirror
-        const float prr = special ? selfr : mr, pii = special ? selfi : mi;
-#endif
-        const float zr = re[pz], zi = im[pz];
-        const float er = zr + prr, ei = zi - pii;
-        const float o_r = zi + pii, o_i = prr - zr;
-        const float wx = tu[k2].x, wy = tu[k2].y;
-        // E + W O by two fused multiply-adds per component, E - W O = 2 E - (E + W O) by one: six instructions where
-        // forming W O first took eight
-        const float ar = __builtin_fmaf(wx, o_r, __builtin_fmaf(-wy, o_i, er));
-        const float ai = __builtin_fmaf(wx, o_i, __builtin_fmaf(wy, o_r, ei));
-        const float br = __builtin_fmaf(2.0f, er, -ar), bi2 = __builtin_fmaf(2.0f, ei, -ai);
-        prow[sigma + R * k2] = ar * ar + ai * ai;
-        prow[kNc - sigma - R * k2] = br * br + bi2 * bi2;  // k == 0: the Nyquist bin
-      });
-      if (is0) {  // the self-paired middle bin Nc/2
-        constexpr int pm = bitrev(R / 2, kBits);
-        prow[kNc / 2] = 4.f * (re[pm] * re[pm] + im[pm] * im[pm]);
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-      // next set's samples: the FFT registers are free, the loads land under the filterbank phase
-      if (s + 1 < s_hi) issue(s + 1);
-
-      // ========================= mel filterbank on 16 4x4 MFMA blocks =========================
-      f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-      {
-        float4 a[S4], bv[S4];
-#if SAPR_WAVE_FRAG64
-        // 16-byte operands as two hand-issued ds_read_b64 each: a ds_read_b128 moves fewer bytes per clock
-        // (scripts/ubench/mix_rate: 0.041 per cycle and SIMD against 0.145 for ds_read_b64)
-        {
-          const unsigned a_aq = lds_addr(aq), a_bq = lds_addr(bq);
-          v2f t[4 * S4];
-          static_for<0, S4>([&](auto q_c) {
-            constexpr int q = decltype(q_c)::value;
-            t[4 * q] = ds_rd64<q * kWave * 16>(a_aq);
-            t[4 * q + 1] = ds_rd64<q * kWave * 16 + 8>(a_aq);
-            t[4 * q + 2] = ds_rd64_mem<q * 16>(a_bq);
-            t[4 * q + 3] = ds_rd64_mem<q * 16 + 8>(a_bq);
-          });
-          lds_wait();
-          lds_dep(t);
+  // samples of a set -> registers.  Offsets before sample 0 are negative = huge unsigned = out of range = 0; the
+  // hardware adds the instruction's immediate offset (128 r bytes, folded by the compiler) to the vector offset
+  // modulo 2^32 before the range check (scripts/ubench/bufoff_probe.hip), so a negative base with an in-range
+  // sum still reads the sample.
+  WaveSet<PREEMPH, NR> nxt;
+  auto load_rows = [&](__amdgpu_buffer_rsrc_t rsrc, int t) {  // frame t of the descriptor's utterance
+    const int vo = (t * P.hop - kNc + 2 * l) * 4;
+    static_for<RLO, RHI>([&](auto r_c) {
+      constexpr int r = decltype(r_c)::value;
+      nxt.y[r - RLO] = __builtin_bit_cast(f2u, __builtin_amdgcn_raw_buffer_load_b64(rsrc, vo + 8 * R * r, 0, 0));
+    });
+    if constexpr (PREEMPH)
+      nxt.m0 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, vo + 8 * R * RLO - 4, 0, 0));
+  };
+  // the set at frame f0; the fetch cursor ends at the utterance that holds the set's last frame
+  auto issue = [&](int f0) {
+    seek(f0);
+    if (f0 + 4 <= cu_fe) {
+      load_rows(cu_rsrc, f0 - cu_fb + grp);
+    } else {
+      // groups past the launch's last frame stay idle: zeros (their rows are never stored)
 #pragma unroll
-          for (int q = 0; q < S4; ++q) {
-            a[q] = float4{t[4 * q].x, t[4 * q].y, t[4 * q + 1].x, t[4 * q + 1].y};
-            bv[q] = float4{t[4 * q + 2].x, t[4 * q + 2].y, t[4 * q + 3].x, t[4 * q + 3].y};
-          }
-        }
-#else
-#pragma unroll
-        for (int q = 0; q < S4; ++q) {
-          a[q] = aq[q * kWave];
-          bv[q] = bq[q];
-        }
-#endif
-#pragma unroll
-        for (int q = 0; q < S4; ++q) {
-          acc0 = __builtin_amdgcn_mfma_f32_4x4x1f32(a[q].x, bv[q].x, acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_f32_4x4x1f32(a[q].y, bv[q].y, acc1, 0, 0, 0);
-          acc0 = __builtin_amdgcn_mfma_f32_4x4x1f32(a[q].z, bv[q].z, acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_f32_4x4x1f32(a[q].w, bv[q].w, acc1, 0, 0, 0);
-        }
-      }
-      float e[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) e[i] = acc0[i] + acc1[i];
-      // parts of a group sit on neighbouring blocks of one DPP row, head first: fold them into the head
-#pragma unroll
-      for (int i = 0; i < 4; ++i) e[i] += f1 * dpp_mov<0x104>(e[i]);  // row_shl:4 = the next block
-#pragma unroll
-      for (int i = 0; i < 4; ++i) e[i] += f2 * dpp_mov<0x108>(e[i]);  // row_shl:8
-      const int t = 4 * s + j4;
-      if (mel0 >= 0 && t < T) {
-        // 10 log10(x) = (10 log10 2) log2(x); the argument is >= amin = 1e-10, a normal number, so the bare
-        // v_log_f32 needs none of the denormal scaling __log10f wraps around it
-        constexpr float kDb = 3.01029995663981195f;
-        float4 v;
-        v.x = kDb * __builtin_amdgcn_logf(fmaxf(P.amin, e[0]));
-        v.y = kDb * __builtin_amdgcn_logf(fmaxf(P.amin, e[1]));
-        v.z = kDb * __builtin_amdgcn_logf(fmaxf(P.amin, e[2]));
-        v.w = kDb * __builtin_amdgcn_logf(fmaxf(P.amin, e[3]));
-        // (address from an opaque copy of mel0: a per-lane base kept across the set is the first thing the register
-        // allocator spills, and a reload here would wait for the sample prefetch issued above)
-        int mel0_here = mel0;
-        asm volatile("" : "+v"(mel0_here));
-        *reinterpret_cast<float4 *>(lm_out + ((f_beg + t) * P.n_mels + mel0_here)) = v;
-        run_max = fmaxf(run_max, fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
+      for (int r = 0; r < NR; ++r) nxt.y[r] = f2u{0.f, 0.f};
+      if constexpr (PREEMPH) nxt.m0 = 0.f;
+      // one batch of loads per utterance under the set, for the groups that belong to it; the cursor's read-ahead
+      // has the second utterance's descriptor ready
+      const int g_end = n_fr - f0 < 4 ? n_fr - f0 : 4;
+      for (int g = 0; g < g_end;) {
+        seek(f0 + g);
+        const int g_hi = cu_fe - f0 < g_end ? cu_fe - f0 : g_end;
+        if (grp >= g && grp < g_hi) load_rows(cu_rsrc, f0 - cu_fb + grp);
+        g = g_hi > g ? g_hi : g + 1;  // (offsets that do not ascend: never stall)
       }
     }
-    // ===================== utterance maximum = top_db reference of the finish pass =====================
+  };
+
+  seek(run_lo);
+  int u_run = cu;
+  int run_fb = cu_fb, run_fe = cu_fe;
+  [[maybe_unused]] int run_ns = PREEMPH ? static_cast<int>(cu_se - so_at(cu)) : 0;
+  // running maximum of utterance u_run (every lane its own; reduced when the wavefront leaves the utterance)
+  float run_max = -3.0e38f;
+  auto flush_max = [&]() {  // mfcc_wave_finish_kernel follows
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) run_max = fmaxf(run_max, __shfl_xor(run_max, o, kWave));
-    if (lane == 0) {  // mfcc_wave_finish_kernel follows
-      if (s_lo == 0 && s_hi == n_sets)
-        gmax_enc[u] = enc_ordered(run_max);
-      else
-        atomicMax(gmax_enc + u, enc_ordered(run_max));
+    if (lane == 0) atomicMax(gmax_enc + u_run, enc_ordered(run_max));
+    run_max = -3.0e38f;
+  };
+  auto enter = [&](int uu, int fb, int fe) {  // the running maximum moves on to utterance uu
+    flush_max();
+    u_run = uu;
+    run_fb = fb;
+    run_fe = fe;
+    if constexpr (PREEMPH) run_ns = static_cast<int>(so_at(uu + 1) - so_at(uu));
+  };
+  float *set_rows = lm_out + (base + run_lo) * P.n_mels;  // log-mel rows of the set in hand
+  issue(run_lo);
+
+  for (int f0 = run_lo; f0 < run_hi; f0 += 4, set_rows += 4 * P.n_mels) {
+    // the utterance after u_run that holds frame f (the one u_run ends at; empty utterances are passed over)
+    auto next_utt = [&](int f) {
+      int uu = u_run + 1 < n_u ? u_run + 1 : u_run, fe = fo_rel(uu + 1);
+      while (fe <= f && uu + 1 < n_u) fe = fo_rel(++uu + 1);
+      enter(uu, run_fe, fe);
+    };
+    if (f0 >= run_fe) next_utt(f0);  // the last set ended with its utterance
+    const bool fast = f0 + 4 <= run_fe;
+    // ============================ window, FFT pass A ============================
+    float re[R], im[R];
+    // n0: the lane's first sample; `inside`: does the last sample lie inside the signal (pre-emphasis must not leak
+    // the last real sample into the first padded one); ns: samples of the lane's utterance
+    auto window = [&](int n0, bool inside, int ns) {
+      v2f w[NR];
+      static_for<RLO, RHI>([&](auto r_c) {
+        constexpr int r = decltype(r_c)::value;
+        w[r - RLO] = ds_rd64<8 * R * r>(a_win);
+      });
+      lds_wait();
+      lds_dep(w);
+      static_for<0, R>([&](auto r_c) {
+        constexpr int r = decltype(r_c)::value;
+        if constexpr (r < RLO || r >= RHI) {
+          re[r] = 0.f;
+          im[r] = 0.f;
+        } else {
+          f2u y = nxt.y[r - RLO];
+          if constexpr (PREEMPH) {
+            // y[2n - 1] is the second sample of lane l - 1's pair of this row (row_shr:1; lane 0 has no source and
+            // keeps `old`) or, for lane 0, of lane 15's pair of the previous row (row_ror:1)
+            float m = nxt.m0;
+            if constexpr (r > RLO) {
+              const int wrap = __builtin_amdgcn_mov_dpp(__float_as_int(nxt.y[r - 1 - RLO].y), 0x121, 0xf, 0xf, true);
+              m = __int_as_float(__builtin_amdgcn_update_dpp(wrap, __float_as_int(y.y), 0x111, 0xf, 0xf, false));
+            }
+            const float ya = y.x - P.preemph * m;
+            const float yb = y.y - P.preemph * y.x;
+            y.x = ya;
+            y.y = yb;
+            if (!inside) {
+              const int idx = n0 + 2 * R * r;
+              y.x = idx < ns ? y.x : 0.f;
+              y.y = idx + 1 < ns ? y.y : 0.f;
+            }
+          }
+          re[r] = y.x * w[r - RLO].x;
+          im[r] = y.y * w[r - RLO].y;
+        }
+      });
+    };
+    if constexpr (!PREEMPH) {
+      window(0, true, 0);
+    } else if (fast) {
+      const int t0 = f0 - run_fb;
+      window((t0 + grp) * P.hop - kNc + 2 * l, (t0 + 3) * P.hop + kNc <= run_ns, run_ns);
+    } else {
+      // every group its own utterance's frame index and sample count (idle groups: no samples, all zero)
+      int t_l = 0, ns_l = 0;
+      for_each_utt(u_run, f0, [&](int g_lo, int g_hi, int uu, int fb, int) {
+        const int ns = static_cast<int>(so_at(uu + 1) - so_at(uu));
+        if (grp >= g_lo && grp < g_hi) {
+          t_l = f0 - fb + grp;
+          ns_l = ns;
+        }
+      });
+      window(t_l * P.hop - kNc + 2 * l, false, ns_l);
+    }
+    {
+      v2f tw[R - 1];  // in flight under the in-lane FFT
+      static_for<1, R>([&](auto k1_c) {
+        constexpr int k1 = decltype(k1_c)::value;
+        tw[k1 - 1] = ds_rd64<8 * R * k1>(a_twab);
+      });
+      fft_inlane<R>(re, im);
+      lds_wait();
+      lds_dep(tw);
+      static_for<1, R>([&](auto k1_c) {
+        constexpr int k1 = decltype(k1_c)::value;
+        constexpr int p = bitrev(k1, kBits);
+        const float tr = re[p] * tw[k1 - 1].x - im[p] * tw[k1 - 1].y;
+        const float ti = re[p] * tw[k1 - 1].y + im[p] * tw[k1 - 1].x;
+        re[p] = tr;
+        im[p] = ti;
+      });
+    }
+    // ================= 16 x 16 transpose through the wavefront's scratch =================
+    // DS instructions of one wavefront execute in order: the stores need no wait before the reads
+    {
+      v2f t[R / 2];
+      static_for<0, R>([&](auto k1_c) {
+        constexpr int k1 = decltype(k1_c)::value;
+        (k1 < 8 ? wlo : whi)[k1 * kWRowPad] = re[bitrev(k1, kBits)];
+      });
+      static_for<0, R / 2>([&](auto c_c) {
+        constexpr int c = decltype(c_c)::value;
+        t[c] = ds_rd64_mem<8 * c>(a_rrow);
+      });
+      lds_wait();
+      lds_dep(t);
+      static_for<0, R / 2>([&](auto c_c) {
+        constexpr int c = decltype(c_c)::value;
+        re[2 * c] = t[c].x;
+        re[2 * c + 1] = t[c].y;
+      });
+      static_for<0, R>([&](auto k1_c) {
+        constexpr int k1 = decltype(k1_c)::value;
+        (k1 < 8 ? wlo : whi)[k1 * kWRowPad] = im[bitrev(k1, kBits)];
+      });
+      static_for<0, R / 2>([&](auto c_c) {
+        constexpr int c = decltype(c_c)::value;
+        t[c] = ds_rd64_mem<8 * c>(a_rrow);
+      });
+      lds_wait();
+      lds_dep(t);
+      static_for<0, R / 2>([&](auto c_c) {
+        constexpr int c = decltype(c_c)::value;
+        im[2 * c] = t[c].x;
+        im[2 * c + 1] = t[c].y;
+      });
+    }
+    // ============================ FFT pass B ============================
+    v2f tu[R / 2];  // untangle twiddles, in flight under the in-lane FFT
+    static_for<0, R / 2>([&](auto k2_c) {
+      constexpr int k2 = decltype(k2_c)::value;
+      tu[k2] = ds_rd64<8 * R * k2>(a_twu);
+    });
+    fft_inlane<R>(re, im);  // Z[sigma + 16 k2] at bitrev(k2)
+    lds_wait();
+    lds_dep(tu);
+
+    // ============== untangle to the real spectrum, power -> the wavefront's four rows ==============
+    // X[k] = E + W_k O and X[Nc - k] = conj(E - W_k O), E = Z[k] + conj Z[Nc - k], O = (Z[k] - conj Z[Nc - k]) / i
+    // (the window carries the 1/2).  Z[Nc - k] is register 15 - k2 of the mirrored lane; lane 0 (residue 0) pairs
+    // its own registers k2 and 16 - k2, lane 15 (residue 8) its own k2 and 15 - k2.
+    static_for<0, R / 2>([&](auto k2_c) {
+      constexpr int k2 = decltype(k2_c)::value;
+      constexpr int pz = bitrev(k2, kBits);
+      constexpr int po = bitrev(R - 1 - k2, kBits);
+      constexpr int ps = bitrev((R - k2) % R, kBits);
+#if SAPR_WAVE_CNDDPP == 2
+      float tr_, ti_;
+      mirror_unless2_e64(re[po], im[po], special_mask, tr_, ti_);
+      const float prr = is0 ? re[ps] : tr_, pii = is0 ? im[ps] : ti_;
+#elif SAPR_WAVE_CNDDPP
+      // fetch and select in one instruction: v_cndmask_b32 with a DPP source takes the mirrored lane's value except
+      // where vcc (lanes 0 and 15 of every row) keeps the lane's own; lane 0 then swaps in its register 16 - k2
+      float tr_, ti_;
+      mirror_unless2(re[po], im[po], special_mask, tr_, ti_);
+      const float prr = is0 ? re[ps] : tr_, pii = is0 ? im[ps] : ti_;
+#else
+      const float selfr = is0 ? re[ps] : re[po], selfi = is0 ? im[ps] : im[po];
+      const float mr = dpp_mov<0x140>(re[po]), mi = dpp_mov<0x140>(im[po]);  // row_mirror
+      const float prr = special ? selfr : mr, pii = special ? selfi : mi;
+#endif
+      const float zr = re[pz], zi = im[pz];
+      const float er = zr + prr, ei = zi - pii;
+      const float o_r = zi + pii, o_i = prr - zr;
+      const float wx = tu[k2].x, wy = tu[k2].y;
+      // E + W O by two fused multiply-adds per component, E - W O = 2 E - (E + W O) by one: six instructions where
+      // forming W O first took eight
+      const float ar = __builtin_fmaf(wx, o_r, __builtin_fmaf(-wy, o_i, er));
+      const float ai = __builtin_fmaf(wx, o_i, __builtin_fmaf(wy, o_r, ei));
+      const float br = __builtin_fmaf(2.0f, er, -ar), bi2 = __builtin_fmaf(2.0f, ei, -ai);
+      prow[sigma + R * k2] = ar * ar + ai * ai;
+      prow[kNc - sigma - R * k2] = br * br + bi2 * bi2;  // k == 0: the Nyquist bin
+    });
+    if (is0) {  // the self-paired middle bin Nc/2
+      constexpr int pm = bitrev(R / 2, kBits);
+      prow[kNc / 2] = 4.f * (re[pm] * re[pm] + im[pm] * im[pm]);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+    // next set's samples, across utterance boundaries: the FFT registers are free, the loads land under the
+    // filterbank phase
+    if (f0 + 4 < run_hi) issue(f0 + 4);
+
+    // ========================= mel filterbank on 16 4x4 MFMA blocks =========================
+    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+    {
+      float4 a[S4], bv[S4];
+#if SAPR_WAVE_FRAG64
+      // 16-byte operands as two hand-issued ds_read_b64 each: a ds_read_b128 moves fewer bytes per clock
+      // (scripts/ubench/mix_rate: 0.041 per cycle and SIMD against 0.145 for ds_read_b64)
+      {
+        const unsigned a_aq = lds_addr(aq), a_bq = lds_addr(bq);
+        v2f t[4 * S4];
+        static_for<0, S4>([&](auto q_c) {
+          constexpr int q = decltype(q_c)::value;
+          t[4 * q] = ds_rd64<q * kWave * 16>(a_aq);
+          t[4 * q + 1] = ds_rd64<q * kWave * 16 + 8>(a_aq);
+          t[4 * q + 2] = ds_rd64_mem<q * 16>(a_bq);
+          t[4 * q + 3] = ds_rd64_mem<q * 16 + 8>(a_bq);
+        });
+        lds_wait();
+        lds_dep(t);
+#pragma unroll
+        for (int q = 0; q < S4; ++q) {
+          a[q] = float4{t[4 * q].x, t[4 * q].y, t[4 * q + 1].x, t[4 * q + 1].y};
+          bv[q] = float4{t[4 * q + 2].x, t[4 * q + 2].y, t[4 * q + 3].x, t[4 * q + 3].y};
+        }
+      }
+#else
+#pragma unroll
+      for (int q = 0; q < S4; ++q) {
+        a[q] = aq[q * kWave];
+        bv[q] = bq[q];
+      }
+#endif
+#pragma unroll
+      for (int q = 0; q < S4; ++q) {
+        acc0 = __builtin_amdgcn_mfma_f32_4x4x1f32(a[q].x, bv[q].x, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_4x4x1f32(a[q].y, bv[q].y, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_4x4x1f32(a[q].z, bv[q].z, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_4x4x1f32(a[q].w, bv[q].w, acc1, 0, 0, 0);
+      }
+    }
+    float e[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) e[i] = acc0[i] + acc1[i];
+    // parts of a group sit on neighbouring blocks of one DPP row, head first: fold them into the head
+#pragma unroll
+    for (int i = 0; i < 4; ++i) e[i] += f1 * dpp_mov<0x104>(e[i]);  // row_shl:4 = the next block
+#pragma unroll
+    for (int i = 0; i < 4; ++i) e[i] += f2 * dpp_mov<0x108>(e[i]);  // row_shl:8
+    // 10 log10(x) = (10 log10 2) log2(x); the argument is >= amin = 1e-10, a normal number, so the bare
+    // v_log_f32 needs none of the denormal scaling __log10f wraps around it.  Row = the global frame f0 + j4.
+    auto store_row = [&]() {
+      constexpr float kDb = 3.01029995663981195f;
+      float4 v;
+      v.x = kDb * __builtin_amdgcn_logf(fmaxf(P.amin, e[0]));
+      v.y = kDb * __builtin_amdgcn_logf(fmaxf(P.amin, e[1]));
+      v.z = kDb * __builtin_amdgcn_logf(fmaxf(P.amin, e[2]));
+      v.w = kDb * __builtin_amdgcn_logf(fmaxf(P.amin, e[3]));
+      // (address from an opaque copy of mel0: a per-lane base kept across the set is the first thing the register
+      // allocator spills, and a reload here would wait for the sample prefetch issued above)
+      int mel0_here = mel0;
+      asm volatile("" : "+v"(mel0_here));
+      // the set's first row is a scalar base, the lane's place in the set's four rows a 32-bit byte offset
+      const unsigned lane_off = static_cast<unsigned>(j4 * P.n_mels + mel0_here) * 4u;
+      *reinterpret_cast<float4 *>(reinterpret_cast<char *>(set_rows) + lane_off) = v;
+      return fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
+    };
+    // ===================== utterance maxima = top_db reference of the finish pass =====================
+    if (fast) {
+      if (mel0 >= 0) run_max = fmaxf(run_max, store_row());
+    } else {
+      // lanes of different j4 feed different utterances: each in turn takes over the running maximum
+      float vm = -3.0e38f;
+      if (mel0 >= 0 && f0 + j4 < n_fr) vm = store_row();
+      const int g_end = n_fr - f0 < 4 ? n_fr - f0 : 4;
+      for (int g = 0;;) {
+        const int g_hi = run_fe - f0 < g_end ? run_fe - f0 : g_end;
+        run_max = fmaxf(run_max, j4 >= g && j4 < g_hi ? vm : -3.0e38f);
+        g = g_hi > g ? g_hi : g + 1;  // (offsets that do not ascend: never stall)
+        if (g >= g_end) break;
+        next_utt(f0 + g);
+      }
     }
   }
+  flush_max();
 }
