@@ -206,6 +206,33 @@ int sapr_forward_vocab(const float *feats, const int64_t *offsets, const int32_t
                        int32_t *best_word /* [n_utts], may be NULL */,
                        double *word_post /* [n_utts][W], may be NULL */, void *stream);
 
+/* State posteriors and MAP decoding: GaussianHMM.score_samples / predict_proba / decode(algorithm="map") (hmmlearn
+ * base.py _compute_posteriors_log, _decode_map; _hmmc.cpp forward_log / backward_log) for a whole batch, every
+ * utterance under the ONE model of its tile — the tile layout of sapr_forward_diag (slot_utt, tile_model).  Only the
+ * exact-kernel operands of the pack are read (SAPR_PACK_EXACT_ONLY packs work).
+ *   loglik[n_utts]                     forward log-likelihood; -inf for an utterance without frames (no rows)
+ *   post[total_frames][n_out_states]   optional: gamma_t(s) = softmax_s(fwd + bwd), frame-major and ragged along
+ *                                      `offsets` — hmmlearn's (n_samples, n_components) layout.  n_out_states <= S
+ *                                      cuts the padded states of a model that runs at a larger kernel state count off
+ *                                      in the store
+ *   path[total_frames]                 optional: argmax_s post[t] over the first n_out_states states; equal values:
+ *                                      the lowest state; a row holding NaN: the index of its first NaN (np.argmax)
+ * post or path may be NULL, not both; with post == NULL no posterior reaches memory in the caller's layout (4 bytes of
+ * output per frame).  Two launches over a slot-major workspace of sapr_state_posteriors_workspace_bytes():
+ *   bidiagonal  (max(max_T, 1) + 1) * S * n_tiles * 256 * 8   (stay shares of the forward pass + its last row)
+ *   dense        2 * max(max_T, 1)  * S * n_tiles * 256 * 8   (forward lattice + log-densities)
+ * max_T must not be smaller than the longest utterance.  Log-densities are evaluated in the E-step's quick form:
+ * results agree with the float64 CPU evaluation to ~1e-13 relative, not bit for bit; every utterance is a function of
+ * its own (features, model) pair.  Bad sizes, a bad topology, n_out_states outside 1..S, a NULL loglik, both outputs
+ * NULL and a workspace that is too small return SAPR_ERR_ARG before anything is launched; n_tiles == 0 returns 0
+ * after the size checks without touching any pointer; D > 39 or S > 18 return SAPR_ERR_UNSUPPORTED. */
+int sapr_state_posteriors_workspace_bytes(int64_t n_tiles, int32_t S, int32_t max_T, int32_t topology, size_t *bytes);
+int sapr_state_posteriors_diag(const float *feats, const int64_t *offsets, const int32_t *slot_utt,
+                               const int32_t *tile_model, int64_t n_tiles, int32_t D, int32_t max_T,
+                               const void *pack, int32_t W, int32_t S, int32_t topology, int32_t n_out_states,
+                               void *workspace, size_t workspace_bytes, double *loglik,
+                               double *post /* may be NULL */, int32_t *path /* may be NULL */, void *stream);
+
 /* Flat start of HMMLearnModel (hmmlearn_hmm.py:83-94: np.mean / np.var over axis 0 of the concatenated float32
  * features): numpy adds row after row in float32, so each column is one sequential float32 chain — reproduced
  * bit for bit.  center == NULL: out[d] = sum_r x[r][d]; else out[d] = sum_r RN32(RN32(x[r][d] - center[d])^2).

@@ -17,7 +17,8 @@ LIB = os.path.join(HERE, "libsapr_hip.so")
 # the exact Viterbi kernels are one translation unit per (D, S) shape: the heavy ones first, so that a cold build on
 # 6-8 cores takes about as long as the slowest of them (~3 minutes) instead of one nine-minute compile
 SOURCES = ["viterbi_exact_39_18_t1s1.hip", "viterbi_exact_39_18_t1s0.hip", "viterbi_exact_39_18_t0s1.hip",
-           "viterbi_exact_39_18_t0s0.hip", "estep.hip", "forward_vocab.hip", "viterbi_exact_39_10_t1s1.hip", "viterbi_exact_39_10_t1s0.hip",
+           "viterbi_exact_39_18_t0s0.hip", "estep.hip", "state_posteriors.hip", "forward_vocab.hip",
+           "viterbi_exact_39_10_t1s1.hip", "viterbi_exact_39_10_t1s0.hip",
            "viterbi_exact_39_10_t0s1.hip", "viterbi_exact_39_10_t0s0.hip", "viterbi_exact_13_18.hip",
            "viterbi_bound.hip", "mfcc.hip", "viterbi_exact_13_10.hip", "custom.hip", "viterbi.hip", "common.hip",
            "resample.hip"]

@@ -10,7 +10,9 @@ words that can still win; same bits as scoring every word) whenever the model pa
 Beyond the reference's API the hmmlearn models can be scored by total (forward) likelihood, ``GaussianHMM.score``
 (hmmlearn_hmm.py:104) under every word model in one launch of ``sapr_forward_vocab``: ``score_batch`` returns the
 [N, W] matrix, ``nbest`` the best words of each utterance with their posteriors, and ``scoring="forward"`` makes
-``decode_batch`` classify by forward likelihood instead of by the Viterbi score.
+``decode_batch`` classify by forward likelihood instead of by the Viterbi score.  ``state_posteriors`` returns the
+state posterior lattice of every utterance under the decoder's word (or a named one) through
+``sapr_state_posteriors_diag``.
 """
 from __future__ import annotations
 
@@ -158,6 +160,36 @@ class Decoder:
         fs = self._forward_scores(feature_list, True)
         ll, post = _lib.to_host(fs.loglik, fs.word_post)
         return self._nbest_rows(ll, post, list(self.models), n)
+
+    # ---- state posteriors ---------------------------------------------------------------------
+    def state_posteriors(self, feature_list: List[np.ndarray], words: List[str] = None) -> List[np.ndarray]:
+        """Per utterance of ``feature_list`` ((D, T) arrays as in ``score_batch``) the ``(T, S)`` float64 lattice of
+        state posteriors P(q_t = s | x_1..T) under one word model: the word the decoder picks (``words=None``: the
+        pruned decoder's best word; an utterance without a word gets the first model) or the one named in ``words``.
+        One launch sequence for the whole batch, utterances grouped into tiles by word."""
+        if self.implementation == "custom":
+            raise ValueError("state posteriors need implementation='hmmlearn': the from-scratch model has no posterior "
+                             "kernel")
+        from .trellis import DiagModelPack, FeatureBatch, state_posteriors, viterbi_decode_best
+        vocab = list(self.models)
+        if self._pack is None:
+            self._pack = DiagModelPack.from_models(self._model_list())
+        batch = FeatureBatch.from_arrays(feature_list, layout="DT")
+        if words is None:
+            tie = _lib.TIE_HIGH if getattr(self._model_list()[0], "tie_break", "high") == "high" else _lib.TIE_LOW
+            best_word, _, _ = viterbi_decode_best(batch, self._pack, tie=tie, sum_order=_lib.SUM_TVIEW)
+            utt_model = np.maximum(_lib.to_host(best_word)[0].astype(np.int64), 0)
+        else:
+            if len(words) != batch.n_utts:
+                raise ValueError("one word per utterance")
+            unknown = sorted({w for w in words if w not in self.models})
+            if unknown:
+                raise ValueError(f"words not in vocabulary {vocab}: {unknown}")
+            utt_model = np.asarray([vocab.index(w) for w in words], dtype=np.int64)
+        res = state_posteriors(batch, self._pack, utt_model, want_path=False)
+        post = _lib.to_host(res.post)[0].copy()  # (out of the pinned buffer)
+        offs = np.r_[0, np.cumsum(batch.lengths)].tolist()
+        return [post[lo:hi] for lo, hi in zip(offs[:-1], offs[1:])]
 
     # ---- the reference's API ------------------------------------------------------------------
     def decode_sequence(self, features: np.ndarray) -> Tuple[str, float, List[int]]:

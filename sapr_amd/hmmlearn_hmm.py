@@ -140,6 +140,28 @@ def _features_f32(X) -> np.ndarray:
     return out
 
 
+DECODER_ALGORITHMS = ("viterbi", "map")
+
+
+def map_decode_host(posteriors, lengths=None):
+    """hmmlearn ``base.py _decode_map`` on a posterior lattice ``(n_samples, n_components)`` (restated from knowledge of
+    hmmlearn 0.3.x): per sequence ``state_sequence = argmax(posteriors, axis=1)`` and ``log_prob =
+    max(posteriors, axis=1).sum()``, the log_probs summed over the sequences → ``(log_prob, state_sequence)``.  numpy's
+    rules: equal values give the lowest state, a row holding NaN gives its first NaN and makes ``log_prob`` NaN."""
+    post = np.asarray(posteriors, dtype=np.float64)
+    if post.ndim != 2:
+        raise ValueError("posteriors must be 2-D (n_samples, n_components)")
+    lengths = [post.shape[0]] if lengths is None else [int(n) for n in lengths]
+    if sum(lengths) != post.shape[0]:
+        raise ValueError("lengths do not sum to n_samples")
+    log_prob, at = 0.0, 0
+    for n in lengths:
+        log_prob += float(np.max(post[at:at + n], axis=1).sum()) if n else 0.0
+        at += n
+    states = np.argmax(post, axis=1).astype(np.int64) if post.shape[0] else np.zeros(0, np.int64)
+    return log_prob, states
+
+
 class GaussianHMM:
     """hmmlearn-shaped diagonal-Gaussian HMM (every state emits) on the HIP kernels."""
 
@@ -151,8 +173,8 @@ class GaussianHMM:
             raise ValueError("only covariance_type='diag' is implemented (hmmlearn_hmm.py:29)")
         if implementation != "log":
             raise ValueError("only implementation='log' is implemented (hmmlearn_hmm.py:32)")
-        if algorithm != "viterbi":
-            raise ValueError("only algorithm='viterbi' is implemented")
+        if algorithm not in DECODER_ALGORITHMS:
+            raise ValueError(f"algorithm must be one of {DECODER_ALGORITHMS}, got {algorithm!r}")
         self.n_components, self.covariance_type, self.min_covar = n_components, covariance_type, min_covar
         self.startprob_prior, self.transmat_prior = startprob_prior, transmat_prior
         self.means_prior, self.means_weight = means_prior, means_weight
@@ -211,10 +233,22 @@ class GaussianHMM:
 
     # ---- GaussianHMM.decode (decoder.py:43) -----------------------------------------------
     def decode(self, X, lengths=None, algorithm=None):
-        """Viterbi: ``(log_prob, state_sequence)``.  The order of numpy's sum inside the log-density
+        """``(log_prob, state_sequence)`` by ``algorithm or self.algorithm``.
+
+        ``"viterbi"``: the order of numpy's sum inside the log-density
         depends on X's memory layout (oracle/hmmlearn_oracle.py): a C-contiguous X reduces pair-wise,
-        the ``feat.T`` view decoder.py:59 passes reduces left to right — both reproduced."""
+        the ``feat.T`` view decoder.py:59 passes reduces left to right — both reproduced.
+
+        ``"map"``: hmmlearn's ``_decode_map`` (restated from knowledge of hmmlearn 0.3.x, like SURVEY §9.3): the
+        per-frame arg-max of the state posteriors, ``log_prob = max(posteriors, axis=1).sum()`` per sequence, summed
+        over the sequences — computed on the host from the lattice the device returns (:func:`map_decode_host`)."""
         from .trellis import FeatureBatch, viterbi_decode
+        algorithm = algorithm or getattr(self, "algorithm", "viterbi")
+        if algorithm not in DECODER_ALGORITHMS:
+            raise ValueError(f"algorithm must be one of {DECODER_ALGORITHMS}, got {algorithm!r}")
+        if algorithm == "map":
+            Xa, lengths = self._split(X, lengths)
+            return map_decode_host(self._state_posteriors(Xa, lengths)[1], lengths)
         self._check()
         Xa = np.asarray(X)
         sum_order = _lib.SUM_PAIRWISE if Xa.flags.c_contiguous else _lib.SUM_TVIEW
@@ -232,6 +266,29 @@ class GaussianHMM:
 
     def predict(self, X, lengths=None):
         return self.decode(X, lengths)[1]
+
+    # ---- GaussianHMM.score_samples / predict_proba (hmmlearn base.py) -----------------------
+    def _state_posteriors(self, Xa, lengths):
+        """(per-sequence log-likelihoods, posterior lattice) as host arrays."""
+        from .trellis import FeatureBatch, state_posteriors
+        self._check()
+        import torch
+        dev = _lib.require_gpu()
+        feats = _features_f32(Xa)
+        batch = FeatureBatch.from_packed(torch.from_numpy(feats).to(dev), np.asarray(lengths))
+        res = state_posteriors(batch, self._pack(), want_path=False)
+        ll, post = _lib.to_host(res.loglik, res.post)
+        return ll, post.copy()  # (out of the pinned buffer)
+
+    def score_samples(self, X, lengths=None):
+        """``(log_prob, posteriors)``: the forward log-likelihood summed over the sequences and the state posteriors
+        ``(n_samples, n_components)`` float64 (hmmlearn ``score_samples``)."""
+        Xa, lengths = self._split(X, lengths)
+        ll, post = self._state_posteriors(Xa, lengths)
+        return float(ll.sum()) if len(lengths) > 1 else float(ll[0]), post
+
+    def predict_proba(self, X, lengths=None):
+        return self.score_samples(X, lengths)[1]
 
     # ---- GaussianHMM.score (hmmlearn_hmm.py:104) ------------------------------------------
     def score(self, X, lengths=None):

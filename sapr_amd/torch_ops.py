@@ -12,6 +12,8 @@ on the current stream; there is no CPU implementation (calling an op on CPU tens
                                              W, S, D, max_T, topology, fast_div)
     loglik_nw, word, post = torch.ops.sapr.hmm_forward_scores(feat, frame_offsets, order, pack.blob, W, S, D, max_T,
                                                               topology)
+    loglik_n, post, path = torch.ops.sapr.hmm_state_posteriors(feat, offsets, slot_utt, tile_model, pack.blob, W, S, D,
+                                                               max_T, topology, n_out_states)
     # the reference's from-scratch HMM (custom_hmm.py), model arrays as custom_hmm.model_arrays() prepares them
     gamma, utt = torch.ops.sapr.custom_estep(feat, offsets, means, inv, cterm, A, logA)
     scores, paths, word, best, best_path = torch.ops.sapr.custom_decode(feat, offsets, means, inv, cterm, A, logA,
@@ -19,7 +21,8 @@ on the current stream; there is no CPU implementation (calling an op on CPU tens
 
 Reference call sites replaced: ``librosa.feature.mfcc`` (mfcc_extract.py:15-23), ``GaussianHMM.decode`` over the
 vocabulary + arg-max (decoder.py:35-49), the E-step of ``GaussianHMM.fit`` (hmmlearn_hmm.py:103), ``GaussianHMM.score``
-(hmmlearn_hmm.py:104) over the model loop of decoder.py:42, the E-step of
+(hmmlearn_hmm.py:104) over the model loop of decoder.py:42, ``GaussianHMM.score_samples`` / ``predict_proba`` /
+``decode(algorithm="map")`` (hmmlearn's inference API; the reference does not call them), the E-step of
 ``HMM.baum_welch`` (custom_hmm.py:422-439) and ``HMM.decode`` over the vocabulary (custom_hmm.py:462-514,
 decoder.py:42-47).
 """
@@ -40,6 +43,8 @@ _LIB.define("hmm_estep(Tensor feats, Tensor offsets, Tensor slot_utt, Tensor til
             "Tensor pack, int W, int S, int D, int max_T, int topology, int fast_div) -> (Tensor, Tensor)")
 _LIB.define("hmm_forward_scores(Tensor feats, Tensor offsets, Tensor order, Tensor pack, int W, int S, int D, int max_T, "
             "int topology) -> (Tensor, Tensor, Tensor)")
+_LIB.define("hmm_state_posteriors(Tensor feats, Tensor offsets, Tensor slot_utt, Tensor tile_model, Tensor pack, int W, "
+            "int S, int D, int max_T, int topology, int n_out_states) -> (Tensor, Tensor, Tensor)")
 _LIB.define("custom_estep(Tensor feats, Tensor offsets, Tensor means, Tensor inv, Tensor cterm, Tensor A, Tensor logA) "
             "-> (Tensor, Tensor)")
 _LIB.define("custom_decode(Tensor feats, Tensor offsets, Tensor means, Tensor inv, Tensor cterm, Tensor A, Tensor logA, "
@@ -130,6 +135,26 @@ def _hmm_forward_scores(feats, offsets, order, pack, W, S, D, max_T, topology):
     return loglik, bw, post
 
 
+def _hmm_state_posteriors(feats, offsets, slot_utt, tile_model, pack, W, S, D, max_T, topology, n_out_states):
+    """loglik[n] of every utterance under its tile's model, post[total_frames][n_out_states] and path[total_frames]."""
+    _check_dev(feats, offsets, slot_utt, tile_model, pack)
+    lib = _lib.load()
+    n, n_tiles, dev = offsets.numel() - 1, tile_model.numel(), feats.device
+    nb = C.c_size_t(0)
+    _lib.check(lib.sapr_state_posteriors_workspace_bytes(n_tiles, S, max_T, topology, C.byref(nb)),
+               "sapr_state_posteriors_workspace_bytes")
+    ws = torch.empty(max(int(nb.value), 1), dtype=torch.uint8, device=dev)
+    loglik = torch.full((n,), float("-inf"), dtype=torch.float64, device=dev)
+    post = torch.empty((feats.shape[0], n_out_states), dtype=torch.float64, device=dev)
+    path = torch.empty(feats.shape[0], dtype=torch.int32, device=dev)
+    _lib.check(lib.sapr_state_posteriors_diag(_lib.ptr(feats), _lib.ptr(offsets), _lib.ptr(slot_utt),
+                                              _lib.ptr(tile_model), n_tiles, D, max_T, _lib.ptr(pack), W, S, topology,
+                                              n_out_states, _lib.ptr(ws), int(nb.value), _lib.ptr(loglik),
+                                              _lib.ptr(post), _lib.ptr(path), _lib.current_stream()),
+               "sapr_state_posteriors_diag")
+    return loglik, post, path
+
+
 def _custom_shapes(feats, means, inv, cterm, A, logA):
     W, S, D = means.shape
     if feats.dim() != 2 or feats.shape[1] != D or feats.dtype != torch.float32:
@@ -182,6 +207,6 @@ def _custom_decode(feats, offsets, means, inv, cterm, A, logA, num_states, Tq):
 
 for _name, _fn in (("pcm16_to_f32", _pcm16_to_f32), ("mfcc_batch", _mfcc_batch),
                    ("viterbi_decode_best", _viterbi_decode_best), ("hmm_estep", _hmm_estep),
-                   ("hmm_forward_scores", _hmm_forward_scores),
+                   ("hmm_forward_scores", _hmm_forward_scores), ("hmm_state_posteriors", _hmm_state_posteriors),
                    ("custom_estep", _custom_estep), ("custom_decode", _custom_decode)):
     _LIB.impl(_name, _fn, "CUDA")

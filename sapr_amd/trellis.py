@@ -11,6 +11,8 @@
 * :func:`viterbi_decode` – two launches (scores + back-trace) through the C ABI.
 * :func:`forward_scores` – forward log-likelihoods of every utterance under every word model, the arg-max
   word and the posterior over the words, in one launch.
+* :func:`state_posteriors` – the state posterior lattice ``post[total_frames, S]`` (hmmlearn's ``predict_proba``
+  layout) and its per-frame arg-max (MAP decoding) of every utterance under one word model each.
 
 PyTorch is used for device memory and streams only.
 """
@@ -470,6 +472,46 @@ def forward_scores(batch: FeatureBatch, pack: DiagModelPack, want_post: bool = T
                                       _lib.ptr(loglik), _lib.ptr(best_word), _lib.ptr(word_post),
                                       _lib.current_stream()), "sapr_forward_vocab")
     return ForwardScores(loglik, best_word, word_post)
+
+
+@dataclass
+class StatePosteriors:
+    loglik: "object"  # [N] f64 — forward log-likelihood under the utterance's model (-inf: no frames)
+    post: "object"    # [total_frames, S_model] f64 — gamma_t(s), frame-major, ragged along batch.offsets; or None
+    path: "object"    # [total_frames] i32 — argmax_s post[t] (np.argmax: lowest index on ties, first NaN); or None
+
+
+def state_posteriors(batch: FeatureBatch, pack: DiagModelPack, utt_model=None, want_post: bool = True,
+                     want_path: bool = True, layout: TileLayout = None) -> StatePosteriors:
+    """State posteriors P(q_t = s | x_1..T) of every utterance under the word model ``utt_model[u]`` (``None``: model 0
+    for every utterance) and their per-frame arg-max, through ``sapr_state_posteriors_diag``.  Device tensors.  ``post``
+    has the caller's ``S_model`` columns: padded kernel states are cut off in the kernel's store.  With
+    ``want_post=False`` the lattice never reaches memory and MAP decoding writes 4 bytes per frame."""
+    torch = _torch()
+    lib = _lib.load()
+    if not (want_post or want_path):
+        raise ValueError("state_posteriors: want_post and want_path are both False")
+    _check_dims(batch, pack)
+    dev = batch.feats.device
+    if layout is None:
+        um = np.zeros(batch.n_utts, dtype=np.int64) if utt_model is None else np.asarray(utt_model, dtype=np.int64)
+        if um.shape != (batch.n_utts,) or (um.size and (um.min() < 0 or um.max() >= pack.W)):
+            raise ValueError("utt_model must name one model 0..W-1 per utterance")
+        layout = TileLayout.build(batch.lengths, um, pack.W, dev)
+    n_out = pack.S_model or pack.S
+    nbytes = C.c_size_t(0)
+    _lib.check(lib.sapr_state_posteriors_workspace_bytes(layout.n_tiles, pack.S, batch.max_T, pack.topology,
+                                                         C.byref(nbytes)), "sapr_state_posteriors_workspace_bytes")
+    ws = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device=dev)
+    loglik = torch.full((batch.n_utts,), float("-inf"), dtype=torch.float64, device=dev)
+    post = torch.empty((batch.total_frames, n_out), dtype=torch.float64, device=dev) if want_post else None
+    path = torch.empty(batch.total_frames, dtype=torch.int32, device=dev) if want_path else None
+    _lib.check(lib.sapr_state_posteriors_diag(
+        _lib.ptr(batch.feats), _lib.ptr(batch.offsets), _lib.ptr(layout.slot_utt), _lib.ptr(layout.tile_model),
+        layout.n_tiles, batch.D, batch.max_T, _lib.ptr(pack.blob), pack.W, pack.S, pack.topology, n_out, _lib.ptr(ws),
+        int(nbytes.value), _lib.ptr(loglik), _lib.ptr(post), _lib.ptr(path), _lib.current_stream()),
+        "sapr_state_posteriors_diag")
+    return StatePosteriors(loglik, post, path)
 
 
 class EStep:
