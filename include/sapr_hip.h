@@ -233,6 +233,34 @@ int sapr_state_posteriors_diag(const float *feats, const int64_t *offsets, const
                                void *workspace, size_t workspace_bytes, double *loglik,
                                double *post /* may be NULL */, int32_t *path /* may be NULL */, void *stream);
 
+/* One Lloyd step of k-means for G independent problems ("groups": the frames of one word model each) and R centre
+ * sets per group ("restarts") side by side — the k-means of hmmlearn's GaussianHMM._init (sklearn KMeans, n_init=10)
+ * batched over the vocabulary.  A frame is loaded once and scored against all R centre sets of its group.  The layout
+ * is tiles of 1..256 consecutive frames of ONE group, sorted by group (kmeans.py FrameTiles builds it from the group
+ * lengths): tile_begin[n_tiles] (first frame), tile_len[n_tiles], tile_group[n_tiles], group_tile_off[G+1].
+ *   stats[G][R][K][2*D+1]       {count, sum_x[D], sqdev[D]} per cluster: the frames whose label is k, their column
+ *                               sums and sum (x_d - c_kd)^2 — new centre = sum_x / count, inertia = sum of sqdev over
+ *                               k and d.  A cluster or a group without frames gets exact zeros
+ *   labels[R][total_frames]     optional: argmin_k sum_d (x_d - c_kd)^2, float64, the difference squared directly
+ *                               (never the |x|^2 - 2x.c + |c|^2 expansion: c0 sits near -300 and it cancels); equal
+ *                               distances: the lowest k; a frame holding NaN: label 0 (np.argmin) and its NaN flows
+ *                               into the sums — nothing is repaired
+ * D in {13, 39} (narrower features run zero-padded: zero columns against zero centre columns add +0.0), K in 1..32,
+ * R >= 1; other D and K > 32 return SAPR_ERR_UNSUPPORTED.  Two launches: per-tile partial statistics into a workspace
+ * of sapr_kmeans_workspace_bytes() = n_tiles * R * K * (2*D+1) * 8, then one sum per group in tile order.  No
+ * floating-point atomics: results are bit-identical run to run, and a group's results do not depend on which other
+ * groups share the launch.  Tiles whose table entries point outside the batch are served as empty.  Bad sizes, NULL
+ * required pointers and a workspace that is too small return SAPR_ERR_ARG before anything is launched; n_tiles == 0
+ * zero-fills stats (one memset on the stream; nothing at all when G == 0) and returns 0 without touching any other
+ * pointer. */
+int sapr_kmeans_workspace_bytes(int64_t n_tiles, int32_t R, int32_t K, int32_t D, size_t *bytes);
+int sapr_kmeans_step(const float *feats /* [total_frames][D] */, int64_t total_frames, const int64_t *tile_begin,
+                     const int32_t *tile_len /* 1..256 */, const int32_t *tile_group,
+                     const int32_t *group_tile_off /* [G+1] */, int64_t n_tiles, int32_t G, int32_t R, int32_t K,
+                     int32_t D, const double *centres /* [G][R][K][D] */, void *workspace, size_t workspace_bytes,
+                     double *stats /* [G][R][K][2*D+1] */, int32_t *labels /* [R][total_frames], may be NULL */,
+                     void *stream);
+
 /* Flat start of HMMLearnModel (hmmlearn_hmm.py:83-94: np.mean / np.var over axis 0 of the concatenated float32
  * features): numpy adds row after row in float32, so each column is one sequential float32 chain — reproduced
  * bit for bit.  center == NULL: out[d] = sum_r x[r][d]; else out[d] = sum_r RN32(RN32(x[r][d] - center[d])^2).

@@ -162,8 +162,41 @@ def map_decode_host(posteriors, lengths=None):
     return log_prob, states
 
 
+def check_random_state(seed):
+    """sklearn.utils.check_random_state: None -> numpy's global RandomState, an int -> a fresh ``RandomState(seed)``,
+    a ``RandomState`` -> itself (and its stream is consumed)."""
+    if seed is None or seed is np.random:
+        return np.random.mtrand._rand
+    if isinstance(seed, (int, np.integer)) and not isinstance(seed, bool):
+        return np.random.RandomState(int(seed))
+    if isinstance(seed, np.random.RandomState):
+        return seed
+    raise ValueError(f"{seed!r} cannot be used to seed a numpy.random.RandomState instance")
+
+
+def kmeans_seed(rs) -> int:
+    """The one integer a model's ``random_state`` contributes to its k-means (drawn after the ``s`` / ``t`` draws)."""
+    return int(rs.randint(np.iinfo(np.int32).max))
+
+
 class GaussianHMM:
-    """hmmlearn-shaped diagonal-Gaussian HMM (every state emits) on the HIP kernels."""
+    """hmmlearn-shaped diagonal-Gaussian HMM (every state emits) on the HIP kernels.
+
+    ``fit`` first initialises what ``init_params`` names — or what is not set yet — the way hmmlearn's ``_init`` does
+    (restated from knowledge of hmmlearn 0.3.x, the reference's pinned version, like SURVEY §9.3), with
+    ``rs = check_random_state(random_state)`` and S = ``n_components``:
+
+    * ``s``  ``startprob_ = rs.dirichlet(np.full(S, 1/S))``
+    * ``t``  ``transmat_ = rs.dirichlet(np.full(S, 1/S), size=S)``  (hmmlearn <= 0.2.7 set both to the uniform value)
+    * ``m``  ``means_`` = the centres of a k-means with S clusters and ``n_init=10`` over all frames of the model, on the
+      device (:func:`sapr_amd.kmeans.kmeans`), seeded by ONE integer drawn from ``rs`` after the ``s`` / ``t`` draws —
+      a model's initialisation depends only on its own ``random_state`` and data, not on what else is trained with it
+    * ``c``  ``covars_ = tile(diag(np.cov(X.T)) + min_covar, (S, 1))``: the ddof = 1 column variance about the column
+      mean, two K = 1 steps of the same kernel
+
+    Not scikit-learn's random stream or seeding, and an empty cluster keeps its centre (``kmeans.py``, DESIGN.md §8);
+    hmmlearn's warning about fewer data points than free parameters is not reproduced.  A preset attribute whose
+    letter is in ``init_params`` is overwritten, with a warning; ``init_params=""`` trains from the preset values."""
 
     def __init__(self, n_components=1, covariance_type="diag", min_covar=1e-3, startprob_prior=1.0,
                  transmat_prior=1.0, means_prior=0, means_weight=0, covars_prior=1e-2, covars_weight=1,
@@ -197,6 +230,18 @@ class GaussianHMM:
         if covars.ndim != 2 or np.any(covars <= 0):
             raise ValueError("'diag' covars must be a positive (n_components, n_features) array")
         self._covars_ = covars
+
+    # ---- initialisation (hmmlearn _needs_init / _init) ---------------------------------------
+    _INIT_ATTRS = (("s", "startprob_"), ("t", "transmat_"), ("m", "means_"), ("c", "covars_"))
+
+    def _needs_init(self, code, name):
+        if code in self.init_params:
+            if hasattr(self, name):
+                logging.getLogger(__name__).warning(
+                    "Even though the %r attribute is set, it will be overwritten during initialization because "
+                    "'init_params' contains %r", name, code)
+            return True
+        return not hasattr(self, name)
 
     # ---- validation (hmmlearn _check) -----------------------------------------------------
     def _check(self):
@@ -315,25 +360,36 @@ class GaussianHMM:
 
 def fit_models(models: List[GaussianHMM], data) -> None:
     """Train several word models together: ``data[w] = (X_w, lengths_w)`` (this rank's shard).
-    One E-step launch sequence covers every word's utterances; converged models stop updating."""
+    One E-step launch sequence covers every word's utterances; converged models stop updating.  Models that need it
+    (``GaussianHMM._needs_init``) are initialised first, all of them in one batched k-means on the device."""
     import torch
     from . import dist as sdist
     from .trellis import DiagModelPack, EStep, FeatureBatch
     dev = _lib.require_gpu()
     W = len(models)
-    for m in models:
-        m._check()
-        m.monitor_ = ConvergenceMonitor(m.tol, m.n_iter, m.verbose)
-    S, D = models[0].n_components, models[0].n_features
-    feats, lengths, utt_model = [], [], []
+    needs = [[code for code, name in GaussianHMM._INIT_ATTRS if m._needs_init(code, name)] for m in models]
+    if not any(needs):
+        for m in models:
+            m._check()
+    feats, lengths, utt_model, frames = [], [], [], []
     for w, (X, ln) in enumerate(data):
         X = _features_f32(X)
         if X.shape[0]:
             feats.append(X)
+        frames.append(X.shape[0])
         lengths += list(ln)
         utt_model += [w] * len(ln)
+    D = models[0].n_features if not any(needs) else int(np.asarray(data[0][0]).shape[1])
     packed = np.concatenate(feats, axis=0) if feats else np.zeros((0, D), np.float32)
-    batch = FeatureBatch.from_packed(torch.from_numpy(packed).to(dev), np.asarray(lengths, dtype=np.int64))
+    dfeats = torch.from_numpy(packed).to(dev)
+    if any(needs):
+        _init_models(models, needs, dfeats, frames)
+        for m in models:
+            m._check()
+    for m in models:
+        m.monitor_ = ConvergenceMonitor(m.tol, m.n_iter, m.verbose)
+    S = models[0].n_components
+    batch = FeatureBatch.from_packed(dfeats, np.asarray(lengths, dtype=np.int64))
     estep = EStep(batch, np.asarray(utt_model), W, S)
     active = [True] * W
     max_iter = max(m.n_iter for m in models)
@@ -377,6 +433,63 @@ def fit_models(models: List[GaussianHMM], data) -> None:
             m.monitor_.report(st["logprob"])
             if m.monitor_.converged:
                 active[w] = False
+
+
+def _init_models(models, needs, dfeats, frames) -> None:
+    """hmmlearn's ``_init`` for the models whose ``needs[w]`` is not empty (see :class:`GaussianHMM`).  ``dfeats``: the
+    packed device features of ALL models, model after model, ``frames[w]`` of them per model (this rank's shard).  The
+    models that need means share ONE batched k-means (G = their number); the column moments behind the covariances and
+    the k-means threshold come from the same kernel.  The random draws run model by model in list order, each from the
+    model's own ``random_state``."""
+    from . import kmeans as km
+    sel = [w for w, n in enumerate(needs) if "m" in n or "c" in n]
+    seeds = {}
+    for w, m in enumerate(models):
+        if not needs[w]:
+            continue
+        S = m.n_components
+        rs = check_random_state(m.random_state)
+        if "s" in needs[w]:
+            m.startprob_ = rs.dirichlet(np.full(S, 1.0 / S))
+        if "t" in needs[w]:
+            m.transmat_ = rs.dirichlet(np.full(S, 1.0 / S), size=S)
+        if "m" in needs[w]:
+            seeds[w] = kmeans_seed(rs)
+    if not sel:
+        return
+    # the selected models' frames as the groups of one layout (the packed tensor itself when every model is selected)
+    off = np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
+    if len(sel) == len(models):
+        feats_sel = dfeats
+    else:
+        import torch
+        feats_sel = torch.cat([dfeats[off[w]:off[w + 1]] for w in sel], dim=0)
+    glen = [frames[w] for w in sel]
+    stepper = km.Stepper(feats_sel, km.FrameTiles.build(glen, dfeats.device))
+    count, mean, sqdev = km.column_moments(stepper)
+    for g, w in enumerate(sel):
+        m = models[w]
+        if "c" in needs[w]:
+            if count[g] < 2:
+                raise ValueError(f"covariance initialisation needs at least 2 frames, model {w} has {int(count[g])}")
+            m._covars_ = np.tile(sqdev[g] / (count[g] - 1) + m.min_covar, (m.n_components, 1))
+    msel = [w for w in sel if "m" in needs[w]]
+    if not msel:
+        return
+    if len({models[w].n_components for w in msel}) != 1:
+        raise ValueError("models initialised together must share n_components")
+    at = [sel.index(w) for w in msel]
+    if len(msel) == len(sel):
+        feats_m, moments = feats_sel, (count, mean, sqdev)
+    else:
+        import torch
+        goff = np.concatenate([[0], np.cumsum(glen)]).astype(np.int64)
+        feats_m = torch.cat([feats_sel[goff[g]:goff[g + 1]] for g in at], dim=0)
+        moments = (count[at], mean[at], sqdev[at])
+    centers, _, _, _ = km.kmeans(feats_m, [frames[w] for w in msel], models[msel[0]].n_components, n_init=10,
+                                 seeds=[seeds[w] for w in msel], moments=moments)
+    for g, w in enumerate(msel):
+        models[w].means_ = centers[g]
 
 
 class HMMLearnModel:

@@ -14,6 +14,8 @@ on the current stream; there is no CPU implementation (calling an op on CPU tens
                                                               topology)
     loglik_n, post, path = torch.ops.sapr.hmm_state_posteriors(feat, offsets, slot_utt, tile_model, pack.blob, W, S, D,
                                                                max_T, topology, n_out_states)
+    stats, labels = torch.ops.sapr.kmeans_step(feat, tiles.tile_begin, tiles.tile_len, tiles.tile_group,
+                                               tiles.group_tile_off, centres, want_labels)
     # the reference's from-scratch HMM (custom_hmm.py), model arrays as custom_hmm.model_arrays() prepares them
     gamma, utt = torch.ops.sapr.custom_estep(feat, offsets, means, inv, cterm, A, logA)
     scores, paths, word, best, best_path = torch.ops.sapr.custom_decode(feat, offsets, means, inv, cterm, A, logA,
@@ -22,7 +24,8 @@ on the current stream; there is no CPU implementation (calling an op on CPU tens
 Reference call sites replaced: ``librosa.feature.mfcc`` (mfcc_extract.py:15-23), ``GaussianHMM.decode`` over the
 vocabulary + arg-max (decoder.py:35-49), the E-step of ``GaussianHMM.fit`` (hmmlearn_hmm.py:103), ``GaussianHMM.score``
 (hmmlearn_hmm.py:104) over the model loop of decoder.py:42, ``GaussianHMM.score_samples`` / ``predict_proba`` /
-``decode(algorithm="map")`` (hmmlearn's inference API; the reference does not call them), the E-step of
+``decode(algorithm="map")`` (hmmlearn's inference API; the reference does not call them), the Lloyd step of the
+k-means inside hmmlearn's ``GaussianHMM._init`` (what ``GaussianHMM(...).fit`` runs first without a flat start), the E-step of
 ``HMM.baum_welch`` (custom_hmm.py:422-439) and ``HMM.decode`` over the vocabulary (custom_hmm.py:462-514,
 decoder.py:42-47).
 """
@@ -45,6 +48,8 @@ _LIB.define("hmm_forward_scores(Tensor feats, Tensor offsets, Tensor order, Tens
             "int topology) -> (Tensor, Tensor, Tensor)")
 _LIB.define("hmm_state_posteriors(Tensor feats, Tensor offsets, Tensor slot_utt, Tensor tile_model, Tensor pack, int W, "
             "int S, int D, int max_T, int topology, int n_out_states) -> (Tensor, Tensor, Tensor)")
+_LIB.define("kmeans_step(Tensor feats, Tensor tile_begin, Tensor tile_len, Tensor tile_group, Tensor group_tile_off, "
+            "Tensor centres, bool want_labels) -> (Tensor, Tensor)")
 _LIB.define("custom_estep(Tensor feats, Tensor offsets, Tensor means, Tensor inv, Tensor cterm, Tensor A, Tensor logA) "
             "-> (Tensor, Tensor)")
 _LIB.define("custom_decode(Tensor feats, Tensor offsets, Tensor means, Tensor inv, Tensor cterm, Tensor A, Tensor logA, "
@@ -155,6 +160,31 @@ def _hmm_state_posteriors(feats, offsets, slot_utt, tile_model, pack, W, S, D, m
     return loglik, post, path
 
 
+def _kmeans_step(feats, tile_begin, tile_len, tile_group, group_tile_off, centres, want_labels):
+    """One Lloyd step at the kernel's own widths (D in {13, 39}): stats[G][R][K][2D+1] = {count, sum_x[D], sqdev[D]} and
+    labels[R][total_frames] (an empty tensor without ``want_labels``)."""
+    _check_dev(feats, tile_begin, tile_len, tile_group, group_tile_off, centres)
+    if feats.dtype != torch.float32 or centres.dtype != torch.float64 or centres.dim() != 4 \
+            or centres.shape[3] != feats.shape[1]:
+        raise ValueError("feats must be float32 [total_frames, D] and centres float64 [G, R, K, D]")
+    lib = _lib.load()
+    dev, total, n_tiles = feats.device, feats.shape[0], tile_begin.numel()
+    G, R, K, D = centres.shape
+    if group_tile_off.numel() != G + 1:
+        raise ValueError("group_tile_off must hold G + 1 entries")
+    nb = C.c_size_t(0)
+    _lib.check(lib.sapr_kmeans_workspace_bytes(n_tiles, R, K, D, C.byref(nb)), "sapr_kmeans_workspace_bytes")
+    ws = torch.empty(max(int(nb.value), 1), dtype=torch.uint8, device=dev)
+    stats = torch.empty((G, R, K, 2 * D + 1), dtype=torch.float64, device=dev)
+    labels = torch.empty((R, total) if want_labels else (0,), dtype=torch.int32, device=dev)
+    _lib.check(lib.sapr_kmeans_step(_lib.ptr(feats), total, _lib.ptr(tile_begin), _lib.ptr(tile_len),
+                                    _lib.ptr(tile_group), _lib.ptr(group_tile_off), n_tiles, G, R, K, D,
+                                    _lib.ptr(centres), _lib.ptr(ws), int(nb.value), _lib.ptr(stats),
+                                    _lib.ptr(labels) if want_labels else None, _lib.current_stream()),
+               "sapr_kmeans_step")
+    return stats, labels
+
+
 def _custom_shapes(feats, means, inv, cterm, A, logA):
     W, S, D = means.shape
     if feats.dim() != 2 or feats.shape[1] != D or feats.dtype != torch.float32:
@@ -208,5 +238,6 @@ def _custom_decode(feats, offsets, means, inv, cterm, A, logA, num_states, Tq):
 for _name, _fn in (("pcm16_to_f32", _pcm16_to_f32), ("mfcc_batch", _mfcc_batch),
                    ("viterbi_decode_best", _viterbi_decode_best), ("hmm_estep", _hmm_estep),
                    ("hmm_forward_scores", _hmm_forward_scores), ("hmm_state_posteriors", _hmm_state_posteriors),
+                   ("kmeans_step", _kmeans_step),
                    ("custom_estep", _custom_estep), ("custom_decode", _custom_decode)):
     _LIB.impl(_name, _fn, "CUDA")
