@@ -261,6 +261,64 @@ int sapr_kmeans_step(const float *feats /* [total_frames][D] */, int64_t total_f
                      double *stats /* [G][R][K][2*D+1] */, int32_t *labels /* [R][total_frames], may be NULL */,
                      void *stream);
 
+/* Gaussian-mixture HMMs (hmmlearn's GMMHMM, diagonal covariances): S states, M components per state, D features.
+ *   lc[t,s,m] = log w[s,m] - (D log 2 pi + sum_d log var[s,m,d] + sum_d (x[t,d] - mu[s,m,d])^2 / var[s,m,d]) / 2
+ *   logb[t,s] = logsumexp_m lc[t,s,m]   (log 0 = -inf flows through: a zero weight switches a component off)
+ * and over logb the log-domain recursions of _hmmc.cpp forward_log / backward_log / viterbi with any pattern of zeros
+ * in the transition matrix (a -inf log transition is skipped), gamma_t(s) = softmax_s(fwd + bwd) and the
+ * responsibilities r[t,s,m] = gamma_t(s) exp(lc[t,s,m] - logb[t,s]).  CPU restatement: tests/_gmmhmm_ref.py.
+ *
+ * Layout: the tile layout of sapr_estep_diag (256 slots per tile, one model per tile: slot_utt, tile_model,
+ * model_tile_off).  S in 1..18, M in 1..8, D in 1..39 are run-time values; the kernels are instantiated for the padded
+ * shapes SP in {4, 10, 18}, MP in {1, 2, 4, 8}, DP in {13, 26, 39} that sapr_gmm_pack_layout returns, and the W
+ * models' parameters arrive in that padded form, `pack` = W blocks of doubles_per_model float64 values each:
+ *   log_start[SP]             log startprob; -inf for a padded state
+ *   log_trans[SP][SP]         log transmat;  -inf in the rows and columns of padded states
+ *   log_transT[SP][SP]        its transpose
+ *   cc[SP][MP]                log w - (D log 2 pi + sum_d log var) / 2; -inf for a padded component or state
+ *   prm[SP][DP][MP][2]        {mean, -1 / (2 var)}; {0, 0} for padded states, components and dimensions
+ * (gmm_hmm.py pack_models builds it).  feats[total_frames][D] keeps its own row stride D.
+ *
+ * sapr_gmm_estep_diag — one E-step:
+ *   loglik[n_utts]            forward log-likelihood; -inf for an utterance without frames
+ *   stats[W][width]           optional; width = sapr_gmm_stats_width = 2 + S + S*S + S + S*M + 2*S*M*D, per model and
+ *                             summed over its utterances: n_seq, sum loglik, start[S] = sum gamma_0, trans[S][S] = sum_t
+ *                             xi_t, post[S] = sum gamma, post_mix[S][M] = sum r, obs[S][M][D] = sum r x,
+ *                             obs2[S][M][D] = sum r x^2 with x^2 rounded to float32 first (as numpy squares a float32
+ *                             feature array).  An utterance without frames contributes nothing (n_seq included).
+ *                             model_tile_off is read only when stats is given
+ *   post[total_frames][S]     optional: gamma, hmmlearn's (n_samples, n_components) layout, ragged along offsets
+ *   path[total_frames]        optional: argmax_s gamma_t(s); equal values: the lowest state; a row holding NaN: the
+ *                             index of its first NaN (np.argmax)
+ * sapr_gmm_viterbi_diag — logprob[n_utts] (-inf without frames) and path[total_frames], hmmlearn's viterbi: the first
+ *   maximum of the last row, then argmax_i (lattice[t][i] + log a[i][next]), ties to the first maximum.
+ *
+ * Launches: frame-parallel emission (logb into the workspace), one lane per utterance for the recursions, frame-
+ * parallel accumulation of post_mix / obs / obs2 into four partial rows per tile, then fixed-order reductions (the 256
+ * slots of a tile, then the model's tiles in order).  No floating-point atomics: results are bit-identical run to run,
+ * a model's statistics do not depend on which other models share the launch, and loglik / post / path of an utterance
+ * are a function of its own (features, model) pair.  Non-finite values propagate; nothing is repaired.  Workspace:
+ * sapr_gmm_workspace_bytes() = 8 * (2 * max(total_frames, 1) * SP + (2 + S + S*S + S) * 257 * max(n_tiles, 1)
+ * + 4 * max(n_tiles, 1) * S*M*(2*D+1)), the same for both entry points.  max_T must not be smaller than the longest
+ * utterance (an utterance that is longer, or whose offsets leave the batch, is served as empty) and is at most 65535.
+ * Bad sizes, NULL required pointers and a workspace that is too small return SAPR_ERR_ARG before anything is launched;
+ * S > 18, M > 8 or D > 39 return SAPR_ERR_UNSUPPORTED (from the size functions too); n_tiles == 0 returns 0 after
+ * these checks without touching any pointer. */
+int sapr_gmm_stats_width(int32_t S, int32_t M, int32_t D, int32_t *width);
+int sapr_gmm_pack_layout(int32_t S, int32_t M, int32_t D, int32_t *SP, int32_t *MP, int32_t *DP,
+                         size_t *doubles_per_model);
+int sapr_gmm_workspace_bytes(int64_t total_frames, int64_t n_tiles, int32_t S, int32_t M, int32_t D, size_t *bytes);
+int sapr_gmm_estep_diag(const float *feats, const int64_t *offsets, const int32_t *slot_utt,
+                        const int32_t *tile_model, const int32_t *model_tile_off /* [W+1]; may be NULL without stats */,
+                        int64_t n_utts, int64_t total_frames, int64_t n_tiles, int32_t D, int32_t max_T,
+                        const double *pack, int32_t W, int32_t S, int32_t M, void *workspace, size_t workspace_bytes,
+                        double *loglik, double *stats /* may be NULL */, double *post /* may be NULL */,
+                        int32_t *path /* may be NULL */, void *stream);
+int sapr_gmm_viterbi_diag(const float *feats, const int64_t *offsets, const int32_t *slot_utt,
+                          const int32_t *tile_model, int64_t n_utts, int64_t total_frames, int64_t n_tiles, int32_t D,
+                          int32_t max_T, const double *pack, int32_t W, int32_t S, int32_t M, void *workspace,
+                          size_t workspace_bytes, double *logprob, int32_t *path, void *stream);
+
 /* Flat start of HMMLearnModel (hmmlearn_hmm.py:83-94: np.mean / np.var over axis 0 of the concatenated float32
  * features): numpy adds row after row in float32, so each column is one sequential float32 chain — reproduced
  * bit for bit.  center == NULL: out[d] = sum_r x[r][d]; else out[d] = sum_r RN32(RN32(x[r][d] - center[d])^2).

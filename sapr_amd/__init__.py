@@ -7,8 +7,17 @@ behaviour) over hand-written HIP kernels in ``libsapr_hip.so``:
 * ``sapr_amd.custom_hmm``    ↔ assignment2/custom_hmm.py
 * ``sapr_amd.hmmlearn_hmm``  ↔ assignment2/hmmlearn_hmm.py (+ a GaussianHMM-shaped model object)
 * ``sapr_amd.decoder``       ↔ assignment2/decoder.py
+* ``sapr_amd.gmm_hmm``       hmmlearn's other Gaussian model class, ``GMMHMM`` (no counterpart in the reference)
 
 ``sapr_amd/compat`` holds same-named top-level shims so the reference's ``train.py`` /
 ``eval.py`` / tests import the drop-in unmodified.
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    """``sapr_amd.GMMHMM`` / ``sapr_amd.fit_gmm_models`` (resolved on first use: importing the package stays light)."""
+    if name in ("GMMHMM", "fit_gmm_models"):
+        from . import gmm_hmm
+        return getattr(gmm_hmm, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

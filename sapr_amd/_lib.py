@@ -59,6 +59,16 @@ SIGNATURES = {
     "sapr_kmeans_workspace_bytes": (c_int, [c_int64, c_int32, c_int32, c_int32, C.POINTER(c_size_t)]),
     "sapr_kmeans_step": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32,
                                  c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "sapr_gmm_stats_width": (c_int, [c_int32, c_int32, c_int32, C.POINTER(c_int32)]),
+    "sapr_gmm_pack_layout": (c_int, [c_int32, c_int32, c_int32, C.POINTER(c_int32), C.POINTER(c_int32),
+                                     C.POINTER(c_int32), C.POINTER(c_size_t)]),
+    "sapr_gmm_workspace_bytes": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int32, C.POINTER(c_size_t)]),
+    "sapr_gmm_estep_diag": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,
+                                    c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_size_t,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sapr_gmm_viterbi_diag": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32,
+                                      c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_size_t, c_void_p,
+                                      c_void_p, c_void_p]),
     "sapr_colsum_f32": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     "sapr_custom_estep": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32] + [c_void_p] * 5
                           + [c_int64] + [c_void_p] * 6 + [c_void_p]),
