@@ -319,6 +319,32 @@ int sapr_gmm_viterbi_diag(const float *feats, const int64_t *offsets, const int3
                           int32_t max_T, const double *pack, int32_t W, int32_t S, int32_t M, void *workspace,
                           size_t workspace_bytes, double *logprob, int32_t *path, void *stream);
 
+/* Scoring over the vocabulary for the Gaussian-mixture HMMs: every utterance under EVERY word model in one launch,
+ * where the two entry points above evaluate an utterance under the one model of its tile — what sapr_forward_vocab is
+ * to sapr_forward_diag.  `pack` is the operand block of sapr_gmm_pack_layout (W models, nothing new is packed); `order`
+ * (optional, may be NULL) is the length-sorted permutation of sapr_forward_vocab.  No tile layout and no workspace: the
+ * recursion's state lives in registers, no lattice and no logb reach memory.
+ *   score[n_utts][W]      SAPR_GMM_VOCAB_FORWARD: the forward log-likelihood of utterance u under model w — the bits
+ *                         sapr_gmm_estep_diag returns as loglik for that pair; SAPR_GMM_VOCAB_VITERBI: the viterbi
+ *                         log-probability — the bits of sapr_gmm_viterbi_diag's logprob.  -inf for an utterance without
+ *                         frames, for one longer than max_T and for one whose offsets leave the batch (served as empty)
+ *   best_word[n_utts]     optional: first strict maximum of the row in model order, starting from -inf
+ *                         (decoder.py:42-47's rule); -1 when no score beats -inf
+ *   word_post[n_utts][W]  optional, forward mode only: exp(score - logsumexp_w score), the posterior over the words
+ *                         under a uniform prior; NaN where the row's maximum is -inf or a score is NaN
+ * Non-finite values propagate; nothing is repaired.  Every score is a function of its (utterance, model) pair alone:
+ * equal models give equal bits, and the launch is deterministic whatever `order` is.  Bad sizes, NULL required
+ * pointers, an unknown mode and a word_post in Viterbi mode (a soft-max of path scores is no posterior) return
+ * SAPR_ERR_ARG, S > 18, M > 8 or D > 39 SAPR_ERR_UNSUPPORTED, both before anything is launched and before any HIP
+ * call; n_utts == 0 returns 0 after these checks without touching any pointer. */
+#define SAPR_GMM_VOCAB_FORWARD 0
+#define SAPR_GMM_VOCAB_VITERBI 1
+int sapr_gmm_vocab_diag(const float *feats, const int64_t *offsets, const int32_t *order /* may be NULL */,
+                        int64_t n_utts, int64_t total_frames, int32_t D, int32_t max_T, const double *pack, int32_t W,
+                        int32_t S, int32_t M, int32_t mode, double *score /* [n_utts][W] */,
+                        int32_t *best_word /* [n_utts], may be NULL */,
+                        double *word_post /* [n_utts][W], may be NULL; FORWARD only */, void *stream);
+
 /* Flat start of HMMLearnModel (hmmlearn_hmm.py:83-94: np.mean / np.var over axis 0 of the concatenated float32
  * features): numpy adds row after row in float32, so each column is one sequential float32 chain — reproduced
  * bit for bit.  center == NULL: out[d] = sum_r x[r][d]; else out[d] = sum_r RN32(RN32(x[r][d] - center[d])^2).

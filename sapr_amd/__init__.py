@@ -16,8 +16,9 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    """``sapr_amd.GMMHMM`` / ``sapr_amd.fit_gmm_models`` (resolved on first use: importing the package stays light)."""
-    if name in ("GMMHMM", "fit_gmm_models"):
+    """``sapr_amd.GMMHMM`` / ``sapr_amd.fit_gmm_models`` / ``sapr_amd.vocab_scores`` (resolved on first use: importing
+    the package stays light)."""
+    if name in ("GMMHMM", "fit_gmm_models", "vocab_scores"):
         from . import gmm_hmm
         return getattr(gmm_hmm, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -39,23 +39,12 @@ namespace sapr {
 namespace {
 
 #include "lse_ops.h"
+#include "gmm_ops.h"
 
 constexpr int kBlock = 256;   // slots per tile
 constexpr int kSub = 4;       // partial rows of the observation sums per tile
 constexpr int kChunk = 64;    // flat frames per chunk of the accumulation pass
-constexpr int kMaxS = 18, kMaxM = 8, kMaxD = 39;
 constexpr int kMaxT = 65535;  // (the emission grid's second dimension)
-
-constexpr int sp_of(int S) { return S <= 4 ? 4 : (S <= 10 ? 10 : 18); }
-constexpr int mp_of(int M) { return M <= 1 ? 1 : (M <= 2 ? 2 : (M <= 4 ? 4 : 8)); }
-constexpr int dp_of(int D) { return D <= 13 ? 13 : (D <= 26 ? 26 : 39); }
-
-// per model: log_start[SP], log_trans[SP][SP], its transpose [SP][SP] (the forward recursion walks columns), cc[SP][MP],
-// prm[SP][DP][MP][2] = {mean, -1 / (2 var)}
-constexpr size_t model_doubles(int SP, int MP, int DP) {
-  return static_cast<size_t>(SP) + 2 * static_cast<size_t>(SP) * SP + static_cast<size_t>(SP) * MP +
-         static_cast<size_t>(SP) * DP * MP * 2;
-}
 
 constexpr int stats_k1(int S) { return 2 + S + S * S + S; }                 // n_seq, loglik, start, trans, post
 constexpr int stats_p(int S, int M, int D) { return S * M * (2 * D + 1); }  // post_mix, obs, obs2
@@ -89,23 +78,8 @@ struct Batch {
 };
 
 // the utterance of a slot: T = 0 for an empty slot and for anything that points outside the batch (never followed)
-struct Span {
-  int64_t u, beg;
-  int T;
-};
-
 __device__ __forceinline__ Span slot_span(const Batch &b, int64_t slot, bool tile_ok) {
-  Span s{-1, 0, 0};
-  const int64_t u = b.slot_utt[slot];
-  if (tile_ok && u >= 0 && u < b.n_utts) {
-    const int64_t beg = b.offsets[u], end = b.offsets[u + 1];
-    s.u = u;
-    if (beg >= 0 && end >= beg && end <= b.total_frames && end - beg <= b.max_T) {
-      s.beg = beg;
-      s.T = static_cast<int>(end - beg);
-    }
-  }
-  return s;
+  return utt_span(b.offsets, b.slot_utt[slot], tile_ok, b.n_utts, b.total_frames, b.max_T);
 }
 
 // A tile's utterances end to end: s_cum[i] = frames of the slots before slot i (s_cum[256] = all), s_beg[i] = first
@@ -145,32 +119,6 @@ __device__ __forceinline__ int find_slot(const int32_t *s_cum, int flat) {
   return lo;
 }
 
-template <int DP>
-__device__ __forceinline__ void load_frame_pad(const float *__restrict__ xp, int D, bool live, double (&x)[DP]) {
-#pragma unroll
-  for (int d = 0; d < DP; ++d) x[d] = (live && d < D) ? static_cast<double>(xp[d]) : 0.0;
-}
-
-// lc[m] = cc[m] + sum_d (x_d - mu_dm)^2 * (-1 / (2 var_dm)) for one state; p, cc wavefront-uniform
-template <int MP, int DP, int UNROLL = DP, class FX>
-__device__ __forceinline__ void mix_log_terms(FX x, const double *__restrict__ p, const double *__restrict__ cc,
-                                              double (&lc)[MP]) {
-  double acc[MP];
-#pragma unroll
-  for (int m = 0; m < MP; ++m) acc[m] = 0.0;
-#pragma unroll UNROLL
-  for (int d = 0; d < DP; ++d) {
-    const double xd = x(d);
-#pragma unroll
-    for (int m = 0; m < MP; ++m) {
-      const double diff = xd - p[(d * MP + m) * 2];
-      acc[m] = fma(diff * diff, p[(d * MP + m) * 2 + 1], acc[m]);
-    }
-  }
-#pragma unroll
-  for (int m = 0; m < MP; ++m) lc[m] = cc[m] + acc[m];
-}
-
 // -------------------------------------------------------------------------------------------
 // pass 1: logb[frame][SP]
 // -------------------------------------------------------------------------------------------
@@ -208,49 +156,6 @@ __global__ __launch_bounds__(kBlock) void gmm_emit_kernel(Batch b, const double 
 // -------------------------------------------------------------------------------------------
 // pass 2: the recursions, one lane per utterance, one wavefront per workgroup
 // -------------------------------------------------------------------------------------------
-__device__ __forceinline__ double quiet_nan() { return __builtin_nan(""); }
-
-// first maximum of the first n values; a NaN, once met, is kept (np.argmax)
-template <int S>
-__device__ __forceinline__ int argmax_first(const double (&g)[S], int n) {
-  int best = 0;
-  double bv = g[0];
-#pragma unroll
-  for (int s = 1; s < S; ++s) {
-    const bool take = s < n && !(bv != bv) && (g[s] > bv || g[s] != g[s]);
-    bv = take ? g[s] : bv;
-    best = take ? s : best;
-  }
-  return best;
-}
-
-// _hmmc.cpp logsumexp (VIT: the maximum) over the terms a(k) + c(k) whose c(k) — a wavefront-uniform log transition —
-// is above -inf; the skipped terms would add exp(-inf) = +0.0.  A NaN term gives NaN.
-template <int S, bool VIT, class FA, class FC>
-__device__ __forceinline__ double reduce_finite(FA a, FC c) {
-  double work[S];
-  double m = neg_inf();
-  bool nan = false;
-#pragma unroll
-  for (int k = 0; k < S; ++k) {
-    const double ck = c(k);
-    if (ck > neg_inf()) {
-      const double v = a(k) + ck;
-      work[k] = v;
-      nan = nan || v != v;
-      m = v > m ? v : m;
-    }
-  }
-  if (nan) return quiet_nan();
-  if (VIT || isinf(m)) return m;
-  double acc = 0.0;
-#pragma unroll
-  for (int k = 0; k < S; ++k) {
-    if (c(k) > neg_inf()) acc += exp_unit(work[k] - m);
-  }
-  return log(acc) + m;
-}
-
 template <int SP, bool VIT>
 __global__ __launch_bounds__(64) void gmm_forward_kernel(Batch b, const double *__restrict__ pack,
                                                          const double *__restrict__ logb,
@@ -681,13 +586,6 @@ int launch_trellis(bool vit, const Batch &b, const double *pack, int64_t n_tiles
   SAPR_LAUNCH((gmm_backward_kernel<SP>), grid, block, 0, stream, b, pack, ws.logb, ws.lat, loglik, ustat, post,
               path);
   SAPR_HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-int check_shape(int32_t S, int32_t M, int32_t D) {
-  if (S > kMaxS || M > kMaxM || D > kMaxD)
-    return fail(SAPR_ERR_UNSUPPORTED, "the mixture kernels serve S in 1..%d, M in 1..%d, D in 1..%d; got S=%d M=%d D=%d",
-                kMaxS, kMaxM, kMaxD, S, M, D);
   return 0;
 }
 

@@ -13,6 +13,11 @@ Beyond the reference's API the hmmlearn models can be scored by total (forward) 
 ``decode_batch`` classify by forward likelihood instead of by the Viterbi score.  ``state_posteriors`` returns the
 state posterior lattice of every utterance under the decoder's word (or a named one) through
 ``sapr_state_posteriors_diag``.
+
+``implementation="gmmhmm"`` serves Gaussian-mixture word models (``sapr_amd.GMMHMM`` pickles named
+``<word>_gmmhmm_<n_iter>.pkl`` under ``models_dir/gmmhmm/``) through the same API: one launch of
+``sapr_gmm_vocab_diag`` scores every utterance under every word model (Viterbi or forward mode, by ``scoring``), one
+``sapr_gmm_viterbi_diag`` over the utterances grouped by their best word walks the winner's path.
 """
 from __future__ import annotations
 
@@ -34,7 +39,8 @@ class Decoder:
         score, that path.  ``scoring="forward"``: the word with the highest forward log-likelihood (first strict maximum
         in load order), that log-likelihood, and the Viterbi path of that word; the path costs one all-vocabulary exact
         Viterbi pass (scores + back-pointers for every word, back-trace of the chosen one) on top of the forward launch,
-        not the pruned decoder's pass over the surviving words."""
+        not the pruned decoder's pass over the surviving words (``implementation="gmmhmm"``: one Viterbi launch under
+        the chosen word only, whatever the scoring)."""
         if scoring not in ("viterbi", "forward"):
             raise ValueError(f"scoring must be 'viterbi' or 'forward', got {scoring!r}")
         if scoring == "forward" and implementation == "custom":
@@ -47,6 +53,7 @@ class Decoder:
         self.models: Dict = {}
         self.vocab: List[str] = []
         self._pack = None
+        self._gmm = None
         self.load_models()
 
     def load_models(self) -> None:
@@ -72,6 +79,8 @@ class Decoder:
         words = list(self.models)
         if self.implementation == "custom":
             return self._decode_custom(feature_list)
+        if self.implementation == "gmmhmm":
+            return self._decode_gmm(*self._gmm_features(feature_list))
         from .trellis import FeatureBatch
         return self._decode_feature_batch(FeatureBatch.from_arrays(feature_list, layout="DT"))
 
@@ -80,6 +89,10 @@ class Decoder:
         sequence); same tuples as ``decode_batch``."""
         if self.implementation == "custom":
             return self._decode_custom(store.to_batch())
+        if self.implementation == "gmmhmm":
+            from .gmm_hmm import vocab_features
+            feats, _, _, lengths, _ = vocab_features(store.to_batch())
+            return self._decode_gmm(feats, lengths)
         return self._decode_feature_batch(store.to_batch())
 
     def _decode_custom(self, features) -> List[Tuple[str, float, object]]:
@@ -90,6 +103,70 @@ class Decoder:
         _, _, bw, bs, bp = decode_batch(self._model_list(), features, with_best=True)
         return [(words[w], float(sc), [int(x) for x in p]) if w >= 0 else (None, float("-inf"), None)
                 for w, sc, p in zip(bw, bs, bp)]
+
+    # ---- Gaussian-mixture word models ---------------------------------------------------------
+    def _gmm_pack(self):
+        """The vocabulary's operand block (``gmm_hmm.GmmPack``), padded to its largest model; built once."""
+        if self._gmm is None:
+            from .gmm_hmm import GmmPack
+            self._gmm = GmmPack.from_models(self._model_list())
+        return self._gmm
+
+    @staticmethod
+    def _gmm_features(feature_list):
+        """(D, T) arrays -> ``(device feats [total_frames, D] float32, host lengths)``, rows of the models' own width."""
+        import torch
+        if len(feature_list) == 0:
+            raise ValueError("empty utterance list")
+        mats = [np.ascontiguousarray(np.asarray(f).T, dtype=np.float32) for f in feature_list]
+        D = mats[0].shape[1]
+        if any(m.ndim != 2 or m.shape[1] != D for m in mats):
+            raise ValueError("all utterances must share the feature dimension")
+        lengths = np.asarray([m.shape[0] for m in mats], dtype=np.int64)
+        packed = np.concatenate(mats, axis=0) if lengths.sum() else np.zeros((0, D), np.float32)
+        return torch.from_numpy(packed).to(_lib.require_gpu()), lengths
+
+    def _decode_gmm(self, feats, lengths) -> List[Tuple[str, float, object]]:
+        """One launch over the vocabulary (Viterbi log-probabilities, or forward log-likelihoods with
+        ``scoring="forward"``) picks the word; one Viterbi launch over the utterances grouped by that word walks its
+        path.  The returned score is the vocabulary launch's (in Viterbi mode the second launch's ``logprob`` carries
+        the same bits)."""
+        from .gmm_hmm import GmmBatch, vocab_scores
+        words = list(self.models)
+        pack = self._gmm_pack()
+        vs = vocab_scores(feats, lengths, pack, mode=self.scoring)
+        bw = _lib.to_host(vs.best_word)[0].astype(np.int64)
+        # an utterance no model scores above -inf has no word (-1): model 0's path is walked and then dropped
+        _, path = GmmBatch(feats, lengths, np.maximum(bw, 0), pack.W, pack.S, pack.M).viterbi(pack)
+        score, path = _lib.to_host(vs.score, path)
+        offs = np.r_[0, np.cumsum(lengths)].tolist()
+        path = path.astype(np.int64)
+        return [(words[w], float(score[u, w]), path[lo:hi]) if w >= 0 else (None, float("-inf"), None)
+                for u, (w, lo, hi) in enumerate(zip(bw.tolist(), offs[:-1], offs[1:]))]
+
+    def _state_posteriors_gmm(self, feature_list, words) -> List[np.ndarray]:
+        from .gmm_hmm import GmmBatch, vocab_scores
+        pack = self._gmm_pack()
+        feats, lengths = self._gmm_features(feature_list)
+        if words is None:
+            vs = vocab_scores(feats, lengths, pack, mode="viterbi")
+            utt_model = np.maximum(_lib.to_host(vs.best_word)[0].astype(np.int64), 0)
+        else:
+            utt_model = self._named_models(words, len(lengths))
+        batch = GmmBatch(feats, lengths, utt_model, pack.W, pack.S, pack.M)
+        post = _lib.to_host(batch.estep(pack, want_stats=False, want_post=True)[2])[0].copy()
+        offs = np.r_[0, np.cumsum(lengths)].tolist()
+        return [post[lo:hi, :pack.n_states[w]] for w, lo, hi in zip(utt_model.tolist(), offs[:-1], offs[1:])]
+
+    def _named_models(self, words, n_utts) -> np.ndarray:
+        """Model index per utterance for the words named by the caller."""
+        vocab = list(self.models)
+        if len(words) != n_utts:
+            raise ValueError("one word per utterance")
+        unknown = sorted({w for w in words if w not in self.models})
+        if unknown:
+            raise ValueError(f"words not in vocabulary {vocab}: {unknown}")
+        return np.asarray([vocab.index(w) for w in words], dtype=np.int64)
 
     def _decode_feature_batch(self, batch) -> List[Tuple[str, float, object]]:
         from .trellis import DiagModelPack, viterbi_decode_best
@@ -128,6 +205,11 @@ class Decoder:
         if self.implementation == "custom":
             raise ValueError("forward scoring over the vocabulary needs implementation='hmmlearn': the from-scratch "
                              "model has no forward scorer over a vocabulary")
+        if self.implementation == "gmmhmm":
+            from .gmm_hmm import vocab_scores
+            from .trellis import ForwardScores
+            vs = vocab_scores(*self._gmm_features(feature_list), self._gmm_pack(), mode="forward", want_post=want_post)
+            return ForwardScores(vs.score, vs.best_word, vs.word_post)
         from .trellis import DiagModelPack, FeatureBatch, forward_scores
         if self._pack is None:
             self._pack = DiagModelPack.from_models(self._model_list())
@@ -170,8 +252,9 @@ class Decoder:
         if self.implementation == "custom":
             raise ValueError("state posteriors need implementation='hmmlearn': the from-scratch model has no posterior "
                              "kernel")
+        if self.implementation == "gmmhmm":
+            return self._state_posteriors_gmm(feature_list, words)
         from .trellis import DiagModelPack, FeatureBatch, state_posteriors, viterbi_decode_best
-        vocab = list(self.models)
         if self._pack is None:
             self._pack = DiagModelPack.from_models(self._model_list())
         batch = FeatureBatch.from_arrays(feature_list, layout="DT")
@@ -180,12 +263,7 @@ class Decoder:
             best_word, _, _ = viterbi_decode_best(batch, self._pack, tie=tie, sum_order=_lib.SUM_TVIEW)
             utt_model = np.maximum(_lib.to_host(best_word)[0].astype(np.int64), 0)
         else:
-            if len(words) != batch.n_utts:
-                raise ValueError("one word per utterance")
-            unknown = sorted({w for w in words if w not in self.models})
-            if unknown:
-                raise ValueError(f"words not in vocabulary {vocab}: {unknown}")
-            utt_model = np.asarray([vocab.index(w) for w in words], dtype=np.int64)
+            utt_model = self._named_models(words, batch.n_utts)
         res = state_posteriors(batch, self._pack, utt_model, want_path=False)
         post = _lib.to_host(res.post)[0].copy()  # (out of the pinned buffer)
         offs = np.r_[0, np.cumsum(batch.lengths)].tolist()

@@ -20,6 +20,7 @@ Anything else non-finite propagates; nothing is repaired.
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 from typing import List
 
 import numpy as np
@@ -143,6 +144,10 @@ class GmmBatch:
 
     def _pack(self, pack):
         torch = _torch()
+        if isinstance(pack, GmmPack):
+            if (pack.W, pack.S, pack.M, pack.D) != (self.W, self.S, self.M, self.D):
+                raise ValueError("the pack was built for another (W, S, M, D)")
+            return pack.device(self.dev)
         pack = np.ascontiguousarray(pack, dtype=np.float64)
         n = pack_layout(self.S, self.M, self.D)[3]
         if pack.shape != (self.W, n):
@@ -179,6 +184,117 @@ class GmmBatch:
             _lib.ptr(self.workspace), self.ws_bytes, _lib.ptr(logprob), _lib.ptr(path), _lib.current_stream()),
             "sapr_gmm_viterbi_diag")
         return logprob, path
+
+
+# ------------------------------------------------------------------------------------------
+# scoring over the vocabulary: every utterance under every word model in one launch
+# ------------------------------------------------------------------------------------------
+class GmmPack:
+    """A vocabulary's operand block ready for the kernels: ``data`` float64 ``[W, doubles_per_model]``
+    (:func:`pack_models`) with the shape it was packed for (W models, S kernel states = the largest model's, M
+    components, D features) and each model's own state count ``n_states``; the device copy is made once."""
+
+    def __init__(self, data, S, M, D, n_states=None):
+        self.data = np.ascontiguousarray(data, dtype=np.float64)
+        self.W, self.S, self.M, self.D = int(self.data.shape[0]), int(S), int(M), int(D)
+        n = pack_layout(self.S, self.M, self.D)[3]
+        if self.data.ndim != 2 or self.data.shape[1] != n:
+            raise ValueError(f"pack must be [W, {n}] (pack_models), got {self.data.shape}")
+        self.n_states = [self.S] * self.W if n_states is None else [int(k) for k in n_states]
+        self._dev = None
+
+    @staticmethod
+    def from_params(params) -> "GmmPack":
+        """``params``: W tuples as :func:`pack_models` takes them; padded to the largest S of the vocabulary."""
+        if len(params) == 0:
+            raise ValueError("empty vocabulary")
+        n_states = [int(np.asarray(p[0]).shape[0]) for p in params]
+        M, D = (int(k) for k in np.asarray(params[0][3]).shape[1:])
+        return GmmPack(pack_models(params, max(n_states)), max(n_states), M, D, n_states)
+
+    @staticmethod
+    def from_models(models) -> "GmmPack":
+        """A list of fitted :class:`GMMHMM` objects that share ``n_mix`` and the feature width."""
+        for m in models:
+            m._check()
+        return GmmPack.from_params([m._params() for m in models])
+
+    def device(self, dev):
+        torch = _torch()
+        if self._dev is None or self._dev.device != dev:
+            self._dev = torch.from_numpy(self.data).to(dev)
+        return self._dev
+
+
+@dataclass
+class VocabScores:
+    score: "object"      # [N, W] f64: forward log-likelihood or Viterbi log-probability under every word model
+    best_word: "object"  # [N] i32 (first strict maximum in model order; -1 if no score beats -inf)
+    word_post: "object"  # [N, W] f64 posterior over the words under a uniform prior (forward mode), or None
+
+
+VOCAB_MODES = {"forward": _lib.GMM_VOCAB_FORWARD, "viterbi": _lib.GMM_VOCAB_VITERBI}
+
+
+def vocab_features(batch_or_feats, lengths=None):
+    """The utterances of :func:`vocab_scores` on the device: ``(feats[total_frames, D] float32, offsets int64[N + 1],
+    order int32[N] | None, host lengths, max_T)``.  A ``trellis.FeatureBatch`` brings its length-sorted ``order`` (the
+    zero columns it appends up to the single-Gaussian kernels' widths are cut off again: the mixture kernels read rows
+    of the models' own width); host ``feats`` / ``lengths`` are uploaded and sorted here."""
+    torch = _torch()
+    if hasattr(batch_or_feats, "offsets") and hasattr(batch_or_feats, "order"):
+        b = batch_or_feats
+        feats = b.feats if b.D == b.D_model else b.feats[:, :b.D_model].contiguous()
+        return feats, b.offsets, b.order, np.asarray(b.lengths, dtype=np.int64), int(b.max_T)
+    if lengths is None:
+        raise ValueError("lengths are needed with a feature array")
+    dev = _lib.require_gpu()
+    feats = batch_or_feats
+    if not torch.is_tensor(feats):
+        feats = torch.from_numpy(_features_f32(feats))
+    feats = feats.to(dev)
+    if feats.dtype != torch.float32 or feats.dim() != 2 or not feats.is_contiguous():
+        raise ValueError("feats must be a contiguous float32 [total_frames, D] tensor")
+    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    if lengths.size and lengths.min() < 0:
+        raise ValueError("lengths must be >= 0")
+    offs = np.zeros(lengths.size + 1, dtype=np.int64)
+    np.cumsum(lengths, out=offs[1:])
+    if feats.shape[0] != offs[-1]:
+        raise ValueError("feats rows do not match sum(lengths)")
+    order = np.argsort(-lengths, kind="stable").astype(np.int32)
+    return (feats, torch.from_numpy(offs).to(dev), torch.from_numpy(order).to(dev), lengths,
+            int(lengths.max()) if lengths.size else 0)
+
+
+def vocab_scores(batch_or_feats, lengths, pack_or_models, mode="forward", want_post=False) -> VocabScores:
+    """Every utterance under EVERY word model in one launch of ``sapr_gmm_vocab_diag``: ``mode="forward"`` gives the
+    forward log-likelihoods (``GMMHMM.score`` per sequence), ``mode="viterbi"`` the Viterbi log-probabilities
+    (``GMMHMM.decode``'s), bit for bit what :class:`GmmBatch` returns for each (utterance, model) pair.  Device tensors;
+    no workspace.  ``batch_or_feats``: a ``trellis.FeatureBatch`` (``lengths`` is ignored) or host / device ``feats``
+    with host ``lengths``.  ``pack_or_models``: a :class:`GmmPack` or a list of :class:`GMMHMM` objects (padded to the
+    largest S of the vocabulary; M and D must match).  ``want_post`` (forward mode only): the posterior over the
+    words."""
+    torch = _torch()
+    if mode not in VOCAB_MODES:
+        raise ValueError(f"mode must be one of {sorted(VOCAB_MODES)}, got {mode!r}")
+    if want_post and mode != "forward":
+        raise ValueError("want_post needs mode='forward': a soft-max of path scores is not a posterior")
+    pack = pack_or_models if isinstance(pack_or_models, GmmPack) else GmmPack.from_models(list(pack_or_models))
+    lib = _lib.load()
+    feats, offsets, order, lengths, max_T = vocab_features(batch_or_feats, lengths)
+    if int(feats.shape[1]) != pack.D:
+        raise ValueError(f"the utterances have {int(feats.shape[1])} features, the models {pack.D}")
+    dev = feats.device
+    N, W = int(lengths.size), pack.W
+    score = torch.empty((N, W), dtype=torch.float64, device=dev)
+    best_word = torch.empty(N, dtype=torch.int32, device=dev)
+    word_post = torch.empty((N, W), dtype=torch.float64, device=dev) if want_post else None
+    _lib.check(lib.sapr_gmm_vocab_diag(_lib.ptr(feats), _lib.ptr(offsets), _lib.ptr(order), N, int(feats.shape[0]),
+                                       pack.D, max_T, _lib.ptr(pack.device(dev)), W, pack.S, pack.M, VOCAB_MODES[mode],
+                                       _lib.ptr(score), _lib.ptr(best_word), _lib.ptr(word_post),
+                                       _lib.current_stream()), "sapr_gmm_vocab_diag")
+    return VocabScores(score, best_word, word_post)
 
 
 # ------------------------------------------------------------------------------------------
