@@ -173,6 +173,9 @@ int sapr_viterbi_pruned_views(int64_t n_utts, int32_t W, int32_t max_T, void *wo
  *                      The first call on a batch copies the features into slot-major order inside the
  *                      workspace; later calls on the same batch and workspace may pass
  *                      fast_div | SAPR_ESTEP_STAGED to skip that copy.
+ * Non-finite features follow numpy's IEEE arithmetic in all entry points of this family, with and without fast_div:
+ * a NaN feature makes its utterance's loglik NaN, an infinite one makes it -inf (every log-density of the frame is
+ * -inf); the other utterances of the batch keep their bits, the word's summed log-prob and statistics do not.
  * ---------------------------------------------------------------------------------- */
 int sapr_fb_workspace_bytes(int64_t n_utts, int64_t n_tiles, int32_t S, int32_t D, int32_t max_T,
                             size_t *bytes);
@@ -194,7 +197,9 @@ int sapr_estep_diag(const float *feats, const int64_t *offsets, const int32_t *s
  * operands of the pack are read (SAPR_PACK_EXACT_ONLY packs work).
  *   loglik[n_utts][W]     log P(utterance | word model w); -inf for an utterance without frames
  *   best_word[n_utts]     optional: first strict maximum of the row in model order, starting from -inf
- *                         (decoder.py:42-47's rule on forward scores); -1 when no score beats -inf
+ *                         (decoder.py:42-47's rule on forward scores); -1 when no score beats -inf.  A NaN score
+ *                         is never a strict maximum: an utterance with a non-finite feature, whose scores are NaN
+ *                         (a NaN feature) or -inf (an infinite one) under every model, gets -1
  *   word_post[n_utts][W]  optional: exp(loglik - logsumexp_w loglik), the posterior over the words under a uniform
  *                         prior; NaN where the row's maximum is -inf or a score is NaN (nothing is repaired)
  * Log-densities are evaluated in the E-step's quick form ((x - mean)^2 * RN(1/var) accumulated by FMA): scores agree

@@ -255,6 +255,21 @@ __global__ __launch_bounds__(kBlock) void fb_forward_kernel(
       else
         load_frame<D>(p, dst);
     };
+    // An infinite feature makes a = (x - mean)^2 infinite, and the correction steps of the FMA division
+    // (emission.h quad_term) then form inf - inf = NaN where IEEE division — numpy, the exact-division build — gives
+    // inf and a log-density of -inf.  a is the same under every state, so a frame's log-densities turn NaN together:
+    // one compare per frame finds such a frame, and unless a feature of it IS NaN it gets numpy's -inf.
+    auto repair = [&](const XT (&x)[D], double (&b)[S]) {
+      if (b[0] != b[0]) {
+        bool nan_in = false;
+#pragma unroll
+        for (int d = 0; d < D; ++d) nan_in |= x[d] != x[d];
+        if (!nan_in) {
+#pragma unroll
+          for (int j = 0; j < S; ++j) b[j] = neg_inf();
+        }
+      }
+    };
     for (int t = 0; t < Tw; t += 2) {
       if (t < T) {
         const bool two = (t + 1) < T;
@@ -262,6 +277,8 @@ __global__ __launch_bounds__(kBlock) void fb_forward_kernel(
         load2(xp + static_cast<int64_t>(two ? t + 1 : t) * D, xb);
         double ba[S], bb[S];
         frame_log_densities2<D, S, false>(xa, xb, prm, gc, ba, bb);
+        repair(xa, ba);
+        repair(xb, bb);
         step(t, ba);
         if (two) step(t + 1, bb);
       }
