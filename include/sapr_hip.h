@@ -379,7 +379,11 @@ int sapr_colsum_f32(const float *x, int64_t n_rows, int32_t D, const float *cent
  * [max_T][S][lane_slots] with the utterance index fastest (coalesced; gamma then goes to the update_b
  * entry points with the same lane_slots).  In the lane_slots layout with xi == NULL (the batched training path) gamma
  * and utt_out are the outputs: E is filled, the alpha (unshifted) and beta lattices are scratch except for the
- * utterances whose backward half had to run in the reference's own order (custom.hip) */
+ * utterances whose backward half had to run in the reference's own order (custom.hip).
+ * An utterance too short to reach the exit state (T < S - 1) has NaN posteriors in EVERY state of every frame and NaN
+ * posterior sums, as in the reference (a soft-max over a row of -inf), and no transition counts; the batched path
+ * used to return exact zeros for the exit state's posteriors of such an utterance.  An utterance of 0 frames gets a
+ * zero utt_out row and nothing else. */
 int sapr_custom_estep(const float *feats, const int64_t *offsets, const int32_t *utt_model, int64_t n_utts,
                       int32_t D, int32_t S, int32_t W, const double *means, const double *inv,
                       const double *cterm, const double *A, const double *logA, int64_t lane_slots, double *E,

@@ -1067,11 +1067,14 @@ __global__ __launch_bounds__(kBlock, (S <= 10 && D <= 13) ? 2 : 1) void custom_e
   //     c0 <  -750   EVERY term underflows to exactly 0 (exp(x) = 0 below -745.2), the frame totals are 0, nothing is
   //                  renormalised: the utterance contributes posteriors but no transition counts (trained models
   //                  with densities >> 1, e.g. digital silence)
-  //     otherwise    (or NaN) some terms are denormal or gone: the reference's own operation order (pass 1)
+  //     otherwise    (or NaN, or -inf) some terms are denormal or gone: the reference's own operation order (pass 1)
   // The exit state's xi term is exp(-inf) = 0 in every mode, so the last step (all mass in the exit state) adds nothing.
   if constexpr (kFirst) {
     const double c0 = (prev[S - 1] - (ll + scale)) - scale;
-    const int mode = c0 >= -678.0 ? 0 : (c0 < -750.0 ? 1 : 2);
+    // c0 = -inf: the utterance is too short to reach the exit state.  The reference's posteriors are then NaN in
+    // every state of every row (softmax over a row of -inf), the exit state included, while the smoothing form keeps
+    // exact zeros there: such an utterance takes the reference's order too.
+    const int mode = c0 >= -678.0 ? 0 : ((c0 < -750.0 && c0 > neg_inf()) ? 1 : 2);
     if (mode == 2) {  // pass 1 takes this utterance again
       redo[atomicAdd(redo_count, 1)] = static_cast<int32_t>(u);
       return;
