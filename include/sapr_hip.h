@@ -324,6 +324,47 @@ int sapr_gmm_viterbi_diag(const float *feats, const int64_t *offsets, const int3
                           int32_t max_T, const double *pack, int32_t W, int32_t S, int32_t M, void *workspace,
                           size_t workspace_bytes, double *logprob, int32_t *path, void *stream);
 
+/* Full covariances (hmmlearn's GaussianHMM, covariance_type "full"; a "tied" model is packed as S copies of its one
+ * matrix): S states, D features, one Gaussian per state,
+ *   logb[t,s] = c_s - 1/2 sum_i (sum_{j<=i} Winv_s[i][j] (x[t,j] - mu_s[j]))^2
+ * with Sigma_s = L_s L_s^T, Winv_s = L_s^-1 (lower triangular, computed by the host: nothing is factorised on the
+ * device) and c_s = -(D log 2 pi + log|Sigma_s|) / 2.  Over logb run the recursions, posteriors, decoders, xi sums and
+ * reductions of the mixture entry points above, unchanged; the tile layout, the arguments, the rules on ties, empty
+ * utterances, non-finite values and determinism are theirs.  CPU restatement: tests/_fullcov_ref.py.
+ *
+ * `pack` = W blocks of doubles_per_model float64 values (sapr_full_pack_layout; SP in {4, 10, 18}, DP in {13, 26, 39}):
+ *   log_start[SP], log_trans[SP][SP], log_transT[SP][SP]     as in the mixture pack, at the same offsets
+ *   c[SP]                     -inf for a padded state
+ *   mu[SP][DP]                0 for padded states and dimensions
+ *   Winv[SP][DP][DP]          row-major, 0 above the diagonal and for padded states and dimensions
+ * (full_cov.py pack_models builds it).
+ *
+ * sapr_full_estep — loglik[n_utts], optional post / path as sapr_gmm_estep_diag gives them, and optional
+ *   stats[W][width]           width = sapr_full_stats_width = 2 + S + S*S + S + S*D + S*D*D: n_seq, sum loglik, start[S],
+ *                             trans[S][S], post[S], obs[S][D] = sum_t gamma_t(s) x_t, oo[S][D][D] = sum_t gamma_t(s) x_t
+ *                             x_t^T with x promoted to float64 before the product.  Every oo[s] is exactly symmetric (the
+ *                             tiles on or above the diagonal are computed on the float64 matrix cores and written to both
+ *                             halves).
+ * sapr_full_viterbi — logprob[n_utts] and path[total_frames] as sapr_gmm_viterbi_diag gives them.
+ *
+ * Workspace: sapr_full_workspace_bytes() = 8 * (2 * max(total_frames, 1) * SP + (2 + S + S*S + S) * 257 * max(n_tiles, 1)
+ * + 4 * max(n_tiles, 1) * S*D*(D+1)), the same for both entry points: the four partial rows of obs / oo cost
+ * 4 * S*D*(D+1) * 8 bytes per tile, about 0.9 MB at (S, D) = (18, 39).  Bad sizes, NULL required pointers and a
+ * workspace that is too small return SAPR_ERR_ARG before anything is launched; S > 18 or D > 39 return
+ * SAPR_ERR_UNSUPPORTED (from the size functions too); n_tiles == 0 returns 0 after these checks. */
+int sapr_full_pack_layout(int32_t S, int32_t D, int32_t *SP, int32_t *DP, size_t *doubles_per_model);
+int sapr_full_stats_width(int32_t S, int32_t D, int32_t *width);
+int sapr_full_workspace_bytes(int64_t total_frames, int64_t n_tiles, int32_t S, int32_t D, size_t *bytes);
+int sapr_full_estep(const float *feats, const int64_t *offsets, const int32_t *slot_utt, const int32_t *tile_model,
+                    const int32_t *model_tile_off /* [W+1]; may be NULL without stats */, int64_t n_utts,
+                    int64_t total_frames, int64_t n_tiles, int32_t D, int32_t max_T, const double *pack, int32_t W,
+                    int32_t S, void *workspace, size_t workspace_bytes, double *loglik, double *stats /* may be NULL */,
+                    double *post /* may be NULL */, int32_t *path /* may be NULL */, void *stream);
+int sapr_full_viterbi(const float *feats, const int64_t *offsets, const int32_t *slot_utt, const int32_t *tile_model,
+                      int64_t n_utts, int64_t total_frames, int64_t n_tiles, int32_t D, int32_t max_T,
+                      const double *pack, int32_t W, int32_t S, void *workspace, size_t workspace_bytes,
+                      double *logprob, int32_t *path, void *stream);
+
 /* Scoring over the vocabulary for the Gaussian-mixture HMMs: every utterance under EVERY word model in one launch,
  * where the two entry points above evaluate an utterance under the one model of its tile — what sapr_forward_vocab is
  * to sapr_forward_diag.  `pack` is the operand block of sapr_gmm_pack_layout (W models, nothing new is packed); `order`

@@ -8,6 +8,7 @@ behaviour) over hand-written HIP kernels in ``libsapr_hip.so``:
 * ``sapr_amd.hmmlearn_hmm``  ↔ assignment2/hmmlearn_hmm.py (+ a GaussianHMM-shaped model object)
 * ``sapr_amd.decoder``       ↔ assignment2/decoder.py
 * ``sapr_amd.gmm_hmm``       hmmlearn's other Gaussian model class, ``GMMHMM`` (no counterpart in the reference)
+* ``sapr_amd.full_cov``      the full-covariance kernels behind ``GaussianHMM(covariance_type="full" | "tied")``
 
 ``sapr_amd/compat`` holds same-named top-level shims so the reference's ``train.py`` /
 ``eval.py`` / tests import the drop-in unmodified.

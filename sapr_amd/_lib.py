@@ -69,6 +69,14 @@ SIGNATURES = {
     "sapr_gmm_viterbi_diag": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32,
                                       c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_size_t, c_void_p,
                                       c_void_p, c_void_p]),
+    "sapr_full_pack_layout": (c_int, [c_int32, c_int32, C.POINTER(c_int32), C.POINTER(c_int32), C.POINTER(c_size_t)]),
+    "sapr_full_stats_width": (c_int, [c_int32, c_int32, C.POINTER(c_int32)]),
+    "sapr_full_workspace_bytes": (c_int, [c_int64, c_int64, c_int32, c_int32, C.POINTER(c_size_t)]),
+    "sapr_full_estep": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32,
+                                c_int32, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p]),
+    "sapr_full_viterbi": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32,
+                                  c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "sapr_gmm_vocab_diag": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_int32,
                                     c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sapr_colsum_f32": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),

@@ -71,7 +71,7 @@ KERNEL_SOURCES = {
     "mfcc": ["mfcc.hip", "mfcc_wave.h", "mfcc_wave_pack.h", "sapr_common.h"],
     "decode": ["viterbi.hip", "viterbi_bound.hip", "viterbi_exact.inc", "viterbi_exact_13_10.hip", "viterbi_shared.h",
                "emission.h", "sapr_common.h"],
-    "gmm": ["gmm_hmm.hip", "gmm_vocab.hip", "gmm_ops.h", "lse_ops.h", "lse_unit.h", "sapr_common.h"],
+    "gmm": ["gmm_hmm.hip", "gmm_vocab.hip", "gmm_ops.h", "fullcov_ops.h", "lse_ops.h", "lse_unit.h", "sapr_common.h"],
 }
 
 

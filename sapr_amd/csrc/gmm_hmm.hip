@@ -693,3 +693,152 @@ extern "C" int sapr_gmm_viterbi_diag(const float *feats, const int64_t *offsets,
   return run(true, feats, offsets, slot_utt, tile_model, nullptr, n_utts, total_frames, n_tiles, D, max_T, pack, W, S,
              M, workspace, workspace_bytes, logprob, nullptr, nullptr, path, stream);
 }
+
+// -------------------------------------------------------------------------------------------
+// full covariances (hmmlearn's GaussianHMM, covariance_type "full" / "tied"): the emission and the accumulation pass
+// of fullcov_ops.h around the recursions above
+// -------------------------------------------------------------------------------------------
+namespace sapr {
+namespace {
+
+#include "fullcov_ops.h"
+
+Ws carve_full(void *base, int64_t total_frames, int64_t n_tiles, int S, int D) {
+  const size_t fr = static_cast<size_t>(total_frames > 0 ? total_frames : 1) * sp_of(S);
+  const size_t nt = static_cast<size_t>(n_tiles > 0 ? n_tiles : 1);
+  Ws w;
+  w.logb = static_cast<double *>(base);
+  w.lat = w.logb + fr;
+  w.ustat = w.lat + fr;
+  w.tile_stats = w.ustat + static_cast<size_t>(stats_k1(S)) * nt * kBlock;
+  w.part = w.tile_stats + nt * stats_k1(S);
+  w.bytes = (2 * fr + static_cast<size_t>(stats_k1(S)) * nt * kBlock + nt * stats_k1(S) +
+             nt * kSub * full_stats_p(S, D)) * sizeof(double);
+  return w;
+}
+
+template <int DP>
+int launch_full_emit(const Batch &b, const double *pack, int64_t n_tiles, double *logb, hipStream_t stream) {
+  SAPR_LAUNCH((full_emit_kernel<DP>), dim3(static_cast<unsigned>(n_tiles), static_cast<unsigned>(b.max_T)),
+              dim3(kBlock), 0, stream, b, pack, sp_of(b.S), logb);
+  SAPR_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+template <int DP>
+int launch_full_accum(const Batch &b, int64_t n_tiles, const double *gam, double *part, hipStream_t stream) {
+  SAPR_LAUNCH((full_accum_kernel<DP>), dim3(static_cast<unsigned>(n_tiles), kSub), dim3(kBlock), 0, stream, b,
+              sp_of(b.S), gam, part);
+  SAPR_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int run_full(bool vit, const float *feats, const int64_t *offsets, const int32_t *slot_utt, const int32_t *tile_model,
+             const int32_t *model_tile_off, int64_t n_utts, int64_t total_frames, int64_t n_tiles, int32_t D,
+             int32_t max_T, const double *pack, int32_t W, int32_t S, void *workspace, size_t workspace_bytes,
+             double *loglik, double *stats, double *post, int32_t *path, void *stream) {
+  SAPR_REQUIRE(n_utts >= 0 && total_frames >= 0 && n_tiles >= 0 && W > 0 && S > 0 && D > 0 && max_T >= 0,
+               "bad sizes (n_utts=%lld total_frames=%lld n_tiles=%lld W=%d S=%d D=%d max_T=%d)", (long long)n_utts,
+               (long long)total_frames, (long long)n_tiles, W, S, D, max_T);
+  if (int rc = check_full_shape(S, D)) return rc;
+  SAPR_REQUIRE(max_T <= kMaxT, "bad sizes: max_T = %d exceeds %d", max_T, kMaxT);
+  SAPR_REQUIRE(n_tiles * (kBlock / 64) <= 0x7fffffffLL, "grid too large (%lld tiles)", (long long)n_tiles);
+  if (n_tiles == 0) return 0;
+  SAPR_REQUIRE(feats && offsets && slot_utt && tile_model && pack && workspace && loglik, "NULL pointer argument");
+  SAPR_REQUIRE(!vit || path, "NULL pointer argument (path)");
+  SAPR_REQUIRE(!stats || model_tile_off, "NULL pointer argument (model_tile_off)");
+  const Ws ws = carve_full(workspace, total_frames, n_tiles, S, D);
+  SAPR_REQUIRE(workspace_bytes >= ws.bytes, "workspace too small: %zu < %zu", workspace_bytes, ws.bytes);
+  Batch b;
+  b.feats = feats;
+  b.offsets = offsets;
+  b.slot_utt = slot_utt;
+  b.tile_model = tile_model;
+  b.n_utts = n_utts;
+  b.total_frames = total_frames;
+  b.n_slots = n_tiles * kBlock;
+  b.D = D;
+  b.max_T = max_T;
+  b.W = W;
+  b.S = S;
+  b.M = 1;
+  b.stride = static_cast<int64_t>(full_model_doubles(sp_of(S), dp_of(D)));
+  hipStream_t st = as_stream(stream);
+  if (max_T > 0 && total_frames > 0) {
+    int rc;
+    switch (dp_of(D)) {
+      case 13: rc = launch_full_emit<13>(b, pack, n_tiles, ws.logb, st); break;
+      case 26: rc = launch_full_emit<26>(b, pack, n_tiles, ws.logb, st); break;
+      default: rc = launch_full_emit<39>(b, pack, n_tiles, ws.logb, st); break;
+    }
+    if (rc) return rc;
+  }
+  double *ustat = stats ? ws.ustat : nullptr;
+  int rc;
+  switch (sp_of(S)) {
+    case 4: rc = launch_trellis<4>(vit, b, pack, n_tiles, ws, loglik, ustat, post, path, st); break;
+    case 10: rc = launch_trellis<10>(vit, b, pack, n_tiles, ws, loglik, ustat, post, path, st); break;
+    default: rc = launch_trellis<18>(vit, b, pack, n_tiles, ws, loglik, ustat, post, path, st); break;
+  }
+  if (rc || !stats) return rc;
+  switch (dp_of(D)) {
+    case 13: rc = launch_full_accum<13>(b, n_tiles, ws.lat, ws.part, st); break;
+    case 26: rc = launch_full_accum<26>(b, n_tiles, ws.lat, ws.part, st); break;
+    default: rc = launch_full_accum<39>(b, n_tiles, ws.lat, ws.part, st); break;
+  }
+  if (rc) return rc;
+  const int K1 = stats_k1(S), P = full_stats_p(S, D);
+  SAPR_LAUNCH(gmm_tile_reduce_kernel, dim3(static_cast<unsigned>(n_tiles)), dim3(kBlock), 0, st, K1, b.n_slots,
+              ws.ustat, ws.tile_stats);
+  SAPR_HIP_TRY(hipGetLastError());
+  const int64_t total = static_cast<int64_t>(W) * (K1 + P);
+  SAPR_LAUNCH(gmm_reduce_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, st, model_tile_off, W,
+              K1, P, n_tiles, ws.tile_stats, ws.part, stats);
+  SAPR_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+}  // namespace
+}  // namespace sapr
+
+extern "C" int sapr_full_pack_layout(int32_t S, int32_t D, int32_t *SP, int32_t *DP, size_t *doubles_per_model) {
+  SAPR_REQUIRE(SP && DP && doubles_per_model && S > 0 && D > 0, "bad sizes (S=%d D=%d)", S, D);
+  if (int rc = check_full_shape(S, D)) return rc;
+  *SP = sp_of(S);
+  *DP = dp_of(D);
+  *doubles_per_model = full_model_doubles(*SP, *DP);
+  return 0;
+}
+
+extern "C" int sapr_full_stats_width(int32_t S, int32_t D, int32_t *width) {
+  SAPR_REQUIRE(width && S > 0 && D > 0, "bad sizes (S=%d D=%d)", S, D);
+  if (int rc = check_full_shape(S, D)) return rc;
+  *width = stats_k1(S) + full_stats_p(S, D);
+  return 0;
+}
+
+extern "C" int sapr_full_workspace_bytes(int64_t total_frames, int64_t n_tiles, int32_t S, int32_t D, size_t *bytes) {
+  SAPR_REQUIRE(bytes && total_frames >= 0 && n_tiles >= 0 && S > 0 && D > 0,
+               "bad sizes (total_frames=%lld n_tiles=%lld S=%d D=%d)", (long long)total_frames, (long long)n_tiles, S,
+               D);
+  if (int rc = check_full_shape(S, D)) return rc;
+  *bytes = carve_full(nullptr, total_frames, n_tiles, S, D).bytes;
+  return 0;
+}
+
+extern "C" int sapr_full_estep(const float *feats, const int64_t *offsets, const int32_t *slot_utt,
+                               const int32_t *tile_model, const int32_t *model_tile_off, int64_t n_utts,
+                               int64_t total_frames, int64_t n_tiles, int32_t D, int32_t max_T, const double *pack,
+                               int32_t W, int32_t S, void *workspace, size_t workspace_bytes, double *loglik,
+                               double *stats, double *post, int32_t *path, void *stream) {
+  return run_full(false, feats, offsets, slot_utt, tile_model, model_tile_off, n_utts, total_frames, n_tiles, D, max_T,
+                  pack, W, S, workspace, workspace_bytes, loglik, stats, post, path, stream);
+}
+
+extern "C" int sapr_full_viterbi(const float *feats, const int64_t *offsets, const int32_t *slot_utt,
+                                 const int32_t *tile_model, int64_t n_utts, int64_t total_frames, int64_t n_tiles,
+                                 int32_t D, int32_t max_T, const double *pack, int32_t W, int32_t S, void *workspace,
+                                 size_t workspace_bytes, double *logprob, int32_t *path, void *stream) {
+  return run_full(true, feats, offsets, slot_utt, tile_model, nullptr, n_utts, total_frames, n_tiles, D, max_T, pack, W,
+                  S, workspace, workspace_bytes, logprob, nullptr, nullptr, path, stream);
+}

@@ -81,6 +81,50 @@ def m_step(stats, startprob, transmat, params="stmc", startprob_prior=1.0, trans
     return startprob, transmat, means, covars
 
 
+COVARIANCE_TYPES = ("diag", "spherical", "tied", "full")
+
+
+def m_step_typed(stats, covariance_type, startprob, transmat, params="stmc", startprob_prior=1.0, transmat_prior=1.0,
+                 means_prior=0.0, means_weight=0.0, covars_prior=1e-2, covars_weight=1.0, means=None, covars=None):
+    """:func:`m_step` for every ``covariance_type`` (hmm.py ``GaussianHMM._do_mstep``, restated from knowledge of
+    hmmlearn 0.3.x); ``covars`` comes and goes in the shape of ``_covars_``.  ``stats`` carries ``obs**2`` for "diag"
+    and "spherical" and ``obs*obs.T`` for "tied" and "full".
+
+    * spherical: the diag formula, then the mean over the features of each state;
+    * full / tied, with mu the new means: ``c_n[s] = means_weight outer(mu_s - means_prior, mu_s - means_prior) +
+      oo[s] - (outer(obs_s, mu_s) + outer(obs_s, mu_s)^T) + outer(mu_s, mu_s) post_s`` (the two cross terms are added
+      to each other first, so that every matrix is exactly symmetric), ``cvweight = max(covars_weight - D, 0)``, full:
+      ``(covars_prior + c_n[s]) / (cvweight + post_s)``, tied: ``(covars_prior + sum_s c_n[s]) / (cvweight + sum_s
+      post_s)``.  No floor and no repair: a result that is not positive-definite is refused when it is next packed."""
+    if covariance_type == "diag":
+        return m_step(stats, startprob, transmat, params, startprob_prior, transmat_prior, means_prior, means_weight,
+                      covars_prior, covars_weight, means, covars)
+    if covariance_type == "spherical":
+        wide = None if covars is None else np.broadcast_to(np.asarray(covars)[:, None], np.shape(means))
+        startprob, transmat, means, wide = m_step(stats, startprob, transmat, params, startprob_prior, transmat_prior,
+                                                  means_prior, means_weight, covars_prior, covars_weight, means, wide)
+        return startprob, transmat, means, (wide.mean(axis=1) if "c" in params else covars)
+    startprob, transmat, means, _ = m_step(stats, startprob, transmat, params.replace("c", ""), startprob_prior,
+                                           transmat_prior, means_prior, means_weight, covars_prior, covars_weight,
+                                           means, None)
+    if "c" in params:
+        S, D = means.shape
+        post = stats["post"]
+        c_n = np.empty((S, D, D))
+        for s in range(S):
+            md = means[s] - means_prior
+            om = np.outer(stats["obs"][s], means[s])
+            c_n[s] = (means_weight * np.outer(md, md) + stats["obs*obs.T"][s] - (om + om.T)
+                      + np.outer(means[s], means[s]) * post[s])
+        cvweight = max(covars_weight - D, 0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            if covariance_type == "tied":
+                covars = (covars_prior + c_n.sum(axis=0)) / (cvweight + post.sum())
+            else:
+                covars = (covars_prior + c_n) / (cvweight + post[:, None, None])
+    return startprob, transmat, means, covars
+
+
 def m_step_batch(rows, S, D, startprob, transmat, means, covars, params="stmc", startprob_prior=1.0,
                  transmat_prior=1.0, means_prior=0.0, means_weight=0.0, covars_prior=1e-2, covars_weight=1.0,
                  S_model=None, D_model=None):
@@ -180,7 +224,11 @@ def kmeans_seed(rs) -> int:
 
 
 class GaussianHMM:
-    """hmmlearn-shaped diagonal-Gaussian HMM (every state emits) on the HIP kernels.
+    """hmmlearn-shaped Gaussian HMM (every state emits) on the HIP kernels, ``covariance_type`` "diag", "spherical",
+    "tied" or "full".  "diag" and "spherical" (one variance per state, broadcast over the features) run on the diagonal
+    kernels; "full" and "tied" on the full-covariance kernels (:mod:`sapr_amd.full_cov`), where Viterbi ties go to the
+    first maximum and ``tie_break`` does not apply.  ``_covars_`` has hmmlearn's shapes — ``(S,)`` spherical, ``(D, D)``
+    tied, ``(S, D, D)`` full, ``(S, D)`` diag — and ``covars_`` always returns ``(S, D, D)``.
 
     ``fit`` first initialises what ``init_params`` names — or what is not set yet — the way hmmlearn's ``_init`` does
     (restated from knowledge of hmmlearn 0.3.x, the reference's pinned version, like SURVEY §9.3), with
@@ -192,7 +240,8 @@ class GaussianHMM:
       device (:func:`sapr_amd.kmeans.kmeans`), seeded by ONE integer drawn from ``rs`` after the ``s`` / ``t`` draws —
       a model's initialisation depends only on its own ``random_state`` and data, not on what else is trained with it
     * ``c``  ``covars_ = tile(diag(np.cov(X.T)) + min_covar, (S, 1))``: the ddof = 1 column variance about the column
-      mean, two K = 1 steps of the same kernel
+      mean, two K = 1 steps of the same kernel ("diag"); the other types start from ``cv = np.cov(X.T) + min_covar I``
+      (float64, on the device): "tied" ``cv``, "full" ``tile(cv)``, "spherical" ``tile(cv.mean())`` over all D x D entries
 
     Not scikit-learn's random stream or seeding, and an empty cluster keeps its centre (``kmeans.py``, DESIGN.md §8);
     hmmlearn's warning about fewer data points than free parameters is not reproduced.  A preset attribute whose
@@ -202,8 +251,8 @@ class GaussianHMM:
                  transmat_prior=1.0, means_prior=0, means_weight=0, covars_prior=1e-2, covars_weight=1,
                  algorithm="viterbi", random_state=None, n_iter=10, tol=1e-2, verbose=False, params="stmc",
                  init_params="stmc", implementation="log"):
-        if covariance_type != "diag":
-            raise ValueError("only covariance_type='diag' is implemented (hmmlearn_hmm.py:29)")
+        if covariance_type not in COVARIANCE_TYPES:
+            raise ValueError(f"covariance_type must be one of {COVARIANCE_TYPES}, got {covariance_type!r}")
         if implementation != "log":
             raise ValueError("only implementation='log' is implemented (hmmlearn_hmm.py:32)")
         if algorithm not in DECODER_ALGORITHMS:
@@ -219,17 +268,61 @@ class GaussianHMM:
         # which back-trace tie-break GaussianHMM.decode uses (oracle/hmmlearn_oracle.py docstring)
         self.tie_break = "high"
 
-    # hmmlearn exposes full matrices through covars_ and keeps the (S, D) array in _covars_
+    # hmmlearn exposes full matrices through covars_ and keeps the type's own array in _covars_
     @property
     def covars_(self):
+        ct = self.covariance_type
+        if ct == "full":
+            return np.array(self._covars_, copy=True)
+        if ct == "tied":
+            return np.tile(self._covars_, (self.n_components, 1, 1))
+        if ct == "spherical":
+            D = int(self.n_features if hasattr(self, "n_features") else np.shape(self.means_)[1])
+            return np.array([np.eye(D) * c for c in self._covars_])
         return np.array([np.diag(c) for c in self._covars_])
 
     @covars_.setter
     def covars_(self, covars):
         covars = np.array(covars, copy=True)
-        if covars.ndim != 2 or np.any(covars <= 0):
-            raise ValueError("'diag' covars must be a positive (n_components, n_features) array")
+        ct, S = self.covariance_type, self.n_components
+        if ct == "diag":
+            if covars.ndim != 2 or np.any(covars <= 0):
+                raise ValueError("'diag' covars must be a positive (n_components, n_features) array")
+        elif ct == "spherical":
+            if covars.ndim != 1 or len(covars) != S or np.any(covars <= 0):
+                raise ValueError("'spherical' covars must be a positive array of length n_components")
+        else:
+            from .full_cov import cholesky_lower
+            if ct == "tied":
+                if covars.ndim != 2 or covars.shape[0] != covars.shape[1]:
+                    raise ValueError("'tied' covars must have shape (n_features, n_features)")
+                cholesky_lower(covars, "tied")
+            else:
+                if covars.ndim != 3 or covars.shape[0] != S or covars.shape[1] != covars.shape[2]:
+                    raise ValueError("'full' covars must have shape (n_components, n_features, n_features)")
+                for cv in covars:
+                    cholesky_lower(cv, "full")
         self._covars_ = covars
+
+    def _is_full(self):
+        return self.covariance_type in ("full", "tied")
+
+    def _full_params(self):
+        """``(startprob, transmat, means[S, D], covars[S, D, D])`` as :func:`sapr_amd.full_cov.pack_models` takes it."""
+        cv = np.asarray(self._covars_, dtype=np.float64)
+        if self.covariance_type == "tied":
+            cv = np.broadcast_to(cv, (self.n_components,) + cv.shape)
+        return (np.asarray(self.startprob_, dtype=np.float64), np.asarray(self.transmat_, dtype=np.float64),
+                np.asarray(self.means_, dtype=np.float64), cv)
+
+    def _full_batch(self, X, lengths):
+        """(batch, pack, lengths) of one model over its sequences on the full-covariance kernels."""
+        from . import full_cov
+        self._check()
+        Xa, lengths = self._split(X, lengths)
+        batch = full_cov.FullCovBatch(_features_f32(Xa), lengths, np.zeros(len(lengths), np.int64), 1,
+                                      self.n_components)
+        return batch, full_cov.pack_models([self._full_params()], name=self.covariance_type), lengths
 
     # ---- initialisation (hmmlearn _needs_init / _init) ---------------------------------------
     _INIT_ATTRS = (("s", "startprob_"), ("t", "transmat_"), ("m", "means_"), ("c", "covars_"))
@@ -253,16 +346,21 @@ class GaussianHMM:
             raise ValueError("startprob_ must have length n_components and sum to 1.0")
         if self.transmat_.shape != (S, S) or not np.allclose(self.transmat_.sum(axis=1), 1.0):
             raise ValueError("rows of transmat_ must sum to 1.0")
-        if self.means_.shape[0] != S or self._covars_.shape != self.means_.shape:
+        self._covars_ = np.asarray(self._covars_)
+        D = self.means_.shape[1] if self.means_.ndim == 2 else -1
+        want = {"diag": (S, D), "spherical": (S,), "tied": (D, D), "full": (S, D, D)}[self.covariance_type]
+        if self.means_.ndim != 2 or self.means_.shape[0] != S or self._covars_.shape != want:
             raise ValueError("means_ / covars_ shape mismatch")
-        self.n_features = self.means_.shape[1]
+        self.n_features = D
 
     def _pack(self):
         from .trellis import DiagModelPack
         # one model, scored or decoded on its own (decode / score below): the exact kernels' operands only
+        cv = np.asarray(self._covars_, dtype=np.float64)
+        if self.covariance_type == "spherical":
+            cv = np.broadcast_to(cv[:, None], np.shape(self.means_))
         return DiagModelPack.from_params(self.startprob_[None], self.transmat_[None],
-                                         np.asarray(self.means_, dtype=np.float64)[None],
-                                         np.asarray(self._covars_, dtype=np.float64)[None], exact_only=True)
+                                         np.asarray(self.means_, dtype=np.float64)[None], cv[None], exact_only=True)
 
     @staticmethod
     def _split(X, lengths):
@@ -294,6 +392,11 @@ class GaussianHMM:
         if algorithm == "map":
             Xa, lengths = self._split(X, lengths)
             return map_decode_host(self._state_posteriors(Xa, lengths)[1], lengths)
+        if self._is_full():
+            batch, pack, lengths = self._full_batch(X, lengths)
+            lp, path = batch.viterbi(pack)
+            lp = lp.cpu().numpy()
+            return (float(lp.sum()) if len(lengths) > 1 else float(lp[0])), path.cpu().numpy().astype(np.int64)
         self._check()
         Xa = np.asarray(X)
         sum_order = _lib.SUM_PAIRWISE if Xa.flags.c_contiguous else _lib.SUM_TVIEW
@@ -316,6 +419,10 @@ class GaussianHMM:
     def _state_posteriors(self, Xa, lengths):
         """(per-sequence log-likelihoods, posterior lattice) as host arrays."""
         from .trellis import FeatureBatch, state_posteriors
+        if self._is_full():
+            batch, pack, _ = self._full_batch(Xa, lengths)
+            ll, _, post, _ = batch.estep(pack, want_stats=False, want_post=True)
+            return ll.cpu().numpy(), post.cpu().numpy()
         self._check()
         import torch
         dev = _lib.require_gpu()
@@ -338,6 +445,9 @@ class GaussianHMM:
     # ---- GaussianHMM.score (hmmlearn_hmm.py:104) ------------------------------------------
     def score(self, X, lengths=None):
         from .trellis import FeatureBatch, forward_loglik
+        if self._is_full():
+            batch, pack, _ = self._full_batch(X, lengths)
+            return float(batch.estep(pack, want_stats=False)[0].cpu().numpy().sum())
         self._check()
         Xa, lengths = self._split(X, lengths)
         import torch
@@ -365,6 +475,16 @@ def fit_models(models: List[GaussianHMM], data) -> None:
     import torch
     from . import dist as sdist
     from .trellis import DiagModelPack, EStep, FeatureBatch
+    # the models are grouped by the kernels that serve them: "diag" / "spherical" and "full" / "tied"
+    families = [m._is_full() for m in models]
+    if any(families) and not all(families):
+        for fam in (False, True):
+            idx = [w for w, f in enumerate(families) if f == fam]
+            fit_models([models[w] for w in idx], [data[w] for w in idx])
+        return
+    if any(m.covariance_type != "diag" for m in models) and sdist.world()[1] > 1:
+        raise NotImplementedError("training a model whose covariance_type is not 'diag' over several ranks is not "
+                                  "implemented")
     dev = _lib.require_gpu()
     W = len(models)
     needs = [[code for code, name in GaussianHMM._INIT_ATTRS if m._needs_init(code, name)] for m in models]
@@ -389,6 +509,9 @@ def fit_models(models: List[GaussianHMM], data) -> None:
     for m in models:
         m.monitor_ = ConvergenceMonitor(m.tol, m.n_iter, m.verbose)
     S = models[0].n_components
+    if families[0]:
+        _fit_full(models, dfeats, lengths, utt_model)
+        return
     batch = FeatureBatch.from_packed(dfeats, np.asarray(lengths, dtype=np.int64))
     estep = EStep(batch, np.asarray(utt_model), W, S)
     active = [True] * W
@@ -402,7 +525,8 @@ def fit_models(models: List[GaussianHMM], data) -> None:
         host = stats.cpu().numpy()
         hyper = [(m.params, m.startprob_prior, m.transmat_prior, m.means_weight, m.covars_prior, m.covars_weight)
                  for m in models]
-        if W > 1 and all(h == hyper[0] for h in hyper) and all(np.ndim(m.means_prior) == 0 for m in models) \
+        if W > 1 and all(m.covariance_type == "diag" for m in models) and all(h == hyper[0] for h in hyper) \
+                and all(np.ndim(m.means_prior) == 0 for m in models) \
                 and len({float(m.means_prior) for m in models}) == 1:
             # one vectorised M-step for the whole vocabulary (same bits as the per-model calls, a tenth of the time)
             m0 = models[0]
@@ -425,11 +549,37 @@ def fit_models(models: List[GaussianHMM], data) -> None:
             if not active[w]:
                 continue
             st = estep.split(host[w])
-            m.startprob_, m.transmat_, m.means_, cov = m_step(
-                st, m.startprob_, m.transmat_, m.params, m.startprob_prior, m.transmat_prior, m.means_prior,
-                m.means_weight, m.covars_prior, m.covars_weight, np.asarray(m.means_, dtype=np.float64),
+            m.startprob_, m.transmat_, m.means_, cov = m_step_typed(
+                st, m.covariance_type, m.startprob_, m.transmat_, m.params, m.startprob_prior, m.transmat_prior,
+                m.means_prior, m.means_weight, m.covars_prior, m.covars_weight, np.asarray(m.means_, dtype=np.float64),
                 np.asarray(m._covars_, dtype=np.float64))
             m._covars_ = cov
+            m.monitor_.report(st["logprob"])
+            if m.monitor_.converged:
+                active[w] = False
+
+
+def _fit_full(models, dfeats, lengths, utt_model) -> None:
+    """The Baum-Welch loop of :func:`fit_models` for "full" / "tied" models (initialised and checked by the caller):
+    one ``sapr_full_estep`` per iteration over every model's utterances, the M-step per model on the host."""
+    from . import full_cov
+    W = len(models)
+    S = max(m.n_components for m in models)
+    batch = full_cov.FullCovBatch(dfeats, lengths, utt_model, W, S)
+    active = [True] * W
+    for _ in range(max(m.n_iter for m in models)):
+        if not any(active):
+            break
+        pack = np.concatenate([full_cov.pack_models([m._full_params()], S, name=m.covariance_type) for m in models])
+        host = batch.estep(pack)[1].cpu().numpy()
+        for w, m in enumerate(models):
+            if not active[w]:
+                continue
+            st = full_cov.split_stats(host[w], S, batch.D, m.n_components)
+            m.startprob_, m.transmat_, m.means_, m._covars_ = m_step_typed(
+                st, m.covariance_type, m.startprob_, m.transmat_, m.params, m.startprob_prior, m.transmat_prior,
+                m.means_prior, m.means_weight, m.covars_prior, m.covars_weight, np.asarray(m.means_, dtype=np.float64),
+                np.asarray(m._covars_, dtype=np.float64))
             m.monitor_.report(st["logprob"])
             if m.monitor_.converged:
                 active[w] = False
@@ -472,7 +622,20 @@ def _init_models(models, needs, dfeats, frames) -> None:
         if "c" in needs[w]:
             if count[g] < 2:
                 raise ValueError(f"covariance initialisation needs at least 2 frames, model {w} has {int(count[g])}")
-            m._covars_ = np.tile(sqdev[g] / (count[g] - 1) + m.min_covar, (m.n_components, 1))
+            if m.covariance_type == "diag":
+                m._covars_ = np.tile(sqdev[g] / (count[g] - 1) + m.min_covar, (m.n_components, 1))
+                continue
+            # np.cov(X.T) + min_covar I in float64 on the device (run once per model)
+            X = dfeats[off[w]:off[w + 1]].double()
+            Xc = X - X.mean(dim=0, keepdim=True)
+            cv = (Xc.T @ Xc / (X.shape[0] - 1)).cpu().numpy()
+            cv = (cv + cv.T) / 2 + m.min_covar * np.eye(cv.shape[0])
+            if m.covariance_type == "tied":
+                m._covars_ = cv
+            elif m.covariance_type == "full":
+                m._covars_ = np.tile(cv, (m.n_components, 1, 1))
+            else:
+                m._covars_ = np.tile(cv.mean(), m.n_components)
     msel = [w for w in sel if "m" in needs[w]]
     if not msel:
         return

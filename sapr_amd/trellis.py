@@ -235,11 +235,19 @@ class DiagModelPack:
 
     @staticmethod
     def from_models(models, device=None, exact_only=False) -> "DiagModelPack":
-        """``models``: objects with hmmlearn's attribute names (startprob_, transmat_, means_, _covars_)."""
+        """``models``: objects with hmmlearn's attribute names (startprob_, transmat_, means_, _covars_).  The diagonal
+        kernels serve ``covariance_type`` "diag" and, broadcast over the features, "spherical"; a "full" or "tied"
+        model is refused (its ``_covars_`` has another shape: :mod:`sapr_amd.full_cov` serves those)."""
+        for m in models:
+            ct = getattr(m, "covariance_type", "diag")
+            if ct not in ("diag", "spherical"):
+                raise ValueError(f"the diagonal kernels cannot serve a model with covariance_type={ct!r}")
         sp = np.stack([np.asarray(m.startprob_, dtype=np.float64) for m in models])
         tm = np.stack([np.asarray(m.transmat_, dtype=np.float64) for m in models])
         mu = np.stack([np.asarray(m.means_, dtype=np.float64) for m in models])
-        cv = np.stack([np.asarray(m._covars_, dtype=np.float64) for m in models])
+        cv = [np.asarray(m._covars_, dtype=np.float64) for m in models]
+        # (spherical: one variance per state, broadcast over the features)
+        cv = np.stack([np.broadcast_to(c[:, None], mu[0].shape) if c.ndim == 1 else c for c in cv])
         return DiagModelPack.from_params(sp, tm, mu, cv, device=device, exact_only=exact_only)
 
 
