@@ -391,6 +391,38 @@ int sapr_gmm_vocab_diag(const float *feats, const int64_t *offsets, const int32_
                         int32_t *best_word /* [n_utts], may be NULL */,
                         double *word_post /* [n_utts][W], may be NULL; FORWARD only */, void *stream);
 
+/* Scoring over the vocabulary for the full-covariance HMMs: every utterance under EVERY word model in one launch —
+ * what sapr_gmm_vocab_diag is to the mixtures.  `pack` is the operand block of sapr_full_pack_layout as it is (W
+ * models, nothing new is packed); `order` (optional, may be NULL) is the length-sorted permutation of
+ * sapr_forward_vocab.  score, best_word, word_post, the rules on empty and unserved utterances, on an `order` entry
+ * outside the batch (never followed), on non-finite values and on determinism are sapr_gmm_vocab_diag's, word for word:
+ *   score[n_utts][W]      SAPR_FULL_VOCAB_FORWARD: the bits sapr_full_estep returns as loglik with every utterance
+ *                         assigned to model w; SAPR_FULL_VOCAB_VITERBI: the bits of sapr_full_viterbi's logprob (first
+ *                         maximum of the last row).  -inf for an utterance without frames, for one longer than max_T and
+ *                         for one whose offsets leave the batch
+ *   best_word[n_utts]     optional: first strict maximum of the row in model order, starting from -inf; -1 if none
+ *   word_post[n_utts][W]  optional, forward mode only: exp(score - logsumexp_w score)
+ * The emission of a state is evaluated where the recursion consumes it, by the device function full_emit_kernel calls
+ * (fullcov_emit.h); the recursion's state lives in registers, no lattice and no logb reach memory.
+ *
+ * Workspace: sapr_full_vocab_workspace_bytes() is 0 today — every instantiation takes the fused path and `workspace`
+ * may be NULL.  The pair is part of the ABI so that a staged path (a frame-parallel emission into a
+ * logb[frames of a slice of utterances][W][SP] block, bounded independently of n_utts) can be added without changing
+ * it; callers size and pass the workspace as for the other entry points.
+ *
+ * Bad sizes, NULL required pointers, an unknown mode, a word_post in Viterbi mode and a workspace that is too small
+ * return SAPR_ERR_ARG, S > 18 or D > 39 SAPR_ERR_UNSUPPORTED (from the size function too), all before any HIP call;
+ * n_utts == 0 returns 0 after these checks without touching any pointer. */
+#define SAPR_FULL_VOCAB_FORWARD 0
+#define SAPR_FULL_VOCAB_VITERBI 1
+int sapr_full_vocab_workspace_bytes(int64_t n_utts, int64_t total_frames, int32_t W, int32_t S, int32_t D,
+                                    size_t *bytes);
+int sapr_full_vocab(const float *feats, const int64_t *offsets, const int32_t *order /* may be NULL */,
+                    int64_t n_utts, int64_t total_frames, int32_t D, int32_t max_T, const double *pack, int32_t W,
+                    int32_t S, int32_t mode, void *workspace, size_t workspace_bytes,
+                    double *score /* [n_utts][W] */, int32_t *best_word /* [n_utts], may be NULL */,
+                    double *word_post /* [n_utts][W], may be NULL; FORWARD only */, void *stream);
+
 /* Flat start of HMMLearnModel (hmmlearn_hmm.py:83-94: np.mean / np.var over axis 0 of the concatenated float32
  * features): numpy adds row after row in float32, so each column is one sequential float32 chain — reproduced
  * bit for bit.  center == NULL: out[d] = sum_r x[r][d]; else out[d] = sum_r RN32(RN32(x[r][d] - center[d])^2).

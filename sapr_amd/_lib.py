@@ -79,6 +79,9 @@ SIGNATURES = {
                                   c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "sapr_gmm_vocab_diag": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_int32,
                                     c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sapr_full_vocab_workspace_bytes": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int32, C.POINTER(c_size_t)]),
+    "sapr_full_vocab": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_int32,
+                                c_int32, c_int32, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sapr_colsum_f32": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     "sapr_custom_estep": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32] + [c_void_p] * 5
                           + [c_int64] + [c_void_p] * 6 + [c_void_p]),
@@ -127,6 +130,7 @@ PACK_FAST_DIV, PACK_BOUND_OK, PACK_GEMM_OK, PACK_BIDIAG, PACK_EXACT_ONLY = 1, 2,
 ESTEP_STAGED = 256
 SUM_PAIRWISE, SUM_TVIEW, SUM_SEQ = 0, 1, 2
 GMM_VOCAB_FORWARD, GMM_VOCAB_VITERBI = 0, 1
+FULL_VOCAB_FORWARD, FULL_VOCAB_VITERBI = 0, 1
 
 _lib = None
 

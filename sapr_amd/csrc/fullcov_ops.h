@@ -17,6 +17,8 @@
 //                           the diagonal are computed; both halves of oo are written from the upper one.
 #pragma once
 
+#include "fullcov_emit.h"
+
 typedef double f64x4_full __attribute__((ext_vector_type(4)));
 
 // per model: log_start[SP], log_trans[SP][SP], log_transT[SP][SP], c[SP], mu[SP][DP], Winv[SP][DP][DP]
@@ -60,19 +62,9 @@ __global__ __launch_bounds__(kBlock) void full_emit_kernel(Batch b, const double
   double *__restrict__ out = logb + frame * SP;
 #pragma unroll 1
   for (int s = 0; s < SP; ++s) {
-    const double *__restrict__ m = mu + s * DP;
-    const double *__restrict__ wr = wi + static_cast<int64_t>(s) * DP * DP;
-    double q = 0.0;
-    // y_i = sum_{j<=i} Winv[i][j] (x_j - mu_j): the difference is taken directly (c0 sits near -300) and again for
-    // every row, so that no second DP-wide vector lives beside the frame
-#pragma unroll
-    for (int i = 0; i < DP; ++i) {
-      double y = 0.0;
-#pragma unroll
-      for (int j = 0; j <= i; ++j) y = fma(wr[i * DP + j], x[j] - m[j], y);
-      q = fma(y, y, q);
-    }
-    out[s] = cc[s] - 0.5 * q;
+    // row after row of Winv_s with one running dot product (fullcov_emit.h, shared with full_vocab.hip)
+    out[s] = full_log_density<DP>([&](int d) { return x[d]; }, mu + s * DP, wi + static_cast<int64_t>(s) * DP * DP,
+                                  cc[s]);
   }
 }
 

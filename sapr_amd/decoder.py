@@ -18,6 +18,11 @@ state posterior lattice of every utterance under the decoder's word (or a named 
 ``<word>_gmmhmm_<n_iter>.pkl`` under ``models_dir/gmmhmm/``) through the same API: one launch of
 ``sapr_gmm_vocab_diag`` scores every utterance under every word model (Viterbi or forward mode, by ``scoring``), one
 ``sapr_gmm_viterbi_diag`` over the utterances grouped by their best word walks the winner's path.
+
+Under ``implementation="hmmlearn"`` a vocabulary in which ANY model has ``covariance_type`` "full" or "tied" runs the
+same way on the full-covariance kernels: ``sapr_full_vocab`` scores, ``sapr_full_viterbi`` under the winner walks
+the path, ``sapr_full_estep`` gives the state posteriors.  "diag" and "spherical" members of such a vocabulary are
+packed as diagonal matrices; a vocabulary of only "diag" / "spherical" models keeps the single-Gaussian kernels.
 """
 from __future__ import annotations
 
@@ -40,7 +45,12 @@ class Decoder:
         in load order), that log-likelihood, and the Viterbi path of that word; the path costs one all-vocabulary exact
         Viterbi pass (scores + back-pointers for every word, back-trace of the chosen one) on top of the forward launch,
         not the pruned decoder's pass over the surviving words (``implementation="gmmhmm"``: one Viterbi launch under
-        the chosen word only, whatever the scoring)."""
+        the chosen word only, whatever the scoring).
+
+        A vocabulary with a "full" or "tied" ``GaussianHMM`` (``implementation="hmmlearn"``) is served like the
+        mixtures: one ``sapr_full_vocab`` launch picks the word, one ``sapr_full_viterbi`` under that word walks its
+        path.  Viterbi ties go to the first maximum there, as in hmmlearn's own ``_hmmc`` code: the models'
+        ``tie_break`` does not apply on this path."""
         if scoring not in ("viterbi", "forward"):
             raise ValueError(f"scoring must be 'viterbi' or 'forward', got {scoring!r}")
         if scoring == "forward" and implementation == "custom":
@@ -54,6 +64,7 @@ class Decoder:
         self.vocab: List[str] = []
         self._pack = None
         self._gmm = None
+        self._full = None
         self.load_models()
 
     def load_models(self) -> None:
@@ -81,6 +92,8 @@ class Decoder:
             return self._decode_custom(feature_list)
         if self.implementation == "gmmhmm":
             return self._decode_gmm(*self._gmm_features(feature_list))
+        if self._is_full():
+            return self._decode_full(*self._gmm_features(feature_list))
         from .trellis import FeatureBatch
         return self._decode_feature_batch(FeatureBatch.from_arrays(feature_list, layout="DT"))
 
@@ -93,6 +106,10 @@ class Decoder:
             from .gmm_hmm import vocab_features
             feats, _, _, lengths, _ = vocab_features(store.to_batch())
             return self._decode_gmm(feats, lengths)
+        if self._is_full():
+            from .gmm_hmm import vocab_features
+            feats, _, _, lengths, _ = vocab_features(store.to_batch())
+            return self._decode_full(feats, lengths)
         return self._decode_feature_batch(store.to_batch())
 
     def _decode_custom(self, features) -> List[Tuple[str, float, object]]:
@@ -158,6 +175,53 @@ class Decoder:
         offs = np.r_[0, np.cumsum(lengths)].tolist()
         return [post[lo:hi, :pack.n_states[w]] for w, lo, hi in zip(utt_model.tolist(), offs[:-1], offs[1:])]
 
+    # ---- full-covariance word models ----------------------------------------------------------
+    def _is_full(self) -> bool:
+        """A vocabulary of hmmlearn-shaped models of which at least one has a "full" or "tied" covariance: all of it
+        runs on the full-covariance kernels (``DiagModelPack`` refuses such models)."""
+        return self.implementation == "hmmlearn" and any(
+            getattr(m, "covariance_type", "diag") in ("full", "tied") for m in self.models.values())
+
+    def _full_pack(self):
+        """The vocabulary's operand block (``full_cov.FullPack``), padded to its largest model; built once."""
+        if self._full is None:
+            from .full_cov import FullPack
+            self._full = FullPack.from_models(self._model_list())
+        return self._full
+
+    def _decode_full(self, feats, lengths) -> List[Tuple[str, float, object]]:
+        """:meth:`_decode_gmm` over the full-covariance kernels: one ``sapr_full_vocab`` launch (Viterbi
+        log-probabilities, or forward log-likelihoods with ``scoring="forward"``) picks the word, one
+        ``sapr_full_viterbi`` over the utterances grouped by that word walks its path (first maximum on ties).  The
+        returned score is the vocabulary launch's (in Viterbi mode the second launch's ``logprob`` carries the same
+        bits)."""
+        from .full_cov import FullCovBatch, vocab_scores
+        words = list(self.models)
+        pack = self._full_pack()
+        vs = vocab_scores(feats, lengths, pack, mode=self.scoring)
+        bw = _lib.to_host(vs.best_word)[0].astype(np.int64)
+        # an utterance no model scores above -inf has no word (-1): model 0's path is walked and then dropped
+        _, path = FullCovBatch(feats, lengths, np.maximum(bw, 0), pack.W, pack.S).viterbi(pack)
+        score, path = _lib.to_host(vs.score, path)
+        offs = np.r_[0, np.cumsum(lengths)].tolist()
+        path = path.astype(np.int64)
+        return [(words[w], float(score[u, w]), path[lo:hi]) if w >= 0 else (None, float("-inf"), None)
+                for u, (w, lo, hi) in enumerate(zip(bw.tolist(), offs[:-1], offs[1:]))]
+
+    def _state_posteriors_full(self, feature_list, words) -> List[np.ndarray]:
+        from .full_cov import FullCovBatch, vocab_scores
+        pack = self._full_pack()
+        feats, lengths = self._gmm_features(feature_list)
+        if words is None:
+            vs = vocab_scores(feats, lengths, pack, mode="viterbi")
+            utt_model = np.maximum(_lib.to_host(vs.best_word)[0].astype(np.int64), 0)
+        else:
+            utt_model = self._named_models(words, len(lengths))
+        batch = FullCovBatch(feats, lengths, utt_model, pack.W, pack.S)
+        post = _lib.to_host(batch.estep(pack, want_stats=False, want_post=True)[2])[0].copy()
+        offs = np.r_[0, np.cumsum(lengths)].tolist()
+        return [post[lo:hi, :pack.n_states[w]] for w, lo, hi in zip(utt_model.tolist(), offs[:-1], offs[1:])]
+
     def _named_models(self, words, n_utts) -> np.ndarray:
         """Model index per utterance for the words named by the caller."""
         vocab = list(self.models)
@@ -210,6 +274,12 @@ class Decoder:
             from .trellis import ForwardScores
             vs = vocab_scores(*self._gmm_features(feature_list), self._gmm_pack(), mode="forward", want_post=want_post)
             return ForwardScores(vs.score, vs.best_word, vs.word_post)
+        if self._is_full():
+            from .full_cov import vocab_scores
+            from .trellis import ForwardScores
+            vs = vocab_scores(*self._gmm_features(feature_list), self._full_pack(), mode="forward",
+                              want_post=want_post)
+            return ForwardScores(vs.score, vs.best_word, vs.word_post)
         from .trellis import DiagModelPack, FeatureBatch, forward_scores
         if self._pack is None:
             self._pack = DiagModelPack.from_models(self._model_list())
@@ -254,6 +324,8 @@ class Decoder:
                              "kernel")
         if self.implementation == "gmmhmm":
             return self._state_posteriors_gmm(feature_list, words)
+        if self._is_full():
+            return self._state_posteriors_full(feature_list, words)
         from .trellis import DiagModelPack, FeatureBatch, state_posteriors, viterbi_decode_best
         if self._pack is None:
             self._pack = DiagModelPack.from_models(self._model_list())

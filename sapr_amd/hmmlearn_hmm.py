@@ -308,10 +308,17 @@ class GaussianHMM:
         return self.covariance_type in ("full", "tied")
 
     def _full_params(self):
-        """``(startprob, transmat, means[S, D], covars[S, D, D])`` as :func:`sapr_amd.full_cov.pack_models` takes it."""
+        """``(startprob, transmat, means[S, D], covars[S, D, D])`` as :func:`sapr_amd.full_cov.pack_models` takes it.
+        A "diag" or "spherical" model is expanded to diagonal matrices, so that a vocabulary may mix the types
+        (``full_cov.FullPack.from_models``)."""
         cv = np.asarray(self._covars_, dtype=np.float64)
         if self.covariance_type == "tied":
             cv = np.broadcast_to(cv, (self.n_components,) + cv.shape)
+        elif self.covariance_type == "spherical":
+            D = int(np.shape(self.means_)[1])
+            cv = cv[:, None, None] * np.eye(D)
+        elif self.covariance_type == "diag":
+            cv = np.array([np.diag(c) for c in cv])
         return (np.asarray(self.startprob_, dtype=np.float64), np.asarray(self.transmat_, dtype=np.float64),
                 np.asarray(self.means_, dtype=np.float64), cv)
 
