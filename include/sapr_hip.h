@@ -423,6 +423,59 @@ int sapr_full_vocab(const float *feats, const int64_t *offsets, const int32_t *o
                     double *score /* [n_utts][W] */, int32_t *best_word /* [n_utts], may be NULL */,
                     double *word_post /* [n_utts][W], may be NULL; FORWARD only */, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Connected-word recognition (csrc/connected.hip): one-pass Viterbi over the word loop — the end of any word may be
+ * followed by the start of any word — for a recording that holds several words in a row.  The definition is the CPU
+ * restatement tests/_connected_ref.py (plain numpy, float64); with b_t(w,s) = logb[t][w * SP + s]:
+ *     delta_0(w,j) = log_start[w][j] + b_0(w,j)
+ *     E_{t-1}      = max over (w,s) in flat order of (delta_{t-1}(w,s) + log_exit[w][s])
+ *     within       = max_i (delta_{t-1}(w,i) + log_trans[w][i][j])            i ascending, the first maximum
+ *     entry        = (E_{t-1} + word_penalty) + log_start[w][j]
+ *     delta_t(w,j) = max(within, entry) + b_t(w,j)                            entry only where strictly greater
+ *     score        = max over (w,s) of (delta_{T-1}(w,s) + log_exit[w][s])    lowest flat index w * SP + s on ties
+ * The additions are made in the order written, so the recursion is float64 adds and compares only and its outputs are
+ * bit for bit numpy's.  log_exit[w][s] = -inf: a word may not end in state s.
+ *
+ * Layout: sapr_connected_layout returns the padded shape — SP in {4, 10, 18} states per word, DP in {13, 26, 39}
+ * features, R = W * SP flat states (R <= 256: the flat states lie along the lanes of one wavefront, up to 4 per lane).
+ * Any of the three outputs may be NULL.
+ *
+ * Stage 1, sapr_connected_emit_diag: logb[total_frames][R] float64 for diagonal Gaussians, frame-parallel,
+ *     logb = -0.5 * (gconst + sum_d ((x_d - mean_d) * (x_d - mean_d)) * (1 / var_d)),  d ascending.
+ *   feats  [total_frames][D] float32
+ *   ops    [R][1 + 2 DP] float64, the operand block the host builds from the arrays sapr_diag_pack takes
+ *          (means[W][S][D], vars, gconst): per flat state {gconst, mean[DP], 1 / var[DP]}.  Padding features carry
+ *          mean 0 and coefficient 0 (they add +0.0); a padding state carries gconst = +inf, mean 0, coefficient 0
+ *          and comes out as -inf.  (sapr_amd/connected.py emit_operands builds it.)
+ * Stage 2, sapr_connected_viterbi: the recursion over a logb it is given (any emission family may supply one).
+ *   logb       [total_frames][R] float64; offsets[n_utts + 1] as everywhere (frames of utterance u:
+ *              offsets[u] .. offsets[u + 1]); offsets that leave the batch are served as an empty utterance
+ *   log_start  [W][S], log_trans [W][S][S], log_exit [W][S] float64 (the models' own S: the kernel pads to SP with
+ *              -inf); word_penalty is added once per word boundary
+ *   workspace  sapr_connected_workspace_bytes: back-pointers, one byte per (frame, flat state), rounded up to 16,
+ *              then one int32 per frame (the flat arg-max of E_t).  logb is the caller's buffer.
+ *   score      [n_utts]; -inf for an utterance without frames
+ *   n_words    [n_utts], may be NULL: words on the best path; 0 where the score is not finite
+ *   path_word, path_state [total_frames] int32, path_entry [total_frames] uint8, each may be NULL: per frame the
+ *              word, its state, and 1 where a word begins (frame 0 and wherever `entry` won; the same word may follow
+ *              itself).  Where the score is not finite: -1, -1, 0.
+ * No atomics: outputs are bit-identical from run to run, and an utterance's outputs are a function of its own frames
+ * and the network alone.  Non-finite values propagate, nothing is repaired.
+ *
+ * Bad sizes, NULL required pointers and a workspace that is too small return SAPR_ERR_ARG, S > 18, D > 39 or
+ * W * SP > 256 SAPR_ERR_UNSUPPORTED (from the layout and size functions too), all before any launch; n_utts == 0
+ * (total_frames == 0 for the emission) returns 0 after these checks. */
+int sapr_connected_layout(int32_t W, int32_t S, int32_t D, int32_t *SP, int32_t *DP, int32_t *R);
+int sapr_connected_workspace_bytes(int64_t total_frames, int64_t n_utts, int32_t W, int32_t S, size_t *bytes);
+int sapr_connected_emit_diag(const float *feats, int64_t total_frames, int32_t D, const double *ops, int32_t W,
+                             int32_t S, double *logb /* [total_frames][R] */, void *stream);
+int sapr_connected_viterbi(const double *logb, const int64_t *offsets, int64_t n_utts, int64_t total_frames,
+                           const double *log_start, const double *log_trans, const double *log_exit,
+                           double word_penalty, int32_t W, int32_t S, void *workspace, size_t workspace_bytes,
+                           double *score, int32_t *n_words /* may be NULL */, int32_t *path_word /* may be NULL */,
+                           int32_t *path_state /* may be NULL */, uint8_t *path_entry /* may be NULL */,
+                           void *stream);
+
 /* Flat start of HMMLearnModel (hmmlearn_hmm.py:83-94: np.mean / np.var over axis 0 of the concatenated float32
  * features): numpy adds row after row in float32, so each column is one sequential float32 chain — reproduced
  * bit for bit.  center == NULL: out[d] = sum_r x[r][d]; else out[d] = sum_r RN32(RN32(x[r][d] - center[d])^2).

@@ -82,7 +82,14 @@ SIGNATURES = {
     "sapr_full_vocab_workspace_bytes": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int32, C.POINTER(c_size_t)]),
     "sapr_full_vocab": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_int32,
                                 c_int32, c_int32, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "sapr_colsum_f32": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
+    "sapr_connected_layout": (c_int, [c_int32, c_int32, c_int32, C.POINTER(c_int32), C.POINTER(c_int32),
+                                      C.POINTER(c_int32)]),
+    "sapr_connected_workspace_bytes": (c_int, [c_int64, c_int64, c_int32, c_int32, C.POINTER(c_size_t)]),
+    "sapr_connected_emit_diag": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "sapr_connected_viterbi": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_double,
+                                       c_int32, c_int32, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p]),
+    "sapr_colsum_f32":(c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     "sapr_custom_estep": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32] + [c_void_p] * 5
                           + [c_int64] + [c_void_p] * 6 + [c_void_p]),
     "sapr_custom_stage_features": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int64, c_void_p, c_void_p,

@@ -21,7 +21,8 @@ SOURCES = ["viterbi_exact_39_18_t1s1.hip", "viterbi_exact_39_18_t1s0.hip", "vite
            "viterbi_exact_39_10_t1s1.hip", "viterbi_exact_39_10_t1s0.hip",
            "viterbi_exact_39_10_t0s1.hip", "viterbi_exact_39_10_t0s0.hip", "viterbi_exact_13_18.hip",
            "viterbi_bound.hip", "mfcc.hip", "viterbi_exact_13_10.hip", "custom.hip", "viterbi.hip", "common.hip",
-           "resample.hip", "kmeans.hip", "gmm_hmm.hip", "gmm_vocab.hip", "full_vocab.hip"]
+           "resample.hip", "kmeans.hip", "gmm_hmm.hip", "gmm_vocab.hip", "full_vocab.hip",
+           "connected.hip"]
 # -ffp-contract=off: the trellis kernels must perform the individually rounded IEEE
 # operations numpy performs (bit-identical Viterbi scores); kernels that want FMAs
 # call fma()/__builtin_fmaf explicitly.

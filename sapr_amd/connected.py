@@ -1,0 +1,277 @@
+"""Connected-word recognition over the HIP kernels of ``csrc/connected.hip``: a one-pass Viterbi search over the word
+loop, in which the end of any word may be followed by the start of any word, so a recording of several words in a row
+comes back as a word string with its segment boundaries (the other scorers label a whole recording as ONE word).
+
+Two stages (include/sapr_hip.h): ``sapr_connected_emit_diag`` evaluates ``logb[total_frames, W * SP]`` for
+diagonal-Gaussian word models, ``sapr_connected_viterbi`` runs the recursion over any ``logb`` it is given.  The CPU
+restatement ``tests/_connected_ref.py`` is the definition; the recursion reproduces it bit for bit.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _lib
+
+MAX_STATES, MAX_DIMS, MAX_FLAT = 18, 39, 256
+_TINY = np.finfo(float).tiny
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def layout(W, S, D=1):
+    """(SP, DP, R): the padded shape the kernels run (W, S, D) at; R = W * SP flat states."""
+    sp, dp, r = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    _lib.check(_lib.load().sapr_connected_layout(W, S, D, C.byref(sp), C.byref(dp), C.byref(r)),
+               "sapr_connected_layout")
+    return int(sp.value), int(dp.value), int(r.value)
+
+
+def workspace_bytes(total_frames, n_utts, W, S) -> int:
+    n = C.c_size_t(0)
+    _lib.check(_lib.load().sapr_connected_workspace_bytes(total_frames, n_utts, W, S, C.byref(n)),
+               "sapr_connected_workspace_bytes")
+    return int(n.value)
+
+
+def emit_operands(means, vars_, gconst, n_states=None) -> np.ndarray:
+    """The operand block of ``sapr_connected_emit_diag`` from the arrays ``sapr_diag_pack`` takes (``means[W, S, D]``,
+    ``vars[W, S, D]``, ``gconst[W, S]``): float64 ``[W * SP, 1 + 2 DP]``, per flat state ``{gconst, mean[DP],
+    1 / var[DP]}``.  Padding features carry mean 0 and coefficient 0; the states from ``n_states[w]`` on (and up to SP)
+    carry ``gconst = +inf`` and emit ``-inf``."""
+    means = np.asarray(means, dtype=np.float64)
+    vars_ = np.asarray(vars_, dtype=np.float64)
+    gconst = np.asarray(gconst, dtype=np.float64)
+    W, S, D = means.shape
+    if vars_.shape != (W, S, D) or gconst.shape != (W, S):
+        raise ValueError("inconsistent model shapes")
+    SP, DP, R = layout(W, S, D)
+    n_states = [S] * W if n_states is None else list(n_states)
+    ops = np.zeros((W, SP, 1 + 2 * DP))
+    ops[:, :, 0] = np.inf
+    for w in range(W):
+        k = int(n_states[w])
+        ops[w, :k, 0] = gconst[w, :k]
+        ops[w, :k, 1:1 + D] = means[w, :k]
+        ops[w, :k, 1 + DP:1 + DP + D] = 1.0 / vars_[w, :k]
+    return ops.reshape(R, 1 + 2 * DP)
+
+
+class ConnectedNetwork:
+    """The word loop: W word models padded to S = the largest model's states.  ``log_start[W, S]``,
+    ``log_trans[W, S, S]``, ``log_exit[W, S]`` (``-inf``: a word may not end in this state; a padded state has ``-inf``
+    everywhere) and the scalar ``word_penalty`` added once per word boundary.  Built from models
+    (:meth:`from_models`) it also carries the diagonal-Gaussian emission parameters ``means``, ``vars``, ``gconst``."""
+
+    def __init__(self, log_start, log_trans, log_exit, word_penalty=0.0, n_states=None, means=None, vars_=None,
+                 gconst=None):
+        self.log_start = np.ascontiguousarray(log_start, dtype=np.float64)
+        self.log_trans = np.ascontiguousarray(log_trans, dtype=np.float64)
+        self.log_exit = np.ascontiguousarray(log_exit, dtype=np.float64)
+        if self.log_start.ndim != 2:
+            raise ValueError("log_start must be [W, S]")
+        self.W, self.S = (int(k) for k in self.log_start.shape)
+        if self.log_trans.shape != (self.W, self.S, self.S) or self.log_exit.shape != (self.W, self.S):
+            raise ValueError("log_trans must be [W, S, S] and log_exit [W, S]")
+        self.word_penalty = float(word_penalty)
+        self.n_states = [self.S] * self.W if n_states is None else [int(k) for k in n_states]
+        self.means = None if means is None else np.ascontiguousarray(means, dtype=np.float64)
+        self.vars = None if vars_ is None else np.ascontiguousarray(vars_, dtype=np.float64)
+        self.gconst = None if gconst is None else np.ascontiguousarray(gconst, dtype=np.float64)
+        self.D = 0 if self.means is None else int(self.means.shape[2])
+        self.SP, self.DP, self.R = layout(self.W, self.S, max(self.D, 1))
+        self._dev = None
+
+    @staticmethod
+    def from_models(models, exit_states="last", word_penalty=0.0) -> "ConnectedNetwork":
+        """``models``: fitted "diag" or "spherical" ``GaussianHMM`` objects that share the feature width, read through
+        the parameters ``trellis.DiagModelPack.from_models`` reads (``startprob_``, ``transmat_``, ``means_``,
+        ``_covars_``; variances floored at float64 tiny, ``gconst = D log 2 pi + sum log var``).  A mixed number of
+        states is padded.  ``exit_states``: ``"last"`` (a word ends in its model's own last state), ``"any"``, or an
+        array ``[W, S]`` of log exit scores."""
+        models = list(models)
+        if not models:
+            raise ValueError("empty vocabulary")
+        for m in models:
+            ct = getattr(m, "covariance_type", "diag")
+            if ct not in ("diag", "spherical"):
+                raise ValueError(f"connected-word decoding serves 'diag' and 'spherical' models; got "
+                                 f"covariance_type={ct!r}")
+        n_states = [int(np.asarray(m.startprob_).shape[0]) for m in models]
+        D = int(np.asarray(models[0].means_).shape[1])
+        W, S = len(models), max(n_states)
+        log_start = np.full((W, S), -np.inf)
+        log_trans = np.full((W, S, S), -np.inf)
+        means = np.zeros((W, S, D))
+        vars_ = np.ones((W, S, D))
+        gconst = np.full((W, S), np.inf)
+        with np.errstate(divide="ignore"):
+            for w, (m, k) in enumerate(zip(models, n_states)):
+                mu = np.asarray(m.means_, dtype=np.float64)
+                if mu.shape != (k, D):
+                    raise ValueError("the models must share the feature width")
+                cv = np.asarray(m._covars_, dtype=np.float64)
+                cv = np.broadcast_to(cv[:, None], mu.shape) if cv.ndim == 1 else cv  # (spherical)
+                var = np.maximum(cv, _TINY)
+                log_start[w, :k] = np.log(np.asarray(m.startprob_, dtype=np.float64))
+                log_trans[w, :k, :k] = np.log(np.asarray(m.transmat_, dtype=np.float64))
+                means[w, :k] = mu
+                vars_[w, :k] = var
+                gconst[w, :k] = D * np.log(2 * np.pi) + np.log(var).sum(axis=-1)
+        if isinstance(exit_states, str):
+            if exit_states not in ("last", "any"):
+                raise ValueError(f"exit_states must be 'last', 'any' or an array [W, S], got {exit_states!r}")
+            log_exit = np.full((W, S), -np.inf)
+            for w, k in enumerate(n_states):
+                if exit_states == "last":
+                    log_exit[w, k - 1] = 0.0
+                else:
+                    log_exit[w, :k] = 0.0
+        else:
+            log_exit = np.array(exit_states, dtype=np.float64)
+            if log_exit.shape != (W, S):
+                raise ValueError(f"exit_states must be [W={W}, S={S}], got {log_exit.shape}")
+            for w, k in enumerate(n_states):
+                log_exit[w, k:] = -np.inf
+        return ConnectedNetwork(log_start, log_trans, log_exit, word_penalty, n_states, means, vars_, gconst)
+
+    def device(self, dev):
+        """The device copies ``(log_start, log_trans, log_exit, ops | None)``; made once per device."""
+        torch = _torch()
+        if self._dev is None or self._dev[0].device != dev:
+            ops = None
+            if self.means is not None:
+                ops = torch.from_numpy(emit_operands(self.means, self.vars, self.gconst, self.n_states)).to(dev)
+            self._dev = tuple(torch.from_numpy(a).to(dev) for a in (self.log_start, self.log_trans, self.log_exit)) \
+                + (ops,)
+        return self._dev
+
+
+@dataclass
+class ConnectedResult:
+    score: np.ndarray       # [N] f64: the best path's log score; -inf for an utterance without frames
+    n_words: np.ndarray     # [N] i32: words on the best path; 0 where the score is not finite
+    path_word: np.ndarray   # [total_frames] i32 (-1 where the score is not finite)
+    path_state: np.ndarray  # [total_frames] i32 (-1 where the score is not finite)
+    path_entry: np.ndarray  # [total_frames] u8: 1 where a word begins
+    offsets: np.ndarray     # [N + 1] i64
+
+    def segments(self, u):
+        """``[(word_index, start, end_exclusive), ...]`` of utterance ``u``, frames counted from its own start."""
+        lo, hi = int(self.offsets[u]), int(self.offsets[u + 1])
+        if int(self.n_words[u]) == 0:
+            return []
+        starts = np.flatnonzero(self.path_entry[lo:hi]).tolist()
+        ends = starts[1:] + [hi - lo]
+        return [(int(self.path_word[lo + a]), a, b) for a, b in zip(starts, ends)]
+
+    def words(self, u):
+        return [w for w, _, _ in self.segments(u)]
+
+
+def _offsets(lengths):
+    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    if lengths.size and lengths.min() < 0:
+        raise ValueError("lengths must be >= 0")
+    offs = np.zeros(lengths.size + 1, dtype=np.int64)
+    np.cumsum(lengths, out=offs[1:])
+    return lengths, offs
+
+
+def emit_diag(feats, network: ConnectedNetwork):
+    """``sapr_connected_emit_diag``: device ``feats[total_frames, D]`` float32 -> device ``logb[total_frames, R]``."""
+    torch = _torch()
+    if network.means is None:
+        raise ValueError("the network carries no emission parameters (build it with ConnectedNetwork.from_models)")
+    if feats.dtype != torch.float32 or feats.dim() != 2 or not feats.is_contiguous():
+        raise ValueError("feats must be a contiguous float32 [total_frames, D] tensor")
+    if int(feats.shape[1]) != network.D:
+        raise ValueError(f"the utterances have {int(feats.shape[1])} features, the models {network.D}")
+    ops = network.device(feats.device)[3]
+    total = int(feats.shape[0])
+    logb = torch.empty((total, network.R), dtype=torch.float64, device=feats.device)
+    _lib.check(_lib.load().sapr_connected_emit_diag(_lib.ptr(feats), total, network.D, _lib.ptr(ops), network.W,
+                                                    network.S, _lib.ptr(logb), _lib.current_stream()),
+               "sapr_connected_emit_diag")
+    return logb
+
+
+def _run_viterbi(logb, offs_dev, n_utts, total, network):
+    """One ``sapr_connected_viterbi`` -> device tensors (score, n_words, path_word, path_state, path_entry)."""
+    torch = _torch()
+    dev = logb.device
+    ls, lt, lx, _ = network.device(dev)
+    ws_bytes = workspace_bytes(total, n_utts, network.W, network.S)
+    workspace = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    score = torch.empty(n_utts, dtype=torch.float64, device=dev)
+    n_words = torch.empty(n_utts, dtype=torch.int32, device=dev)
+    path_word = torch.empty(total, dtype=torch.int32, device=dev)
+    path_state = torch.empty(total, dtype=torch.int32, device=dev)
+    path_entry = torch.empty(total, dtype=torch.uint8, device=dev)
+    _lib.check(_lib.load().sapr_connected_viterbi(
+        _lib.ptr(logb), _lib.ptr(offs_dev), n_utts, total, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx),
+        network.word_penalty, network.W, network.S, _lib.ptr(workspace), ws_bytes, _lib.ptr(score), _lib.ptr(n_words),
+        _lib.ptr(path_word), _lib.ptr(path_state), _lib.ptr(path_entry), _lib.current_stream()),
+        "sapr_connected_viterbi")
+    return score, n_words, path_word, path_state, path_entry
+
+
+def _result(tensors, offs) -> ConnectedResult:
+    host = [a.copy() for a in _lib.to_host(*tensors)]  # (out of the pinned buffers)
+    return ConnectedResult(*host, offsets=offs)
+
+
+def connected_viterbi(logb, lengths, network: ConnectedNetwork) -> ConnectedResult:
+    """The recursion over a given ``logb``: float64 ``[total_frames, W, S]`` (the network's own S: padded here with
+    ``-inf``), ``[total_frames, W, SP]`` or ``[total_frames, W * SP]``, a host array or a device tensor; host
+    ``lengths``.  Any emission family may supply ``logb``."""
+    torch = _torch()
+    dev = _lib.require_gpu()
+    lengths, offs = _offsets(lengths)
+    if not torch.is_tensor(logb):
+        logb = torch.from_numpy(np.ascontiguousarray(logb, dtype=np.float64))
+    logb = logb.to(dev)
+    total = int(offs[-1])
+    if logb.dtype != torch.float64 or int(logb.shape[0]) != total:
+        raise ValueError("logb must be float64 with sum(lengths) rows")
+    W, S, SP, R = network.W, network.S, network.SP, network.R
+    if tuple(logb.shape[1:]) == (W, S) and S != SP:
+        wide = torch.full((total, W, SP), float("-inf"), dtype=torch.float64, device=dev)
+        wide[:, :, :S] = logb
+        logb = wide
+    if tuple(logb.shape[1:]) not in ((W, SP), (R,)):
+        raise ValueError(f"logb must be [total_frames, {W}, {S}], [total_frames, {W}, {SP}] or [total_frames, {R}]; "
+                         f"got {tuple(logb.shape)}")
+    logb = logb.reshape(total, R).contiguous()
+    offs_dev = torch.from_numpy(offs).to(dev)
+    return _result(_run_viterbi(logb, offs_dev, int(lengths.size), total, network), offs)
+
+
+def connected_decode(batch_or_feature_list, network: ConnectedNetwork) -> ConnectedResult:
+    """Emission and recursion for diagonal-Gaussian word models: a ``trellis.FeatureBatch`` or a list of frame-major
+    ``(T, D)`` feature arrays -> :class:`ConnectedResult`."""
+    torch = _torch()
+    from .gmm_hmm import vocab_features
+    b = batch_or_feature_list
+    if hasattr(b, "offsets") and hasattr(b, "order"):
+        feats, offs_dev, _, lengths, _ = vocab_features(b)
+        lengths, offs = _offsets(lengths)
+    else:
+        mats = [np.ascontiguousarray(np.asarray(f), dtype=np.float32) for f in b]
+        if len(mats) == 0:
+            raise ValueError("empty utterance list")
+        D = mats[0].shape[1] if mats[0].ndim == 2 else -1
+        if any(m.ndim != 2 or m.shape[1] != D for m in mats):
+            raise ValueError("all utterances must be (T, D) arrays that share the feature dimension")
+        lengths, offs = _offsets([m.shape[0] for m in mats])
+        dev = _lib.require_gpu()
+        packed = np.concatenate(mats, axis=0) if offs[-1] else np.zeros((0, D), np.float32)
+        feats = torch.from_numpy(packed).to(dev)
+        offs_dev = torch.from_numpy(offs).to(dev)
+    logb = emit_diag(feats, network)
+    return _result(_run_viterbi(logb, offs_dev, int(lengths.size), int(offs[-1]), network), offs)

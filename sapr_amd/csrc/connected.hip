@@ -1,0 +1,383 @@
+// Connected-word recognition on gfx950: one-pass Viterbi over the word loop (the end of any word may be followed by
+// the start of any word), in two stages cut where the dependence changes.  CPU restatement, which is
+// the definition: tests/_connected_ref.py.
+//
+// Stage 1, sapr_connected_emit_diag: logb[total_frames][R = W * SP] for diagonal Gaussians, frame-parallel, one
+// thread per frame.  The frame's DP features stay in registers as float64, the lane walks the R flat states in a
+// rolled loop and every parameter is wavefront-uniform: the operand block comes in through a __restrict__
+// kernel-argument pointer, so the compiler issues scalar loads (as gmm_hmm.hip does; no inline assembly).  The
+// operand block is built by the host from the arrays sapr_diag_pack takes (connected.py emit_operands), per flat
+// state 1 + 2 DP doubles: {gconst, mean[DP], 1 / var[DP]}; padding features carry mean 0 and coefficient 0 and add
+// +0.0, a padding state carries gconst = +inf and comes out as -inf.
+//     logb = -0.5 * (gconst + sum_d ((x_d - mean_d) * (x_d - mean_d)) * (1 / var_d)),   d ascending
+//
+// Stage 2, sapr_connected_viterbi: the recursion over a given logb; it knows nothing about the emission family.
+//     One wavefront serves one utterance (four utterances per workgroup, which share the transition table in LDS).
+//     The R <= 256 flat states lie along the lanes, RL in {1, 2, 4} per lane: flat state r = k * 64 + lane sits in
+//     register k of its lane, so row t of logb is RL coalesced 512-byte reads and the next frame's row is in flight
+//     under the current frame.  The predecessor at distance d = j - i of state r is flat state r - d: lane
+//     (lane - d) & 63 (ds_bpermute), register k, or k -/+ 1 where lane - d leaves 0..63 (d runs over
+//     -(SP - 1) .. SP - 1: a dense model also steps back).  Distances at which no transition of the
+//     vocabulary is finite are skipped wavefront-uniformly (the mask is taken from the table by the kernel itself:
+//     a bidiagonal vocabulary costs two candidates per state, a dense one 2 S - 1).  E_{t-1} = max_r (delta + log_exit)
+//     is one wave-wide butterfly over (value, flat index), the lowest index among equals.
+//     Back-pointers: one byte per (frame, flat state) — the predecessor state, or kEntry where the word entry won —
+//     and the flat arg-max of E per frame (int32), both in the workspace.  A second kernel, one lane per utterance,
+//     walks back and writes path_word, path_state, path_entry, n_words.
+//
+// The recursion is float64 adds and compares in the order of the definition (within candidates i ascending, first
+// maximum; entry only where strictly greater; the emission added last): bit for bit the reference.  No atomics; an
+// utterance's outputs are a function of its own frames and the network alone.  Non-finite values propagate.
+#include "sapr_common.h"
+
+namespace sapr {
+namespace {
+
+constexpr int kCnMaxS = 18, kCnMaxD = 39, kCnMaxR = 256;
+constexpr int kCnBlock = 256;         // 4 wavefronts per workgroup
+constexpr int kCnWaves = kCnBlock / kWave;
+constexpr int kEntry = 255;           // back-pointer byte: the word was entered at this frame
+
+constexpr int cn_sp_of(int S) { return S <= 4 ? 4 : (S <= 10 ? 10 : 18); }
+constexpr int cn_dp_of(int D) { return D <= 13 ? 13 : (D <= 26 ? 26 : 39); }
+
+inline int cn_check_shape(int32_t W, int32_t S, int32_t D) {
+  if (S > kCnMaxS || D > kCnMaxD || static_cast<int64_t>(W) * cn_sp_of(S) > kCnMaxR)
+    return fail(SAPR_ERR_UNSUPPORTED,
+                "the connected-word kernels serve S in 1..%d, D in 1..%d and W * SP <= %d; got W=%d S=%d D=%d",
+                kCnMaxS, kCnMaxD, kCnMaxR, W, S, D);
+  return 0;
+}
+
+inline size_t cn_align16(size_t x) { return (x + 15) / 16 * 16; }
+
+// ---------------------------------------------------------------------------------------
+// stage 1: diagonal-Gaussian emissions
+// ---------------------------------------------------------------------------------------
+template <int DP>
+__global__ __launch_bounds__(kCnBlock) void connected_emit_kernel(const float *__restrict__ feats,
+                                                                   int64_t total_frames, int32_t D, int32_t R,
+                                                                   const double *__restrict__ ops,
+                                                                   double *__restrict__ logb) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * kCnBlock + threadIdx.x;
+  const bool live = t < total_frames;
+  double x[DP];
+  const float *__restrict__ xp = feats + (live ? t : 0) * D;
+#pragma unroll
+  for (int d = 0; d < DP; ++d) x[d] = (live && d < D) ? static_cast<double>(xp[d]) : 0.0;
+  double *__restrict__ out = logb + (live ? t : 0) * R;
+#pragma unroll 1
+  for (int r = 0; r < R; ++r) {
+    const double *__restrict__ o = ops + static_cast<int64_t>(r) * (1 + 2 * DP);  // wavefront-uniform: scalar loads
+    double acc = 0.0;
+#pragma unroll
+    for (int d = 0; d < DP; ++d) {
+      const double diff = x[d] - o[1 + d];
+      acc += (diff * diff) * o[1 + DP + d];
+    }
+    const double v = -0.5 * (o[0] + acc);
+    if (live) out[r] = v;
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// stage 2: the recursion
+// ---------------------------------------------------------------------------------------
+struct ValIdx {
+  double v;
+  int i;
+};
+
+// wave-wide first maximum: the greatest value, among equals the lowest flat index; every lane gets the result
+__device__ __forceinline__ ValIdx wave_argmax_first(ValIdx a) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double ov = __shfl_xor(a.v, o, kWave);
+    const int oi = __shfl_xor(a.i, o, kWave);
+    const bool take = ov > a.v || (ov == a.v && oi < a.i);
+    a.v = take ? ov : a.v;
+    a.i = take ? oi : a.i;
+  }
+  return a;
+}
+
+template <int RL>
+__global__ __launch_bounds__(kCnBlock) void connected_viterbi_kernel(
+    const double *__restrict__ logb, const int64_t *__restrict__ offsets, int64_t n_utts, int64_t total_frames,
+    const double *__restrict__ log_start, const double *__restrict__ log_trans, const double *__restrict__ log_exit,
+    double word_penalty, int32_t W, int32_t S, int32_t SP, uint8_t *__restrict__ bp, int32_t *__restrict__ exit_idx,
+    double *__restrict__ score) {
+  constexpr int RP = kWave * RL;  // flat states the lanes hold (R <= RP)
+  extern __shared__ double tab[];  // [SP][RP]: tab[i][r] = log_trans[w][i][s], the transition INTO flat state r from i
+  const int R = W * SP;
+  for (int n = threadIdx.x; n < SP * RP; n += kCnBlock) {
+    const int i = n / RP, r = n - i * RP;
+    const int w = r / SP, s = r - w * SP;
+    double v = neg_inf();
+    if (r < R && s < S && i < S) v = log_trans[(static_cast<int64_t>(w) * S + i) * S + s];
+    tab[n] = v;
+  }
+  __syncthreads();
+
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t u = static_cast<int64_t>(blockIdx.x) * kCnWaves + (threadIdx.x / kWave);
+  if (u >= n_utts) return;  // (after the only barrier; a whole wavefront leaves)
+  int64_t beg = offsets[u], end = offsets[u + 1];
+  if (beg < 0 || end < beg || end > total_frames) end = beg = 0;  // offsets that leave the batch: served as empty
+  const int64_t T = end - beg;
+
+  double ls[RL], lx[RL], delta[RL], bn[RL];
+  int sk[RL];
+  bool ok[RL];
+#pragma unroll
+  for (int k = 0; k < RL; ++k) {
+    const int r = k * kWave + lane;
+    const int w = r / SP, s = r - w * SP;
+    ok[k] = r < R;
+    sk[k] = s;
+    const bool real = ok[k] && s < S;
+    ls[k] = real ? log_start[w * S + s] : neg_inf();
+    lx[k] = real ? log_exit[w * S + s] : neg_inf();
+    delta[k] = neg_inf();
+  }
+  // the distances d = j - i in -(SP - 1) .. SP - 1 at which some transition of the vocabulary is finite
+  // (wavefront-uniform; bit d + SP - 1)
+  uint64_t dmask = 0;
+  for (int d = 1 - SP; d < SP; ++d) {
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < RL; ++k) {
+      const int i = sk[k] - d;
+      const bool in = i >= 0 && i < SP;
+      any |= in && !(tab[(in ? i : 0) * RP + k * kWave + lane] == neg_inf());
+    }
+    if (__ballot(any)) dmask |= 1ull << (d + SP - 1);
+  }
+  dmask = (static_cast<uint64_t>(__builtin_amdgcn_readfirstlane(static_cast<unsigned>(dmask >> 32))) << 32) |
+          __builtin_amdgcn_readfirstlane(static_cast<unsigned>(dmask));
+
+  const double *__restrict__ brow = logb + beg * R;
+#pragma unroll
+  for (int k = 0; k < RL; ++k) bn[k] = (ok[k] && T > 0) ? brow[k * kWave + lane] : neg_inf();
+
+  ValIdx E{neg_inf(), 0};
+  for (int64_t t = 0; t < T; ++t) {
+    double b[RL];
+#pragma unroll
+    for (int k = 0; k < RL; ++k) b[k] = bn[k];
+    {  // the next frame's row in flight under this frame's chain
+      const int64_t tn = t + 1 < T ? t + 1 : t;
+#pragma unroll
+      for (int k = 0; k < RL; ++k) bn[k] = ok[k] ? brow[tn * R + k * kWave + lane] : neg_inf();
+    }
+    double v[RL];
+    int back[RL];
+    if (t == 0) {
+#pragma unroll
+      for (int k = 0; k < RL; ++k) {
+        v[k] = ls[k];
+        back[k] = kEntry;
+      }
+    } else {
+      double best[RL];
+#pragma unroll
+      for (int k = 0; k < RL; ++k) {
+        best[k] = neg_inf();
+        back[k] = 0;
+      }
+      // predecessors i ascending = distances descending; the first maximum stays (strict compare)
+      for (int d = SP - 1; d > -SP; --d) {
+        if (!((dmask >> (d + SP - 1)) & 1ull)) continue;  // (uniform)
+        // flat state r - d: lane (lane - d) & 63 of register k, of k - 1 where lane < d, of k + 1 where lane - d >= 64
+        const int off = lane - d;
+        const int src = off & (kWave - 1);
+        double rot[RL];
+#pragma unroll
+        for (int k = 0; k < RL; ++k) rot[k] = __shfl(delta[k], src, kWave);
+#pragma unroll
+        for (int k = 0; k < RL; ++k) {
+          const double below = k > 0 ? rot[k > 0 ? k - 1 : 0] : neg_inf();
+          const double above = k + 1 < RL ? rot[k + 1 < RL ? k + 1 : k] : neg_inf();
+          const double prev = off < 0 ? below : (off >= kWave ? above : rot[k]);
+          const int i = sk[k] - d;
+          const bool in = i >= 0 && i < SP;  // (outside the word: no such predecessor)
+          const double lt = tab[(in ? i : 0) * RP + k * kWave + lane];
+          const double c = prev + (in ? lt : neg_inf());
+          const bool take = c > best[k];
+          best[k] = take ? c : best[k];
+          back[k] = take ? i : back[k];
+        }
+      }
+      const double ep = E.v + word_penalty;
+#pragma unroll
+      for (int k = 0; k < RL; ++k) {
+        const double entry = ep + ls[k];
+        const bool take = entry > best[k];
+        v[k] = take ? entry : best[k];
+        back[k] = take ? kEntry : back[k];
+      }
+    }
+    uint8_t *__restrict__ bprow = bp + (beg + t) * R;
+    ValIdx e{neg_inf(), lane};
+#pragma unroll
+    for (int k = 0; k < RL; ++k) {
+      delta[k] = v[k] + b[k];
+      if (ok[k]) bprow[k * kWave + lane] = static_cast<uint8_t>(back[k]);
+      const double c = delta[k] + lx[k];
+      const bool take = k == 0 || c > e.v;  // the lane's own states in flat order: the first maximum stays
+      e.i = take ? k * kWave + lane : e.i;
+      e.v = take ? c : e.v;
+    }
+    E = wave_argmax_first(e);
+    E.i = __builtin_amdgcn_readfirstlane(E.i);
+    E.i = E.i < R ? E.i : R - 1;  // (only a NaN lattice can name a lane without a state: keep the walk inside the row)
+    if (lane == 0) exit_idx[beg + t] = E.i;
+  }
+  if (lane == 0) score[u] = T > 0 ? E.v : neg_inf();
+}
+
+// one lane per utterance walks back from the best exit of the last frame
+__global__ __launch_bounds__(kCnBlock) void connected_backtrace_kernel(
+    const int64_t *__restrict__ offsets, int64_t n_utts, int64_t total_frames, int32_t SP, int32_t R,
+    const uint8_t *__restrict__ bp, const int32_t *__restrict__ exit_idx, const double *__restrict__ score,
+    int32_t *__restrict__ n_words, int32_t *__restrict__ path_word, int32_t *__restrict__ path_state,
+    uint8_t *__restrict__ path_entry) {
+  const int64_t u = static_cast<int64_t>(blockIdx.x) * kCnBlock + threadIdx.x;
+  if (u >= n_utts) return;
+  const int64_t beg = offsets[u], end = offsets[u + 1];
+  if (beg < 0 || end < beg || end > total_frames) {
+    if (n_words) n_words[u] = 0;
+    return;
+  }
+  const int64_t T = end - beg;
+  const double sc = score[u];
+  if (!(sc - sc == 0.0) || T == 0) {  // a non-finite score has no path
+    for (int64_t t = 0; t < T; ++t) {
+      if (path_word) path_word[beg + t] = -1;
+      if (path_state) path_state[beg + t] = -1;
+      if (path_entry) path_entry[beg + t] = 0;
+    }
+    if (n_words) n_words[u] = 0;
+    return;
+  }
+  int r = exit_idx[beg + T - 1];
+  int nw = 0;
+  for (int64_t t = T - 1; t >= 0; --t) {
+    const int w = r / SP;
+    if (path_word) path_word[beg + t] = w;
+    if (path_state) path_state[beg + t] = r - w * SP;
+    const int b = bp[(beg + t) * R + r];
+    const bool entry = t == 0 || b == kEntry;
+    if (path_entry) path_entry[beg + t] = entry ? 1 : 0;
+    if (entry) {
+      ++nw;
+      if (t > 0) r = exit_idx[beg + t - 1];
+    } else {
+      r = w * SP + (b < SP ? b : 0);
+    }
+  }
+  if (n_words) n_words[u] = nw;
+}
+
+template <int RL>
+int launch_connected(const double *logb, const int64_t *offsets, int64_t n_utts, int64_t total_frames,
+                     const double *log_start, const double *log_trans, const double *log_exit, double word_penalty,
+                     int32_t W, int32_t S, int32_t SP, uint8_t *bp, int32_t *exit_idx, double *score,
+                     hipStream_t stream) {
+  const size_t lds = static_cast<size_t>(SP) * kWave * RL * sizeof(double);
+  const int64_t blocks = (n_utts + kCnWaves - 1) / kCnWaves;
+  SAPR_LAUNCH((connected_viterbi_kernel<RL>), dim3(static_cast<unsigned>(blocks)), dim3(kCnBlock), lds, stream, logb,
+              offsets, n_utts, total_frames, log_start, log_trans, log_exit, word_penalty, W, S, SP, bp, exit_idx,
+              score);
+  SAPR_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+}  // namespace
+}  // namespace sapr
+
+using namespace sapr;
+
+extern "C" int sapr_connected_layout(int32_t W, int32_t S, int32_t D, int32_t *SP, int32_t *DP, int32_t *R) {
+  SAPR_REQUIRE(W > 0 && S > 0 && D > 0, "bad sizes (W=%d S=%d D=%d)", W, S, D);
+  if (int rc = cn_check_shape(W, S, D)) return rc;
+  if (SP) *SP = cn_sp_of(S);
+  if (DP) *DP = cn_dp_of(D);
+  if (R) *R = W * cn_sp_of(S);
+  return 0;
+}
+
+extern "C" int sapr_connected_workspace_bytes(int64_t total_frames, int64_t n_utts, int32_t W, int32_t S,
+                                              size_t *bytes) {
+  SAPR_REQUIRE(bytes && total_frames >= 0 && n_utts >= 0 && W > 0 && S > 0,
+               "bad sizes (total_frames=%lld n_utts=%lld W=%d S=%d)", (long long)total_frames, (long long)n_utts, W, S);
+  if (int rc = cn_check_shape(W, S, 1)) return rc;
+  const size_t R = static_cast<size_t>(W) * cn_sp_of(S);
+  // back-pointers [total_frames][R] bytes (padded to 16), then the exit index of every frame (int32)
+  *bytes = cn_align16(static_cast<size_t>(total_frames) * R) + static_cast<size_t>(total_frames) * sizeof(int32_t);
+  return 0;
+}
+
+extern "C" int sapr_connected_emit_diag(const float *feats, int64_t total_frames, int32_t D, const double *ops,
+                                        int32_t W, int32_t S, double *logb, void *stream) {
+  SAPR_REQUIRE(total_frames >= 0 && W > 0 && S > 0 && D > 0, "bad sizes (total_frames=%lld W=%d S=%d D=%d)",
+               (long long)total_frames, W, S, D);
+  if (int rc = cn_check_shape(W, S, D)) return rc;
+  const int64_t blocks = (total_frames + kCnBlock - 1) / kCnBlock;
+  SAPR_REQUIRE(blocks <= 0x7fffffffLL, "grid too large (%lld blocks)", (long long)blocks);
+  if (total_frames == 0) return 0;
+  SAPR_REQUIRE(feats && ops && logb, "NULL pointer argument");
+  const int32_t R = W * cn_sp_of(S);
+  const dim3 grid(static_cast<unsigned>(blocks)), block(kCnBlock);
+  hipStream_t st = as_stream(stream);
+  switch (cn_dp_of(D)) {
+    case 13: SAPR_LAUNCH((connected_emit_kernel<13>), grid, block, 0, st, feats, total_frames, D, R, ops, logb); break;
+    case 26: SAPR_LAUNCH((connected_emit_kernel<26>), grid, block, 0, st, feats, total_frames, D, R, ops, logb); break;
+    default: SAPR_LAUNCH((connected_emit_kernel<39>), grid, block, 0, st, feats, total_frames, D, R, ops, logb); break;
+  }
+  SAPR_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int sapr_connected_viterbi(const double *logb, const int64_t *offsets, int64_t n_utts,
+                                      int64_t total_frames, const double *log_start, const double *log_trans,
+                                      const double *log_exit, double word_penalty, int32_t W, int32_t S,
+                                      void *workspace, size_t workspace_bytes, double *score, int32_t *n_words,
+                                      int32_t *path_word, int32_t *path_state, uint8_t *path_entry, void *stream) {
+  SAPR_REQUIRE(n_utts >= 0 && total_frames >= 0 && W > 0 && S > 0,
+               "bad sizes (n_utts=%lld total_frames=%lld W=%d S=%d)", (long long)n_utts, (long long)total_frames, W, S);
+  if (int rc = cn_check_shape(W, S, 1)) return rc;
+  size_t need = 0;
+  if (int rc = sapr_connected_workspace_bytes(total_frames, n_utts, W, S, &need)) return rc;
+  SAPR_REQUIRE(workspace_bytes >= need && (need == 0 || workspace), "workspace too small: %zu < %zu", workspace_bytes,
+               need);
+  const int64_t blocks = (n_utts + kCnWaves - 1) / kCnWaves;
+  SAPR_REQUIRE(blocks <= 0x7fffffffLL, "grid too large (%lld blocks)", (long long)blocks);
+  if (n_utts == 0) return 0;
+  SAPR_REQUIRE(offsets && log_start && log_trans && log_exit && score && (total_frames == 0 || logb),
+               "NULL pointer argument");
+  const int32_t SP = cn_sp_of(S);
+  const int32_t R = W * SP;
+  uint8_t *bp = static_cast<uint8_t *>(workspace);
+  int32_t *exit_idx =
+      reinterpret_cast<int32_t *>(bp + cn_align16(static_cast<size_t>(total_frames) * static_cast<size_t>(R)));
+  hipStream_t st = as_stream(stream);
+  int rc;
+  if (R <= kWave)
+    rc = launch_connected<1>(logb, offsets, n_utts, total_frames, log_start, log_trans, log_exit, word_penalty, W, S,
+                             SP, bp, exit_idx, score, st);
+  else if (R <= 2 * kWave)
+    rc = launch_connected<2>(logb, offsets, n_utts, total_frames, log_start, log_trans, log_exit, word_penalty, W, S,
+                             SP, bp, exit_idx, score, st);
+  else
+    rc = launch_connected<4>(logb, offsets, n_utts, total_frames, log_start, log_trans, log_exit, word_penalty, W, S,
+                             SP, bp, exit_idx, score, st);
+  if (rc) return rc;
+  if (n_words || path_word || path_state || path_entry) {
+    SAPR_LAUNCH(connected_backtrace_kernel, dim3(static_cast<unsigned>((n_utts + kCnBlock - 1) / kCnBlock)),
+                dim3(kCnBlock), 0, st, offsets, n_utts, total_frames, SP, R, bp, exit_idx, score, n_words, path_word,
+                path_state, path_entry);
+    SAPR_HIP_TRY(hipGetLastError());
+  }
+  return 0;
+}

@@ -112,6 +112,37 @@ class Decoder:
             return self._decode_full(feats, lengths)
         return self._decode_feature_batch(store.to_batch())
 
+    # ---- connected words ------------------------------------------------------------------------
+    def decode_connected(self, feature_list: List[np.ndarray], word_penalty: float = 0.0,
+                         exit_states="last") -> List[Dict]:
+        """Recordings that hold several words in a row: one-pass Viterbi over the word loop (``sapr_amd.connected``:
+        ``sapr_connected_emit_diag`` + ``sapr_connected_viterbi``).  ``feature_list``: (D, T) arrays as in
+        ``decode_batch``.  Per utterance ``{"words": [...], "log_likelihood": float, "segments": [(word, start,
+        end_exclusive), ...], "state_sequence": ndarray}`` with the words in load order of the vocabulary; an utterance
+        no word string can explain (or one without frames) has no words, ``-inf`` and states of -1.  ``word_penalty`` is
+        added once per word boundary; ``exit_states``: "last", "any" or an array [W, S]
+        (``ConnectedNetwork.from_models``).  Served for "diag" and "spherical" ``GaussianHMM`` vocabularies."""
+        if self.implementation != "hmmlearn":
+            raise ValueError(f"connected-word decoding needs implementation='hmmlearn' with 'diag' or 'spherical' "
+                             f"models: it has no emission stage for implementation={self.implementation!r}")
+        if self._is_full():
+            raise ValueError("connected-word decoding has no emission stage for covariance_type 'full' or 'tied': it "
+                             "serves 'diag' and 'spherical' models")
+        from .connected import ConnectedNetwork, connected_decode
+        if len(feature_list) == 0:
+            raise ValueError("empty utterance list")
+        words = list(self.models)
+        net = ConnectedNetwork.from_models(self._model_list(), exit_states=exit_states, word_penalty=word_penalty)
+        res = connected_decode([np.asarray(f).T for f in feature_list], net)
+        out = []
+        for u in range(len(feature_list)):
+            segs = res.segments(u)
+            lo, hi = int(res.offsets[u]), int(res.offsets[u + 1])
+            out.append({"words": [words[w] for w, _, _ in segs], "log_likelihood": float(res.score[u]),
+                        "segments": [(words[w], a, b) for w, a, b in segs],
+                        "state_sequence": res.path_state[lo:hi].astype(np.int64)})
+        return out
+
     def _decode_custom(self, features) -> List[Tuple[str, float, object]]:
         """The reference's from-scratch models: emission rows, trellis and the arg-max over the models
         (decoder.py:42-47, first strict maximum in load order) all on the device."""

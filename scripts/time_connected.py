@@ -1,0 +1,163 @@
+"""Ad-hoc timing of connected-word recognition (dev tool):
+    python scripts/time_connected.py [N] [--frames 505] [--shapes 11,10,13 11,18,39] [--trace DIR]
+The two stages and the back-trace of sapr_amd.connected on N utterances x 505 frames (five words of ~101 frames in a
+row) for (W, S, D) = (11, 10, 13) and (11, 18, 39), bidiagonal word models, exits in the last state:
+  emit       sapr_connected_emit_diag                          logb[total_frames][W * SP]
+  viterbi    sapr_connected_viterbi without any path output    (the recursion kernel alone)
+  decode     sapr_connected_viterbi with every output          (recursion + back-trace; back-trace = decode - viterbi)
+and, as a yardstick with the same emission work on the same frames in the same run, the all-vocabulary isolated-word
+scorer sapr_viterbi_diag_scores (+ its back-trace launch, trellis.viterbi_decode without a path).  Every route is
+warmed twice, then the routes are timed in turn, five times each, between device events.  Prints one JSON line per
+shape with the bytes each stage moves and the float64 operations it needs from the shapes alone: per frame and flat
+state 3 D + 2 for the emission, and per finite transition distance one add and one compare in the recursion.
+
+--trace DIR: afterwards the script starts itself once more under rocprofv3 --kernel-trace --stats (a run of its own:
+one warm-up and one timed call of every route per shape) and writes DIR/connected_rocprofv3_summary.txt."""
+import argparse
+import csv
+import glob
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+
+sys.path.insert(0, ".")
+
+REPEATS = 5
+
+ap = argparse.ArgumentParser()
+ap.add_argument("N", nargs="?", type=int, default=10000)
+ap.add_argument("--frames", type=int, default=505)
+ap.add_argument("--shapes", nargs="+", default=["11,10,13", "11,18,39"])
+ap.add_argument("--trace", default=None, help="directory for the rocprofv3 summary (a second run of its own)")
+ap.add_argument("--child", action="store_true", help="(internal) the run under rocprofv3")
+args = ap.parse_args()
+N, T = args.N, args.frames
+
+
+def ev_time(fn):
+    import torch
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b)
+
+
+def summary(t):
+    return {"min": round(min(t), 3), "max": round(max(t), 3), "median": round(float(np.median(t)), 3)}
+
+
+def setup(W, S, D):
+    import torch
+    from sapr_amd import _lib, connected
+    from sapr_amd.trellis import DiagModelPack, FeatureBatch, viterbi_decode
+    from tests._connected_ref import sample_case
+    model, _, _ = sample_case(7, W, S, D, 0)
+    net = connected.ConnectedNetwork(model["log_start"], model["log_trans"], model["log_exit"], 0.0, None,
+                                     model["means"], model["vars"], model["gconst"])
+    # five words in a row per utterance, the frames scattered about the means of the states they walk through
+    torch.manual_seed(0)
+    per = (T + 4) // 5
+    t = torch.arange(T, device="cuda")
+    word = (torch.randint(0, W, (N, 5), device="cuda"))[:, (t // per).clamp(max=4)]          # [N, T]
+    state = ((t % per) * S // per).expand(N, T)
+    mu = torch.from_numpy(model["means"]).cuda()[word.reshape(-1), state.reshape(-1)]
+    sd = torch.from_numpy(np.sqrt(model["vars"])).cuda()[word.reshape(-1), state.reshape(-1)]
+    feats = (mu + torch.randn(N * T, D, device="cuda", dtype=torch.float64) * sd).float().contiguous()
+    del mu, sd, word, state
+    lengths = np.full(N, T)
+    offs = torch.from_numpy(np.r_[0, np.cumsum(lengths)].astype(np.int64)).cuda()
+    total = N * T
+    lib = _lib.load()
+    ls, lt, lx, ops = net.device(feats.device)
+    logb = torch.empty((total, net.R), dtype=torch.float64, device="cuda")
+    ws_bytes = connected.workspace_bytes(total, N, W, S)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
+    score = torch.empty(N, dtype=torch.float64, device="cuda")
+    n_words = torch.empty(N, dtype=torch.int32, device="cuda")
+    pw = torch.empty(total, dtype=torch.int32, device="cuda")
+    ps = torch.empty(total, dtype=torch.int32, device="cuda")
+    pe = torch.empty(total, dtype=torch.uint8, device="cuda")
+
+    def emit():
+        _lib.check(lib.sapr_connected_emit_diag(_lib.ptr(feats), total, D, _lib.ptr(ops), W, S, _lib.ptr(logb),
+                                                _lib.current_stream()), "sapr_connected_emit_diag")
+
+    def viterbi(paths):
+        out = (n_words, pw, ps, pe) if paths else (None,) * 4
+        _lib.check(lib.sapr_connected_viterbi(_lib.ptr(logb), _lib.ptr(offs), N, total, _lib.ptr(ls), _lib.ptr(lt),
+                                              _lib.ptr(lx), 0.0, W, S, _lib.ptr(ws), ws_bytes, _lib.ptr(score),
+                                              *(_lib.ptr(o) for o in out), _lib.current_stream()),
+                   "sapr_connected_viterbi")
+
+    pack = DiagModelPack.from_params(model["startprob"], model["transmat"], model["means"], model["vars"])
+    fb = FeatureBatch.from_packed(feats, lengths)
+    routes = {"emit": emit, "viterbi": lambda: viterbi(False), "decode": lambda: viterbi(True),
+              "isolated_word_scores": lambda: viterbi_decode(fb, pack, want_path=False)}
+    nd = 2  # finite transition distances of a bidiagonal vocabulary
+    facts = {"R": net.R, "logb_GB": round(total * net.R * 8 / 1e9, 3), "workspace_GB": round(ws_bytes / 1e9, 3),
+             "emit_bytes_per_frame": 4 * D + 8 * net.R, "viterbi_bytes_per_frame": 9 * net.R + 4,
+             "emit_flops_per_frame": net.R * (3 * net.DP + 2), "viterbi_flops_per_frame": net.R * (2 * nd + 5)}
+    return routes, facts, (n_words, score)
+
+
+def measure():
+    import torch
+    for shape in args.shapes:
+        W, S, D = (int(v) for v in shape.split(","))
+        routes, facts, (n_words, score) = setup(W, S, D)
+        out = {"shape": {"N": N, "T": T, "W": W, "S": S, "D": D}, **facts}
+        for _ in range(1 if args.child else 2):
+            for fn in routes.values():
+                fn()
+        torch.cuda.synchronize()
+        assert torch.isfinite(score).all()
+        out["mean_words_found"] = round(float(n_words.float().mean()), 2)
+        times = {k: [] for k in routes}
+        for _ in range(1 if args.child else REPEATS):
+            for k, fn in routes.items():
+                times[k].append(ev_time(fn))
+        for k, t in times.items():
+            out[f"{k}_ms"] = summary(t)
+        med = {k: float(np.median(t)) for k, t in times.items()}
+        out["backtrace_ms_median"] = round(med["decode"] - med["viterbi"], 3)
+        out["connected_total_ms_median"] = round(med["emit"] + med["decode"], 3)
+        out["ratio_connected_over_isolated"] = round((med["emit"] + med["decode"]) / med["isolated_word_scores"], 3)
+        out["emit_GBps"] = round(facts["emit_bytes_per_frame"] * N * T / med["emit"] / 1e6, 1)
+        out["viterbi_GBps"] = round(facts["viterbi_bytes_per_frame"] * N * T / med["viterbi"] / 1e6, 1)
+        print(json.dumps(out), flush=True)
+        del routes
+        torch.cuda.empty_cache()
+
+
+measure()
+if args.child or not args.trace:
+    sys.exit(0)
+
+os.makedirs(args.trace, exist_ok=True)
+trace = os.path.join(args.trace, "trace")
+cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", trace, "--", sys.executable,
+       os.path.abspath(__file__), str(N), "--frames", str(T), "--shapes", *args.shapes, "--child"]
+with open(os.path.join(args.trace, "child.log"), "w") as log:
+    subprocess.run(cmd, check=True, stdout=log, stderr=subprocess.STDOUT, stdin=subprocess.DEVNULL, timeout=900)
+rows = []
+for f in glob.glob(os.path.join(trace, "**", "*kernel_stats.csv"), recursive=True):
+    with open(f) as fh:
+        rows += [r for r in csv.DictReader(fh) if "sapr" in r["Name"]]
+rows.sort(key=lambda r: -float(r["TotalDurationNs"]))
+lines = [f"# rocprofv3 --kernel-trace --stats of: python scripts/time_connected.py {N} --frames {T} --shapes "
+         f"{' '.join(args.shapes)} --child",
+         "# one warm-up and one timed call of every route (emission; recursion alone; recursion + back-trace; the",
+         "# all-vocabulary isolated-word scorer on the same frames) per shape; sapr kernels only",
+         "# calls  total_ms  avg_ms  min_ms  max_ms  name"]
+for r in rows:
+    lines.append("%5s %9.3f %8.3f %8.3f %8.3f  %s" % (r["Calls"], float(r["TotalDurationNs"]) / 1e6,
+                                                     float(r["AverageNs"]) / 1e6, float(r["MinNs"]) / 1e6,
+                                                     float(r["MaxNs"]) / 1e6, r["Name"]))
+with open(os.path.join(args.trace, "connected_rocprofv3_summary.txt"), "w") as fh:
+    fh.write("\n".join(lines) + "\n")
+print("\n".join(lines))
