@@ -24,6 +24,7 @@ namespace sapr {
 namespace {
 
 #include "lse_ops.h"
+#include "vocab_epilogue.h"
 
 using namespace emission;
 
@@ -106,34 +107,6 @@ __global__ __launch_bounds__(kBlock) void forward_vocab_kernel(
   if (live) loglik[u * W + w] = T > 0 ? lse_all<S>(fwd) : neg_inf();
 }
 
-// One lane per utterance over its row of W scores: the arg-max word of decoder.py:42-47 (first strict maximum in model
-// order from -inf; -1 when no score beats -inf) and the posterior over the words under a uniform prior,
-// exp(loglik - logsumexp_w loglik), evaluated as exp(loglik - max) / sum_w exp(loglik - max): the subtraction of a
-// rounded logsumexp of magnitude 10^4 would cost the posteriors three digits.  A row whose maximum is -inf gives NaN
-// (exp(-inf + inf)), a NaN score makes the row's sum NaN: nothing is repaired.
-__global__ __launch_bounds__(kBlock) void forward_vocab_epilogue_kernel(int64_t n_utts, int32_t W,
-                                                                        const double *__restrict__ loglik,
-                                                                        int32_t *__restrict__ best_word,
-                                                                        double *__restrict__ word_post) {
-  const int64_t u = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-  if (u >= n_utts) return;
-  const double *__restrict__ row = loglik + u * W;
-  int bw = -1;
-  double bs = neg_inf();
-  for (int w = 0; w < W; ++w) {
-    const double sc = row[w];
-    if (sc > bs) {
-      bs = sc;
-      bw = w;
-    }
-  }
-  if (best_word) best_word[u] = bw;
-  if (!word_post) return;
-  double den = 0.0;
-  for (int w = 0; w < W; ++w) den += exp(row[w] - bs);
-  for (int w = 0; w < W; ++w) word_post[u * W + w] = exp(row[w] - bs) / den;
-}
-
 struct VocabArgs {
   const float *feats;
   const int64_t *offsets;
@@ -193,10 +166,6 @@ extern "C" int sapr_forward_vocab(const float *feats, const int64_t *offsets, co
     rc = fail(SAPR_ERR_UNSUPPORTED, "trellis kernels are instantiated for (D,S) in {13,39}x{10,18}; got D=%d S=%d", D,
               S);
   if (rc) return rc;
-  if (best_word || word_post) {
-    SAPR_LAUNCH(forward_vocab_epilogue_kernel, dim3(static_cast<unsigned>((n_utts + kBlock - 1) / kBlock)),
-                dim3(kBlock), 0, a.stream, n_utts, W, loglik, best_word, word_post);
-    SAPR_HIP_TRY(hipGetLastError());
-  }
+  if (best_word || word_post) return launch_vocab_epilogue(n_utts, W, loglik, best_word, word_post, a.stream);
   return 0;
 }

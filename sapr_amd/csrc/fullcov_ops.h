@@ -21,19 +21,7 @@
 
 typedef double f64x4_full __attribute__((ext_vector_type(4)));
 
-// per model: log_start[SP], log_trans[SP][SP], log_transT[SP][SP], c[SP], mu[SP][DP], Winv[SP][DP][DP]
-constexpr size_t full_model_doubles(int SP, int DP) {
-  return static_cast<size_t>(SP) + 2 * static_cast<size_t>(SP) * SP + static_cast<size_t>(SP) +
-         static_cast<size_t>(SP) * DP + static_cast<size_t>(SP) * DP * DP;
-}
 constexpr int full_stats_p(int S, int D) { return S * D + S * D * D; }  // obs, oo
-
-inline int check_full_shape(int32_t S, int32_t D) {
-  if (S > kMaxS || D > kMaxD)
-    return fail(SAPR_ERR_UNSUPPORTED, "the full-covariance kernels serve S in 1..%d, D in 1..%d; got S=%d D=%d", kMaxS,
-                kMaxD, S, D);
-  return 0;
-}
 
 // -------------------------------------------------------------------------------------------
 // pass 1: logb[frame][SP]

@@ -8,12 +8,12 @@
 //
 // Mapping: the (utterance tile, word) grid of forward_vocab.hip (viterbi_shared.h decode_block: the W workgroups that
 // read the same 256 utterances sit on one XCD, so the features cross HBM once), one lane per utterance, the model
-// wavefront-uniform (scalar loads from the pack of sapr_gmm_pack_layout, nothing else is packed).  Per frame the lane
-// walks the model's own S states in a rolled loop: the mixture emission of state j (gmm_ops.h mix_log_terms, then
-// lse_all over the components) is evaluated where it is consumed, next to the transition term of column j
-// (reduce_finite: a -inf log transition is skipped by a uniform branch).  The recursion's state is SP float64
-// registers per lane: no lattice and no logb ever reach memory, and there is no workspace.  Lanes whose utterance has
-// ended idle until the wavefront's longest one ends.
+// wavefront-uniform (scalar loads from the pack of sapr_gmm_pack_layout, nothing else is packed); the scan body is
+// vocab_scan.h's, shared with full_vocab.hip.  Per frame the lane walks the model's own S states in a rolled loop: the
+// mixture emission of state j (gmm_ops.h mix_log_terms, then lse_all over the components) is evaluated where it is
+// consumed, next to the transition term of column j (reduce_finite: a -inf log transition is skipped by a uniform
+// branch).  The recursion's state is SP float64 registers per lane: no lattice and no logb ever reach memory, and
+// there is no workspace.  Lanes whose utterance has ended idle until the wavefront's longest one ends.
 //
 // These are the device functions of gmm_emit_kernel and gmm_forward_kernel, called in the same order on the same
 // values (the build runs with -ffp-contract=off, the emission's one FMA is an explicit fma(); a float32 frame promoted
@@ -28,13 +28,7 @@ namespace {
 
 #include "lse_ops.h"
 #include "gmm_ops.h"
-#include "vocab_epilogue.h"
-
-template <int DP, class XT>
-__device__ __forceinline__ void load_frame_as(const float *__restrict__ xp, int D, bool live, XT (&x)[DP]) {
-#pragma unroll
-  for (int d = 0; d < DP; ++d) x[d] = (live && d < D) ? static_cast<XT>(xp[d]) : static_cast<XT>(0);
-}
+#include "vocab_scan.h"
 
 template <int SP, int MP, int DP, bool VIT>
 __global__ __launch_bounds__(kBlock) void gmm_vocab_kernel(
@@ -46,102 +40,29 @@ __global__ __launch_bounds__(kBlock) void gmm_vocab_kernel(
   decode_block(W, n_tiles, tile, w);
   if (tile >= n_tiles) return;  // grid padding (whole block leaves together)
 
-  const int64_t slot = tile * kBlock + threadIdx.x;
-  const bool live = slot < n_utts;
-  const int64_t u = live ? (order ? static_cast<int64_t>(order[slot]) : slot) : -1;
-  const Span sp = utt_span(offsets, u, live, n_utts, total_frames, max_T);  // served as empty: T = 0
-  const int T = sp.T;
-  const int Tw = __builtin_amdgcn_readfirstlane(wave_max_i32(T));
-
   // wavefront-uniform model pointers -> scalar loads
   const double *__restrict__ mdl = pack + static_cast<int64_t>(w) * static_cast<int64_t>(model_doubles(SP, MP, DP));
-  const double *__restrict__ ls = mdl + off_log_start();
-  const double *__restrict__ ltT = mdl + off_log_transT(SP);
   const double *__restrict__ cc = mdl + off_cc(SP);
   const double *__restrict__ prm = mdl + off_prm(SP, MP);
-  const float *__restrict__ xp = feats + sp.beg * D;
 
-  // 39-dimensional frames stay float32 in registers and are promoted inside the chain (exact)
+  // 39-dimensional frames stay float32 in registers and are promoted inside the chain (exact); the next frame is
+  // always in flight under this frame's arithmetic
   using XT = std::conditional_t<(DP >= 39), float, double>;
-  XT xn[DP];
-  load_frame_as<DP>(xp, D, T > 0, xn);
-
-  double fwd[SP];
-#pragma unroll
-  for (int s = 0; s < SP; ++s) fwd[s] = neg_inf();  // (a padded state keeps it: -inf + -inf in the per-model kernels)
-
-  for (int t = 0; t < Tw; ++t) {
-    if (t < T) {
-      XT x[DP];
-      double prev[SP];
-#pragma unroll
-      for (int d = 0; d < DP; ++d) x[d] = xn[d];
-#pragma unroll
-      for (int s = 0; s < SP; ++s) prev[s] = fwd[s];
-      const int tn = t + 1 < T ? t + 1 : t;  // the next frame in flight under this frame's arithmetic
-      load_frame_as<DP>(xp + static_cast<int64_t>(tn) * D, D, true, xn);
-      // state after state in a rolled loop over the model's own S states: the parameters of state j and column j of
-      // the transition matrix are runs of scalar loads, and the value lands in register j by a uniform select
-#pragma unroll 1
-      for (int j = 0; j < S; ++j) {
-        double lc[MP];
-        mix_log_terms<MP, DP>([&](int d) { return static_cast<double>(x[d]); },
-                              prm + static_cast<int64_t>(j) * DP * MP * 2, cc + j * MP, lc);
-        double lb;
-        if constexpr (MP == 1)
-          lb = lc[0];
-        else
-          lb = lse_all<MP>(lc);
-        double v;
-        if (t == 0) {  // (uniform)
-          v = ls[j];
-        } else {
-          const double *__restrict__ col = ltT + j * SP;
-          v = reduce_finite<SP, VIT>([&](int i) { return prev[i]; }, [&](int i) { return col[i]; });
-        }
-#pragma unroll
-        for (int k = 0; k < SP; ++k) fwd[k] = k == j ? v + lb : fwd[k];
-      }
-    }
-  }
-  if (sp.u < 0) return;  // no utterance in this slot (or an `order` entry outside the batch: never followed)
-  double out = neg_inf();
-  if (T > 0) {
-    if constexpr (!VIT) {
-      out = lse_all<SP>(fwd);
-    } else {  // _hmmc.cpp viterbi: the first maximum of the last row
-      const int st = argmax_first<SP>(fwd, S);
-      out = fwd[0];
-#pragma unroll
-      for (int s = 1; s < SP; ++s) out = s == st ? fwd[s] : out;
-    }
-  }
-  score[sp.u * W + w] = out;
+  vocab_scan<SP, DP, VIT, XT, true>(feats, offsets, order, n_utts, total_frames, tile, w, D, max_T, W, S,
+                                    mdl + off_log_start(), mdl + off_log_transT(SP), score, [=](auto x, int j) {
+                                      double lc[MP];
+                                      mix_log_terms<MP, DP>(x, prm + static_cast<int64_t>(j) * DP * MP * 2,
+                                                            cc + j * MP, lc);
+                                      if constexpr (MP == 1)
+                                        return lc[0];
+                                      else
+                                        return lse_all<MP>(lc);
+                                    });
 }
-
-struct VocabArgs {
-  const float *feats;
-  const int64_t *offsets;
-  const int32_t *order;
-  int64_t n_utts, total_frames, n_tiles;
-  int32_t D, max_T, W, S;
-  const double *pack;
-  double *score;
-  unsigned blocks;
-  hipStream_t stream;
-};
 
 template <int SP, int MP, int DP>
 int launch_vocab(const VocabArgs &a, bool vit) {
-  const dim3 grid(a.blocks), block(kBlock);
-  if (vit)
-    SAPR_LAUNCH((gmm_vocab_kernel<SP, MP, DP, true>), grid, block, 0, a.stream, a.feats, a.offsets, a.order, a.n_utts,
-                a.total_frames, a.n_tiles, a.D, a.max_T, a.W, a.S, a.pack, a.score);
-  else
-    SAPR_LAUNCH((gmm_vocab_kernel<SP, MP, DP, false>), grid, block, 0, a.stream, a.feats, a.offsets, a.order, a.n_utts,
-                a.total_frames, a.n_tiles, a.D, a.max_T, a.W, a.S, a.pack, a.score);
-  SAPR_HIP_TRY(hipGetLastError());
-  return 0;
+  return launch_vocab_kernel(vit ? gmm_vocab_kernel<SP, MP, DP, true> : gmm_vocab_kernel<SP, MP, DP, false>, a);
 }
 
 template <int SP, int MP>
@@ -177,39 +98,12 @@ extern "C" int sapr_gmm_vocab_diag(const float *feats, const int64_t *offsets, c
                (long long)total_frames, W, S, M, D, max_T);
   SAPR_REQUIRE(mode == SAPR_GMM_VOCAB_FORWARD || mode == SAPR_GMM_VOCAB_VITERBI, "bad mode %d", mode);
   if (int rc = check_shape(S, M, D)) return rc;
-  const bool vit = mode == SAPR_GMM_VOCAB_VITERBI;
-  SAPR_REQUIRE(!vit || !word_post, "word_post is served in forward mode only: a soft-max of path scores is no posterior");
-  const int64_t n_tiles = (n_utts + kBlock - 1) / kBlock;
-  const int64_t blocks = round_up(n_tiles, kXcd) * W;
-  SAPR_REQUIRE(blocks <= 0x7fffffffLL, "grid too large (%lld blocks)", (long long)blocks);
-  if (n_utts == 0) return 0;
-  SAPR_REQUIRE(feats && offsets && pack && score, "NULL pointer argument");
-  VocabArgs a;
-  a.feats = feats;
-  a.offsets = offsets;
-  a.order = order;
-  a.n_utts = n_utts;
-  a.total_frames = total_frames;
-  a.n_tiles = n_tiles;
-  a.D = D;
-  a.max_T = max_T;
-  a.W = W;
-  a.S = S;
-  a.pack = pack;
-  a.score = score;
-  a.blocks = static_cast<unsigned>(blocks);
-  a.stream = as_stream(stream);
-  int rc;
-  switch (sp_of(S)) {
-    case 4: rc = launch_vocab_mp<4>(a, vit, M); break;
-    case 10: rc = launch_vocab_mp<10>(a, vit, M); break;
-    default: rc = launch_vocab_mp<18>(a, vit, M); break;
-  }
-  if (rc) return rc;
-  if (best_word || word_post) {
-    SAPR_LAUNCH(vocab_epilogue_kernel, dim3(static_cast<unsigned>(n_tiles)), dim3(kBlock), 0, a.stream, n_utts, W,
-                score, best_word, word_post);
-    SAPR_HIP_TRY(hipGetLastError());
-  }
-  return 0;
+  return vocab_run({feats, offsets, order, n_utts, total_frames, D, max_T, W, S, pack, score, as_stream(stream)},
+                   mode == SAPR_GMM_VOCAB_VITERBI, best_word, word_post, [M](const VocabArgs &a, bool vit) {
+                     switch (sp_of(a.S)) {
+                       case 4: return launch_vocab_mp<4>(a, vit, M);
+                       case 10: return launch_vocab_mp<10>(a, vit, M);
+                       default: return launch_vocab_mp<18>(a, vit, M);
+                     }
+                   });
 }

@@ -63,8 +63,7 @@ class Decoder:
         self.models: Dict = {}
         self.vocab: List[str] = []
         self._pack = None
-        self._gmm = None
-        self._full = None
+        self._vocab = None
         self.load_models()
 
     def load_models(self) -> None:
@@ -90,10 +89,8 @@ class Decoder:
         words = list(self.models)
         if self.implementation == "custom":
             return self._decode_custom(feature_list)
-        if self.implementation == "gmmhmm":
-            return self._decode_gmm(*self._gmm_features(feature_list))
-        if self._is_full():
-            return self._decode_full(*self._gmm_features(feature_list))
+        if self._uses_vocab_pack():
+            return self._decode_vocab(*self._gmm_features(feature_list))
         from .trellis import FeatureBatch
         return self._decode_feature_batch(FeatureBatch.from_arrays(feature_list, layout="DT"))
 
@@ -102,14 +99,10 @@ class Decoder:
         sequence); same tuples as ``decode_batch``."""
         if self.implementation == "custom":
             return self._decode_custom(store.to_batch())
-        if self.implementation == "gmmhmm":
+        if self._uses_vocab_pack():
             from .gmm_hmm import vocab_features
             feats, _, _, lengths, _ = vocab_features(store.to_batch())
-            return self._decode_gmm(feats, lengths)
-        if self._is_full():
-            from .gmm_hmm import vocab_features
-            feats, _, _, lengths, _ = vocab_features(store.to_batch())
-            return self._decode_full(feats, lengths)
+            return self._decode_vocab(feats, lengths)
         return self._decode_feature_batch(store.to_batch())
 
     # ---- connected words ------------------------------------------------------------------------
@@ -152,13 +145,27 @@ class Decoder:
         return [(words[w], float(sc), [int(x) for x in p]) if w >= 0 else (None, float("-inf"), None)
                 for w, sc, p in zip(bw, bs, bp)]
 
-    # ---- Gaussian-mixture word models ---------------------------------------------------------
-    def _gmm_pack(self):
-        """The vocabulary's operand block (``gmm_hmm.GmmPack``), padded to its largest model; built once."""
-        if self._gmm is None:
-            from .gmm_hmm import GmmPack
-            self._gmm = GmmPack.from_models(self._model_list())
-        return self._gmm
+    # ---- Gaussian-mixture and full-covariance word models --------------------------------------
+    def _is_full(self) -> bool:
+        """A vocabulary of hmmlearn-shaped models of which at least one has a "full" or "tied" covariance: all of it
+        runs on the full-covariance kernels (``DiagModelPack`` refuses such models)."""
+        return self.implementation == "hmmlearn" and any(
+            getattr(m, "covariance_type", "diag") in ("full", "tied") for m in self.models.values())
+
+    def _uses_vocab_pack(self) -> bool:
+        return self.implementation == "gmmhmm" or self._is_full()
+
+    def _vocab_pack(self):
+        """The vocabulary's operand block (``gmm_hmm.GmmPack`` for the mixtures, ``full_cov.FullPack`` for a
+        full-covariance vocabulary), padded to its largest model; built once.  The pack names what is the family's
+        own: the per-model batch class (``pack.batch``) and the scorer over the vocabulary (``pack.vocab_scores``)."""
+        if self._vocab is None:
+            if self.implementation == "gmmhmm":
+                from .gmm_hmm import GmmPack as Pack
+            else:
+                from .full_cov import FullPack as Pack
+            self._vocab = Pack.from_models(self._model_list())
+        return self._vocab
 
     @staticmethod
     def _gmm_features(feature_list):
@@ -174,81 +181,33 @@ class Decoder:
         packed = np.concatenate(mats, axis=0) if lengths.sum() else np.zeros((0, D), np.float32)
         return torch.from_numpy(packed).to(_lib.require_gpu()), lengths
 
-    def _decode_gmm(self, feats, lengths) -> List[Tuple[str, float, object]]:
-        """One launch over the vocabulary (Viterbi log-probabilities, or forward log-likelihoods with
-        ``scoring="forward"``) picks the word; one Viterbi launch over the utterances grouped by that word walks its
-        path.  The returned score is the vocabulary launch's (in Viterbi mode the second launch's ``logprob`` carries
-        the same bits)."""
-        from .gmm_hmm import GmmBatch, vocab_scores
+    def _decode_vocab(self, feats, lengths) -> List[Tuple[str, float, object]]:
+        """One launch over the vocabulary (``sapr_gmm_vocab_diag`` / ``sapr_full_vocab``: Viterbi log-probabilities, or
+        forward log-likelihoods with ``scoring="forward"``) picks the word; one Viterbi launch
+        (``sapr_gmm_viterbi_diag`` / ``sapr_full_viterbi``) over the utterances grouped by that word walks its path
+        (first maximum on ties).  The returned score is the vocabulary launch's (in Viterbi mode the second launch's
+        ``logprob`` carries the same bits)."""
         words = list(self.models)
-        pack = self._gmm_pack()
-        vs = vocab_scores(feats, lengths, pack, mode=self.scoring)
+        pack = self._vocab_pack()
+        vs = pack.vocab_scores(feats, lengths, mode=self.scoring)
         bw = _lib.to_host(vs.best_word)[0].astype(np.int64)
         # an utterance no model scores above -inf has no word (-1): model 0's path is walked and then dropped
-        _, path = GmmBatch(feats, lengths, np.maximum(bw, 0), pack.W, pack.S, pack.M).viterbi(pack)
+        _, path = pack.batch(feats, lengths, np.maximum(bw, 0)).viterbi(pack)
         score, path = _lib.to_host(vs.score, path)
         offs = np.r_[0, np.cumsum(lengths)].tolist()
         path = path.astype(np.int64)
         return [(words[w], float(score[u, w]), path[lo:hi]) if w >= 0 else (None, float("-inf"), None)
                 for u, (w, lo, hi) in enumerate(zip(bw.tolist(), offs[:-1], offs[1:]))]
 
-    def _state_posteriors_gmm(self, feature_list, words) -> List[np.ndarray]:
-        from .gmm_hmm import GmmBatch, vocab_scores
-        pack = self._gmm_pack()
+    def _state_posteriors_vocab(self, feature_list, words) -> List[np.ndarray]:
+        pack = self._vocab_pack()
         feats, lengths = self._gmm_features(feature_list)
         if words is None:
-            vs = vocab_scores(feats, lengths, pack, mode="viterbi")
+            vs = pack.vocab_scores(feats, lengths, mode="viterbi")
             utt_model = np.maximum(_lib.to_host(vs.best_word)[0].astype(np.int64), 0)
         else:
             utt_model = self._named_models(words, len(lengths))
-        batch = GmmBatch(feats, lengths, utt_model, pack.W, pack.S, pack.M)
-        post = _lib.to_host(batch.estep(pack, want_stats=False, want_post=True)[2])[0].copy()
-        offs = np.r_[0, np.cumsum(lengths)].tolist()
-        return [post[lo:hi, :pack.n_states[w]] for w, lo, hi in zip(utt_model.tolist(), offs[:-1], offs[1:])]
-
-    # ---- full-covariance word models ----------------------------------------------------------
-    def _is_full(self) -> bool:
-        """A vocabulary of hmmlearn-shaped models of which at least one has a "full" or "tied" covariance: all of it
-        runs on the full-covariance kernels (``DiagModelPack`` refuses such models)."""
-        return self.implementation == "hmmlearn" and any(
-            getattr(m, "covariance_type", "diag") in ("full", "tied") for m in self.models.values())
-
-    def _full_pack(self):
-        """The vocabulary's operand block (``full_cov.FullPack``), padded to its largest model; built once."""
-        if self._full is None:
-            from .full_cov import FullPack
-            self._full = FullPack.from_models(self._model_list())
-        return self._full
-
-    def _decode_full(self, feats, lengths) -> List[Tuple[str, float, object]]:
-        """:meth:`_decode_gmm` over the full-covariance kernels: one ``sapr_full_vocab`` launch (Viterbi
-        log-probabilities, or forward log-likelihoods with ``scoring="forward"``) picks the word, one
-        ``sapr_full_viterbi`` over the utterances grouped by that word walks its path (first maximum on ties).  The
-        returned score is the vocabulary launch's (in Viterbi mode the second launch's ``logprob`` carries the same
-        bits)."""
-        from .full_cov import FullCovBatch, vocab_scores
-        words = list(self.models)
-        pack = self._full_pack()
-        vs = vocab_scores(feats, lengths, pack, mode=self.scoring)
-        bw = _lib.to_host(vs.best_word)[0].astype(np.int64)
-        # an utterance no model scores above -inf has no word (-1): model 0's path is walked and then dropped
-        _, path = FullCovBatch(feats, lengths, np.maximum(bw, 0), pack.W, pack.S).viterbi(pack)
-        score, path = _lib.to_host(vs.score, path)
-        offs = np.r_[0, np.cumsum(lengths)].tolist()
-        path = path.astype(np.int64)
-        return [(words[w], float(score[u, w]), path[lo:hi]) if w >= 0 else (None, float("-inf"), None)
-                for u, (w, lo, hi) in enumerate(zip(bw.tolist(), offs[:-1], offs[1:]))]
-
-    def _state_posteriors_full(self, feature_list, words) -> List[np.ndarray]:
-        from .full_cov import FullCovBatch, vocab_scores
-        pack = self._full_pack()
-        feats, lengths = self._gmm_features(feature_list)
-        if words is None:
-            vs = vocab_scores(feats, lengths, pack, mode="viterbi")
-            utt_model = np.maximum(_lib.to_host(vs.best_word)[0].astype(np.int64), 0)
-        else:
-            utt_model = self._named_models(words, len(lengths))
-        batch = FullCovBatch(feats, lengths, utt_model, pack.W, pack.S)
+        batch = pack.batch(feats, lengths, utt_model)
         post = _lib.to_host(batch.estep(pack, want_stats=False, want_post=True)[2])[0].copy()
         offs = np.r_[0, np.cumsum(lengths)].tolist()
         return [post[lo:hi, :pack.n_states[w]] for w, lo, hi in zip(utt_model.tolist(), offs[:-1], offs[1:])]
@@ -300,16 +259,10 @@ class Decoder:
         if self.implementation == "custom":
             raise ValueError("forward scoring over the vocabulary needs implementation='hmmlearn': the from-scratch "
                              "model has no forward scorer over a vocabulary")
-        if self.implementation == "gmmhmm":
-            from .gmm_hmm import vocab_scores
+        if self._uses_vocab_pack():
             from .trellis import ForwardScores
-            vs = vocab_scores(*self._gmm_features(feature_list), self._gmm_pack(), mode="forward", want_post=want_post)
-            return ForwardScores(vs.score, vs.best_word, vs.word_post)
-        if self._is_full():
-            from .full_cov import vocab_scores
-            from .trellis import ForwardScores
-            vs = vocab_scores(*self._gmm_features(feature_list), self._full_pack(), mode="forward",
-                              want_post=want_post)
+            vs = self._vocab_pack().vocab_scores(*self._gmm_features(feature_list), mode="forward",
+                                                 want_post=want_post)
             return ForwardScores(vs.score, vs.best_word, vs.word_post)
         from .trellis import DiagModelPack, FeatureBatch, forward_scores
         if self._pack is None:
@@ -353,10 +306,8 @@ class Decoder:
         if self.implementation == "custom":
             raise ValueError("state posteriors need implementation='hmmlearn': the from-scratch model has no posterior "
                              "kernel")
-        if self.implementation == "gmmhmm":
-            return self._state_posteriors_gmm(feature_list, words)
-        if self._is_full():
-            return self._state_posteriors_full(feature_list, words)
+        if self._uses_vocab_pack():
+            return self._state_posteriors_vocab(feature_list, words)
         from .trellis import DiagModelPack, FeatureBatch, state_posteriors, viterbi_decode_best
         if self._pack is None:
             self._pack = DiagModelPack.from_models(self._model_list())

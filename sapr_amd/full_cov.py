@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .hmmlearn_hmm import _features_f32
+from .hmmlearn_hmm import VocabPack, _features_f32
 
 MAX_STATES, MAX_DIMS = 18, 39
 VOCAB_MODES = {"forward": _lib.FULL_VOCAB_FORWARD, "viterbi": _lib.FULL_VOCAB_VITERBI}
@@ -193,19 +193,13 @@ class FullCovBatch:
 # ------------------------------------------------------------------------------------------
 # scoring over the vocabulary: every utterance under every word model in one launch
 # ------------------------------------------------------------------------------------------
-class FullPack:
+class FullPack(VocabPack):
     """A vocabulary's operand block ready for the kernels: ``data`` float64 ``[W, doubles_per_model]``
     (:func:`pack_models`) with the shape it was packed for (W models, S kernel states = the largest model's, D
     features) and each model's own state count ``n_states``; the device copy is made once."""
 
     def __init__(self, data, S, D, n_states=None):
-        self.data = np.ascontiguousarray(data, dtype=np.float64)
-        self.W, self.S, self.D = int(self.data.shape[0]), int(S), int(D)
-        n = pack_layout(self.S, self.D)[2]
-        if self.data.ndim != 2 or self.data.shape[1] != n:
-            raise ValueError(f"pack must be [W, {n}] (pack_models), got {self.data.shape}")
-        self.n_states = [self.S] * self.W if n_states is None else [int(k) for k in n_states]
-        self._dev = None
+        super().__init__(data, S, D, pack_layout(int(S), int(D))[2], n_states)
 
     @staticmethod
     def from_params(params, name="full") -> "FullPack":
@@ -224,11 +218,25 @@ class FullPack:
             m._check()
         return FullPack.from_params([m._full_params() for m in models])
 
-    def device(self, dev):
+    def batch(self, feats, lengths, utt_model) -> FullCovBatch:
+        """The utterances under ONE model each (``utt_model[u]``) of this vocabulary."""
+        return FullCovBatch(feats, lengths, utt_model, self.W, self.S)
+
+    def launch(self, feats, offsets, order, N, max_T, mode, score, best_word, word_post):
         torch = _torch()
-        if self._dev is None or self._dev.device != dev:
-            self._dev = torch.from_numpy(self.data).to(dev)
-        return self._dev
+        lib, dev, total = _lib.load(), feats.device, int(feats.shape[0])
+        n = C.c_size_t(0)
+        _lib.check(lib.sapr_full_vocab_workspace_bytes(N, total, self.W, self.S, self.D, C.byref(n)),
+                   "sapr_full_vocab_workspace_bytes")
+        ws_bytes = int(n.value)
+        workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+        _lib.check(lib.sapr_full_vocab(_lib.ptr(feats), _lib.ptr(offsets), _lib.ptr(order), N, total, self.D, max_T,
+                                       _lib.ptr(self.device(dev)), self.W, self.S, VOCAB_MODES[mode],
+                                       _lib.ptr(workspace), ws_bytes, _lib.ptr(score), _lib.ptr(best_word),
+                                       _lib.ptr(word_post), _lib.current_stream()), "sapr_full_vocab")
+
+    def vocab_scores(self, batch_or_feats, lengths=None, mode="forward", want_post=False):
+        return vocab_scores(batch_or_feats, lengths, self, mode=mode, want_post=want_post)
 
 
 def vocab_scores(batch_or_feats, lengths, pack_or_models, mode="forward", want_post=False):
@@ -239,29 +247,5 @@ def vocab_scores(batch_or_feats, lengths, pack_or_models, mode="forward", want_p
     ``trellis.FeatureBatch`` (``lengths`` is ignored) or host / device ``feats`` with host ``lengths``.
     ``pack_or_models``: a :class:`FullPack` or a list of ``GaussianHMM`` objects (padded to the largest S of the
     vocabulary; D must match).  ``want_post`` (forward mode only): the posterior over the words."""
-    from .gmm_hmm import VocabScores, vocab_features
-    torch = _torch()
-    if mode not in VOCAB_MODES:
-        raise ValueError(f"mode must be one of {sorted(VOCAB_MODES)}, got {mode!r}")
-    if want_post and mode != "forward":
-        raise ValueError("want_post needs mode='forward': a soft-max of path scores is not a posterior")
-    pack = pack_or_models if isinstance(pack_or_models, FullPack) else FullPack.from_models(list(pack_or_models))
-    lib = _lib.load()
-    feats, offsets, order, lengths, max_T = vocab_features(batch_or_feats, lengths)
-    if int(feats.shape[1]) != pack.D:
-        raise ValueError(f"the utterances have {int(feats.shape[1])} features, the models {pack.D}")
-    dev = feats.device
-    N, W, total = int(lengths.size), pack.W, int(feats.shape[0])
-    n = C.c_size_t(0)
-    _lib.check(lib.sapr_full_vocab_workspace_bytes(N, total, W, pack.S, pack.D, C.byref(n)),
-               "sapr_full_vocab_workspace_bytes")
-    ws_bytes = int(n.value)
-    workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-    score = torch.empty((N, W), dtype=torch.float64, device=dev)
-    best_word = torch.empty(N, dtype=torch.int32, device=dev)
-    word_post = torch.empty((N, W), dtype=torch.float64, device=dev) if want_post else None
-    _lib.check(lib.sapr_full_vocab(_lib.ptr(feats), _lib.ptr(offsets), _lib.ptr(order), N, total, pack.D, max_T,
-                                   _lib.ptr(pack.device(dev)), W, pack.S, VOCAB_MODES[mode], _lib.ptr(workspace),
-                                   ws_bytes, _lib.ptr(score), _lib.ptr(best_word), _lib.ptr(word_post),
-                                   _lib.current_stream()), "sapr_full_vocab")
-    return VocabScores(score, best_word, word_post)
+    from .gmm_hmm import _vocab_scores
+    return _vocab_scores(FullPack, batch_or_feats, lengths, pack_or_models, mode, want_post)

@@ -26,8 +26,8 @@ from typing import List
 import numpy as np
 
 from . import _lib
-from .hmmlearn_hmm import (DECODER_ALGORITHMS, ConvergenceMonitor, _features_f32, check_random_state, kmeans_seed,
-                           m_step, map_decode_host)
+from .hmmlearn_hmm import (DECODER_ALGORITHMS, ConvergenceMonitor, VocabPack, _features_f32, check_random_state,
+                           kmeans_seed, m_step, map_decode_host)
 
 MAX_STATES, MAX_MIX, MAX_DIMS = 18, 8, 39
 
@@ -189,19 +189,14 @@ class GmmBatch:
 # ------------------------------------------------------------------------------------------
 # scoring over the vocabulary: every utterance under every word model in one launch
 # ------------------------------------------------------------------------------------------
-class GmmPack:
+class GmmPack(VocabPack):
     """A vocabulary's operand block ready for the kernels: ``data`` float64 ``[W, doubles_per_model]``
     (:func:`pack_models`) with the shape it was packed for (W models, S kernel states = the largest model's, M
     components, D features) and each model's own state count ``n_states``; the device copy is made once."""
 
     def __init__(self, data, S, M, D, n_states=None):
-        self.data = np.ascontiguousarray(data, dtype=np.float64)
-        self.W, self.S, self.M, self.D = int(self.data.shape[0]), int(S), int(M), int(D)
-        n = pack_layout(self.S, self.M, self.D)[3]
-        if self.data.ndim != 2 or self.data.shape[1] != n:
-            raise ValueError(f"pack must be [W, {n}] (pack_models), got {self.data.shape}")
-        self.n_states = [self.S] * self.W if n_states is None else [int(k) for k in n_states]
-        self._dev = None
+        self.M = int(M)
+        super().__init__(data, S, D, pack_layout(int(S), self.M, int(D))[3], n_states)
 
     @staticmethod
     def from_params(params) -> "GmmPack":
@@ -219,11 +214,18 @@ class GmmPack:
             m._check()
         return GmmPack.from_params([m._params() for m in models])
 
-    def device(self, dev):
-        torch = _torch()
-        if self._dev is None or self._dev.device != dev:
-            self._dev = torch.from_numpy(self.data).to(dev)
-        return self._dev
+    def batch(self, feats, lengths, utt_model) -> GmmBatch:
+        """The utterances under ONE model each (``utt_model[u]``) of this vocabulary."""
+        return GmmBatch(feats, lengths, utt_model, self.W, self.S, self.M)
+
+    def launch(self, feats, offsets, order, N, max_T, mode, score, best_word, word_post):
+        _lib.check(_lib.load().sapr_gmm_vocab_diag(
+            _lib.ptr(feats), _lib.ptr(offsets), _lib.ptr(order), N, int(feats.shape[0]), self.D, max_T,
+            _lib.ptr(self.device(feats.device)), self.W, self.S, self.M, VOCAB_MODES[mode], _lib.ptr(score),
+            _lib.ptr(best_word), _lib.ptr(word_post), _lib.current_stream()), "sapr_gmm_vocab_diag")
+
+    def vocab_scores(self, batch_or_feats, lengths=None, mode="forward", want_post=False) -> "VocabScores":
+        return vocab_scores(batch_or_feats, lengths, self, mode=mode, want_post=want_post)
 
 
 @dataclass
@@ -275,13 +277,18 @@ def vocab_scores(batch_or_feats, lengths, pack_or_models, mode="forward", want_p
     with host ``lengths``.  ``pack_or_models``: a :class:`GmmPack` or a list of :class:`GMMHMM` objects (padded to the
     largest S of the vocabulary; M and D must match).  ``want_post`` (forward mode only): the posterior over the
     words."""
+    return _vocab_scores(GmmPack, batch_or_feats, lengths, pack_or_models, mode, want_post)
+
+
+def _vocab_scores(pack_type, batch_or_feats, lengths, pack_or_models, mode, want_post) -> VocabScores:
+    """The one implementation behind :func:`vocab_scores` and ``full_cov.vocab_scores``: ``pack_type`` is the family's
+    :class:`sapr_amd.hmmlearn_hmm.VocabPack`, whose ``launch`` calls the family's entry point."""
     torch = _torch()
     if mode not in VOCAB_MODES:
         raise ValueError(f"mode must be one of {sorted(VOCAB_MODES)}, got {mode!r}")
     if want_post and mode != "forward":
         raise ValueError("want_post needs mode='forward': a soft-max of path scores is not a posterior")
-    pack = pack_or_models if isinstance(pack_or_models, GmmPack) else GmmPack.from_models(list(pack_or_models))
-    lib = _lib.load()
+    pack = pack_or_models if isinstance(pack_or_models, pack_type) else pack_type.from_models(list(pack_or_models))
     feats, offsets, order, lengths, max_T = vocab_features(batch_or_feats, lengths)
     if int(feats.shape[1]) != pack.D:
         raise ValueError(f"the utterances have {int(feats.shape[1])} features, the models {pack.D}")
@@ -290,10 +297,7 @@ def vocab_scores(batch_or_feats, lengths, pack_or_models, mode="forward", want_p
     score = torch.empty((N, W), dtype=torch.float64, device=dev)
     best_word = torch.empty(N, dtype=torch.int32, device=dev)
     word_post = torch.empty((N, W), dtype=torch.float64, device=dev) if want_post else None
-    _lib.check(lib.sapr_gmm_vocab_diag(_lib.ptr(feats), _lib.ptr(offsets), _lib.ptr(order), N, int(feats.shape[0]),
-                                       pack.D, max_T, _lib.ptr(pack.device(dev)), W, pack.S, pack.M, VOCAB_MODES[mode],
-                                       _lib.ptr(score), _lib.ptr(best_word), _lib.ptr(word_post),
-                                       _lib.current_stream()), "sapr_gmm_vocab_diag")
+    pack.launch(feats, offsets, order, N, max_T, mode, score, best_word, word_post)
     return VocabScores(score, best_word, word_post)
 
 

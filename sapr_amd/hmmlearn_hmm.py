@@ -184,6 +184,28 @@ def _features_f32(X) -> np.ndarray:
     return out
 
 
+class VocabPack:
+    """A vocabulary's operand block ready for the kernels: ``data`` float64 ``[W, doubles_per_model]`` (the family's
+    ``pack_models``) with the shape it was packed for (W models, S kernel states = the largest model's, D features)
+    and each model's own state count ``n_states``; the device copy is made once.  The families
+    (``gmm_hmm.GmmPack``, ``full_cov.FullPack``) add what is theirs: how a pack is built, the per-model batch class
+    (:meth:`batch`) and the entry point that scores the vocabulary (:meth:`launch`, :meth:`vocab_scores`)."""
+
+    def __init__(self, data, S, D, doubles_per_model, n_states=None):
+        self.data = np.ascontiguousarray(data, dtype=np.float64)
+        self.W, self.S, self.D = int(self.data.shape[0]), int(S), int(D)
+        if self.data.ndim != 2 or self.data.shape[1] != doubles_per_model:
+            raise ValueError(f"pack must be [W, {doubles_per_model}] (pack_models), got {self.data.shape}")
+        self.n_states = [self.S] * self.W if n_states is None else [int(k) for k in n_states]
+        self._dev = None
+
+    def device(self, dev):
+        import torch
+        if self._dev is None or self._dev.device != dev:
+            self._dev = torch.from_numpy(self.data).to(dev)
+        return self._dev
+
+
 DECODER_ALGORITHMS = ("viterbi", "map")
 
 

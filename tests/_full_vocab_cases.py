@@ -24,6 +24,12 @@ CASES = {
     "d27_s11_bidiag": (27, 11, "bidiag", 3, 6, 30, 60, (), 0),       # smallest DP 39 / SP 18
     "d39_s18_bidiag": (39, 18, "bidiag", 3, 6, 40, 90, (), 0),       # largest instantiation
     "d13_s4_dense_300": (13, 4, "dense", 2, 150, 12, 14, (), 0),     # 300 utterances: two tiles, the second partial
+    # the (SP, DP) pairs the cases above leave out: with them every full_vocab_kernel instantiation is run
+    "d13_s11_bidiag": (13, 11, "bidiag", 3, 6, 30, 60, (), 0),       # SP 18 / DP 13
+    "d14_s4_dense": (14, 4, "dense", 3, 6, 12, 40, (), 0),           # SP 4 / DP 26
+    "d26_s11_bidiag": (26, 11, "bidiag", 3, 6, 30, 60, (), 0),       # SP 18 / DP 26
+    "d27_s4_dense": (27, 4, "dense", 3, 6, 12, 40, (), 0),           # SP 4 / DP 39
+    "d27_s10_bidiag": (27, 10, "bidiag", 3, 6, 30, 60, (), 0),       # SP 10 / DP 39
 }
 MODES = ("forward", "viterbi")
 

@@ -198,8 +198,8 @@ def test_decoder_routes_full_and_tied_models_without_a_gpu(tmp_path, monkeypatch
         dec = Decoder(models_dir=str(root), implementation="hmmlearn", scoring=scoring)
         assert sorted(dec.vocab) == ["heed", "hid", "hood"] and dec.vocab == list(dec.models)
         assert dec._is_full()
-        pack = dec._full_pack()
-        assert isinstance(pack, full_cov.FullPack) and dec._full_pack() is pack
+        pack = dec._vocab_pack()
+        assert isinstance(pack, full_cov.FullPack) and dec._vocab_pack() is pack
         assert (pack.W, pack.S, pack.D, pack.n_states) == (3, 3, 5, [3, 3, 3])
         assert dec._pack is None                               # DiagModelPack.from_models was never called
     with pytest.raises(ValueError):
@@ -212,7 +212,7 @@ def test_decoder_routes_full_and_tied_models_without_a_gpu(tmp_path, monkeypatch
     for word, prm in zip(("heed", "hid"), c["params"]):
         _write(diag, word, _model(prm, "diag"))
     dec = Decoder(models_dir=str(diag), implementation="hmmlearn")
-    assert not dec._is_full() and dec._full is None
+    assert not dec._is_full() and dec._vocab is None
 
     class Reached(Exception):
         pass

@@ -298,7 +298,7 @@ def test_decoder_over_full_covariance_models(tmp_path, name, types):
     want = vc.reference(name)
     rvit, rfwd = want["viterbi"][0][:, order], want["forward"][0][:, order]
     vbw, fbw = vc.first_strict_max(rvit), vc.first_strict_max(rfwd)
-    pack = dec._full_pack()
+    pack = dec._vocab_pack()
     launch = {mode: full_cov.vocab_scores(c["feats"], c["lengths"], pack, mode=mode).score.cpu().numpy()
               for mode in MODES}
     N = len(utts)
@@ -384,4 +384,4 @@ def test_a_vocabulary_of_diagonal_models_keeps_the_single_gaussian_path(tmp_path
     dec = Decoder(models_dir=_model_dir(tmp_path, c["params"], ("diag", "diag", "diag")), implementation="hmmlearn")
     assert not dec._is_full()
     got = dec.decode_batch([np.ascontiguousarray(x.T) for x in c["flat"]])
-    assert isinstance(dec._pack, DiagModelPack) and dec._full is None and len(got) == len(c["flat"])
+    assert isinstance(dec._pack, DiagModelPack) and dec._vocab is None and len(got) == len(c["flat"])

@@ -257,7 +257,7 @@ def test_decoder_gmmhmm(tmp_path, name):
     want = _reference(name)
     rvit, rfwd = want["viterbi"][0][:, order], want["forward"][0][:, order]
     vbw, fbw = _first_strict_max(rvit), _first_strict_max(rfwd)
-    pack = dec._gmm_pack()
+    pack = dec._vocab_pack()
     launch = {mode: gh.vocab_scores(c["feats"], c["lengths"], pack, mode=mode).score.cpu().numpy() for mode in MODES}
 
     def check(got, rsc, rbw, mode):
