@@ -73,7 +73,7 @@ KERNEL_SOURCES = {
     "decode": ["viterbi.hip", "viterbi_bound.hip", "viterbi_exact.inc", "viterbi_exact_13_10.hip", "viterbi_shared.h",
                "emission.h", "sapr_common.h"],
     "gmm": ["gmm_hmm.hip", "gmm_vocab.hip", "gmm_ops.h", "fullcov_ops.h", "lse_ops.h", "lse_unit.h", "sapr_common.h",
-            "full_vocab.hip", "fullcov_emit.h", "vocab_epilogue.h", "vocab_scan.h"],
+            "full_vocab.hip", "fullcov_emit.h", "vocab_epilogue.h", "vocab_scan.h", "tile_trellis.h"],
 }
 
 

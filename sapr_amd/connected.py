@@ -256,7 +256,7 @@ def connected_decode(batch_or_feature_list, network: ConnectedNetwork) -> Connec
     """Emission and recursion for diagonal-Gaussian word models: a ``trellis.FeatureBatch`` or a list of frame-major
     ``(T, D)`` feature arrays -> :class:`ConnectedResult`."""
     torch = _torch()
-    from .gmm_hmm import vocab_features
+    from .tile_family import vocab_features
     b = batch_or_feature_list
     if hasattr(b, "offsets") and hasattr(b, "order"):
         feats, offs_dev, _, lengths, _ = vocab_features(b)

@@ -1,14 +1,15 @@
-// Full-covariance Gaussian emissions for the trellis kernels of gmm_hmm.hip (hmmlearn's GaussianHMM with
-// covariance_type "full" or "tied"; a tied model is packed as S copies of its one matrix).  Included INSIDE the unit's
-// `namespace sapr { namespace {`, after gmm_ops.h and after the tile helpers of gmm_hmm.hip (Batch, tile_scan,
-// find_slot, kBlock, kSub, kChunk).  CPU restatement: tests/_fullcov_ref.py.
+// The full-covariance family of the per-model trellis (hmmlearn's GaussianHMM with covariance_type "full" or "tied"; a
+// tied model is packed as S copies of its one matrix): its two frame-parallel kernels over the tile helpers of
+// tile_trellis.h and its family description (Full) for run<Family> of gmm_hmm.hip.  Needs sapr_common.h; included
+// INSIDE the unit's `namespace sapr { namespace {` like the headers it includes.  CPU restatement:
+// tests/_fullcov_ref.py.
 //
 //   Sigma_s = L_s L_s^T        Winv_s = L_s^-1 (lower triangular, from the host)
 //   logb[t,s] = c_s - 1/2 sum_i (sum_{j<=i} Winv_s[i][j] (x_j - mu_s[j]))^2       c_s = -(D log 2 pi + log|Sigma_s|) / 2
 //
-// The pack keeps the head of the mixture pack (log_start[SP], log_trans[SP][SP], its transpose), so the recursions,
-// the posteriors, both decoders, the xi sums and the reductions of gmm_hmm.hip run unchanged over logb; only the two
-// frame-parallel passes are new:
+// The pack keeps the head every family's pack has (log_start[SP], log_trans[SP][SP], its transpose), so the recursions,
+// the posteriors, both decoders, the xi sums and the reductions of tile_trellis.h run unchanged over logb; the two
+// frame-parallel passes are the family's own:
 //   full_emit_kernel<DP>    one thread per flat frame, the frame as DP doubles in registers, the tile's model
 //                           wavefront-uniform (scalar loads); row after row of Winv_s with one running dot product
 //   full_accum_kernel<DP>   obs[s] = sum_t gamma_t(s) x_t and oo[s] = sum_t gamma_t(s) x_t x_t^T as weighted Gram
@@ -17,6 +18,7 @@
 //                           the diagonal are computed; both halves of oo are written from the upper one.
 #pragma once
 
+#include "tile_trellis.h"
 #include "fullcov_emit.h"
 
 typedef double f64x4_full __attribute__((ext_vector_type(4)));
@@ -38,9 +40,7 @@ __global__ __launch_bounds__(kBlock) void full_emit_kernel(Batch b, const double
   const int total = tile_scan(b, tile, tile_ok, s_cum, s_beg, s_wave);
   const int64_t flat64 = static_cast<int64_t>(blockIdx.y) * kBlock + threadIdx.x;
   if (flat64 >= total) return;
-  const int flat = static_cast<int>(flat64);
-  const int slot = find_slot(s_cum, flat);
-  const int64_t frame = s_beg[slot] + (flat - s_cum[slot]);
+  const int64_t frame = flat_frame(s_cum, s_beg, static_cast<int>(flat64));
   double x[DP];
   load_frame_pad<DP>(b.feats + frame * b.D, b.D, true, x);
   const double *__restrict__ mdl = pack + static_cast<int64_t>(w) * b.stride;  // wavefront-uniform
@@ -101,10 +101,7 @@ __global__ __launch_bounds__(kBlock) void full_accum_kernel(Batch b, int SP, con
       if (tid < kChunk) {
         const int flat = c * kChunk + tid;
         int64_t frame = -1;
-        if (flat < total) {
-          const int slot = find_slot(s_cum, flat);
-          frame = s_beg[slot] + (flat - s_cum[slot]);
-        }
+        if (flat < total) frame = flat_frame(s_cum, s_beg, flat);
         s_frame[tid] = frame;
       }
       __syncthreads();
@@ -182,3 +179,33 @@ __global__ __launch_bounds__(kBlock) void full_accum_kernel(Batch b, int SP, con
     }
   }
 }
+
+// -------------------------------------------------------------------------------------------
+// the family description (gmm_hmm.hip: run<Family>); there are no components: M is passed as 1 and ignored
+// -------------------------------------------------------------------------------------------
+struct Full {
+  static int check(int32_t S, int32_t, int32_t D) { return check_full_shape(S, D); }
+  static size_t model_doubles(int S, int, int D) { return full_model_doubles(sp_of(S), dp_of(D)); }
+  static int stats_p(int S, int, int D) { return full_stats_p(S, D); }
+  static int launch_emit(const Batch &b, const double *pack, int64_t n_tiles, double *logb, hipStream_t stream) {
+    const dim3 grid(static_cast<unsigned>(n_tiles), static_cast<unsigned>(b.max_T));
+    switch (dp_of(b.D)) {
+      case 13: SAPR_LAUNCH(full_emit_kernel<13>, grid, dim3(kBlock), 0, stream, b, pack, sp_of(b.S), logb); break;
+      case 26: SAPR_LAUNCH(full_emit_kernel<26>, grid, dim3(kBlock), 0, stream, b, pack, sp_of(b.S), logb); break;
+      default: SAPR_LAUNCH(full_emit_kernel<39>, grid, dim3(kBlock), 0, stream, b, pack, sp_of(b.S), logb); break;
+    }
+    SAPR_HIP_TRY(hipGetLastError());
+    return 0;
+  }
+  static int launch_accum(const Batch &b, const double *, int64_t n_tiles, const double *gam, double *part,
+                          hipStream_t stream) {
+    const dim3 grid(static_cast<unsigned>(n_tiles), kSub);
+    switch (dp_of(b.D)) {
+      case 13: SAPR_LAUNCH(full_accum_kernel<13>, grid, dim3(kBlock), 0, stream, b, sp_of(b.S), gam, part); break;
+      case 26: SAPR_LAUNCH(full_accum_kernel<26>, grid, dim3(kBlock), 0, stream, b, sp_of(b.S), gam, part); break;
+      default: SAPR_LAUNCH(full_accum_kernel<39>, grid, dim3(kBlock), 0, stream, b, sp_of(b.S), gam, part); break;
+    }
+    SAPR_HIP_TRY(hipGetLastError());
+    return 0;
+  }
+};

@@ -13,18 +13,14 @@
 //        after slot: a scan of the 256 lengths in LDS and a binary search per thread), one workgroup per 256 flat
 //        frames, the frame as DP doubles in registers, the tile's model wavefront-uniform (scalar loads).  Writes
 //        logb[frame][SP].  The difference is squared directly (c0 sits near -300: the expanded form cancels).
-//   2  gmm_forward_kernel<SP, VIT>   one lane per utterance over logb: _hmmc.cpp forward_log (VIT: viterbi, the max
-//        semiring, and its back-trace over the stored lattice).  Transitions whose log is -inf are skipped by a
-//        wavefront-uniform branch (a bidiagonal matrix is just a sparse dense one: 2 S - 1 terms instead of S^2).
-//      gmm_backward_kernel<SP>       backward_log, gamma (replaces the forward lattice in place; post / path are
-//        written from the same registers), start, sum gamma and the xi sums in the linear domain, kept slot-major
-//        (coalesced read-modify-write of the finite transitions only).
+//   2  gmm_forward_kernel<SP, VIT>, gmm_backward_kernel<SP>   one lane per utterance over logb: the recursions, the
+//        posteriors, both decoders, start and the xi sums (tile_trellis.h; they never look at an emission parameter).
 //   3  gmm_accum_kernel<MP, DP>      FRAME-parallel again: chunks of 64 flat frames of a tile; phase A recomputes lc
 //        (state per wavefront, frame per lane) and puts r into LDS, phase B is the product r^T [x, x^2, 1] with threads
 //        owning (state, component, dimension) accumulators in registers over the workgroup's chunks (vector ALU,
 //        float64; x^2 rounded to float32 first, as numpy squares a float32 feature array).  kSub partial rows per tile.
-//      gmm_tile_reduce_kernel / gmm_reduce_kernel   the 256 slots of a tile in a fixed shape, then a model's partial
-//        rows in tile order.
+//      gmm_tile_reduce_kernel / gmm_reduce_kernel   (tile_trellis.h) the 256 slots of a tile in a fixed shape, then a
+//        model's partial rows in tile order.
 // No floating-point atomics; every sum has one fixed order that depends only on the model's own tiles, so results are
 // bit-identical run to run and independent of which other models share the launch; loglik, post and path of an
 // utterance are a function of its own (features, model) pair.
@@ -33,91 +29,19 @@
 // and log transitions -inf and every component switched off), MP in {1, 2, 4, 8} components (a padded component has
 // the constant -inf: exp(-inf) adds +0.0), DP in {13, 26, 39} dimensions (zero features against zero means and zero
 // inverse variances add +0.0).  The pack (sapr_gmm_pack_layout) is built by the host in this padded form.
+//
+// What is specific to the mixtures is here: the two frame-parallel kernels and the family description (Mix).  The
+// recursions, the reductions and the tile helpers are tile_trellis.h; the full-covariance family (Full: hmmlearn's
+// GaussianHMM, covariance_type "full" / "tied") is fullcov_ops.h; run<Family> below is the one host engine behind both.
 #include "sapr_common.h"
 
 namespace sapr {
 namespace {
 
-#include "lse_ops.h"
-#include "gmm_ops.h"
+#include "tile_trellis.h"
+#include "fullcov_ops.h"
 
-constexpr int kBlock = 256;   // slots per tile
-constexpr int kSub = 4;       // partial rows of the observation sums per tile
-constexpr int kChunk = 64;    // flat frames per chunk of the accumulation pass
-constexpr int kMaxT = 65535;  // (the emission grid's second dimension)
-
-constexpr int stats_k1(int S) { return 2 + S + S * S + S; }                 // n_seq, loglik, start, trans, post
 constexpr int stats_p(int S, int M, int D) { return S * M * (2 * D + 1); }  // post_mix, obs, obs2
-
-struct Ws {
-  double *logb, *lat, *ustat, *tile_stats, *part;
-  size_t bytes;
-};
-
-Ws carve(void *base, int64_t total_frames, int64_t n_tiles, int S, int M, int D) {
-  const size_t fr = static_cast<size_t>(total_frames > 0 ? total_frames : 1) * sp_of(S);
-  const size_t nt = static_cast<size_t>(n_tiles > 0 ? n_tiles : 1);
-  Ws w;
-  w.logb = static_cast<double *>(base);
-  w.lat = w.logb + fr;
-  w.ustat = w.lat + fr;
-  w.tile_stats = w.ustat + static_cast<size_t>(stats_k1(S)) * nt * kBlock;
-  w.part = w.tile_stats + nt * stats_k1(S);
-  w.bytes = (2 * fr + static_cast<size_t>(stats_k1(S)) * nt * kBlock + nt * stats_k1(S) +
-             nt * kSub * stats_p(S, M, D)) * sizeof(double);
-  return w;
-}
-
-struct Batch {
-  const float *feats;
-  const int64_t *offsets;
-  const int32_t *slot_utt, *tile_model;
-  int64_t n_utts, total_frames, n_slots;
-  int32_t D, max_T, W, S, M;
-  int64_t stride;  // doubles per model of the pack
-};
-
-// the utterance of a slot: T = 0 for an empty slot and for anything that points outside the batch (never followed)
-__device__ __forceinline__ Span slot_span(const Batch &b, int64_t slot, bool tile_ok) {
-  return utt_span(b.offsets, b.slot_utt[slot], tile_ok, b.n_utts, b.total_frames, b.max_T);
-}
-
-// A tile's utterances end to end: s_cum[i] = frames of the slots before slot i (s_cum[256] = all), s_beg[i] = first
-// frame of slot i in the batch.  Every thread of the 256-thread workgroup must call it.
-__device__ __forceinline__ int tile_scan(const Batch &b, int64_t tile, bool tile_ok, int32_t *s_cum, int64_t *s_beg,
-                                         int32_t *s_wave) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const Span sp = slot_span(b, tile * kBlock + tid, tile_ok);
-  s_beg[tid] = sp.beg;
-  int incl = sp.T;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int up = __shfl_up(incl, o, 64);
-    incl += lane >= o ? up : 0;
-  }
-  if (lane == 63) s_wave[wv] = incl;
-  __syncthreads();
-  int base = 0;
-#pragma unroll
-  for (int w = 0; w < kBlock / 64; ++w) base += w < wv ? s_wave[w] : 0;
-  s_cum[tid + 1] = base + incl;
-  if (tid == 0) s_cum[0] = 0;
-  __syncthreads();
-  return s_cum[kBlock];
-}
-
-// the slot that owns flat frame `flat` (0 <= flat < s_cum[256]): s_cum[slot] <= flat < s_cum[slot + 1]
-__device__ __forceinline__ int find_slot(const int32_t *s_cum, int flat) {
-  int lo = 0, hi = kBlock;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int mid = (lo + hi) >> 1;
-    const bool up = s_cum[mid] <= flat;
-    lo = up ? mid : lo;
-    hi = up ? hi : mid;
-  }
-  return lo;
-}
 
 // -------------------------------------------------------------------------------------------
 // pass 1: logb[frame][SP]
@@ -134,9 +58,7 @@ __global__ __launch_bounds__(kBlock) void gmm_emit_kernel(Batch b, const double 
   const int total = tile_scan(b, tile, tile_ok, s_cum, s_beg, s_wave);
   const int64_t flat64 = static_cast<int64_t>(blockIdx.y) * kBlock + threadIdx.x;
   if (flat64 >= total) return;
-  const int flat = static_cast<int>(flat64);
-  const int slot = find_slot(s_cum, flat);
-  const int64_t frame = s_beg[slot] + (flat - s_cum[slot]);
+  const int64_t frame = flat_frame(s_cum, s_beg, static_cast<int>(flat64));
   double x[DP];
   load_frame_pad<DP>(b.feats + frame * b.D, b.D, true, x);
   const double *__restrict__ mdl = pack + static_cast<int64_t>(w) * b.stride;  // wavefront-uniform
@@ -150,203 +72,6 @@ __global__ __launch_bounds__(kBlock) void gmm_emit_kernel(Batch b, const double 
       out[s] = lc[0];
     else
       out[s] = lse_all<MP>(lc);
-  }
-}
-
-// -------------------------------------------------------------------------------------------
-// pass 2: the recursions, one lane per utterance, one wavefront per workgroup
-// -------------------------------------------------------------------------------------------
-template <int SP, bool VIT>
-__global__ __launch_bounds__(64) void gmm_forward_kernel(Batch b, const double *__restrict__ pack,
-                                                         const double *__restrict__ logb,
-                                                         double *__restrict__ lat, double *__restrict__ loglik,
-                                                         int32_t *__restrict__ path) {
-  const int64_t tile = blockIdx.x / (kBlock / 64);
-  const int64_t slot = static_cast<int64_t>(blockIdx.x) * 64 + threadIdx.x;
-  const int w = b.tile_model[tile];
-  const bool tile_ok = w >= 0 && w < b.W;
-  const Span sp = slot_span(b, slot, tile_ok);
-  if (sp.u < 0) return;
-  const int T = sp.T;
-  if (T <= 0) {
-    loglik[sp.u] = neg_inf();
-    return;
-  }
-  const double *__restrict__ mdl = pack + static_cast<int64_t>(tile_ok ? w : 0) * b.stride;  // wavefront-uniform
-  const double *__restrict__ ls = mdl;
-  const double *__restrict__ lt = mdl + SP;
-  const double *__restrict__ ltT = lt + SP * SP;
-  const double *__restrict__ lb = logb + sp.beg * SP;
-  double *__restrict__ la = lat + sp.beg * SP;
-  const int S = b.S;
-
-  double fwd[SP], bn[SP];
-#pragma unroll
-  for (int s = 0; s < SP; ++s) {
-    fwd[s] = ls[s] + lb[s];
-    la[s] = fwd[s];
-  }
-  if (T > 1) {
-#pragma unroll
-    for (int s = 0; s < SP; ++s) bn[s] = lb[SP + s];
-  }
-  for (int t = 1; t < T; ++t) {
-    double bt[SP], prev[SP];
-#pragma unroll
-    for (int s = 0; s < SP; ++s) {
-      bt[s] = bn[s];
-      prev[s] = fwd[s];
-    }
-    const int tn = t + 1 < T ? t + 1 : t;  // the next frame's row in flight under this frame's exponentials
-#pragma unroll
-    for (int s = 0; s < SP; ++s) bn[s] = lb[static_cast<int64_t>(tn) * SP + s];
-    // state after state in a rolled loop over the model's own S states (a padded state keeps its -inf): column j of
-    // the transition matrix is one run of scalar loads, and the value lands in register j by a uniform select
-#pragma unroll 1
-    for (int j = 0; j < S; ++j) {
-      const double *__restrict__ col = ltT + j * SP;
-      const double v = reduce_finite<SP, VIT>([&](int i) { return prev[i]; }, [&](int i) { return col[i]; });
-#pragma unroll
-      for (int k = 0; k < SP; ++k) fwd[k] = k == j ? v + bt[k] : fwd[k];
-    }
-#pragma unroll
-    for (int s = 0; s < SP; ++s) la[static_cast<int64_t>(t) * SP + s] = fwd[s];
-  }
-  if constexpr (!VIT) {
-    loglik[sp.u] = lse_all<SP>(fwd);
-  } else {
-    // _hmmc.cpp viterbi: the first maximum of the last row, then argmax_i (lattice[t][i] + log a[i][next]), first
-    // maximum — the next state differs from lane to lane: its column is gathered from memory
-    int st = argmax_first<SP>(fwd, S);
-    double best = fwd[0];
-#pragma unroll
-    for (int s = 1; s < SP; ++s) best = s == st ? fwd[s] : best;
-    loglik[sp.u] = best;
-    int32_t *__restrict__ po = path + sp.beg;
-    po[T - 1] = st;
-    for (int t = T - 2; t >= 0; --t) {
-      double cand[SP];
-#pragma unroll
-      for (int i = 0; i < SP; ++i) cand[i] = la[static_cast<int64_t>(t) * SP + i] + lt[i * SP + st];
-      st = argmax_first<SP>(cand, S);
-      po[t] = st;
-    }
-  }
-}
-
-template <int SP>
-__global__ __launch_bounds__(64) void gmm_backward_kernel(Batch b, const double *__restrict__ pack,
-                                                          const double *__restrict__ logb,
-                                                          double *__restrict__ lat,
-                                                          const double *__restrict__ loglik,
-                                                          double *__restrict__ ustat, double *__restrict__ post,
-                                                          int32_t *__restrict__ path) {
-  const int S = b.S;
-  const int K1 = stats_k1(S);
-  const int64_t tile = blockIdx.x / (kBlock / 64);
-  const int64_t slot = static_cast<int64_t>(blockIdx.x) * 64 + threadIdx.x;
-  const int w = b.tile_model[tile];
-  const bool tile_ok = w >= 0 && w < b.W;
-  const Span sp = slot_span(b, slot, tile_ok);
-  double *__restrict__ us = ustat ? ustat + slot : nullptr;  // statistic k of this slot: us[k * n_slots]
-  const int64_t ns = b.n_slots;
-  if (us) {
-    for (int k = 0; k < K1; ++k) us[k * ns] = 0.0;  // (an empty slot contributes zeros)
-  }
-  const int T = sp.T;
-  if (T <= 0) return;
-  const double *__restrict__ lt = pack + static_cast<int64_t>(w) * b.stride + SP;  // wavefront-uniform
-  const double *__restrict__ lb = logb + sp.beg * SP;
-  double *__restrict__ la = lat + sp.beg * SP;
-  const double logprob = loglik[sp.u];
-
-  double bwd[SP], psum[SP], fw[SP], g[SP];
-#pragma unroll
-  for (int s = 0; s < SP; ++s) {
-    bwd[s] = 0.0;
-    psum[s] = 0.0;
-    fw[s] = la[static_cast<int64_t>(T - 1) * SP + s];
-  }
-  for (int t = T - 1; t >= 0; --t) {
-    // the rows of the step to t - 1 in flight under this frame's exponentials
-    double bt[SP], fp[SP];
-    const int tp = t >= 1 ? t - 1 : 0;
-#pragma unroll
-    for (int s = 0; s < SP; ++s) {
-      bt[s] = lb[static_cast<int64_t>(t) * SP + s];
-      fp[s] = la[static_cast<int64_t>(tp) * SP + s];
-    }
-    // base.py _compute_posteriors_log: row soft-max of fwd + bwd as exp(lg - max) / sum
-    double mx = fw[0] + bwd[0];
-#pragma unroll
-    for (int s = 0; s < SP; ++s) {
-      g[s] = fw[s] + bwd[s];
-      mx = g[s] > mx ? g[s] : mx;
-    }
-    double den = 0.0;
-#pragma unroll
-    for (int s = 0; s < SP; ++s) {
-      g[s] = exp_unit(g[s] - mx);  // all -inf: NaN, as exp(lg - (-inf)) is in the reference
-      den += g[s];
-    }
-    const double inv = 1.0 / den;
-#pragma unroll
-    for (int s = 0; s < SP; ++s) {
-      g[s] *= inv;
-      psum[s] += g[s];
-      la[static_cast<int64_t>(t) * SP + s] = g[s];  // gamma replaces the forward lattice in place
-      if (t == 0 && us && s < S) us[static_cast<int64_t>(2 + s) * ns] = g[s];  // stats['start'] += posteriors[0]
-    }
-    if (post) {
-      double *__restrict__ pr = post + (sp.beg + t) * S;
-#pragma unroll
-      for (int s = 0; s < SP; ++s)
-        if (s < S) pr[s] = g[s];
-    }
-    if (path) path[sp.beg + t] = argmax_first<SP>(g, S);
-    if (t == 0) break;
-    // _hmmc.cpp backward_log: bwd_(t-1)[i] = logsumexp_j(log a_ij + b_t[j] + bwd_t[j]); xi_t(i, j) beside it
-    double nb[SP];
-#pragma unroll
-    for (int j = 0; j < SP; ++j) {
-      bt[j] += bwd[j];  // b_t[j] + bwd_t[j], the part of every term that depends on j alone
-      nb[j] = neg_inf();
-    }
-    // row after row in a rolled loop over the model's own S states (as in the forward kernel)
-#pragma unroll 1
-    for (int i = 0; i < S; ++i) {
-      const double *__restrict__ row = lt + i * SP;
-      const double v = reduce_finite<SP, false>([&](int j) { return bt[j]; }, [&](int j) { return row[j]; });
-      double fpi = fp[0];
-#pragma unroll
-      for (int k = 0; k < SP; ++k) {
-        nb[k] = k == i ? v : nb[k];
-        fpi = k == i ? fp[k] : fpi;
-      }
-      if (us) {
-        const double base = fpi - logprob;
-#pragma unroll
-        for (int j = 0; j < SP; ++j) {
-          const double a = row[j];
-          if (j < S && a > neg_inf()) {  // (a padded state's column is -inf in a well-formed pack: never trusted)
-            double *__restrict__ x = us + static_cast<int64_t>(2 + S + i * S + j) * ns;
-            *x += exp_unit(base + a + bt[j]);
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int s = 0; s < SP; ++s) {
-      bwd[s] = nb[s];
-      fw[s] = fp[s];
-    }
-  }
-  if (us) {
-    us[0] = 1.0;
-    us[ns] = logprob;
-#pragma unroll
-    for (int s = 0; s < SP; ++s)
-      if (s < S) us[static_cast<int64_t>(2 + S + S * S + s) * ns] = psum[s];
   }
 }
 
@@ -398,8 +123,7 @@ __global__ __launch_bounds__(kBlock) void gmm_accum_kernel(Batch b, const double
       const bool live = flat < total;
       int64_t frame = 0;
       if (live) {
-        const int slot = find_slot(s_cum, flat);
-        frame = s_beg[slot] + (flat - s_cum[slot]);
+        frame = flat_frame(s_cum, s_beg, flat);
       }
       // the chunk's frames into LDS, float32 as they are: columns [0, D) the features, column D the ones behind
       // post_mix (against a padded dimension's zero mean and zero inverse variance it adds +0.0), zeros after it;
@@ -484,54 +208,6 @@ __global__ __launch_bounds__(kBlock) void gmm_accum_kernel(Batch b, const double
   }
 }
 
-// tile_stats[tile][k] = the statistic's 256 slot values added in one fixed shape: four per lane in slot order, then
-// the butterfly over the wavefront's lanes.  One wavefront per statistic at a time, coalesced.
-__global__ __launch_bounds__(kBlock) void gmm_tile_reduce_kernel(int K1, int64_t n_slots,
-                                                                 const double *__restrict__ ustat,
-                                                                 double *__restrict__ tile_stats) {
-  const int64_t tile = blockIdx.x;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  for (int k = wv; k < K1; k += kBlock / 64) {
-    const double *__restrict__ src = ustat + static_cast<int64_t>(k) * n_slots + tile * kBlock + lane;
-    double v = src[0];
-    v += src[64];
-    v += src[128];
-    v += src[192];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if (lane == 0) tile_stats[tile * K1 + k] = v;
-  }
-}
-
-// stats[w] = {n_seq, loglik, start[S], trans[S][S], post[S], post_mix[S][M], obs[S][M][D], obs2[S][M][D]} summed over
-// the model's partial rows in tile order (kSub rows per tile for the observation sums); eight rows in flight
-__global__ void gmm_reduce_kernel(const int32_t *__restrict__ model_tile_off, int W, int K1, int P, int64_t n_tiles,
-                                  const double *__restrict__ tile_stats, const double *__restrict__ part,
-                                  double *__restrict__ stats) {
-  const int Kw = K1 + P;
-  const int64_t idx = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
-  if (idx >= static_cast<int64_t>(W) * Kw) return;
-  const int w = static_cast<int>(idx / Kw), k = static_cast<int>(idx - static_cast<int64_t>(w) * Kw);
-  int64_t t0 = model_tile_off[w], t1 = model_tile_off[w + 1];
-  t0 = t0 < 0 ? 0 : t0;  // (a table that points past the workspace's rows is cut, never followed)
-  t1 = t1 > n_tiles ? n_tiles : t1;
-  const int sub = k < K1 ? 1 : kSub;
-  const double *__restrict__ src = k < K1 ? tile_stats + k : part + (k - K1);
-  const int64_t stride = k < K1 ? K1 : P;
-  double acc = 0.0;
-  int64_t r = t0 * sub;
-  const int64_t r1 = t1 * sub;
-  for (; r + 8 <= r1; r += 8) {
-    double v[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = src[(r + i) * stride];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) acc += v[i];
-  }
-  for (; r < r1; ++r) acc += src[r * stride];
-  stats[idx] = acc;
-}
-
 // -------------------------------------------------------------------------------------------
 // launches
 // -------------------------------------------------------------------------------------------
@@ -570,25 +246,25 @@ int launch_frames(bool emit, const Batch &b, const double *pack, int64_t n_tiles
   }
 }
 
-template <int SP>
-int launch_trellis(bool vit, const Batch &b, const double *pack, int64_t n_tiles, const Ws &ws, double *loglik, double *ustat,
-                   double *post, int32_t *path, hipStream_t stream) {
-  const dim3 grid(static_cast<unsigned>(n_tiles * (kBlock / 64))), block(64);
-  if (vit) {
-    SAPR_LAUNCH((gmm_forward_kernel<SP, true>), grid, block, 0, stream, b, pack, ws.logb, ws.lat, loglik, path);
-    SAPR_HIP_TRY(hipGetLastError());
-    return 0;
+// -------------------------------------------------------------------------------------------
+// A family of emissions is four things: its shape check, its pack stride, the width of its observation statistics and
+// its two frame-parallel launches (emit: logb; accumulate: the partial rows from the gamma lattice).  Full
+// (fullcov_ops.h) has no M: it is passed 1.  Everything else is the engine.
+// -------------------------------------------------------------------------------------------
+struct Mix {
+  static int check(int32_t S, int32_t M, int32_t D) { return check_shape(S, M, D); }
+  static size_t model_doubles(int S, int M, int D) { return sapr::model_doubles(sp_of(S), mp_of(M), dp_of(D)); }
+  static int stats_p(int S, int M, int D) { return sapr::stats_p(S, M, D); }
+  static int launch_emit(const Batch &b, const double *pack, int64_t n_tiles, double *logb, hipStream_t stream) {
+    return launch_frames(true, b, pack, n_tiles, logb, nullptr, stream);
   }
-  SAPR_LAUNCH((gmm_forward_kernel<SP, false>), grid, block, 0, stream, b, pack, ws.logb, ws.lat, loglik,
-              static_cast<int32_t *>(nullptr));
-  SAPR_HIP_TRY(hipGetLastError());
-  if (!ustat && !post && !path) return 0;  // scores only
-  SAPR_LAUNCH((gmm_backward_kernel<SP>), grid, block, 0, stream, b, pack, ws.logb, ws.lat, loglik, ustat, post,
-              path);
-  SAPR_HIP_TRY(hipGetLastError());
-  return 0;
-}
+  static int launch_accum(const Batch &b, const double *pack, int64_t n_tiles, double *gam, double *part,
+                          hipStream_t stream) {
+    return launch_frames(false, b, pack, n_tiles, gam, part, stream);
+  }
+};
 
+template <class Family>
 int run(bool vit, const float *feats, const int64_t *offsets, const int32_t *slot_utt, const int32_t *tile_model,
         const int32_t *model_tile_off, int64_t n_utts, int64_t total_frames, int64_t n_tiles, int32_t D, int32_t max_T,
         const double *pack, int32_t W, int32_t S, int32_t M, void *workspace, size_t workspace_bytes, double *loglik,
@@ -596,14 +272,15 @@ int run(bool vit, const float *feats, const int64_t *offsets, const int32_t *slo
   SAPR_REQUIRE(n_utts >= 0 && total_frames >= 0 && n_tiles >= 0 && W > 0 && S > 0 && M > 0 && D > 0 && max_T >= 0,
                "bad sizes (n_utts=%lld total_frames=%lld n_tiles=%lld W=%d S=%d M=%d D=%d max_T=%d)", (long long)n_utts,
                (long long)total_frames, (long long)n_tiles, W, S, M, D, max_T);
-  if (int rc = check_shape(S, M, D)) return rc;
+  if (int rc = Family::check(S, M, D)) return rc;
   SAPR_REQUIRE(max_T <= kMaxT, "bad sizes: max_T = %d exceeds %d", max_T, kMaxT);
   SAPR_REQUIRE(n_tiles * (kBlock / 64) <= 0x7fffffffLL, "grid too large (%lld tiles)", (long long)n_tiles);
   if (n_tiles == 0) return 0;
   SAPR_REQUIRE(feats && offsets && slot_utt && tile_model && pack && workspace && loglik, "NULL pointer argument");
   SAPR_REQUIRE(!vit || path, "NULL pointer argument (path)");
   SAPR_REQUIRE(!stats || model_tile_off, "NULL pointer argument (model_tile_off)");
-  const Ws ws = carve(workspace, total_frames, n_tiles, S, M, D);
+  const int K1 = stats_k1(S), P = Family::stats_p(S, M, D);
+  const Ws ws = carve(workspace, total_frames, n_tiles, S, P);
   SAPR_REQUIRE(workspace_bytes >= ws.bytes, "workspace too small: %zu < %zu", workspace_bytes, ws.bytes);
   Batch b;
   b.feats = feats;
@@ -618,10 +295,10 @@ int run(bool vit, const float *feats, const int64_t *offsets, const int32_t *slo
   b.W = W;
   b.S = S;
   b.M = M;
-  b.stride = static_cast<int64_t>(model_doubles(sp_of(S), mp_of(M), dp_of(D)));
+  b.stride = static_cast<int64_t>(Family::model_doubles(S, M, D));
   hipStream_t st = as_stream(stream);
   if (max_T > 0 && total_frames > 0) {
-    if (int rc = launch_frames(true, b, pack, n_tiles, ws.logb, nullptr, st)) return rc;
+    if (int rc = Family::launch_emit(b, pack, n_tiles, ws.logb, st)) return rc;
   }
   double *ustat = stats ? ws.ustat : nullptr;
   int rc;
@@ -631,8 +308,7 @@ int run(bool vit, const float *feats, const int64_t *offsets, const int32_t *slo
     default: rc = launch_trellis<18>(vit, b, pack, n_tiles, ws, loglik, ustat, post, path, st); break;
   }
   if (rc || !stats) return rc;
-  if (int rc2 = launch_frames(false, b, pack, n_tiles, ws.lat, ws.part, st)) return rc2;
-  const int K1 = stats_k1(S), P = stats_p(S, M, D);
+  if (int rc2 = Family::launch_accum(b, pack, n_tiles, ws.lat, ws.part, st)) return rc2;
   SAPR_LAUNCH(gmm_tile_reduce_kernel, dim3(static_cast<unsigned>(n_tiles)), dim3(kBlock), 0, st, K1, b.n_slots,
               ws.ustat, ws.tile_stats);
   SAPR_HIP_TRY(hipGetLastError());
@@ -650,19 +326,19 @@ using namespace sapr;
 
 extern "C" int sapr_gmm_stats_width(int32_t S, int32_t M, int32_t D, int32_t *width) {
   SAPR_REQUIRE(width && S > 0 && M > 0 && D > 0, "bad sizes (S=%d M=%d D=%d)", S, M, D);
-  if (int rc = check_shape(S, M, D)) return rc;
-  *width = stats_k1(S) + stats_p(S, M, D);
+  if (int rc = Mix::check(S, M, D)) return rc;
+  *width = stats_k1(S) + Mix::stats_p(S, M, D);
   return 0;
 }
 
 extern "C" int sapr_gmm_pack_layout(int32_t S, int32_t M, int32_t D, int32_t *SP, int32_t *MP, int32_t *DP,
                                     size_t *doubles_per_model) {
   SAPR_REQUIRE(SP && MP && DP && doubles_per_model && S > 0 && M > 0 && D > 0, "bad sizes (S=%d M=%d D=%d)", S, M, D);
-  if (int rc = check_shape(S, M, D)) return rc;
+  if (int rc = Mix::check(S, M, D)) return rc;
   *SP = sp_of(S);
   *MP = mp_of(M);
   *DP = dp_of(D);
-  *doubles_per_model = model_doubles(*SP, *MP, *DP);
+  *doubles_per_model = Mix::model_doubles(S, M, D);
   return 0;
 }
 
@@ -671,8 +347,8 @@ extern "C" int sapr_gmm_workspace_bytes(int64_t total_frames, int64_t n_tiles, i
   SAPR_REQUIRE(bytes && total_frames >= 0 && n_tiles >= 0 && S > 0 && M > 0 && D > 0,
                "bad sizes (total_frames=%lld n_tiles=%lld S=%d M=%d D=%d)", (long long)total_frames, (long long)n_tiles,
                S, M, D);
-  if (int rc = check_shape(S, M, D)) return rc;
-  *bytes = carve(nullptr, total_frames, n_tiles, S, M, D).bytes;
+  if (int rc = Mix::check(S, M, D)) return rc;
+  *bytes = carve(nullptr, total_frames, n_tiles, S, Mix::stats_p(S, M, D)).bytes;
   return 0;
 }
 
@@ -681,8 +357,8 @@ extern "C" int sapr_gmm_estep_diag(const float *feats, const int64_t *offsets, c
                                    int64_t total_frames, int64_t n_tiles, int32_t D, int32_t max_T, const double *pack,
                                    int32_t W, int32_t S, int32_t M, void *workspace, size_t workspace_bytes,
                                    double *loglik, double *stats, double *post, int32_t *path, void *stream) {
-  return run(false, feats, offsets, slot_utt, tile_model, model_tile_off, n_utts, total_frames, n_tiles, D, max_T, pack,
-             W, S, M, workspace, workspace_bytes, loglik, stats, post, path, stream);
+  return run<Mix>(false, feats, offsets, slot_utt, tile_model, model_tile_off, n_utts, total_frames, n_tiles, D, max_T,
+                  pack, W, S, M, workspace, workspace_bytes, loglik, stats, post, path, stream);
 }
 
 extern "C" int sapr_gmm_viterbi_diag(const float *feats, const int64_t *offsets, const int32_t *slot_utt,
@@ -690,130 +366,23 @@ extern "C" int sapr_gmm_viterbi_diag(const float *feats, const int64_t *offsets,
                                      int32_t D, int32_t max_T, const double *pack, int32_t W, int32_t S, int32_t M,
                                      void *workspace, size_t workspace_bytes, double *logprob, int32_t *path,
                                      void *stream) {
-  return run(true, feats, offsets, slot_utt, tile_model, nullptr, n_utts, total_frames, n_tiles, D, max_T, pack, W, S,
-             M, workspace, workspace_bytes, logprob, nullptr, nullptr, path, stream);
+  return run<Mix>(true, feats, offsets, slot_utt, tile_model, nullptr, n_utts, total_frames, n_tiles, D, max_T, pack, W, S,
+                  M, workspace, workspace_bytes, logprob, nullptr, nullptr, path, stream);
 }
-
-// -------------------------------------------------------------------------------------------
-// full covariances (hmmlearn's GaussianHMM, covariance_type "full" / "tied"): the emission and the accumulation pass
-// of fullcov_ops.h around the recursions above
-// -------------------------------------------------------------------------------------------
-namespace sapr {
-namespace {
-
-#include "fullcov_ops.h"
-
-Ws carve_full(void *base, int64_t total_frames, int64_t n_tiles, int S, int D) {
-  const size_t fr = static_cast<size_t>(total_frames > 0 ? total_frames : 1) * sp_of(S);
-  const size_t nt = static_cast<size_t>(n_tiles > 0 ? n_tiles : 1);
-  Ws w;
-  w.logb = static_cast<double *>(base);
-  w.lat = w.logb + fr;
-  w.ustat = w.lat + fr;
-  w.tile_stats = w.ustat + static_cast<size_t>(stats_k1(S)) * nt * kBlock;
-  w.part = w.tile_stats + nt * stats_k1(S);
-  w.bytes = (2 * fr + static_cast<size_t>(stats_k1(S)) * nt * kBlock + nt * stats_k1(S) +
-             nt * kSub * full_stats_p(S, D)) * sizeof(double);
-  return w;
-}
-
-template <int DP>
-int launch_full_emit(const Batch &b, const double *pack, int64_t n_tiles, double *logb, hipStream_t stream) {
-  SAPR_LAUNCH((full_emit_kernel<DP>), dim3(static_cast<unsigned>(n_tiles), static_cast<unsigned>(b.max_T)),
-              dim3(kBlock), 0, stream, b, pack, sp_of(b.S), logb);
-  SAPR_HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-template <int DP>
-int launch_full_accum(const Batch &b, int64_t n_tiles, const double *gam, double *part, hipStream_t stream) {
-  SAPR_LAUNCH((full_accum_kernel<DP>), dim3(static_cast<unsigned>(n_tiles), kSub), dim3(kBlock), 0, stream, b,
-              sp_of(b.S), gam, part);
-  SAPR_HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-int run_full(bool vit, const float *feats, const int64_t *offsets, const int32_t *slot_utt, const int32_t *tile_model,
-             const int32_t *model_tile_off, int64_t n_utts, int64_t total_frames, int64_t n_tiles, int32_t D,
-             int32_t max_T, const double *pack, int32_t W, int32_t S, void *workspace, size_t workspace_bytes,
-             double *loglik, double *stats, double *post, int32_t *path, void *stream) {
-  SAPR_REQUIRE(n_utts >= 0 && total_frames >= 0 && n_tiles >= 0 && W > 0 && S > 0 && D > 0 && max_T >= 0,
-               "bad sizes (n_utts=%lld total_frames=%lld n_tiles=%lld W=%d S=%d D=%d max_T=%d)", (long long)n_utts,
-               (long long)total_frames, (long long)n_tiles, W, S, D, max_T);
-  if (int rc = check_full_shape(S, D)) return rc;
-  SAPR_REQUIRE(max_T <= kMaxT, "bad sizes: max_T = %d exceeds %d", max_T, kMaxT);
-  SAPR_REQUIRE(n_tiles * (kBlock / 64) <= 0x7fffffffLL, "grid too large (%lld tiles)", (long long)n_tiles);
-  if (n_tiles == 0) return 0;
-  SAPR_REQUIRE(feats && offsets && slot_utt && tile_model && pack && workspace && loglik, "NULL pointer argument");
-  SAPR_REQUIRE(!vit || path, "NULL pointer argument (path)");
-  SAPR_REQUIRE(!stats || model_tile_off, "NULL pointer argument (model_tile_off)");
-  const Ws ws = carve_full(workspace, total_frames, n_tiles, S, D);
-  SAPR_REQUIRE(workspace_bytes >= ws.bytes, "workspace too small: %zu < %zu", workspace_bytes, ws.bytes);
-  Batch b;
-  b.feats = feats;
-  b.offsets = offsets;
-  b.slot_utt = slot_utt;
-  b.tile_model = tile_model;
-  b.n_utts = n_utts;
-  b.total_frames = total_frames;
-  b.n_slots = n_tiles * kBlock;
-  b.D = D;
-  b.max_T = max_T;
-  b.W = W;
-  b.S = S;
-  b.M = 1;
-  b.stride = static_cast<int64_t>(full_model_doubles(sp_of(S), dp_of(D)));
-  hipStream_t st = as_stream(stream);
-  if (max_T > 0 && total_frames > 0) {
-    int rc;
-    switch (dp_of(D)) {
-      case 13: rc = launch_full_emit<13>(b, pack, n_tiles, ws.logb, st); break;
-      case 26: rc = launch_full_emit<26>(b, pack, n_tiles, ws.logb, st); break;
-      default: rc = launch_full_emit<39>(b, pack, n_tiles, ws.logb, st); break;
-    }
-    if (rc) return rc;
-  }
-  double *ustat = stats ? ws.ustat : nullptr;
-  int rc;
-  switch (sp_of(S)) {
-    case 4: rc = launch_trellis<4>(vit, b, pack, n_tiles, ws, loglik, ustat, post, path, st); break;
-    case 10: rc = launch_trellis<10>(vit, b, pack, n_tiles, ws, loglik, ustat, post, path, st); break;
-    default: rc = launch_trellis<18>(vit, b, pack, n_tiles, ws, loglik, ustat, post, path, st); break;
-  }
-  if (rc || !stats) return rc;
-  switch (dp_of(D)) {
-    case 13: rc = launch_full_accum<13>(b, n_tiles, ws.lat, ws.part, st); break;
-    case 26: rc = launch_full_accum<26>(b, n_tiles, ws.lat, ws.part, st); break;
-    default: rc = launch_full_accum<39>(b, n_tiles, ws.lat, ws.part, st); break;
-  }
-  if (rc) return rc;
-  const int K1 = stats_k1(S), P = full_stats_p(S, D);
-  SAPR_LAUNCH(gmm_tile_reduce_kernel, dim3(static_cast<unsigned>(n_tiles)), dim3(kBlock), 0, st, K1, b.n_slots,
-              ws.ustat, ws.tile_stats);
-  SAPR_HIP_TRY(hipGetLastError());
-  const int64_t total = static_cast<int64_t>(W) * (K1 + P);
-  SAPR_LAUNCH(gmm_reduce_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, st, model_tile_off, W,
-              K1, P, n_tiles, ws.tile_stats, ws.part, stats);
-  SAPR_HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-}  // namespace
-}  // namespace sapr
 
 extern "C" int sapr_full_pack_layout(int32_t S, int32_t D, int32_t *SP, int32_t *DP, size_t *doubles_per_model) {
   SAPR_REQUIRE(SP && DP && doubles_per_model && S > 0 && D > 0, "bad sizes (S=%d D=%d)", S, D);
-  if (int rc = check_full_shape(S, D)) return rc;
+  if (int rc = Full::check(S, 1, D)) return rc;
   *SP = sp_of(S);
   *DP = dp_of(D);
-  *doubles_per_model = full_model_doubles(*SP, *DP);
+  *doubles_per_model = Full::model_doubles(S, 1, D);
   return 0;
 }
 
 extern "C" int sapr_full_stats_width(int32_t S, int32_t D, int32_t *width) {
   SAPR_REQUIRE(width && S > 0 && D > 0, "bad sizes (S=%d D=%d)", S, D);
-  if (int rc = check_full_shape(S, D)) return rc;
-  *width = stats_k1(S) + full_stats_p(S, D);
+  if (int rc = Full::check(S, 1, D)) return rc;
+  *width = stats_k1(S) + Full::stats_p(S, 1, D);
   return 0;
 }
 
@@ -821,8 +390,8 @@ extern "C" int sapr_full_workspace_bytes(int64_t total_frames, int64_t n_tiles, 
   SAPR_REQUIRE(bytes && total_frames >= 0 && n_tiles >= 0 && S > 0 && D > 0,
                "bad sizes (total_frames=%lld n_tiles=%lld S=%d D=%d)", (long long)total_frames, (long long)n_tiles, S,
                D);
-  if (int rc = check_full_shape(S, D)) return rc;
-  *bytes = carve_full(nullptr, total_frames, n_tiles, S, D).bytes;
+  if (int rc = Full::check(S, 1, D)) return rc;
+  *bytes = carve(nullptr, total_frames, n_tiles, S, Full::stats_p(S, 1, D)).bytes;
   return 0;
 }
 
@@ -831,14 +400,14 @@ extern "C" int sapr_full_estep(const float *feats, const int64_t *offsets, const
                                int64_t total_frames, int64_t n_tiles, int32_t D, int32_t max_T, const double *pack,
                                int32_t W, int32_t S, void *workspace, size_t workspace_bytes, double *loglik,
                                double *stats, double *post, int32_t *path, void *stream) {
-  return run_full(false, feats, offsets, slot_utt, tile_model, model_tile_off, n_utts, total_frames, n_tiles, D, max_T,
-                  pack, W, S, workspace, workspace_bytes, loglik, stats, post, path, stream);
+  return run<Full>(false, feats, offsets, slot_utt, tile_model, model_tile_off, n_utts, total_frames, n_tiles, D, max_T,
+                   pack, W, S, 1, workspace, workspace_bytes, loglik, stats, post, path, stream);
 }
 
 extern "C" int sapr_full_viterbi(const float *feats, const int64_t *offsets, const int32_t *slot_utt,
                                  const int32_t *tile_model, int64_t n_utts, int64_t total_frames, int64_t n_tiles,
                                  int32_t D, int32_t max_T, const double *pack, int32_t W, int32_t S, void *workspace,
                                  size_t workspace_bytes, double *logprob, int32_t *path, void *stream) {
-  return run_full(true, feats, offsets, slot_utt, tile_model, nullptr, n_utts, total_frames, n_tiles, D, max_T, pack, W,
-                  S, workspace, workspace_bytes, logprob, nullptr, nullptr, path, stream);
+  return run<Full>(true, feats, offsets, slot_utt, tile_model, nullptr, n_utts, total_frames, n_tiles, D, max_T, pack, W,
+                   S, 1, workspace, workspace_bytes, logprob, nullptr, nullptr, path, stream);
 }

@@ -100,7 +100,7 @@ class Decoder:
         if self.implementation == "custom":
             return self._decode_custom(store.to_batch())
         if self._uses_vocab_pack():
-            from .gmm_hmm import vocab_features
+            from .tile_family import vocab_features
             feats, _, _, lengths, _ = vocab_features(store.to_batch())
             return self._decode_vocab(feats, lengths)
         return self._decode_feature_batch(store.to_batch())

@@ -20,14 +20,15 @@ Anything else non-finite propagates; nothing is repaired.
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass
 from typing import List
 
 import numpy as np
 
 from . import _lib
-from .hmmlearn_hmm import (DECODER_ALGORITHMS, ConvergenceMonitor, VocabPack, _features_f32, check_random_state,
-                           kmeans_seed, m_step, map_decode_host)
+from .hmmlearn_hmm import (DECODER_ALGORITHMS, ConvergenceMonitor, check_random_state, kmeans_seed, m_step,
+                           map_decode_host)
+from .tile_family import (VOCAB_MODES, TileBatch, VocabPack, VocabScores, _features_f32,  # noqa: F401  (re-exported)
+                          _vocab_scores, baum_welch, pack_head, stats_head, vocab_features)
 
 MAX_STATES, MAX_MIX, MAX_DIMS = 18, 8, 39
 
@@ -70,16 +71,12 @@ def pack_models(params, S=None) -> np.ndarray:
             s = sp.shape[0]
             if tm.shape != (s, s) or wt.shape != (s, M) or mu.shape != (s, M, D) or cv.shape != (s, M, D) or s > S:
                 raise ValueError("pack_models: the models must share n_mix and the feature width")
-            ls = np.full(SP, -np.inf)
-            ls[:s] = np.log(sp)
-            lt = np.full((SP, SP), -np.inf)
-            lt[:s, :s] = np.log(tm)
             cc = np.full((SP, MP), -np.inf)
             cc[:s, :M] = np.log(wt) - 0.5 * (D * np.log(2 * np.pi) + np.log(cv).sum(axis=-1))
             prm = np.zeros((SP, DP, MP, 2))
             prm[:s, :D, :M, 0] = mu.transpose(0, 2, 1)
             prm[:s, :D, :M, 1] = (-0.5 / cv).transpose(0, 2, 1)
-            out[w] = np.concatenate([ls, lt.ravel(), lt.T.ravel(), cc.ravel(), prm.ravel()])
+            out[w] = np.concatenate([pack_head(sp, tm, SP), cc.ravel(), prm.ravel()])
     return out
 
 
@@ -88,102 +85,29 @@ def split_stats(row, S, M, D, S_model=None):
     ``S_model <= S`` states (the padding states carry exact zeros)."""
     row = np.asarray(row, dtype=np.float64)
     m = S if S_model is None else S_model
-    o = 2
-    start = row[o:o + S][:m].copy()
-    o += S
-    trans = row[o:o + S * S].reshape(S, S)[:m, :m].copy()
-    o += S * S
-    post = row[o:o + S][:m].copy()
-    o += S
+    st, o = stats_head(row, S, m)
     post_mix = row[o:o + S * M].reshape(S, M)[:m].copy()
     o += S * M
     obs = row[o:o + S * M * D].reshape(S, M, D)[:m].copy()
     o += S * M * D
     obs2 = row[o:o + S * M * D].reshape(S, M, D)[:m].copy()
-    return {"nobs": row[0], "logprob": row[1], "start": start, "trans": trans, "post": post, "post_mix": post_mix,
-            "obs": obs, "obs**2": obs2}
+    return {**st, "post_mix": post_mix, "obs": obs, "obs**2": obs2}
 
 
-class GmmBatch:
-    """A packed batch on the device, every utterance under the model ``utt_model[u]``: ``feats`` float32
-    ``[total_frames, D]`` (device tensor, or a host array that is uploaded) and host ``lengths``; builds the tile
-    layout (``trellis.TileLayout``) and owns the workspace for (W, S, M)."""
+class GmmBatch(TileBatch):
+    """The :class:`sapr_amd.tile_family.TileBatch` of the mixtures: the utterances under the model ``utt_model[u]`` of W
+    models of S kernel states and M components (``sapr_gmm_estep_diag``, ``sapr_gmm_viterbi_diag``)."""
+    STATS_WIDTH, WORKSPACE_BYTES = "sapr_gmm_stats_width", "sapr_gmm_workspace_bytes"
+    ESTEP, VITERBI = "sapr_gmm_estep_diag", "sapr_gmm_viterbi_diag"
+    pack_layout = staticmethod(pack_layout)
 
     def __init__(self, feats, lengths, utt_model, W, S, M):
-        torch = _torch()
-        from .trellis import TileLayout
-        self.lib = _lib.load()
-        dev = _lib.require_gpu()
-        if not torch.is_tensor(feats):
-            feats = torch.from_numpy(_features_f32(feats))
-        feats = feats.to(dev)
-        if feats.dtype != torch.float32 or feats.dim() != 2 or not feats.is_contiguous():
-            raise ValueError("feats must be a contiguous float32 [total_frames, D] tensor")
-        self.lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
-        if self.lengths.size and self.lengths.min() < 0:
-            raise ValueError("lengths must be >= 0")
-        offs = np.zeros(self.lengths.size + 1, dtype=np.int64)
-        np.cumsum(self.lengths, out=offs[1:])
-        if feats.shape[0] != offs[-1]:
-            raise ValueError("feats rows do not match sum(lengths)")
-        um = np.asarray(utt_model, dtype=np.int64).reshape(-1)
-        if um.shape != self.lengths.shape or (um.size and (um.min() < 0 or um.max() >= W)):
-            raise ValueError("utt_model must name one model 0..W-1 per utterance")
-        self.feats, self.dev = feats, dev
-        self.offsets = torch.from_numpy(offs).to(dev)
-        self.n_utts, self.total_frames = int(self.lengths.size), int(offs[-1])
-        self.max_T = int(self.lengths.max()) if self.lengths.size else 0
-        self.D, self.W, self.S, self.M = int(feats.shape[1]), int(W), int(S), int(M)
-        self.layout = TileLayout.build(self.lengths, um, W, dev)
-        self.width = stats_width(self.S, self.M, self.D)
-        n = C.c_size_t(0)
-        _lib.check(self.lib.sapr_gmm_workspace_bytes(self.total_frames, self.layout.n_tiles, self.S, self.M, self.D,
-                                                     C.byref(n)), "sapr_gmm_workspace_bytes")
-        self.ws_bytes = int(n.value)
-        self.workspace = torch.empty(max(self.ws_bytes, 1), dtype=torch.uint8, device=dev)
+        self.M = int(M)
+        super().__init__(feats, lengths, utt_model, W, S)
 
-    def _pack(self, pack):
-        torch = _torch()
-        if isinstance(pack, GmmPack):
-            if (pack.W, pack.S, pack.M, pack.D) != (self.W, self.S, self.M, self.D):
-                raise ValueError("the pack was built for another (W, S, M, D)")
-            return pack.device(self.dev)
-        pack = np.ascontiguousarray(pack, dtype=np.float64)
-        n = pack_layout(self.S, self.M, self.D)[3]
-        if pack.shape != (self.W, n):
-            raise ValueError(f"pack must be [W={self.W}, {n}] (pack_models), got {pack.shape}")
-        return torch.from_numpy(pack).to(self.dev)
-
-    def estep(self, pack, want_stats=True, want_post=False, want_path=False):
-        """One ``sapr_gmm_estep_diag`` -> device tensors ``(loglik[n_utts], stats[W, width] | None,
-        post[total_frames, S] | None, path[total_frames] | None)``."""
-        torch = _torch()
-        dpack = self._pack(pack)
-        lay = self.layout
-        loglik = torch.full((self.n_utts,), float("-inf"), dtype=torch.float64, device=self.dev)
-        stats = torch.zeros((self.W, self.width), dtype=torch.float64, device=self.dev) if want_stats else None
-        post = torch.empty((self.total_frames, self.S), dtype=torch.float64, device=self.dev) if want_post else None
-        path = torch.empty(self.total_frames, dtype=torch.int32, device=self.dev) if want_path else None
-        _lib.check(self.lib.sapr_gmm_estep_diag(
-            _lib.ptr(self.feats), _lib.ptr(self.offsets), _lib.ptr(lay.slot_utt), _lib.ptr(lay.tile_model),
-            _lib.ptr(lay.model_tile_off), self.n_utts, self.total_frames, lay.n_tiles, self.D, self.max_T,
-            _lib.ptr(dpack), self.W, self.S, self.M, _lib.ptr(self.workspace), self.ws_bytes, _lib.ptr(loglik),
-            _lib.ptr(stats), _lib.ptr(post), _lib.ptr(path), _lib.current_stream()), "sapr_gmm_estep_diag")
-        return loglik, stats, post, path
-
-    def viterbi(self, pack):
-        """One ``sapr_gmm_viterbi_diag`` -> device tensors ``(logprob[n_utts], path[total_frames])``."""
-        torch = _torch()
-        dpack = self._pack(pack)
-        lay = self.layout
-        logprob = torch.full((self.n_utts,), float("-inf"), dtype=torch.float64, device=self.dev)
-        path = torch.empty(self.total_frames, dtype=torch.int32, device=self.dev)
-        _lib.check(self.lib.sapr_gmm_viterbi_diag(
-            _lib.ptr(self.feats), _lib.ptr(self.offsets), _lib.ptr(lay.slot_utt), _lib.ptr(lay.tile_model),
-            self.n_utts, self.total_frames, lay.n_tiles, self.D, self.max_T, _lib.ptr(dpack), self.W, self.S, self.M,
-            _lib.ptr(self.workspace), self.ws_bytes, _lib.ptr(logprob), _lib.ptr(path), _lib.current_stream()),
-            "sapr_gmm_viterbi_diag")
-        return logprob, path
+    @staticmethod
+    def dims(o):
+        return o.W, o.S, o.M, o.D
 
 
 # ------------------------------------------------------------------------------------------
@@ -228,47 +152,6 @@ class GmmPack(VocabPack):
         return vocab_scores(batch_or_feats, lengths, self, mode=mode, want_post=want_post)
 
 
-@dataclass
-class VocabScores:
-    score: "object"      # [N, W] f64: forward log-likelihood or Viterbi log-probability under every word model
-    best_word: "object"  # [N] i32 (first strict maximum in model order; -1 if no score beats -inf)
-    word_post: "object"  # [N, W] f64 posterior over the words under a uniform prior (forward mode), or None
-
-
-VOCAB_MODES = {"forward": _lib.GMM_VOCAB_FORWARD, "viterbi": _lib.GMM_VOCAB_VITERBI}
-
-
-def vocab_features(batch_or_feats, lengths=None):
-    """The utterances of :func:`vocab_scores` on the device: ``(feats[total_frames, D] float32, offsets int64[N + 1],
-    order int32[N] | None, host lengths, max_T)``.  A ``trellis.FeatureBatch`` brings its length-sorted ``order`` (the
-    zero columns it appends up to the single-Gaussian kernels' widths are cut off again: the mixture kernels read rows
-    of the models' own width); host ``feats`` / ``lengths`` are uploaded and sorted here."""
-    torch = _torch()
-    if hasattr(batch_or_feats, "offsets") and hasattr(batch_or_feats, "order"):
-        b = batch_or_feats
-        feats = b.feats if b.D == b.D_model else b.feats[:, :b.D_model].contiguous()
-        return feats, b.offsets, b.order, np.asarray(b.lengths, dtype=np.int64), int(b.max_T)
-    if lengths is None:
-        raise ValueError("lengths are needed with a feature array")
-    dev = _lib.require_gpu()
-    feats = batch_or_feats
-    if not torch.is_tensor(feats):
-        feats = torch.from_numpy(_features_f32(feats))
-    feats = feats.to(dev)
-    if feats.dtype != torch.float32 or feats.dim() != 2 or not feats.is_contiguous():
-        raise ValueError("feats must be a contiguous float32 [total_frames, D] tensor")
-    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
-    if lengths.size and lengths.min() < 0:
-        raise ValueError("lengths must be >= 0")
-    offs = np.zeros(lengths.size + 1, dtype=np.int64)
-    np.cumsum(lengths, out=offs[1:])
-    if feats.shape[0] != offs[-1]:
-        raise ValueError("feats rows do not match sum(lengths)")
-    order = np.argsort(-lengths, kind="stable").astype(np.int32)
-    return (feats, torch.from_numpy(offs).to(dev), torch.from_numpy(order).to(dev), lengths,
-            int(lengths.max()) if lengths.size else 0)
-
-
 def vocab_scores(batch_or_feats, lengths, pack_or_models, mode="forward", want_post=False) -> VocabScores:
     """Every utterance under EVERY word model in one launch of ``sapr_gmm_vocab_diag``: ``mode="forward"`` gives the
     forward log-likelihoods (``GMMHMM.score`` per sequence), ``mode="viterbi"`` the Viterbi log-probabilities
@@ -278,27 +161,6 @@ def vocab_scores(batch_or_feats, lengths, pack_or_models, mode="forward", want_p
     largest S of the vocabulary; M and D must match).  ``want_post`` (forward mode only): the posterior over the
     words."""
     return _vocab_scores(GmmPack, batch_or_feats, lengths, pack_or_models, mode, want_post)
-
-
-def _vocab_scores(pack_type, batch_or_feats, lengths, pack_or_models, mode, want_post) -> VocabScores:
-    """The one implementation behind :func:`vocab_scores` and ``full_cov.vocab_scores``: ``pack_type`` is the family's
-    :class:`sapr_amd.hmmlearn_hmm.VocabPack`, whose ``launch`` calls the family's entry point."""
-    torch = _torch()
-    if mode not in VOCAB_MODES:
-        raise ValueError(f"mode must be one of {sorted(VOCAB_MODES)}, got {mode!r}")
-    if want_post and mode != "forward":
-        raise ValueError("want_post needs mode='forward': a soft-max of path scores is not a posterior")
-    pack = pack_or_models if isinstance(pack_or_models, pack_type) else pack_type.from_models(list(pack_or_models))
-    feats, offsets, order, lengths, max_T = vocab_features(batch_or_feats, lengths)
-    if int(feats.shape[1]) != pack.D:
-        raise ValueError(f"the utterances have {int(feats.shape[1])} features, the models {pack.D}")
-    dev = feats.device
-    N, W = int(lengths.size), pack.W
-    score = torch.empty((N, W), dtype=torch.float64, device=dev)
-    best_word = torch.empty(N, dtype=torch.int32, device=dev)
-    word_post = torch.empty((N, W), dtype=torch.float64, device=dev) if want_post else None
-    pack.launch(feats, offsets, order, N, max_T, mode, score, best_word, word_post)
-    return VocabScores(score, best_word, word_post)
 
 
 # ------------------------------------------------------------------------------------------
@@ -511,21 +373,13 @@ def fit_gmm_models(models: List[GMMHMM], data) -> None:
         m.monitor_ = ConvergenceMonitor(m.tol, m.n_iter, m.verbose)
     S = max(m.n_components for m in models)
     batch = GmmBatch(dfeats, lengths, utt_model, W, S, M)
-    active = [True] * W
-    for _ in range(max(m.n_iter for m in models)):
-        if not any(active):
-            break
-        host = batch.estep(pack_models([m._params() for m in models], S))[1].cpu().numpy()
-        for w, m in enumerate(models):
-            if not active[w]:
-                continue
-            st = split_stats(host[w], S, M, D, m.n_components)
-            m.startprob_, m.transmat_, m.weights_, m.means_, m.covars_ = gmm_m_step(
-                st, *m._params(), m.params, m.startprob_prior, m.transmat_prior, m.weights_prior, m.means_prior,
-                m.means_weight, m.covars_prior, m.covars_weight, m.min_covar)
-            m.monitor_.report(float(st["logprob"]))
-            if m.monitor_.converged:
-                active[w] = False
+
+    def update(m, st):
+        m.startprob_, m.transmat_, m.weights_, m.means_, m.covars_ = gmm_m_step(
+            st, *m._params(), m.params, m.startprob_prior, m.transmat_prior, m.weights_prior, m.means_prior,
+            m.means_weight, m.covars_prior, m.covars_weight, m.min_covar)
+    baum_welch(models, batch, lambda ms: pack_models([m._params() for m in ms], S),
+               lambda row, m: split_stats(row, S, M, D, m.n_components), update)
 
 
 def _init_gmm_models(models, needs, dfeats, frames) -> None:

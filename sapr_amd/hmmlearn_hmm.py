@@ -23,6 +23,7 @@ import numpy as np
 
 from . import _lib
 from .mfcc_extract import load_mfccs, load_mfccs_by_word  # noqa: F401  (same import surface as the reference)
+from .tile_family import VocabPack, _features_f32, baum_welch  # noqa: F401  (VocabPack: imported from here too)
 
 logging.getLogger("matplotlib").setLevel(logging.WARNING)
 
@@ -168,42 +169,6 @@ def m_step_batch(rows, S, D, startprob, transmat, means, covars, params="stmc", 
             c_d = max(covars_weight - 1, 0) + denom
             covars = (covars_prior + c_n) / np.maximum(c_d, 1e-5)
     return startprob, transmat, means, covars, logprob
-
-
-def _features_f32(X) -> np.ndarray:
-    """The kernels read float32 features — what ``mfcc_extract.py:15-24`` produces and every reference call site
-    passes (``hmmlearn_hmm.py:80-81``, ``decoder.py:59``).  hmmlearn itself would compute with a float64 ``X`` at full
-    width, so silently narrowing one would change results: values that do not survive the round trip through
-    float32 are refused instead (float64 arrays holding float32 values, integers etc. pass unchanged)."""
-    Xa = np.asarray(X)
-    out = np.ascontiguousarray(Xa, dtype=np.float32)
-    if Xa.dtype != np.float32 and Xa.size and not np.array_equal(out.astype(Xa.dtype, copy=False), Xa, equal_nan=True):
-        raise ValueError(f"features of dtype {Xa.dtype} do not round-trip through float32: the HIP kernels compute "
-                         "on float32 features (the reference's MFCCs are float32); cast explicitly if the loss is "
-                         "intended")
-    return out
-
-
-class VocabPack:
-    """A vocabulary's operand block ready for the kernels: ``data`` float64 ``[W, doubles_per_model]`` (the family's
-    ``pack_models``) with the shape it was packed for (W models, S kernel states = the largest model's, D features)
-    and each model's own state count ``n_states``; the device copy is made once.  The families
-    (``gmm_hmm.GmmPack``, ``full_cov.FullPack``) add what is theirs: how a pack is built, the per-model batch class
-    (:meth:`batch`) and the entry point that scores the vocabulary (:meth:`launch`, :meth:`vocab_scores`)."""
-
-    def __init__(self, data, S, D, doubles_per_model, n_states=None):
-        self.data = np.ascontiguousarray(data, dtype=np.float64)
-        self.W, self.S, self.D = int(self.data.shape[0]), int(S), int(D)
-        if self.data.ndim != 2 or self.data.shape[1] != doubles_per_model:
-            raise ValueError(f"pack must be [W, {doubles_per_model}] (pack_models), got {self.data.shape}")
-        self.n_states = [self.S] * self.W if n_states is None else [int(k) for k in n_states]
-        self._dev = None
-
-    def device(self, dev):
-        import torch
-        if self._dev is None or self._dev.device != dev:
-            self._dev = torch.from_numpy(self.data).to(dev)
-        return self._dev
 
 
 DECODER_ALGORITHMS = ("viterbi", "map")
@@ -592,26 +557,18 @@ def _fit_full(models, dfeats, lengths, utt_model) -> None:
     """The Baum-Welch loop of :func:`fit_models` for "full" / "tied" models (initialised and checked by the caller):
     one ``sapr_full_estep`` per iteration over every model's utterances, the M-step per model on the host."""
     from . import full_cov
-    W = len(models)
     S = max(m.n_components for m in models)
-    batch = full_cov.FullCovBatch(dfeats, lengths, utt_model, W, S)
-    active = [True] * W
-    for _ in range(max(m.n_iter for m in models)):
-        if not any(active):
-            break
-        pack = np.concatenate([full_cov.pack_models([m._full_params()], S, name=m.covariance_type) for m in models])
-        host = batch.estep(pack)[1].cpu().numpy()
-        for w, m in enumerate(models):
-            if not active[w]:
-                continue
-            st = full_cov.split_stats(host[w], S, batch.D, m.n_components)
-            m.startprob_, m.transmat_, m.means_, m._covars_ = m_step_typed(
-                st, m.covariance_type, m.startprob_, m.transmat_, m.params, m.startprob_prior, m.transmat_prior,
-                m.means_prior, m.means_weight, m.covars_prior, m.covars_weight, np.asarray(m.means_, dtype=np.float64),
-                np.asarray(m._covars_, dtype=np.float64))
-            m.monitor_.report(st["logprob"])
-            if m.monitor_.converged:
-                active[w] = False
+    batch = full_cov.FullCovBatch(dfeats, lengths, utt_model, len(models), S)
+
+    def pack(ms):
+        return np.concatenate([full_cov.pack_models([m._full_params()], S, name=m.covariance_type) for m in ms])
+
+    def update(m, st):
+        m.startprob_, m.transmat_, m.means_, m._covars_ = m_step_typed(
+            st, m.covariance_type, m.startprob_, m.transmat_, m.params, m.startprob_prior, m.transmat_prior,
+            m.means_prior, m.means_weight, m.covars_prior, m.covars_weight, np.asarray(m.means_, dtype=np.float64),
+            np.asarray(m._covars_, dtype=np.float64))
+    baum_welch(models, batch, pack, lambda row, m: full_cov.split_stats(row, S, batch.D, m.n_components), update)
 
 
 def _init_models(models, needs, dfeats, frames) -> None:

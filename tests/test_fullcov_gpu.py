@@ -1,5 +1,5 @@
-"""GaussianHMM with "full", "tied" and "spherical" covariances on the GPU (csrc/fullcov_ops.h inside csrc/gmm_hmm.hip,
-through sapr_amd/full_cov.py and sapr_amd/hmmlearn_hmm.py) against the numpy restatement tests/_fullcov_ref.py on the
+"""GaussianHMM with "full", "tied" and "spherical" covariances on the GPU (the family of csrc/fullcov_ops.h over the
+engine of csrc/tile_trellis.h, through sapr_amd/full_cov.py and sapr_amd/hmmlearn_hmm.py) against the numpy restatement tests/_fullcov_ref.py on the
 seeded cases of tests/_fullcov_cases.py (shapes, seeds and the reference results, computed once per case; their
 conditioning is established by tests/test_fullcov_cpu.py).
 
