@@ -447,6 +447,18 @@ int sapr_full_vocab(const float *feats, const int64_t *offsets, const int32_t *o
  *          (means[W][S][D], vars, gconst): per flat state {gconst, mean[DP], 1 / var[DP]}.  Padding features carry
  *          mean 0 and coefficient 0 (they add +0.0); a padding state carries gconst = +inf, mean 0, coefficient 0
  *          and comes out as -inf.  (sapr_amd/connected.py emit_operands builds it.)
+ * Stage 1 has two more variants, which read a family's own operand block in place (nothing is repacked) and write the
+ * same logb[total_frames][R], frame-parallel over a (frame block, word) grid:
+ *   sapr_connected_emit_gmm   Gaussian mixtures.  pack [W][doubles per model] as sapr_gmm_pack_layout(S, M, D)
+ *          describes it (the block sapr_gmm_vocab_diag takes); read: cc[SP][MP] and prm[SP][DP][MP][2].
+ *              logb[t][w * SP + s] = logsumexp_m (cc[s][m] + sum_d (x_d - mean_dm)^2 * (-1 / (2 var_dm)))
+ *   sapr_connected_emit_full  full covariances ("full", "tied").  pack [W][doubles per model] as
+ *          sapr_full_pack_layout(S, D) describes it (the block sapr_full_vocab takes); read: c[SP], mu[SP][DP],
+ *          Winv[SP][DP][DP].
+ *              logb[t][w * SP + s] = c[s] - 1/2 |Winv_s (x - mu_s)|^2
+ *   Both call the device functions of the per-model emission kernels (sapr_gmm_estep_diag / sapr_full_estep) in the
+ *   same order: the values carry the same bits.  A state whose constants are all -inf (the padding states of a pack)
+ *   comes out as -inf.  S is the vocabulary's kernel state count (the pack's), M its component count.
  * Stage 2, sapr_connected_viterbi: the recursion over a logb it is given (any emission family may supply one).
  *   logb       [total_frames][R] float64; offsets[n_utts + 1] as everywhere (frames of utterance u:
  *              offsets[u] .. offsets[u + 1]); offsets that leave the batch are served as an empty utterance
@@ -462,12 +474,16 @@ int sapr_full_vocab(const float *feats, const int64_t *offsets, const int32_t *o
  * No atomics: outputs are bit-identical from run to run, and an utterance's outputs are a function of its own frames
  * and the network alone.  Non-finite values propagate, nothing is repaired.
  *
- * Bad sizes, NULL required pointers and a workspace that is too small return SAPR_ERR_ARG, S > 18, D > 39 or
+ * Bad sizes, NULL required pointers and a workspace that is too small return SAPR_ERR_ARG, S > 18, D > 39, M > 8 or
  * W * SP > 256 SAPR_ERR_UNSUPPORTED (from the layout and size functions too), all before any launch; n_utts == 0
- * (total_frames == 0 for the emission) returns 0 after these checks. */
+ * (total_frames == 0 for the emissions) returns 0 after these checks. */
 int sapr_connected_layout(int32_t W, int32_t S, int32_t D, int32_t *SP, int32_t *DP, int32_t *R);
 int sapr_connected_workspace_bytes(int64_t total_frames, int64_t n_utts, int32_t W, int32_t S, size_t *bytes);
 int sapr_connected_emit_diag(const float *feats, int64_t total_frames, int32_t D, const double *ops, int32_t W,
+                             int32_t S, double *logb /* [total_frames][R] */, void *stream);
+int sapr_connected_emit_gmm(const float *feats, int64_t total_frames, int32_t D, const double *pack, int32_t W,
+                            int32_t S, int32_t M, double *logb /* [total_frames][R] */, void *stream);
+int sapr_connected_emit_full(const float *feats, int64_t total_frames, int32_t D, const double *pack, int32_t W,
                              int32_t S, double *logb /* [total_frames][R] */, void *stream);
 int sapr_connected_viterbi(const double *logb, const int64_t *offsets, int64_t n_utts, int64_t total_frames,
                            const double *log_start, const double *log_trans, const double *log_exit,

@@ -86,6 +86,9 @@ SIGNATURES = {
                                       C.POINTER(c_int32)]),
     "sapr_connected_workspace_bytes": (c_int, [c_int64, c_int64, c_int32, c_int32, C.POINTER(c_size_t)]),
     "sapr_connected_emit_diag": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "sapr_connected_emit_gmm": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p,
+                                        c_void_p]),
+    "sapr_connected_emit_full": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "sapr_connected_viterbi": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_double,
                                        c_int32, c_int32, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p]),

@@ -2,8 +2,11 @@
 loop, in which the end of any word may be followed by the start of any word, so a recording of several words in a row
 comes back as a word string with its segment boundaries (the other scorers label a whole recording as ONE word).
 
-Two stages (include/sapr_hip.h): ``sapr_connected_emit_diag`` evaluates ``logb[total_frames, W * SP]`` for
-diagonal-Gaussian word models, ``sapr_connected_viterbi`` runs the recursion over any ``logb`` it is given.  The CPU
+Two stages (include/sapr_hip.h).  Stage 1 evaluates ``logb[total_frames, W * SP]`` for the vocabulary's emission
+family: ``sapr_connected_emit_diag`` for diagonal-Gaussian word models ("diag", "spherical"),
+``sapr_connected_emit_gmm`` for Gaussian mixtures (``GMMHMM``) over the vocabulary's ``gmm_hmm.GmmPack``,
+``sapr_connected_emit_full`` for a vocabulary with a "full" or "tied" model over its ``full_cov.FullPack`` (both packs
+are read as they are).  Stage 2, ``sapr_connected_viterbi``, runs the recursion over any ``logb`` it is given.  The CPU
 restatement ``tests/_connected_ref.py`` is the definition; the recursion reproduces it bit for bit.
 """
 from __future__ import annotations
@@ -62,14 +65,66 @@ def emit_operands(means, vars_, gconst, n_states=None) -> np.ndarray:
     return ops.reshape(R, 1 + 2 * DP)
 
 
+FAMILIES = ("diag", "gmm", "full")
+_GAUSS_ATTRS = ("startprob_", "transmat_", "means_", "_covars_")
+_GMM_ATTRS = ("startprob_", "transmat_", "weights_", "means_", "covars_")
+
+
+def vocabulary_family(models, names=None, implementation=None) -> str:
+    """The emission family a vocabulary is decoded with — "diag" (only "diag" / "spherical" ``GaussianHMM``), "full"
+    (a ``GaussianHMM`` vocabulary in which any model is "full" or "tied") or "gmm" (``GMMHMM``) — after checking,
+    before anything is packed, that every model is one of the family's class and carries fitted parameters.  A model
+    that does not is refused with a ``ValueError`` that names it (``names[i]``, or its index).
+    ``implementation``: "gmmhmm" demands mixtures and "hmmlearn" ``GaussianHMM`` models (a decoder's vocabulary);
+    ``None`` takes a vocabulary that holds a ``GMMHMM`` as mixtures."""
+    from .gmm_hmm import GMMHMM
+    models = list(models)
+    if not models:
+        raise ValueError("empty vocabulary")
+
+    def label(i):
+        return f"word {names[i]!r}" if names is not None else f"model {i}"
+
+    def missing(m, attrs):
+        return [a for a in attrs if getattr(m, a, None) is None]
+
+    if implementation == "gmmhmm" or (implementation is None and any(isinstance(m, GMMHMM) for m in models)):
+        for i, m in enumerate(models):
+            if not isinstance(m, GMMHMM):
+                raise ValueError(f"{label(i)}: a {type(m).__name__} is not a GMMHMM; connected-word decoding with "
+                                 f"implementation='gmmhmm' serves fitted GMMHMM models")
+            if missing(m, _GMM_ATTRS):
+                raise ValueError(f"{label(i)}: the GMMHMM (implementation='gmmhmm') is not fitted: "
+                                 f"{', '.join(missing(m, _GMM_ATTRS))} missing")
+        return "gmm"
+    types = [getattr(m, "covariance_type", "diag") for m in models]
+    full = any(ct in ("full", "tied") for ct in types)
+    for i, (m, ct) in enumerate(zip(models, types)):
+        if isinstance(m, GMMHMM):
+            raise ValueError(f"{label(i)}: a GMMHMM is served by implementation='gmmhmm', not by "
+                             f"implementation={implementation!r}")
+        if ct not in ("diag", "spherical", "full", "tied"):
+            raise ValueError(f"{label(i)}: connected-word decoding serves 'diag', 'spherical', 'full' and 'tied' "
+                             f"models; got covariance_type={ct!r}")
+        if missing(m, _GAUSS_ATTRS):
+            raise ValueError(f"{label(i)}: the model with covariance_type={ct!r} is not fitted: "
+                             f"{', '.join(missing(m, _GAUSS_ATTRS))} missing")
+        if full and not (hasattr(m, "_check") and hasattr(m, "_full_params")):
+            raise ValueError(f"{label(i)}: a {type(m).__name__} with covariance_type={ct!r} cannot join a vocabulary "
+                             f"that holds a 'full' or 'tied' model: its members must be GaussianHMM objects")
+    return "full" if full else "diag"
+
+
 class ConnectedNetwork:
     """The word loop: W word models padded to S = the largest model's states.  ``log_start[W, S]``,
     ``log_trans[W, S, S]``, ``log_exit[W, S]`` (``-inf``: a word may not end in this state; a padded state has ``-inf``
     everywhere) and the scalar ``word_penalty`` added once per word boundary.  Built from models
-    (:meth:`from_models`) it also carries the diagonal-Gaussian emission parameters ``means``, ``vars``, ``gconst``."""
+    (:meth:`from_models`) it also carries its emission ``family``: "diag" with the diagonal-Gaussian parameters
+    ``means``, ``vars``, ``gconst``; "gmm" or "full" with the ``tile_family.VocabPack`` it was built from (``pack``: a
+    ``gmm_hmm.GmmPack`` or a ``full_cov.FullPack``, whose device copy the emission reads in place)."""
 
     def __init__(self, log_start, log_trans, log_exit, word_penalty=0.0, n_states=None, means=None, vars_=None,
-                 gconst=None):
+                 gconst=None, family="diag", pack=None):
         self.log_start = np.ascontiguousarray(log_start, dtype=np.float64)
         self.log_trans = np.ascontiguousarray(log_trans, dtype=np.float64)
         self.log_exit = np.ascontiguousarray(log_exit, dtype=np.float64)
@@ -83,46 +138,73 @@ class ConnectedNetwork:
         self.means = None if means is None else np.ascontiguousarray(means, dtype=np.float64)
         self.vars = None if vars_ is None else np.ascontiguousarray(vars_, dtype=np.float64)
         self.gconst = None if gconst is None else np.ascontiguousarray(gconst, dtype=np.float64)
-        self.D = 0 if self.means is None else int(self.means.shape[2])
+        if family not in FAMILIES:
+            raise ValueError(f"family must be one of {FAMILIES}, got {family!r}")
+        if (family == "diag") != (pack is None):
+            raise ValueError("the 'gmm' and 'full' families come with their VocabPack, 'diag' with means / vars / gconst")
+        if pack is not None and (pack.W, pack.S) != (self.W, self.S):
+            raise ValueError(f"the pack was built for (W, S) = {(pack.W, pack.S)}, the network for {(self.W, self.S)}")
+        self.family, self.pack = family, pack
+        self.D = int(pack.D) if pack is not None else (0 if self.means is None else int(self.means.shape[2]))
         self.SP, self.DP, self.R = layout(self.W, self.S, max(self.D, 1))
         self._dev = None
 
     @staticmethod
-    def from_models(models, exit_states="last", word_penalty=0.0) -> "ConnectedNetwork":
-        """``models``: fitted "diag" or "spherical" ``GaussianHMM`` objects that share the feature width, read through
-        the parameters ``trellis.DiagModelPack.from_models`` reads (``startprob_``, ``transmat_``, ``means_``,
-        ``_covars_``; variances floored at float64 tiny, ``gconst = D log 2 pi + sum log var``).  A mixed number of
-        states is padded.  ``exit_states``: ``"last"`` (a word ends in its model's own last state), ``"any"``, or an
-        array ``[W, S]`` of log exit scores."""
+    def from_models(models, exit_states="last", word_penalty=0.0, names=None, implementation=None,
+                    pack=None) -> "ConnectedNetwork":
+        """``models``: the fitted word models of one family (:func:`vocabulary_family` decides and validates; ``names``
+        and ``implementation`` are what its messages speak of):
+
+        * only "diag" / "spherical" ``GaussianHMM`` objects that share the feature width, read through the parameters
+          ``trellis.DiagModelPack.from_models`` reads (``startprob_``, ``transmat_``, ``means_``, ``_covars_``;
+          variances floored at float64 tiny, ``gconst = D log 2 pi + sum log var``);
+        * ``GaussianHMM`` objects of which any is "full" or "tied": the whole vocabulary goes through
+          ``full_cov.FullPack.from_models`` ("diag" / "spherical" members as diagonal matrices), as in the isolated-word
+          scorer;
+        * ``GMMHMM`` objects that share ``n_mix`` and the feature width (``gmm_hmm.GmmPack.from_models``).
+
+        ``pack``: the vocabulary's ``VocabPack`` if the caller has built it already.  A mixed number of states is
+        padded.  ``exit_states``: ``"last"`` (a word ends in its model's own last state), ``"any"``, or an array
+        ``[W, S]`` of log exit scores."""
         models = list(models)
-        if not models:
-            raise ValueError("empty vocabulary")
-        for m in models:
-            ct = getattr(m, "covariance_type", "diag")
-            if ct not in ("diag", "spherical"):
-                raise ValueError(f"connected-word decoding serves 'diag' and 'spherical' models; got "
-                                 f"covariance_type={ct!r}")
-        n_states = [int(np.asarray(m.startprob_).shape[0]) for m in models]
-        D = int(np.asarray(models[0].means_).shape[1])
-        W, S = len(models), max(n_states)
-        log_start = np.full((W, S), -np.inf)
-        log_trans = np.full((W, S, S), -np.inf)
-        means = np.zeros((W, S, D))
-        vars_ = np.ones((W, S, D))
-        gconst = np.full((W, S), np.inf)
-        with np.errstate(divide="ignore"):
-            for w, (m, k) in enumerate(zip(models, n_states)):
-                mu = np.asarray(m.means_, dtype=np.float64)
-                if mu.shape != (k, D):
-                    raise ValueError("the models must share the feature width")
-                cv = np.asarray(m._covars_, dtype=np.float64)
-                cv = np.broadcast_to(cv[:, None], mu.shape) if cv.ndim == 1 else cv  # (spherical)
-                var = np.maximum(cv, _TINY)
-                log_start[w, :k] = np.log(np.asarray(m.startprob_, dtype=np.float64))
-                log_trans[w, :k, :k] = np.log(np.asarray(m.transmat_, dtype=np.float64))
-                means[w, :k] = mu
-                vars_[w, :k] = var
-                gconst[w, :k] = D * np.log(2 * np.pi) + np.log(var).sum(axis=-1)
+        family = vocabulary_family(models, names, implementation)
+        means = vars_ = gconst = None
+        if family == "diag":
+            n_states = [int(np.asarray(m.startprob_).shape[0]) for m in models]
+            D = int(np.asarray(models[0].means_).shape[1])
+            W, S = len(models), max(n_states)
+            log_start = np.full((W, S), -np.inf)
+            log_trans = np.full((W, S, S), -np.inf)
+            means = np.zeros((W, S, D))
+            vars_ = np.ones((W, S, D))
+            gconst = np.full((W, S), np.inf)
+            with np.errstate(divide="ignore"):
+                for w, (m, k) in enumerate(zip(models, n_states)):
+                    mu = np.asarray(m.means_, dtype=np.float64)
+                    if mu.shape != (k, D):
+                        raise ValueError("the models must share the feature width")
+                    cv = np.asarray(m._covars_, dtype=np.float64)
+                    cv = np.broadcast_to(cv[:, None], mu.shape) if cv.ndim == 1 else cv  # (spherical)
+                    var = np.maximum(cv, _TINY)
+                    log_start[w, :k] = np.log(np.asarray(m.startprob_, dtype=np.float64))
+                    log_trans[w, :k, :k] = np.log(np.asarray(m.transmat_, dtype=np.float64))
+                    means[w, :k] = mu
+                    vars_[w, :k] = var
+                    gconst[w, :k] = D * np.log(2 * np.pi) + np.log(var).sum(axis=-1)
+        else:
+            if pack is None:
+                if family == "gmm":
+                    from .gmm_hmm import GmmPack
+                    pack = GmmPack.from_models(models)  # (refuses models that do not share n_mix and the width)
+                else:
+                    from .full_cov import FullPack
+                    pack = FullPack.from_models(models)
+            # the head of every model in the pack (tile_family.pack_head): log_start[SP], log_trans[SP][SP] — the very
+            # values the per-model kernels run on
+            n_states, (W, S) = list(pack.n_states), (pack.W, pack.S)
+            SP = layout(W, S, pack.D)[0]
+            log_start = pack.data[:, :SP][:, :S].copy()
+            log_trans = pack.data[:, SP:SP + SP * SP].reshape(W, SP, SP)[:, :S, :S].copy()
         if isinstance(exit_states, str):
             if exit_states not in ("last", "any"):
                 raise ValueError(f"exit_states must be 'last', 'any' or an array [W, S], got {exit_states!r}")
@@ -138,14 +220,18 @@ class ConnectedNetwork:
                 raise ValueError(f"exit_states must be [W={W}, S={S}], got {log_exit.shape}")
             for w, k in enumerate(n_states):
                 log_exit[w, k:] = -np.inf
-        return ConnectedNetwork(log_start, log_trans, log_exit, word_penalty, n_states, means, vars_, gconst)
+        return ConnectedNetwork(log_start, log_trans, log_exit, word_penalty, n_states, means, vars_, gconst, family,
+                                pack)
 
     def device(self, dev):
-        """The device copies ``(log_start, log_trans, log_exit, ops | None)``; made once per device."""
+        """The device copies ``(log_start, log_trans, log_exit, ops | None)``; made once per device.  ``ops`` is the
+        operand block of the family's emission: :func:`emit_operands` for "diag", the pack's own device copy else."""
         torch = _torch()
         if self._dev is None or self._dev[0].device != dev:
             ops = None
-            if self.means is not None:
+            if self.pack is not None:
+                ops = self.pack.device(dev)
+            elif self.means is not None:
                 ops = torch.from_numpy(emit_operands(self.means, self.vars, self.gconst, self.n_states)).to(dev)
             self._dev = tuple(torch.from_numpy(a).to(dev) for a in (self.log_start, self.log_trans, self.log_exit)) \
                 + (ops,)
@@ -183,11 +269,13 @@ def _offsets(lengths):
     return lengths, offs
 
 
-def emit_diag(feats, network: ConnectedNetwork):
-    """``sapr_connected_emit_diag``: device ``feats[total_frames, D]`` float32 -> device ``logb[total_frames, R]``."""
+def _emit(name, feats, network: ConnectedNetwork, family, *shape):
+    """One stage-1 entry point: device ``feats[total_frames, D]`` float32 -> device ``logb[total_frames, R]``;
+    ``shape``: what the entry point takes between D's operand block and ``logb`` (W, S and, for the mixtures, M)."""
     torch = _torch()
-    if network.means is None:
-        raise ValueError("the network carries no emission parameters (build it with ConnectedNetwork.from_models)")
+    if network.family != family or (network.means is None and network.pack is None):
+        raise ValueError(f"{name} needs a network of the {family!r} family that carries its emission parameters "
+                         f"(ConnectedNetwork.from_models); this one is {network.family!r}")
     if feats.dtype != torch.float32 or feats.dim() != 2 or not feats.is_contiguous():
         raise ValueError("feats must be a contiguous float32 [total_frames, D] tensor")
     if int(feats.shape[1]) != network.D:
@@ -195,10 +283,28 @@ def emit_diag(feats, network: ConnectedNetwork):
     ops = network.device(feats.device)[3]
     total = int(feats.shape[0])
     logb = torch.empty((total, network.R), dtype=torch.float64, device=feats.device)
-    _lib.check(_lib.load().sapr_connected_emit_diag(_lib.ptr(feats), total, network.D, _lib.ptr(ops), network.W,
-                                                    network.S, _lib.ptr(logb), _lib.current_stream()),
-               "sapr_connected_emit_diag")
+    _lib.check(getattr(_lib.load(), name)(_lib.ptr(feats), total, network.D, _lib.ptr(ops), *shape, _lib.ptr(logb),
+                                          _lib.current_stream()), name)
     return logb
+
+
+def emit_diag(feats, network: ConnectedNetwork):
+    """``sapr_connected_emit_diag``: device ``feats[total_frames, D]`` float32 -> device ``logb[total_frames, R]``."""
+    return _emit("sapr_connected_emit_diag", feats, network, "diag", network.W, network.S)
+
+
+def emit_gmm(feats, network: ConnectedNetwork):
+    """``sapr_connected_emit_gmm``: the same for a mixture vocabulary, over the network's ``GmmPack`` as it is."""
+    return _emit("sapr_connected_emit_gmm", feats, network, "gmm", network.W, network.S,
+                 network.pack.M if network.pack is not None else 0)
+
+
+def emit_full(feats, network: ConnectedNetwork):
+    """``sapr_connected_emit_full``: the same for a full-covariance vocabulary, over the network's ``FullPack``."""
+    return _emit("sapr_connected_emit_full", feats, network, "full", network.W, network.S)
+
+
+_EMIT = {"diag": emit_diag, "gmm": emit_gmm, "full": emit_full}
 
 
 def _run_viterbi(logb, offs_dev, n_utts, total, network):
@@ -253,7 +359,7 @@ def connected_viterbi(logb, lengths, network: ConnectedNetwork) -> ConnectedResu
 
 
 def connected_decode(batch_or_feature_list, network: ConnectedNetwork) -> ConnectedResult:
-    """Emission and recursion for diagonal-Gaussian word models: a ``trellis.FeatureBatch`` or a list of frame-major
+    """Emission (by the network's family) and recursion: a ``trellis.FeatureBatch`` or a list of frame-major
     ``(T, D)`` feature arrays -> :class:`ConnectedResult`."""
     torch = _torch()
     from .tile_family import vocab_features
@@ -273,5 +379,5 @@ def connected_decode(batch_or_feature_list, network: ConnectedNetwork) -> Connec
         packed = np.concatenate(mats, axis=0) if offs[-1] else np.zeros((0, D), np.float32)
         feats = torch.from_numpy(packed).to(dev)
         offs_dev = torch.from_numpy(offs).to(dev)
-    logb = emit_diag(feats, network)
+    logb = _EMIT[network.family](feats, network)
     return _result(_run_viterbi(logb, offs_dev, int(lengths.size), int(offs[-1]), network), offs)

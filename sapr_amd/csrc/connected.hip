@@ -11,6 +11,16 @@
 // +0.0, a padding state carries gconst = +inf and comes out as -inf.
 //     logb = -0.5 * (gconst + sum_d ((x_d - mean_d) * (x_d - mean_d)) * (1 / var_d)),   d ascending
 //
+// Stage 1 for the other two families, sapr_connected_emit_gmm and sapr_connected_emit_full: the same geometry over a
+// (frame block, word) grid — every (frame, word) pair is independent, and one word's SP states cost up to
+// SP * DP^2 / 2 FMAs per frame, so a small batch still fills the device.  The operand is the family's own pack
+// ([W][doubles per model] of sapr_gmm_pack_layout / sapr_full_pack_layout, read in place behind the head the
+// recursions of the per-model kernels use), the arithmetic the shared device functions of gmm_emit_kernel /
+// full_emit_kernel (gmm_ops.h mix_log_terms + lse_ops.h lse_all; fullcov_emit.h full_log_density) called in the same
+// order: the emitted bits are the per-model emissions' bits.  A state whose every component constant (whose constant)
+// is -inf — the padding states of the pack — is written as -inf by a wavefront-uniform branch, whatever the frame
+// holds, and costs no arithmetic.
+//
 // Stage 2, sapr_connected_viterbi: the recursion over a given logb; it knows nothing about the emission family.
 //     One wavefront serves one utterance (four utterances per workgroup, which share the transition table in LDS).
 //     The R <= 256 flat states lie along the lanes, RL in {1, 2, 4} per lane: flat state r = k * 64 + lane sits in
@@ -33,13 +43,17 @@
 namespace sapr {
 namespace {
 
-constexpr int kCnMaxS = 18, kCnMaxD = 39, kCnMaxR = 256;
+#include "lse_ops.h"
+#include "gmm_ops.h"
+#include "fullcov_emit.h"
+
+constexpr int kCnMaxS = kMaxS, kCnMaxD = kMaxD, kCnMaxR = 256;
 constexpr int kCnBlock = 256;         // 4 wavefronts per workgroup
 constexpr int kCnWaves = kCnBlock / kWave;
 constexpr int kEntry = 255;           // back-pointer byte: the word was entered at this frame
 
-constexpr int cn_sp_of(int S) { return S <= 4 ? 4 : (S <= 10 ? 10 : 18); }
-constexpr int cn_dp_of(int D) { return D <= 13 ? 13 : (D <= 26 ? 26 : 39); }
+constexpr int cn_sp_of(int S) { return sp_of(S); }  // (the padding rules of every family: gmm_ops.h)
+constexpr int cn_dp_of(int D) { return dp_of(D); }
 
 inline int cn_check_shape(int32_t W, int32_t S, int32_t D) {
   if (S > kCnMaxS || D > kCnMaxD || static_cast<int64_t>(W) * cn_sp_of(S) > kCnMaxR)
@@ -77,6 +91,71 @@ __global__ __launch_bounds__(kCnBlock) void connected_emit_kernel(const float *_
     }
     const double v = -0.5 * (o[0] + acc);
     if (live) out[r] = v;
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// stage 1: mixture and full-covariance emissions, grid (frame blocks, W)
+// ---------------------------------------------------------------------------------------
+template <int MP, int DP>
+__global__ __launch_bounds__(kCnBlock) void connected_emit_gmm_kernel(const float *__restrict__ feats,
+                                                                       int64_t total_frames, int32_t D, int32_t SP,
+                                                                       int32_t R, const double *__restrict__ pack,
+                                                                       double *__restrict__ logb) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * kCnBlock + threadIdx.x;
+  if (t >= total_frames) return;
+  const int w = blockIdx.y;
+  double x[DP];
+  load_frame_pad<DP>(feats + t * D, D, true, x);
+  // the word's model in the pack of sapr_gmm_pack_layout, wavefront-uniform: scalar loads
+  const double *__restrict__ mdl = pack + static_cast<int64_t>(w) * static_cast<int64_t>(model_doubles(SP, MP, DP));
+  const double *__restrict__ cc = mdl + off_cc(SP);
+  const double *__restrict__ prm = mdl + off_prm(SP, MP);
+  double *__restrict__ out = logb + t * R + w * SP;
+#pragma unroll 1
+  for (int s = 0; s < SP; ++s) {
+    bool off = true;  // (uniform) every component switched off: a padding state
+#pragma unroll
+    for (int m = 0; m < MP; ++m) off = off && cc[s * MP + m] == neg_inf();
+    if (off) {
+      out[s] = neg_inf();
+      continue;
+    }
+    double lc[MP];
+    mix_log_terms<MP, DP>([&](int d) { return x[d]; }, prm + static_cast<int64_t>(s) * DP * MP * 2, cc + s * MP, lc);
+    double v;
+    if constexpr (MP == 1)
+      v = lc[0];
+    else
+      v = lse_all<MP>(lc);
+    out[s] = v;
+  }
+}
+
+template <int DP>
+__global__ __launch_bounds__(kCnBlock) void connected_emit_full_kernel(const float *__restrict__ feats,
+                                                                        int64_t total_frames, int32_t D, int32_t SP,
+                                                                        int32_t R, const double *__restrict__ pack,
+                                                                        double *__restrict__ logb) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * kCnBlock + threadIdx.x;
+  if (t >= total_frames) return;
+  const int w = blockIdx.y;
+  double x[DP];
+  load_frame_pad<DP>(feats + t * D, D, true, x);
+  // the word's model in the pack of sapr_full_pack_layout, wavefront-uniform: scalar loads
+  const double *__restrict__ mdl = pack + static_cast<int64_t>(w) * static_cast<int64_t>(full_model_doubles(SP, DP));
+  const double *__restrict__ cc = mdl + SP + 2 * SP * SP;
+  const double *__restrict__ mu = cc + SP;
+  const double *__restrict__ wi = mu + SP * DP;
+  double *__restrict__ out = logb + t * R + w * SP;
+#pragma unroll 1
+  for (int s = 0; s < SP; ++s) {
+    const double c = cc[s];
+    if (c == neg_inf()) {
+      out[s] = neg_inf();
+      continue;
+    }
+    out[s] = full_log_density<DP>([&](int d) { return x[d]; }, mu + s * DP, wi + static_cast<int64_t>(s) * DP * DP, c);
   }
 }
 
@@ -334,6 +413,86 @@ extern "C" int sapr_connected_emit_diag(const float *feats, int64_t total_frames
     case 13: SAPR_LAUNCH((connected_emit_kernel<13>), grid, block, 0, st, feats, total_frames, D, R, ops, logb); break;
     case 26: SAPR_LAUNCH((connected_emit_kernel<26>), grid, block, 0, st, feats, total_frames, D, R, ops, logb); break;
     default: SAPR_LAUNCH((connected_emit_kernel<39>), grid, block, 0, st, feats, total_frames, D, R, ops, logb); break;
+  }
+  SAPR_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+namespace sapr {
+namespace {
+
+// what both pack-reading emission entry points check before any launch; *blocks: the frame blocks of the grid
+int cn_emit_checks(const void *feats, int64_t total_frames, int32_t D, const void *pack, int32_t W, int32_t S,
+                   const void *logb, int64_t *blocks) {
+  if (int rc = cn_check_shape(W, S, D)) return rc;
+  *blocks = (total_frames + kCnBlock - 1) / kCnBlock;
+  SAPR_REQUIRE(*blocks <= 0x7fffffffLL, "grid too large (%lld blocks)", (long long)*blocks);
+  if (total_frames == 0) return 0;
+  SAPR_REQUIRE(feats && pack && logb, "NULL pointer argument");
+  return 0;
+}
+
+template <int MP>
+int launch_emit_gmm(dim3 grid, hipStream_t st, const float *feats, int64_t total_frames, int32_t D, int32_t SP,
+                    int32_t R, const double *pack, double *logb) {
+  const dim3 block(kCnBlock);
+  switch (cn_dp_of(D)) {
+    case 13:
+      SAPR_LAUNCH((connected_emit_gmm_kernel<MP, 13>), grid, block, 0, st, feats, total_frames, D, SP, R, pack, logb);
+      break;
+    case 26:
+      SAPR_LAUNCH((connected_emit_gmm_kernel<MP, 26>), grid, block, 0, st, feats, total_frames, D, SP, R, pack, logb);
+      break;
+    default:
+      SAPR_LAUNCH((connected_emit_gmm_kernel<MP, 39>), grid, block, 0, st, feats, total_frames, D, SP, R, pack, logb);
+      break;
+  }
+  SAPR_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+}  // namespace
+}  // namespace sapr
+
+extern "C" int sapr_connected_emit_gmm(const float *feats, int64_t total_frames, int32_t D, const double *pack,
+                                       int32_t W, int32_t S, int32_t M, double *logb, void *stream) {
+  SAPR_REQUIRE(total_frames >= 0 && W > 0 && S > 0 && M > 0 && D > 0,
+               "bad sizes (total_frames=%lld W=%d S=%d M=%d D=%d)", (long long)total_frames, W, S, M, D);
+  if (int rc = check_shape(S, M, D)) return rc;
+  int64_t blocks = 0;
+  if (int rc = cn_emit_checks(feats, total_frames, D, pack, W, S, logb, &blocks)) return rc;
+  if (total_frames == 0) return 0;
+  const int32_t SP = cn_sp_of(S), R = W * SP;
+  const dim3 grid(static_cast<unsigned>(blocks), static_cast<unsigned>(W));
+  hipStream_t st = as_stream(stream);
+  switch (mp_of(M)) {
+    case 1: return launch_emit_gmm<1>(grid, st, feats, total_frames, D, SP, R, pack, logb);
+    case 2: return launch_emit_gmm<2>(grid, st, feats, total_frames, D, SP, R, pack, logb);
+    case 4: return launch_emit_gmm<4>(grid, st, feats, total_frames, D, SP, R, pack, logb);
+    default: return launch_emit_gmm<8>(grid, st, feats, total_frames, D, SP, R, pack, logb);
+  }
+}
+
+extern "C" int sapr_connected_emit_full(const float *feats, int64_t total_frames, int32_t D, const double *pack,
+                                        int32_t W, int32_t S, double *logb, void *stream) {
+  SAPR_REQUIRE(total_frames >= 0 && W > 0 && S > 0 && D > 0, "bad sizes (total_frames=%lld W=%d S=%d D=%d)",
+               (long long)total_frames, W, S, D);
+  int64_t blocks = 0;
+  if (int rc = cn_emit_checks(feats, total_frames, D, pack, W, S, logb, &blocks)) return rc;
+  if (total_frames == 0) return 0;
+  const int32_t SP = cn_sp_of(S), R = W * SP;
+  const dim3 grid(static_cast<unsigned>(blocks), static_cast<unsigned>(W)), block(kCnBlock);
+  hipStream_t st = as_stream(stream);
+  switch (cn_dp_of(D)) {
+    case 13:
+      SAPR_LAUNCH((connected_emit_full_kernel<13>), grid, block, 0, st, feats, total_frames, D, SP, R, pack, logb);
+      break;
+    case 26:
+      SAPR_LAUNCH((connected_emit_full_kernel<26>), grid, block, 0, st, feats, total_frames, D, SP, R, pack, logb);
+      break;
+    default:
+      SAPR_LAUNCH((connected_emit_full_kernel<39>), grid, block, 0, st, feats, total_frames, D, SP, R, pack, logb);
+      break;
   }
   SAPR_HIP_TRY(hipGetLastError());
   return 0;

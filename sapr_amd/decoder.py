@@ -109,23 +109,30 @@ class Decoder:
     def decode_connected(self, feature_list: List[np.ndarray], word_penalty: float = 0.0,
                          exit_states="last") -> List[Dict]:
         """Recordings that hold several words in a row: one-pass Viterbi over the word loop (``sapr_amd.connected``:
-        ``sapr_connected_emit_diag`` + ``sapr_connected_viterbi``).  ``feature_list``: (D, T) arrays as in
-        ``decode_batch``.  Per utterance ``{"words": [...], "log_likelihood": float, "segments": [(word, start,
-        end_exclusive), ...], "state_sequence": ndarray}`` with the words in load order of the vocabulary; an utterance
-        no word string can explain (or one without frames) has no words, ``-inf`` and states of -1.  ``word_penalty`` is
-        added once per word boundary; ``exit_states``: "last", "any" or an array [W, S]
-        (``ConnectedNetwork.from_models``).  Served for "diag" and "spherical" ``GaussianHMM`` vocabularies."""
-        if self.implementation != "hmmlearn":
+        the emission stage of the vocabulary's family, then ``sapr_connected_viterbi``).  ``feature_list``: (D, T)
+        arrays as in ``decode_batch``.  Per utterance ``{"words": [...], "log_likelihood": float, "segments": [(word,
+        start, end_exclusive), ...], "state_sequence": ndarray}`` with the words in load order of the vocabulary; an
+        utterance no word string can explain (or one without frames) has no words, ``-inf`` and states of -1.
+        ``word_penalty`` is added once per word boundary; ``exit_states``: "last", "any" or an array [W, S]
+        (``ConnectedNetwork.from_models``).
+
+        Served for ``implementation="hmmlearn"`` — "diag" / "spherical" vocabularies through
+        ``sapr_connected_emit_diag``, a vocabulary with a "full" or "tied" model through ``sapr_connected_emit_full``
+        over the decoder's ``FullPack`` — and for ``implementation="gmmhmm"`` through ``sapr_connected_emit_gmm`` over
+        its ``GmmPack``.  A loaded object that is not a fitted model of the implementation's class is refused with a
+        ``ValueError`` that names its word."""
+        if self.implementation not in ("hmmlearn", "gmmhmm"):
             raise ValueError(f"connected-word decoding needs implementation='hmmlearn' with 'diag' or 'spherical' "
                              f"models: it has no emission stage for implementation={self.implementation!r}")
-        if self._is_full():
-            raise ValueError("connected-word decoding has no emission stage for covariance_type 'full' or 'tied': it "
-                             "serves 'diag' and 'spherical' models")
-        from .connected import ConnectedNetwork, connected_decode
+        from .connected import ConnectedNetwork, connected_decode, vocabulary_family
         if len(feature_list) == 0:
             raise ValueError("empty utterance list")
         words = list(self.models)
-        net = ConnectedNetwork.from_models(self._model_list(), exit_states=exit_states, word_penalty=word_penalty)
+        # (validated before the pack is built: packing reads the fitted attributes)
+        family = vocabulary_family(self._model_list(), words, self.implementation)
+        net = ConnectedNetwork.from_models(self._model_list(), exit_states=exit_states, word_penalty=word_penalty,
+                                           names=words, implementation=self.implementation,
+                                           pack=None if family == "diag" else self._vocab_pack())
         res = connected_decode([np.asarray(f).T for f in feature_list], net)
         out = []
         for u in range(len(feature_list)):

@@ -1,18 +1,26 @@
 """Ad-hoc timing of connected-word recognition (dev tool):
-    python scripts/time_connected.py [N] [--frames 505] [--shapes 11,10,13 11,18,39] [--trace DIR]
+    python scripts/time_connected.py [N] [--frames 505] [--families diag gmm full] [--shapes 11,10,13 11,18,39]
+                                     [--gmm-shapes 11,10,2,13 11,18,2,39] [--full-shapes 11,10,13 11,18,39] [--trace DIR]
 The two stages and the back-trace of sapr_amd.connected on N utterances x 505 frames (five words of ~101 frames in a
-row) for (W, S, D) = (11, 10, 13) and (11, 18, 39), bidiagonal word models, exits in the last state:
-  emit       sapr_connected_emit_diag                          logb[total_frames][W * SP]
+row), bidiagonal word models, exits in the last state, for every emission family: diagonal Gaussians at
+(W, S, D) = (11, 10, 13) and (11, 18, 39), mixtures at (W, S, M, D) = (11, 10, 2, 13) and (11, 18, 2, 39), full
+covariances (odd words tied) at (W, S, D) = (11, 10, 13) and (11, 18, 39):
+  emit       sapr_connected_emit_diag / _gmm / _full            logb[total_frames][W * SP]
   viterbi    sapr_connected_viterbi without any path output    (the recursion kernel alone)
   decode     sapr_connected_viterbi with every output          (recursion + back-trace; back-trace = decode - viterbi)
-and, as a yardstick with the same emission work on the same frames in the same run, the all-vocabulary isolated-word
-scorer sapr_viterbi_diag_scores (+ its back-trace launch, trellis.viterbi_decode without a path).  Every route is
-warmed twice, then the routes are timed in turn, five times each, between device events.  Prints one JSON line per
-shape with the bytes each stage moves and the float64 operations it needs from the shapes alone: per frame and flat
-state 3 D + 2 for the emission, and per finite transition distance one add and one compare in the recursion.
+and a yardstick on the same frames in the same run: for the diagonal family the all-vocabulary isolated-word scorer
+sapr_viterbi_diag_scores (+ its back-trace launch, trellis.viterbi_decode without a path); for the other two the
+per-model decoder (sapr_gmm_viterbi_diag / sapr_full_viterbi) of every utterance under ONE word, whose frame-parallel
+emission kernel (gmm_emit_kernel / full_emit_kernel) does the arithmetic of one word of the connected emission: its
+time from the kernel trace, times W, is what the connected emission kernel is compared with.  Every route is warmed
+twice, then the routes are timed in turn, five times each, between device events.  Prints one JSON line per family
+and shape with the bytes each stage moves and the float64 operations it needs from the shapes alone: per frame and
+flat state 3 D + 2 (diag), M (4 D + 1) plus the log-sum-exp (gmm), 3 D (D + 1) / 2 + 2 D + 2 (full) for the emission, and
+per finite transition distance one add and one compare in the recursion.
 
 --trace DIR: afterwards the script starts itself once more under rocprofv3 --kernel-trace --stats (a run of its own:
-one warm-up and one timed call of every route per shape) and writes DIR/connected_rocprofv3_summary.txt."""
+one warm-up and one timed call of every route per shape) and writes DIR/connected_rocprofv3_summary.txt, which ends
+with the yardstick comparison: connected emission kernel against W x the per-model emission kernel."""
 import argparse
 import csv
 import glob
@@ -30,7 +38,10 @@ REPEATS = 5
 ap = argparse.ArgumentParser()
 ap.add_argument("N", nargs="?", type=int, default=10000)
 ap.add_argument("--frames", type=int, default=505)
-ap.add_argument("--shapes", nargs="+", default=["11,10,13", "11,18,39"])
+ap.add_argument("--families", nargs="+", default=["diag", "gmm", "full"], choices=["diag", "gmm", "full"])
+ap.add_argument("--shapes", nargs="+", default=["11,10,13", "11,18,39"], help="W,S,D of the diagonal family")
+ap.add_argument("--gmm-shapes", nargs="+", default=["11,10,2,13", "11,18,2,39"], help="W,S,M,D")
+ap.add_argument("--full-shapes", nargs="+", default=["11,10,13", "11,18,39"], help="W,S,D")
 ap.add_argument("--trace", default=None, help="directory for the rocprofv3 summary (a second run of its own)")
 ap.add_argument("--child", action="store_true", help="(internal) the run under rocprofv3")
 args = ap.parse_args()
@@ -51,22 +62,32 @@ def summary(t):
     return {"min": round(min(t), 3), "max": round(max(t), 3), "median": round(float(np.median(t)), 3)}
 
 
-def setup(W, S, D):
+def setup(family, shape):
     import torch
     from sapr_amd import _lib, connected
     from sapr_amd.trellis import DiagModelPack, FeatureBatch, viterbi_decode
+    from tests import _connected_family_cases as cases
     from tests._connected_ref import sample_case
-    model, _, _ = sample_case(7, W, S, D, 0)
-    net = connected.ConnectedNetwork(model["log_start"], model["log_trans"], model["log_exit"], 0.0, None,
-                                     model["means"], model["vars"], model["gconst"])
+    W, S, D = shape[0], shape[1], shape[-1]
+    if family == "diag":
+        model, _, _ = sample_case(7, W, S, D, 0)
+        net = connected.ConnectedNetwork(model["log_start"], model["log_trans"], model["log_exit"], 0.0, None,
+                                         model["means"], model["vars"], model["gconst"])
+        centres, spread = model["means"], np.sqrt(model["vars"])
+    else:
+        model, _, _ = cases.gmm_case(7, *shape, 0) if family == "gmm" else cases.full_case(7, *shape, 0)
+        net = connected.ConnectedNetwork.from_models(cases.models_of(family, model))
+        # (timing only: the frames lie about the first component's mean / the state's mean, a few units wide)
+        centres = model["means"][:, :, 0] if family == "gmm" else model["means"]
+        spread = np.sqrt(model["covars"][:, :, 0]) if family == "gmm" else np.full(centres.shape, 3.0)
     # five words in a row per utterance, the frames scattered about the means of the states they walk through
     torch.manual_seed(0)
     per = (T + 4) // 5
     t = torch.arange(T, device="cuda")
     word = (torch.randint(0, W, (N, 5), device="cuda"))[:, (t // per).clamp(max=4)]          # [N, T]
     state = ((t % per) * S // per).expand(N, T)
-    mu = torch.from_numpy(model["means"]).cuda()[word.reshape(-1), state.reshape(-1)]
-    sd = torch.from_numpy(np.sqrt(model["vars"])).cuda()[word.reshape(-1), state.reshape(-1)]
+    mu = torch.from_numpy(centres).cuda()[word.reshape(-1), state.reshape(-1)]
+    sd = torch.from_numpy(spread).cuda()[word.reshape(-1), state.reshape(-1)]
     feats = (mu + torch.randn(N * T, D, device="cuda", dtype=torch.float64) * sd).float().contiguous()
     del mu, sd, word, state
     lengths = np.full(N, T)
@@ -84,8 +105,10 @@ def setup(W, S, D):
     pe = torch.empty(total, dtype=torch.uint8, device="cuda")
 
     def emit():
-        _lib.check(lib.sapr_connected_emit_diag(_lib.ptr(feats), total, D, _lib.ptr(ops), W, S, _lib.ptr(logb),
-                                                _lib.current_stream()), "sapr_connected_emit_diag")
+        name = f"sapr_connected_emit_{family}"
+        extra = (net.pack.M,) if family == "gmm" else ()
+        _lib.check(getattr(lib, name)(_lib.ptr(feats), total, D, _lib.ptr(ops), W, S, *extra, _lib.ptr(logb),
+                                      _lib.current_stream()), name)
 
     def viterbi(paths):
         out = (n_words, pw, ps, pe) if paths else (None,) * 4
@@ -94,23 +117,36 @@ def setup(W, S, D):
                                               *(_lib.ptr(o) for o in out), _lib.current_stream()),
                    "sapr_connected_viterbi")
 
-    pack = DiagModelPack.from_params(model["startprob"], model["transmat"], model["means"], model["vars"])
-    fb = FeatureBatch.from_packed(feats, lengths)
-    routes = {"emit": emit, "viterbi": lambda: viterbi(False), "decode": lambda: viterbi(True),
-              "isolated_word_scores": lambda: viterbi_decode(fb, pack, want_path=False)}
+    routes = {"emit": emit, "viterbi": lambda: viterbi(False), "decode": lambda: viterbi(True)}
+    DP = net.DP
+    if family == "diag":
+        pack = DiagModelPack.from_params(model["startprob"], model["transmat"], model["means"], model["vars"])
+        fb = FeatureBatch.from_packed(feats, lengths)
+        routes["isolated_word_scores"] = lambda: viterbi_decode(fb, pack, want_path=False)
+        state_flops = 3 * DP + 2
+    else:
+        one_word = net.pack.batch(feats, lengths, np.zeros(N, dtype=np.int64))   # every utterance under word 0
+        routes["per_model_viterbi_one_word"] = lambda: one_word.viterbi(net.pack)
+        MP = {1: 1, 2: 2, 3: 4, 4: 4}.get(net.pack.M, 8) if family == "gmm" else 0
+        state_flops = MP * (4 * DP + 1) if family == "gmm" else 3 * DP * (DP + 1) // 2 + 2 * DP + 2
     nd = 2  # finite transition distances of a bidiagonal vocabulary
     facts = {"R": net.R, "logb_GB": round(total * net.R * 8 / 1e9, 3), "workspace_GB": round(ws_bytes / 1e9, 3),
              "emit_bytes_per_frame": 4 * D + 8 * net.R, "viterbi_bytes_per_frame": 9 * net.R + 4,
-             "emit_flops_per_frame": net.R * (3 * net.DP + 2), "viterbi_flops_per_frame": net.R * (2 * nd + 5)}
+             "emit_flops_per_frame": net.R * state_flops, "viterbi_flops_per_frame": net.R * (2 * nd + 5)}
     return routes, facts, (n_words, score)
+
+
+def family_shapes():
+    given = {"diag": args.shapes, "gmm": args.gmm_shapes, "full": args.full_shapes}
+    return [(f, tuple(int(v) for v in s.split(","))) for f in args.families for s in given[f]]
 
 
 def measure():
     import torch
-    for shape in args.shapes:
-        W, S, D = (int(v) for v in shape.split(","))
-        routes, facts, (n_words, score) = setup(W, S, D)
-        out = {"shape": {"N": N, "T": T, "W": W, "S": S, "D": D}, **facts}
+    for family, shape in family_shapes():
+        routes, facts, (n_words, score) = setup(family, shape)
+        names = ("W", "S", "M", "D") if family == "gmm" else ("W", "S", "D")
+        out = {"family": family, "shape": {"N": N, "T": T, **dict(zip(names, shape))}, **facts}
         for _ in range(1 if args.child else 2):
             for fn in routes.values():
                 fn()
@@ -126,11 +162,12 @@ def measure():
         med = {k: float(np.median(t)) for k, t in times.items()}
         out["backtrace_ms_median"] = round(med["decode"] - med["viterbi"], 3)
         out["connected_total_ms_median"] = round(med["emit"] + med["decode"], 3)
-        out["ratio_connected_over_isolated"] = round((med["emit"] + med["decode"]) / med["isolated_word_scores"], 3)
+        if "isolated_word_scores" in med:
+            out["ratio_connected_over_isolated"] = round((med["emit"] + med["decode"]) / med["isolated_word_scores"], 3)
         out["emit_GBps"] = round(facts["emit_bytes_per_frame"] * N * T / med["emit"] / 1e6, 1)
         out["viterbi_GBps"] = round(facts["viterbi_bytes_per_frame"] * N * T / med["viterbi"] / 1e6, 1)
         print(json.dumps(out), flush=True)
-        del routes
+        del routes, n_words, score
         torch.cuda.empty_cache()
 
 
@@ -140,8 +177,10 @@ if args.child or not args.trace:
 
 os.makedirs(args.trace, exist_ok=True)
 trace = os.path.join(args.trace, "trace")
+shape_args = ["--families", *args.families, "--shapes", *args.shapes, "--gmm-shapes", *args.gmm_shapes,
+              "--full-shapes", *args.full_shapes]
 cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", trace, "--", sys.executable,
-       os.path.abspath(__file__), str(N), "--frames", str(T), "--shapes", *args.shapes, "--child"]
+       os.path.abspath(__file__), str(N), "--frames", str(T), *shape_args, "--child"]
 with open(os.path.join(args.trace, "child.log"), "w") as log:
     subprocess.run(cmd, check=True, stdout=log, stderr=subprocess.STDOUT, stdin=subprocess.DEVNULL, timeout=900)
 rows = []
@@ -149,15 +188,38 @@ for f in glob.glob(os.path.join(trace, "**", "*kernel_stats.csv"), recursive=Tru
     with open(f) as fh:
         rows += [r for r in csv.DictReader(fh) if "sapr" in r["Name"]]
 rows.sort(key=lambda r: -float(r["TotalDurationNs"]))
-lines = [f"# rocprofv3 --kernel-trace --stats of: python scripts/time_connected.py {N} --frames {T} --shapes "
-         f"{' '.join(args.shapes)} --child",
+lines = [f"# rocprofv3 --kernel-trace --stats of: python scripts/time_connected.py {N} --frames {T} "
+         f"{' '.join(shape_args)} --child",
          "# one warm-up and one timed call of every route (emission; recursion alone; recursion + back-trace; the",
-         "# all-vocabulary isolated-word scorer on the same frames) per shape; sapr kernels only",
+         "# yardstick on the same frames: the all-vocabulary isolated-word scorer (diag), the per-model decoder under",
+         "# one word (gmm, full)) per family and shape; sapr kernels only",
          "# calls  total_ms  avg_ms  min_ms  max_ms  name"]
 for r in rows:
     lines.append("%5s %9.3f %8.3f %8.3f %8.3f  %s" % (r["Calls"], float(r["TotalDurationNs"]) / 1e6,
                                                      float(r["AverageNs"]) / 1e6, float(r["MinNs"]) / 1e6,
                                                      float(r["MaxNs"]) / 1e6, r["Name"]))
+
+
+def kernel_avg_ms(kernel, targs):
+    """Average duration of the instantiation ``kernel<targs>`` (the name without its namespace and arguments)."""
+    for r in rows:
+        if f"{kernel}<{targs}>".replace(" ", "") in r["Name"].replace(" ", ""):
+            return float(r["AverageNs"]) / 1e6
+    return None
+
+
+lines.append("# yardstick: connected emission kernel against W x the per-model emission kernel of the same arithmetic")
+for family, shape in family_shapes():
+    if family == "diag":
+        continue
+    DP = 13 if shape[-1] <= 13 else (26 if shape[-1] <= 26 else 39)
+    targs = f"{ {1: 1, 2: 2, 3: 4, 4: 4}.get(shape[2], 8)}, {DP}" if family == "gmm" else f"{DP}"
+    new, old = kernel_avg_ms(f"connected_emit_{family}_kernel", targs), kernel_avg_ms(f"{family}_emit_kernel", targs)
+    if new is None or old is None:
+        lines.append(f"# {family} {shape}: kernels not found in the trace")
+        continue
+    lines.append(f"# {family} {shape}: connected_emit_{family}_kernel<{targs}> {new:.3f} ms, {family}_emit_kernel<{targs}> "
+                 f"{old:.3f} ms x W = {old * shape[0]:.3f} ms, ratio {new / (old * shape[0]):.3f}")
 with open(os.path.join(args.trace, "connected_rocprofv3_summary.txt"), "w") as fh:
     fh.write("\n".join(lines) + "\n")
 print("\n".join(lines))
