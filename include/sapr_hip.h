@@ -635,6 +635,9 @@ int sapr_custom_global_cov(const float *feats, int64_t total_frames, int32_t D, 
  *          (grid_blocks > 0), a capturing stream and small batches keep the single launch sequence.  The plan's
  *          stream and events are guarded by a mutex: concurrent calls on one plan from several host threads are
  *          serialised at the launch, not undefined.
+ *   finish The finish pass of that core has bodies specialised on 40 mels without and with deltas and a generic
+ *          body for every other shape (same bits; SAPR_FINISH_GENERIC=1 at plan creation: the generic body for
+ *          every plan).
  * ---------------------------------------------------------------------------------- */
 int sapr_mfcc_plan_create(double sr, int32_t n_fft, int32_t win_length, int32_t hop,
                           int32_t n_mels, int32_t n_mfcc, double fmin, double fmax /* <=0: sr/2 */,

@@ -189,6 +189,13 @@ constexpr int kMaxSlices = 32;  // utterance slices of one batch (SAPR_MFCC_SLIC
 #endif
 constexpr int kDefaultSlices = SAPR_MFCC_DEFAULT_SLICES;  // power of two (halved until a batch is large enough)
 constexpr int kSliceMinSets = SAPR_MFCC_SLICE_MIN_SETS;   // 4-frame sets per spectral wavefront and slice
+#ifndef SAPR_FINISH_BESIDE_MAX
+#define SAPR_FINISH_BESIDE_MAX 8
+#endif
+constexpr int kFinishBesideMax = SAPR_FINISH_BESIDE_MAX;  // finish workgroups per CU beside a spectral grid, at most
+
+using FinishKernel = void (*)(const float *, const unsigned *, const int64_t *, int64_t, MfccDev, float *, int, int64_t,
+                              const int64_t *, int);
 
 struct MfccPlan {
   MfccDev dev;
@@ -200,7 +207,11 @@ struct MfccPlan {
   int wave_blocks_per_cu = 0;       // resident workgroups per CU (occupancy query at plan creation)
   // slice pipeline of the wave-private core (sapr_mfcc_batch): finish(slice k) on `side` under spectral(slice k + 1)
   int slices_env = 0;               // SAPR_MFCC_SLICES at plan creation: 0 = unset (default), 1 = single launch, n = forced
-  int finish_beside = 1;            // finish workgroups per CU that fit next to the resident spectral grid
+  int finish_beside = 1;            // finish workgroups per CU of the launches beside a spectral grid
+  // the finish body this plan launches (mfcc_wave.h): specialised on the presets' shapes, generic for every other plan
+  // and under SAPR_FINISH_GENERIC=1 at plan creation; finish_occ = its wavefronts per SIMD = workgroups per CU
+  FinishKernel finish_kernel = nullptr;
+  int finish_occ = 0;
   mutable std::mutex side_mu;       // the stream and the events below serve one sapr_mfcc_batch call at a time
   mutable bool side_tried = false;  // created on the first call that cuts a batch
   mutable hipStream_t side = nullptr;
@@ -1466,9 +1477,20 @@ extern "C" int sapr_mfcc_plan_create(double sr, int32_t n_fft, int32_t win_lengt
       const int v = std::atoi(sl);
       pl->slices_env = v < 1 ? 0 : (v > kMaxSlices ? kMaxSlices : v);
     }
-    // finish workgroups per CU that fit into the LDS the resident spectral workgroups leave free (both rounded up to
-    // the allocation granule, 320 dwords on gfx950), at least 1 (it then waits for a slot), at most the finish pass's
-    // own occupancy.  Registers and wave slots do not bind before that: 4 x 64 + 2 x 88 of 512 VGPRs per SIMD lane.
+    // SAPR_FINISH_GENERIC=1: the generic finish body for every plan (tests, A/B timing inside one build)
+    const char *fg = std::getenv("SAPR_FINISH_GENERIC");
+    const bool finish_generic = fg && std::atoi(fg) != 0;
+    pl->finish_kernel = &mfcc_wave_finish_kernel<0, false>;
+    pl->finish_occ = finish_occ(0, false);
+    if (!finish_generic && d.n_mels == 40) {
+      pl->finish_kernel = d.deltas ? &mfcc_wave_finish_kernel<10, true> : &mfcc_wave_finish_kernel<10, false>;
+      pl->finish_occ = finish_occ(10, d.deltas != 0);
+    }
+    // finish workgroups per CU of a launch beside a spectral grid: what fits into the LDS the resident spectral
+    // workgroups leave free (both rounded up to the allocation granule, 320 dwords on gfx950), at least 1, at most the
+    // finish pass's own occupancy.  LDS is not what places them: four spectral wavefronts per SIMD at 128 VGPRs are
+    // all 512 registers of a SIMD lane, so beside a full spectral grid no finish workgroup is resident — they run
+    // where spectral workgroups are not yet placed or have left.
     {
       int dev = 0, lds_cu = 0;
       if (hipGetDevice(&dev) != hipSuccess ||
@@ -1479,7 +1501,8 @@ extern "C" int sapr_mfcc_plan_create(double sr, int32_t n_fft, int32_t win_lengt
       const int spec = align_up(static_cast<int>(pl->wave_lds), kGranule) * pl->wave_blocks_per_cu;
       const int fin = align_up(static_cast<int>(wave_finish_lds(d.n_mels, d.deltas)), kGranule);
       const int fit = spec < lds_cu ? (lds_cu - spec) / fin : 0;
-      pl->finish_beside = fit < 1 ? 1 : (fit > SAPR_FINISH_OCC ? SAPR_FINISH_OCC : fit);
+      pl->finish_beside = fit < 1 ? 1 : (fit > pl->finish_occ ? pl->finish_occ : fit);
+      if (pl->finish_beside > kFinishBesideMax) pl->finish_beside = kFinishBesideMax;
     }
   }
   *plan_out = pl;
@@ -1587,7 +1610,8 @@ extern "C" int sapr_mfcc_batch(const void *plan, const float *pcm, const int64_t
     // (mfcc_wave.h)
     const int full_grid = cus * pl->wave_blocks_per_cu;
     const int64_t n_waves_full = static_cast<int64_t>(full_grid) * kWaves;
-    // second half: a wavefront per utterance again (16 resident wavefronts per CU keep ~48 log-mel tiles in flight)
+    // second half: a wavefront per utterance again, finish_occ workgroups per CU (the occupancy of the plan's body)
+    const int finish_grid = cus * pl->finish_occ;
     const size_t flds = wave_finish_lds(pl->dev.n_mels, pl->dev.deltas);
     const int64_t *fo_end = frame_offsets + n_utts;
     auto finish = [&](hipStream_t s, int64_t u0, int64_t n, int fgrid, int fill) -> hipError_t {
@@ -1598,7 +1622,7 @@ extern "C" int sapr_mfcc_batch(const void *plan, const float *pcm, const int64_t
         const int64_t need_blocks = (n * fsplit + kWaves - 1) / kWaves;
         if (need_blocks < fgrid) fgrid = static_cast<int>(need_blocks);
       }
-      SAPR_LAUNCH(mfcc_wave_finish_kernel, dim3(fgrid), dim3(kThreads), flds, s, lm, gmax + u0, frame_offsets + u0, n,
+      SAPR_LAUNCH(pl->finish_kernel, dim3(fgrid), dim3(kThreads), flds, s, lm, gmax + u0, frame_offsets + u0, n,
                   pl->dev, out, fsplit, total_frames, fo_end, fill);
       return hipGetLastError();
     };
@@ -1616,7 +1640,7 @@ extern "C" int sapr_mfcc_batch(const void *plan, const float *pcm, const int64_t
         // default: every slice keeps the finish pass at one wavefront per utterance (fsplit == 1, as in the single
         // launch of a batch this size) and gives each spectral wavefront at least kSliceMinSets sets per launch
         n_slices = kDefaultSlices;
-        const int64_t fwaves = static_cast<int64_t>(cus) * SAPR_FINISH_OCC * kWaves;
+        const int64_t fwaves = static_cast<int64_t>(finish_grid) * kWaves;
         while (n_slices > 1 && (n_utts / n_slices < fwaves || total_frames / n_slices < 4 * kSliceMinSets * n_waves_full))
           n_slices >>= 1;
       }
@@ -1663,7 +1687,7 @@ extern "C" int sapr_mfcc_batch(const void *plan, const float *pcm, const int64_t
           } else {
             // nothing runs beside the last slice's finish: the full grid, on the caller's stream; it is also the one
             // launch that marks the output when the frame-count guard fires
-            SAPR_HIP_TRY(finish(st, u0, n, cus * SAPR_FINISH_OCC, 1));
+            SAPR_HIP_TRY(finish(st, u0, n, finish_grid, 1));
           }
         }
         // the side stream is in order: its last finish done = all of them done.  Whatever the caller enqueues next
@@ -1682,7 +1706,7 @@ extern "C" int sapr_mfcc_batch(const void *plan, const float *pcm, const int64_t
     SAPR_HIP_TRY(hipMemsetAsync(gmax, 0, static_cast<size_t>(n_utts) * sizeof(unsigned), st));
     SAPR_HIP_TRY(wave_dispatch(*pl, nullptr, pcm, sample_offsets, frame_offsets, n_utts, wgrid, span, st, lm, gmax,
                                total_frames, fo_end));
-    SAPR_HIP_TRY(finish(st, 0, n_utts, cus * SAPR_FINISH_OCC, 1));
+    SAPR_HIP_TRY(finish(st, 0, n_utts, finish_grid, 1));
     return 0;
   } else if (pl->R == 16)
     SAPR_HIP_TRY((launch<16, true>(*pl, pcm, sample_offsets, frame_offsets, n_utts, out, grid, st, lm, gmax)));

@@ -158,14 +158,41 @@ __device__ __forceinline__ void wave_fence() {
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+#ifndef SAPR_FINISH_OCC
+#define SAPR_FINISH_OCC 3  // wavefronts per SIMD of the generic finish body (workgroups per CU of its grid)
+#endif
+#ifndef SAPR_FINISH_OCC_S
+#define SAPR_FINISH_OCC_S 5  // ... of a body specialised on its shape, without deltas
+#endif
+#ifndef SAPR_FINISH_OCC_SD
+#define SAPR_FINISH_OCC_SD 3  // ... of a body specialised on its shape, with deltas
+#endif
+#ifndef SAPR_FINISH_TILES
+#define SAPR_FINISH_TILES 3  // log-mel tiles a wavefront of a specialised body keeps in flight (the generic body: 3)
+#endif
+// NQT = n_mels / 4 of a specialised body, 0 = the generic body (n_mels and deltas read from the plan at run time)
+constexpr int finish_occ(int NQT, bool DELTAST) {
+  return NQT == 0 ? SAPR_FINISH_OCC : (DELTAST ? SAPR_FINISH_OCC_SD : SAPR_FINISH_OCC_S);
+}
+constexpr int finish_tiles(int NQT) { return NQT == 0 ? 3 : SAPR_FINISH_TILES; }
+
+// NQT > 0: n_mels = 4 NQT and DELTAST are constants of the body: a lane holds ceil(16 NQT / 64) float4 pieces of a tile
+// instead of 4, the DCT walks NQT K-steps instead of 16 (the others multiplied finite values by a zero fragment: the
+// sums are the same bits), and a body without deltas has no filter taps, no cepstra ring and one emit path.
+template <int NQT, bool DELTAST>
 __device__ __forceinline__ void wave_finish(const float *__restrict__ lm, int T, float floor_db, float *__restrict__ out,
                                             const MfccDev &P, float *s_tile, float *s_ceps, const float *s_dtab,
                                             int lane, int tile_lo, int tile_hi) {
+  constexpr bool GEN = NQT == 0;
+  constexpr int NP = GEN ? 4 : (16 * NQT + kWave - 1) / kWave;  // float4 pieces per lane and tile
+  constexpr int KS = GEN ? 16 : NQT;                             // K-steps of the DCT
+  constexpr int NT = finish_tiles(NQT);                          // tiles in flight
   const int q = lane >> 4, j16 = lane & 15;
-  const int NQ = P.n_mels >> 2, LS = P.n_mels + 4, per_tile = 16 * NQ;  // NQ <= 16: at most 4 float4 per lane and tile
+  const int n_mels = GEN ? P.n_mels : 4 * NQT;
+  const int NQ = n_mels >> 2, LS = n_mels + 4, per_tile = 16 * NQ;  // NQ <= 16: at most 4 float4 per lane and tile
   const float inv_nm = 1.0f / static_cast<float>(P.n_mfcc);
   const int n_tiles = (T + 15) >> 4;
-  const bool deltas = P.deltas != 0;
+  const bool deltas = GEN ? P.deltas != 0 : DELTAST;
   float dc1[9], dc2[9];  // the centred Savitzky-Golay filters (row 0 of either table)
 #pragma unroll
   for (int k = 0; k < 9; ++k) {
@@ -175,35 +202,35 @@ __device__ __forceinline__ void wave_finish(const float *__restrict__ lm, int T,
   // this wavefront emits tiles [tile_lo, tile_hi); with deltas it also needs the cepstra of one tile either side
   const int first = deltas && tile_lo > 0 ? tile_lo - 1 : tile_lo;
   const int last = deltas && tile_hi < n_tiles ? tile_hi + 1 : tile_hi;  // one past the last tile transformed
-  // DCT rows as MFMA A fragments, 16 K-steps (zero beyond n_mels)
-  float afr[16];
+  // DCT rows as MFMA A fragments, one per K-step (the generic body: 16, zero beyond n_mels)
+  float afr[KS];
 #pragma unroll
-  for (int ks = 0; ks < 16; ++ks) afr[ks] = P.dct_frag[ks * kWave + lane];
+  for (int ks = 0; ks < KS; ++ks) afr[ks] = P.dct_frag[ks * kWave + lane];
   // (row, column quad) of this lane's float4 pieces of a tile
-  int prow_[4], pcg_[4];
+  int prow_[NP], pcg_[NP];
   {
     const float inv_nq = 1.0f / static_cast<float>(NQ);
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
+    for (int c = 0; c < NP; ++c) {
       const int idx = lane + kWave * c;
-      prow_[c] = static_cast<int>((static_cast<float>(idx) + 0.5f) * inv_nq);
+      prow_[c] = GEN ? static_cast<int>((static_cast<float>(idx) + 0.5f) * inv_nq) : idx / NQ;
       pcg_[c] = idx - prow_[c] * NQ;
     }
   }
-  auto fetch = [&](int nt, float4 (&v)[4]) {  // rows past the utterance repeat its last row: never stored
+  auto fetch = [&](int nt, float4 (&v)[NP]) {  // rows past the utterance repeat its last row: never stored
 #pragma unroll
-    for (int c = 0; c < 4; ++c)
+    for (int c = 0; c < NP; ++c)
       if (lane + kWave * c < per_tile) {
         const int t = 16 * nt + prow_[c] < T ? 16 * nt + prow_[c] : T - 1;
-        v[c] = reinterpret_cast<const float4 *>(lm + static_cast<int64_t>(t) * P.n_mels)[pcg_[c]];
+        v[c] = reinterpret_cast<const float4 *>(lm + static_cast<int64_t>(t) * n_mels)[pcg_[c]];
       }
   };
   // The rows were written ~26 sets ago and have left the L2 (the PCM stream runs through it): each fetch is an
-  // Infinity Cache / HBM round trip, so three tiles are kept in flight.
-  auto tile = [&](int nt, float4 (&cur)[4]) {
+  // Infinity Cache / HBM round trip, so NT tiles are kept in flight.
+  auto tile = [&](int nt, float4 (&cur)[NP]) {
     if (nt < last) {
 #pragma unroll
-      for (int c = 0; c < 4; ++c)
+      for (int c = 0; c < NP; ++c)
         if (lane + kWave * c < per_tile) {
           float4 v = cur[c];
           v.x = fmaxf(v.x, floor_db);
@@ -212,18 +239,20 @@ __device__ __forceinline__ void wave_finish(const float *__restrict__ lm, int T,
           v.w = fmaxf(v.w, floor_db);
           *reinterpret_cast<float4 *>(s_tile + prow_[c] * LS + 4 * pcg_[c]) = v;
         }
-      if (nt + 3 < last) fetch(nt + 3, cur);
+      if (nt + NT < last) fetch(nt + NT, cur);
       wave_fence();
-      // K-steps past n_mels read the next rows' values times a zero fragment
+      // generic body: K-steps past n_mels read the next rows' values times a zero fragment
       f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
       const float *lrow = s_tile + j16 * LS + q;
-      float bv[16];
+      float bv[KS];
 #pragma unroll
-      for (int ks = 0; ks < 16; ++ks) bv[ks] = lrow[4 * ks];
+      for (int ks = 0; ks < KS; ++ks) bv[ks] = lrow[4 * ks];
 #pragma unroll
-      for (int ks = 0; ks < 16; ks += 2) {
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(afr[ks], bv[ks], acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(afr[ks + 1], bv[ks + 1], acc1, 0, 0, 0);
+      for (int ks = 0; ks < KS; ++ks) {  // even K-steps into acc0, odd ones into acc1
+        if (ks & 1)
+          acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(afr[ks], bv[ks], acc1, 0, 0, 0);
+        else
+          acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(afr[ks], bv[ks], acc0, 0, 0, 0);
       }
       *reinterpret_cast<f32x4 *>(s_ceps + (deltas ? (nt % 3) * 256 : 0) + j16 * 16 + 4 * q) = acc0 + acc1;
       wave_fence();
@@ -276,24 +305,25 @@ __device__ __forceinline__ void wave_finish(const float *__restrict__ lm, int T,
       wave_fence();
     }
   };
-  float4 t0[4], t1[4], t2[4];
-  if (first < last) fetch(first, t0);
-  if (first + 1 < last) fetch(first + 1, t1);
-  if (first + 2 < last) fetch(first + 2, t2);
+  float4 ring[NT][NP];
+#pragma unroll
+  for (int i = 0; i < NT; ++i)
+    if (first + i < last) fetch(first + i, ring[i]);
   const int end = last + (deltas ? 1 : 0);  // the last emission trails the last transform by one tile
-  for (int base = first; base < end; base += 3) {
-    tile(base, t0);
-    if (base + 1 < end) tile(base + 1, t1);
-    if (base + 2 < end) tile(base + 2, t2);
+  for (int base = first; base < end; base += NT) {
+#pragma unroll
+    for (int i = 0; i < NT; ++i)
+      if (i == 0 || base + i < end) tile(base + i, ring[i]);
   }
 }
 
-#ifndef SAPR_FINISH_OCC
-#define SAPR_FINISH_OCC 3  // wavefronts per SIMD of the finish pass (workgroups per CU of its grid)
-#endif
 // The finish pass as its own launch: a wavefront per utterance (long utterances: `split` wavefronts take contiguous
 // runs of its tiles), wave-private LDS, no workgroup barrier after the table load.  gmax_enc holds the utterance
 // maxima the spectral kernel found.
+//
+// Instantiations: <10, false> and <10, true> are the 40-mel presets without and with deltas; <0, false> serves every
+// other plan (and every plan under SAPR_FINISH_GENERIC=1).  The launch bounds are finish_occ() wavefronts per SIMD:
+// the host sizes its grids by the same function.
 //
 // Slices: a launch serves the `n_utts` utterances whose offsets start at `frame_offsets` and whose maxima start at
 // `gmax_enc` — the whole batch, or a range [u0, u1) of it (the caller passes frame_offsets + u0, gmax + u0).  The offsets
@@ -301,25 +331,26 @@ __device__ __forceinline__ void wave_finish(const float *__restrict__ lm, int T,
 // last offset (the frame-count guard is about the whole batch); of the launches of one batch exactly one has
 // `fill_on_mismatch` set and writes the NaN marker.
 //
-// A tile's result does NOT depend on `split`, on the grid or on the slice it is launched with: its 16 cepstra rows
-// come from its own 16 log-mel rows (rows past the utterance repeat the last one and are never stored), the clip
-// floor is the utterance's, and with deltas the wavefront that emits tile e transforms tiles e - 1 and e + 1 itself
-// — the same values whichever wavefront, in whatever launch, holds them.  The K-steps past n_mels multiply finite LDS
-// contents (zeroed below, later clipped log-mel values and cepstra) by a zero fragment.
-__global__ __launch_bounds__(kThreads, SAPR_FINISH_OCC) void mfcc_wave_finish_kernel(const float *__restrict__ lm,
-                                                                       const unsigned *__restrict__ gmax_enc,
-                                                                       const int64_t *__restrict__ frame_offsets,
-                                                                       int64_t n_utts, MfccDev P, float *__restrict__ out,
-                                                                       int split, int64_t total_cap,
-                                                                       const int64_t *__restrict__ batch_end,
-                                                                       int fill_on_mismatch) {
+// A tile's result does NOT depend on `split`, on the grid, on the slice it is launched with or on the instantiation:
+// its 16 cepstra rows come from its own 16 log-mel rows (rows past the utterance repeat the last one and are never
+// stored), the clip floor is the utterance's, and with deltas the wavefront that emits tile e transforms tiles e - 1
+// and e + 1 itself — the same values whichever wavefront, in whatever launch, holds them.  In the generic body the
+// K-steps past n_mels multiply finite LDS contents (zeroed below, later clipped log-mel values and cepstra) by a zero
+// fragment (tests/test_mfcc_finish_shapes_gpu.py: specialised against generic, torch.equal).
+template <int NQT, bool DELTAST>
+__global__ __launch_bounds__(kThreads, finish_occ(NQT, DELTAST)) void mfcc_wave_finish_kernel(
+    const float *__restrict__ lm, const unsigned *__restrict__ gmax_enc, const int64_t *__restrict__ frame_offsets,
+    int64_t n_utts, MfccDev P, float *__restrict__ out, int split, int64_t total_cap,
+    const int64_t *__restrict__ batch_end, int fill_on_mismatch) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float *s_dtab = reinterpret_cast<float *>(smem);
-  const int per_wave = 16 * (P.n_mels + 4) + (P.deltas ? 3 : 1) * 256;
+  const int n_mels = NQT == 0 ? P.n_mels : 4 * NQT;
+  const bool deltas = NQT == 0 ? P.deltas != 0 : DELTAST;
+  const int per_wave = 16 * (n_mels + 4) + (deltas ? 3 : 1) * 256;
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid / kWave), lane = tid % kWave;
   for (int i = tid; i < 2 * 81; i += kThreads) s_dtab[i] = P.delta_tab[i];
-  // DCT K-steps past n_mels read whatever follows a row (times a zero fragment): it has to be finite
+  // generic body: DCT K-steps past n_mels read whatever follows a row (times a zero fragment): it has to be finite
   for (int i = tid; i < kWaves * per_wave; i += kThreads) s_dtab[168 + i] = 0.f;
   __syncthreads();
   float *s_tile = s_dtab + 168 + wave * per_wave;
@@ -343,8 +374,8 @@ __global__ __launch_bounds__(kThreads, SAPR_FINISH_OCC) void mfcc_wave_finish_ke
     const int n_tiles = (T + 15) >> 4, per = (n_tiles + split - 1) / split;
     const int lo = part * per, hi = lo + per < n_tiles ? lo + per : n_tiles;
     if (lo >= hi) continue;
-    wave_finish(lm + f_beg * P.n_mels, T, dec_ordered(gmax_enc[u]) - P.top_db, out + f_beg * P.d_out, P, s_tile,
-                s_tile + 16 * (P.n_mels + 4), s_dtab, lane, lo, hi);
+    wave_finish<NQT, DELTAST>(lm + f_beg * n_mels, T, dec_ordered(gmax_enc[u]) - P.top_db, out + f_beg * P.d_out, P,
+                              s_tile, s_tile + 16 * (n_mels + 4), s_dtab, lane, lo, hi);
   }
 }
 inline size_t wave_finish_lds(int n_mels, int deltas) {
