@@ -1,4 +1,5 @@
-// Quick-form log-densities of the Baum-Welch E-step (estep.hip only: fb_emit_kernel, fb_forward_kernel<..., QEMIT>).
+// Quick-form log-densities of the Baum-Welch E-step (estep.hip: fb_emit_kernel, fb_forward_kernel) and of
+// quick_forward_walk (diag_forward.h: sp_forward_kernel, forward_vocab_kernel).
 // Split from emission.h so that an edit here rebuilds one translation unit, not the thirteen that include emission.h.
 #pragma once
 

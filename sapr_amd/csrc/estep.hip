@@ -3,9 +3,11 @@
 // Replaces, for a whole batch of utterances at once, what hmmlearn does per sequence inside
 // GaussianHMM.fit / .score as the reference calls them (hmmlearn_hmm.py:103-104):
 //   _compute_log_likelihood (stats.py)           -> frame_log_densities (emission.h)
-//   _hmmc.cpp forward_log / backward_log         -> fb_forward_kernel / fb_backward_kernel
-//   _compute_posteriors_log, compute_log_xi_sum  -> fb_backward_kernel
-//   _accumulate_sufficient_statistics (hmm.py)   -> fb_backward_kernel + fb_obs_kernel
+//   _hmmc.cpp forward_log                        -> forward_step (diag_forward.h) inside fb_score_kernel (.score),
+//                                                   fb_forward_kernel / fb_forward_dense_kernel (the E-step)
+//   _hmmc.cpp backward_log, _compute_posteriors_log, compute_log_xi_sum
+//                                                -> fb_smooth_obs_kernel (bidiagonal) / fb_backward_dense_kernel
+//   _accumulate_sufficient_statistics (hmm.py)   -> fb_smooth_obs_kernel / fb_backward_dense_kernel + fb_obs_kernel
 // followed by a fixed-order (deterministic, atomics-free) reduction over the utterances of each
 // word model.  CPU restatement: oracle/hmmlearn_oracle.py (accumulate / forward_log / ...).
 //
@@ -23,6 +25,7 @@ namespace sapr {
 namespace {
 
 #include "lse_ops.h"  // lse2, lse2_share, logaddexp, lse_all (on lse_unit.h)
+#include "diag_forward.h"  // Lane, DiagModel, forward_step, quick_forward_walk, dispatch_ds
 
 using namespace emission;
 
@@ -104,157 +107,30 @@ __global__ __launch_bounds__(kBlock) void fb_emit_kernel(
   }
 }
 
-// PREB: the log-densities are already in lat_b (fb_emit_kernel); otherwise they are evaluated here, in numpy's
-// operation order (GaussianHMM.score: sapr_forward_diag), and stored when lat_b is given
-// QEMIT (bidiagonal E-step): the log-densities are evaluated here, four frames per walk over the SGPR-resident
-// parameters, from the slot-major feature copy and in fb_emit_kernel's quick form (same operations: the same values) —
-// no log-density lattice: 0.8 GB written by the emission grid and read back here per 100 000 utterances fall away
-template <int D, int S, bool BIDIAG, bool FASTDIV, bool PREB, bool QEMIT = false>
-__global__ __launch_bounds__(kBlock) void fb_forward_kernel(
-    const float *__restrict__ feats, const int64_t *__restrict__ offsets,
-    const int32_t *__restrict__ slot_utt, const int32_t *__restrict__ tile_model, int64_t n_slots,
-    const double4 *__restrict__ prm_all, const double *__restrict__ gconst,
-    const double *__restrict__ log_start, const double *__restrict__ log_trans,
-    double *__restrict__ lat_b, double *__restrict__ lat_f, double *__restrict__ loglik,
-    const float *__restrict__ feat_t = nullptr) {
+// -------------------------------------------------------------------------------------------
+// The forward pass, three kernels on diag_forward.h.  No frames: loglik = 0.0 (an empty sum, as the E-step adds it up).
+// -------------------------------------------------------------------------------------------
+// GaussianHMM.score (sapr_forward_diag): the log-densities in numpy's operation order, nothing kept but loglik
+template <int D, int S, bool BIDIAG, bool FASTDIV>
+__global__ __launch_bounds__(kBlock) void fb_score_kernel(
+    const float *__restrict__ feats, const int64_t *__restrict__ offsets, const int32_t *__restrict__ slot_utt,
+    const int32_t *__restrict__ tile_model, const double4 *__restrict__ prm_all, const double *__restrict__ gconst,
+    const double *__restrict__ log_start, const double *__restrict__ log_trans, double *__restrict__ loglik) {
   const int64_t tile = blockIdx.x;
-  const int w = tile_model[tile];
-  const int64_t slot = tile * kBlock + threadIdx.x;
-  const int64_t u = slot_utt[slot];
-  const bool live = u >= 0;
-  const int64_t beg = live ? offsets[u] : 0;
-  const int T = live ? static_cast<int>(offsets[u + 1] - beg) : 0;
-  const int Tw = wave_max_i32(T);
-
-  const double4 *__restrict__ prm = prm_all + static_cast<int64_t>(w) * S * D;
-  const double *__restrict__ gc = gconst + static_cast<int64_t>(w) * S;
-  const double *__restrict__ ls = log_start + static_cast<int64_t>(w) * S;
-  const double *__restrict__ lt = log_trans + static_cast<int64_t>(w) * S * S;
-  const float *__restrict__ xp = feats + beg * D;
+  const Lane ln = lane_of(offsets, slot_utt[tile * kBlock + threadIdx.x]);
+  const DiagModel m = diag_model<D, S>(prm_all, gconst, log_start, log_trans, tile_model[tile]);
+  const int T = ln.T;
+  const float *__restrict__ xp = feats + ln.beg * D;
 
   double fwd[S];
 #pragma unroll
-  for (int s = 0; s < S; ++s) fwd[s] = ls[s];
-
-  // one frame of the recursion from its log-densities
-  auto step = [&](int t, const double (&b)[S]) {
-    if (t == 0) {
-#pragma unroll
-      for (int j = 0; j < S; ++j) fwd[j] += b[j];
-    } else if constexpr (BIDIAG) {
-      if (lat_f) {  // E-step: keep the share of each state's mass that STAYED (the rest came from j - 1)
-        const int64_t row = static_cast<int64_t>(t) * S;
-#pragma unroll
-        for (int j = S - 1; j >= 1; --j) {
-          double stay;
-          fwd[j] = lse2_share(fwd[j - 1] + lt[(j - 1) * S + j], fwd[j] + lt[j * S + j], stay) + b[j];
-          lat_f[(row + j) * n_slots + slot] = stay;
-        }  // (state 0 has no predecessor: its share is the constant 1 and is not stored)
-      } else {
-#pragma unroll
-        for (int j = S - 1; j >= 1; --j)
-          fwd[j] = lse2(fwd[j - 1] + lt[(j - 1) * S + j], fwd[j] + lt[j * S + j]) + b[j];
-      }
-      fwd[0] = (fwd[0] + lt[0]) + b[0];
-    } else {
-      double prev[S], work[S];
-#pragma unroll
-      for (int s = 0; s < S; ++s) prev[s] = fwd[s];
-#pragma unroll
-      for (int j = 0; j < S; ++j) {
-#pragma unroll
-        for (int i = 0; i < S; ++i) work[i] = prev[i] + lt[i * S + j];
-        fwd[j] = lse_all<S>(work) + b[j];
-      }
-    }
-    if constexpr (!BIDIAG) {
-      if (lat_f) {
-        const int64_t row = static_cast<int64_t>(t) * S;
-#pragma unroll
-        for (int j = 0; j < S; ++j) {
-          if constexpr (!PREB) lat_b[(row + j) * n_slots + slot] = b[j];
-          lat_f[(row + j) * n_slots + slot] = fwd[j];
-        }
-      }
-    }
-  };
-  // bidiagonal E-step: the last forward row (the posteriors of the last frame start from it) goes where that frame's
-  // log-densities were — nothing reads them after the forward pass
-  auto finish = [&]() {
-    if constexpr (BIDIAG) {
-      if (lat_f && T > 0) {
-        const int64_t row = static_cast<int64_t>(T - 1) * S;
-#pragma unroll
-        for (int j = 0; j < S; ++j) lat_b[(row + j) * n_slots + slot] = fwd[j];
-      }
-    }
-  };
-
-  if constexpr (QEMIT) {
-    static_assert(BIDIAG && !PREB, "the fused form of the bidiagonal E-step");
-    using XT = std::conditional_t<(D >= 39), float, double>;
-#ifndef SAPR_FWD_NF
-#define SAPR_FWD_NF ((D >= 39 || S > 10) ? 2 : 4)
-#endif
-    constexpr int NF = SAPR_FWD_NF;  // (256 registers: two wavefronts per SIMD)
-    for (int t0 = 0; t0 < Tw; t0 += NF) {
-      if (t0 < T) {
-        XT xq[NF][D];
-#pragma unroll
-        for (int f = 0; f < NF; ++f) {
-          const int t = t0 + f < T ? t0 + f : T - 1;  // frames past the end: evaluated, not used
-          const float *row = feat_t + (static_cast<int64_t>(t) * D) * n_slots + slot;
-#pragma unroll
-          for (int d = 0; d < D; ++d) xq[f][d] = static_cast<XT>(row[static_cast<int64_t>(d) * n_slots]);
-        }
-        double bq[NF][S];
-        frame_log_densities_quick<D, S, NF>(xq, prm, gc, [&](auto jc, int f, double bv) {
-          bq[f][decltype(jc)::value] = bv;
-        });
-#pragma unroll
-        for (int f = 0; f < NF; ++f)
-          if (t0 + f < T) step(t0 + f, bq[f]);
-      }
-    }
-    finish();
-    if (live) loglik[u] = T > 0 ? lse_all<S>(fwd) : 0.0;
-    return;
-  }
-
-  if constexpr (PREB) {
-    double b[S], nb[S];
-    if (T > 0) {
-#pragma unroll
-      for (int j = 0; j < S; ++j) b[j] = lat_b[static_cast<int64_t>(j) * n_slots + slot];
-    }
-    for (int t = 0; t < Tw; ++t) {
-      if (t < T) {
-        if (t + 1 < T) {  // next frame's row: in flight behind this frame's exp / log work
-          const int64_t row = static_cast<int64_t>(t + 1) * S;
-#pragma unroll
-          for (int j = 0; j < S; ++j) nb[j] = lat_b[(row + j) * n_slots + slot];
-        }
-        step(t, b);
-#pragma unroll
-        for (int j = 0; j < S; ++j) b[j] = nb[j];
-      }
-    }
-    finish();
-    if (live) loglik[u] = T > 0 ? lse_all<S>(fwd) : 0.0;
-    return;
-  }
+  for (int s = 0; s < S; ++s) fwd[s] = m.ls[s];
 
   if constexpr (FASTDIV) {
     // two frames per walk over the parameters (emission.h EmitLoop2): a training batch gives every utterance ONE
     // word model, so this grid holds ~1.5 wavefronts per SIMD and the scalar loads' latency would show
-    using XT = std::conditional_t<(D >= 39), float, double>;
+    using XT = quick_x_t<D>;
     XT xa[D], xb[D];
-    auto load2 = [&](const float *p, XT (&dst)[D]) {
-      if constexpr (D >= 39)
-        load_frame_f32<D>(p, dst);
-      else
-        load_frame<D>(p, dst);
-    };
     // An infinite feature makes a = (x - mean)^2 infinite, and the correction steps of the FMA division
     // (emission.h quad_term) then form inf - inf = NaN where IEEE division — numpy, the exact-division build — gives
     // inf and a log-density of -inf.  a is the same under every state, so a frame's log-densities turn NaN together:
@@ -270,32 +146,125 @@ __global__ __launch_bounds__(kBlock) void fb_forward_kernel(
         }
       }
     };
-    for (int t = 0; t < Tw; t += 2) {
+    for (int t = 0; t < ln.Tw; t += 2) {
       if (t < T) {
         const bool two = (t + 1) < T;
-        load2(xp + static_cast<int64_t>(t) * D, xa);
-        load2(xp + static_cast<int64_t>(two ? t + 1 : t) * D, xb);
+        load_quick_frame<D>(xp + static_cast<int64_t>(t) * D, xa);
+        load_quick_frame<D>(xp + static_cast<int64_t>(two ? t + 1 : t) * D, xb);
         double ba[S], bb[S];
-        frame_log_densities2<D, S, false>(xa, xb, prm, gc, ba, bb);
+        frame_log_densities2<D, S, false>(xa, xb, m.prm, m.gc, ba, bb);
         repair(xa, ba);
         repair(xb, bb);
-        step(t, ba);
-        if (two) step(t + 1, bb);
+        forward_step<S, BIDIAG>(t, ba, m.lt, fwd);
+        if (two) forward_step<S, BIDIAG>(t + 1, bb, m.lt, fwd);
       }
     }
   } else {
     double x[D];
-    for (int t = 0; t < Tw; ++t) {
+    for (int t = 0; t < ln.Tw; ++t) {
       if (t < T) {
         load_frame<D>(xp + static_cast<int64_t>(t) * D, x);
         double b[S];
-        frame_log_densities<D, S, false, false>(x, prm, gc, b);
-        step(t, b);
+        frame_log_densities<D, S, false, false>(x, m.prm, m.gc, b);
+        forward_step<S, BIDIAG>(t, b, m.lt, fwd);
       }
     }
   }
-  finish();
-  if (live) loglik[u] = T > 0 ? lse_all<S>(fwd) : 0.0;
+  if (ln.live) loglik[ln.u] = T > 0 ? lse_all<S>(fwd) : 0.0;
+}
+
+// The bidiagonal E-step — the form bench.py's label fb_forward_kernel<13,10,QEMIT> names: QEMIT was the template flag
+// of the quick emission, which is now the only form of this kernel.  The log-densities are evaluated here, NF frames
+// per walk over the SGPR-resident parameters, from the slot-major feature copy and in fb_emit_kernel's quick form —
+// no log-density lattice: 0.8 GB written by the emission grid and read back here per 100 000 utterances fall away.
+// Kept for the smoothing pass: the stay shares in lat_f and, in lat_b where the last frame's log-densities would have
+// been, the last forward row (the posteriors of the last frame start from it).
+// The NF-frame loop is spelled out here and not taken from quick_forward_walk: with the loop arriving through a
+// function this kernel compiled to two more VGPRs and 30 more SGPR spills at (13, 10) and the E-step was 3 % slower.
+template <int D, int S>
+__global__ __launch_bounds__(kBlock) void fb_forward_kernel(
+    const float *__restrict__ feat_t, const int64_t *__restrict__ offsets, const int32_t *__restrict__ slot_utt,
+    const int32_t *__restrict__ tile_model, int64_t n_slots, const double4 *__restrict__ prm_all,
+    const double *__restrict__ gconst, const double *__restrict__ log_start, const double *__restrict__ log_trans,
+    double *__restrict__ lat_b, double *__restrict__ lat_f, double *__restrict__ loglik) {
+  const int64_t tile = blockIdx.x;
+  const int64_t slot = tile * kBlock + threadIdx.x;
+  const Lane ln = lane_of(offsets, slot_utt[slot]);
+  const DiagModel m = diag_model<D, S>(prm_all, gconst, log_start, log_trans, tile_model[tile]);
+  const int T = ln.T;
+  double fwd[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) fwd[s] = m.ls[s];
+  auto step = [&](int t, const double (&b)[S]) {
+    forward_step<S, true>(t, b, m.lt, fwd, [&](int tt, int j, double stay) {
+      lat_f[(static_cast<int64_t>(tt) * S + j) * n_slots + slot] = stay;
+    });
+  };
+  using XT = quick_x_t<D>;
+  constexpr int NF = quick_frames<D, S>();
+  for (int t0 = 0; t0 < ln.Tw; t0 += NF) {
+    if (t0 < T) {
+      XT xq[NF][D];
+#pragma unroll
+      for (int f = 0; f < NF; ++f) {
+        const int t = t0 + f < T ? t0 + f : T - 1;  // frames past the end: evaluated, not used
+        const float *row = feat_t + (static_cast<int64_t>(t) * D) * n_slots + slot;
+#pragma unroll
+        for (int d = 0; d < D; ++d) xq[f][d] = static_cast<XT>(row[static_cast<int64_t>(d) * n_slots]);
+      }
+      double bq[NF][S];
+      frame_log_densities_quick<D, S, NF>(xq, m.prm, m.gc, [&](auto jc, int f, double bv) {
+        bq[f][decltype(jc)::value] = bv;
+      });
+#pragma unroll
+      for (int f = 0; f < NF; ++f)
+        if (t0 + f < T) step(t0 + f, bq[f]);
+    }
+  }
+  if (ln.T > 0) {
+    const int64_t row = static_cast<int64_t>(ln.T - 1) * S;
+#pragma unroll
+    for (int j = 0; j < S; ++j) lat_b[(row + j) * n_slots + slot] = fwd[j];
+  }
+  if (ln.live) loglik[ln.u] = ln.T > 0 ? lse_all<S>(fwd) : 0.0;
+}
+
+// The dense E-step: the recursion over the log-densities fb_emit_kernel stored in lat_b, forward rows into lat_f
+template <int S>
+__global__ __launch_bounds__(kBlock) void fb_forward_dense_kernel(
+    const int64_t *__restrict__ offsets, const int32_t *__restrict__ slot_utt, const int32_t *__restrict__ tile_model,
+    int64_t n_slots, const double *__restrict__ log_start, const double *__restrict__ log_trans,
+    const double *__restrict__ lat_b, double *__restrict__ lat_f, double *__restrict__ loglik) {
+  const int64_t tile = blockIdx.x;
+  const int64_t slot = tile * kBlock + threadIdx.x;
+  const Lane ln = lane_of(offsets, slot_utt[slot]);
+  const DiagModel m = diag_model<S>(log_start, log_trans, tile_model[tile]);
+  const int T = ln.T;
+
+  double fwd[S], b[S], nb[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) fwd[s] = m.ls[s];
+  if (T > 0) {
+#pragma unroll
+    for (int j = 0; j < S; ++j) b[j] = lat_b[static_cast<int64_t>(j) * n_slots + slot];
+  }
+  for (int t = 0; t < ln.Tw; ++t) {
+    if (t < T) {
+      if (t + 1 < T) {  // next frame's row: in flight behind this frame's exp / log work
+        const int64_t row = static_cast<int64_t>(t + 1) * S;
+#pragma unroll
+        for (int j = 0; j < S; ++j) nb[j] = lat_b[(row + j) * n_slots + slot];
+      }
+      forward_step<S, false>(t, b, m.lt, fwd);
+      const int64_t row = static_cast<int64_t>(t) * S;
+#pragma unroll
+      for (int j = 0; j < S; ++j) {
+        lat_f[(row + j) * n_slots + slot] = fwd[j];
+        b[j] = nb[j];
+      }
+    }
+  }
+  if (ln.live) loglik[ln.u] = T > 0 ? lse_all<S>(fwd) : 0.0;
 }
 
 // -------------------------------------------------------------------------------------------
@@ -593,27 +562,16 @@ __global__ __launch_bounds__(kBlock) void fb_backward_dense_kernel(
 #pragma unroll
   for (int s = 0; s < S; ++s) fw[s] = lat_f[(static_cast<int64_t>(T - 1) * S + s) * n_slots + slot];
   for (int t = T - 1; t >= 0; --t) {
-    // posteriors of frame t (base.py _compute_posteriors_log: row soft-max of fwd + bwd).  exp(lg - logsumexp(lg))
-    // is evaluated as exp(lg - max) / sum: the S exponentials of the logsumexp are the numerators
-    double lg[S];
+    // posteriors of frame t (base.py _compute_posteriors_log: row soft-max of fwd + bwd)
+    double lg[S], g[S];
 #pragma unroll
     for (int s = 0; s < S; ++s) lg[s] = fw[s] + bwd[s];
-    double mx = lg[0];
-#pragma unroll
-    for (int s = 1; s < S; ++s) mx = lg[s] > mx ? lg[s] : mx;
-    double den = 0.0;
+    softmax_row<S>(lg, g);
 #pragma unroll
     for (int s = 0; s < S; ++s) {
-      lg[s] = exp_unit(lg[s] - mx);  // all -inf: NaN, as exp(lg - (-inf)) is in the reference
-      den += lg[s];
-    }
-    const double inv = 1.0 / den;
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-      const double g = lg[s] * inv;
-      post[s] += g;
-      lat_f[(static_cast<int64_t>(t) * S + s) * n_slots + slot] = g;  // gamma replaces fwd in place
-      if (t == 0) out[2 + s] = g;                                      // stats['start'] += posteriors[0]
+      post[s] += g[s];
+      lat_f[(static_cast<int64_t>(t) * S + s) * n_slots + slot] = g[s];  // gamma replaces fwd in place
+      if (t == 0) out[2 + s] = g[s];                                      // stats['start'] += posteriors[0]
     }
     if (t == 0) break;
     // step to t-1: needs b[t][.] and fwd[t-1][.]
@@ -623,17 +581,16 @@ __global__ __launch_bounds__(kBlock) void fb_backward_dense_kernel(
       bt[s] = lat_b[(static_cast<int64_t>(t) * S + s) * n_slots + slot];
       fw[s] = lat_f[(static_cast<int64_t>(t - 1) * S + s) * n_slots + slot];
     }
-    double nb[S], work[S];
 #pragma unroll
     for (int i = 0; i < S; ++i) {
 #pragma unroll
       for (int j = 0; j < S; ++j) {
-        work[j] = lt[i * S + j] + bt[j] + bwd[j];
         const double lx = fw[i] + lt[i * S + j] + bt[j] + bwd[j] - logprob;
         out[2 + S + i * S + j] = logaddexp(out[2 + S + i * S + j], lx);
       }
-      nb[i] = lse_all<S>(work);
     }
+    double nb[S];
+    dense_backward_row<S>(lt, bt, bwd, nb);
 #pragma unroll
     for (int i = 0; i < S; ++i) bwd[i] = nb[i];
   }
@@ -807,45 +764,11 @@ struct FbArgs {
 };
 
 template <int D, int S>
-int launch_forward(const FbArgs &a, int topology, int fast, int max_T) {
+int launch_score(const FbArgs &a, int topology, int fast) {
   dim3 grid(static_cast<unsigned>(a.n_tiles)), block(kBlock);
-  if (a.lat_b) {  // E-step: emission at full occupancy first, then the recursion over the stored rows
-    constexpr int NF = D >= 39 ? 2 : 4;
-    const int n_fc = ((max_T > 0 ? max_T : 1) + kEmitFrames - 1) / kEmitFrames;
-    const int64_t blocks = a.n_tiles * n_fc;
-    if (blocks > 0x7fffffffLL) return fail(SAPR_ERR_ARG, "grid too large (%lld blocks)", (long long)blocks);
-    if (!a.staged)
-      SAPR_LAUNCH((fb_stage_kernel<D>), dim3(static_cast<unsigned>(blocks)), block, 0, a.stream, a.feats, a.offsets,
-                  a.slot_utt, a.n_slots, n_fc, a.feat_t);
-    static const bool fused = [] {  // SAPR_ESTEP_EMIT=grid: the emission grid + the forward pass over its lattice
-      const char *e = getenv("SAPR_ESTEP_EMIT");
-      return !(e && e[0] == 'g');
-    }();
-    if (topology == SAPR_TOPO_BIDIAG && fused && a.lat_f) {
-      SAPR_LAUNCH((fb_forward_kernel<D, S, true, false, false, true>), grid, block, 0, a.stream, a.feats, a.offsets,
-                  a.slot_utt, a.tile_model, a.n_slots, a.pv.prm, a.pv.gconst, a.pv.log_start, a.pv.log_trans, a.lat_b,
-                  a.lat_f, a.loglik, a.feat_t);
-      SAPR_HIP_TRY(hipGetLastError());
-      return 0;
-    }
-    SAPR_LAUNCH((fb_emit_kernel<D, S, NF>), dim3(static_cast<unsigned>(blocks)), block, 0, a.stream, a.feat_t,
-                a.offsets, a.slot_utt, a.tile_model, a.n_slots, n_fc, a.pv.prm, a.pv.gconst, a.lat_b);
-    SAPR_HIP_TRY(hipGetLastError());
-    if (topology == SAPR_TOPO_BIDIAG)
-      SAPR_LAUNCH((fb_forward_kernel<D, S, true, false, true>), grid, block, 0, a.stream, a.feats, a.offsets,
-                  a.slot_utt, a.tile_model, a.n_slots, a.pv.prm, a.pv.gconst, a.pv.log_start, a.pv.log_trans, a.lat_b,
-                  a.lat_f, a.loglik);
-    else
-      SAPR_LAUNCH((fb_forward_kernel<D, S, false, false, true>), grid, block, 0, a.stream, a.feats, a.offsets,
-                  a.slot_utt, a.tile_model, a.n_slots, a.pv.prm, a.pv.gconst, a.pv.log_start, a.pv.log_trans, a.lat_b,
-                  a.lat_f, a.loglik);
-    SAPR_HIP_TRY(hipGetLastError());
-    return 0;
-  }
-#define SAPR_FWD(BD, FD)                                                                               \
-  SAPR_LAUNCH((fb_forward_kernel<D, S, BD, FD, false>), grid, block, 0, a.stream, a.feats, a.offsets, \
-                     a.slot_utt, a.tile_model, a.n_slots, a.pv.prm, a.pv.gconst, a.pv.log_start,     \
-                     a.pv.log_trans, a.lat_b, a.lat_f, a.loglik)
+#define SAPR_FWD(BD, FD)                                                                                          \
+  SAPR_LAUNCH((fb_score_kernel<D, S, BD, FD>), grid, block, 0, a.stream, a.feats, a.offsets, a.slot_utt,         \
+              a.tile_model, a.pv.prm, a.pv.gconst, a.pv.log_start, a.pv.log_trans, a.loglik)
   if (topology == SAPR_TOPO_BIDIAG) {
     if (fast)
       SAPR_FWD(true, true);
@@ -858,6 +781,32 @@ int launch_forward(const FbArgs &a, int topology, int fast, int max_T) {
       SAPR_FWD(false, false);
   }
 #undef SAPR_FWD
+  SAPR_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// E-step: the features into slot-major order (once per batch), then the forward pass — bidiagonal models fused with
+// their emission, dense models over the emission grid's lattice
+template <int D, int S>
+int launch_forward(const FbArgs &a, int topology, int max_T) {
+  dim3 grid(static_cast<unsigned>(a.n_tiles)), block(kBlock);
+  const int n_fc = ((max_T > 0 ? max_T : 1) + kEmitFrames - 1) / kEmitFrames;
+  const int64_t blocks = a.n_tiles * n_fc;
+  if (blocks > 0x7fffffffLL) return fail(SAPR_ERR_ARG, "grid too large (%lld blocks)", (long long)blocks);
+  if (!a.staged)
+    SAPR_LAUNCH((fb_stage_kernel<D>), dim3(static_cast<unsigned>(blocks)), block, 0, a.stream, a.feats, a.offsets,
+                a.slot_utt, a.n_slots, n_fc, a.feat_t);
+  if (topology == SAPR_TOPO_BIDIAG) {
+    SAPR_LAUNCH((fb_forward_kernel<D, S>), grid, block, 0, a.stream, a.feat_t, a.offsets, a.slot_utt, a.tile_model,
+                a.n_slots, a.pv.prm, a.pv.gconst, a.pv.log_start, a.pv.log_trans, a.lat_b, a.lat_f, a.loglik);
+  } else {
+    constexpr int NF = D >= 39 ? 2 : 4;
+    SAPR_LAUNCH((fb_emit_kernel<D, S, NF>), dim3(static_cast<unsigned>(blocks)), block, 0, a.stream, a.feat_t,
+                a.offsets, a.slot_utt, a.tile_model, a.n_slots, n_fc, a.pv.prm, a.pv.gconst, a.lat_b);
+    SAPR_HIP_TRY(hipGetLastError());
+    SAPR_LAUNCH((fb_forward_dense_kernel<S>), grid, block, 0, a.stream, a.offsets, a.slot_utt, a.tile_model,
+                a.n_slots, a.pv.log_start, a.pv.log_trans, a.lat_b, a.lat_f, a.loglik);
+  }
   SAPR_HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -937,14 +886,9 @@ extern "C" int sapr_forward_diag(const float *feats, const int64_t *offsets, con
   a.loglik = loglik;
   a.stream = as_stream(stream);
   const int fast = fast_div ? 1 : 0;
-  if (D == 13 && S == 10) return launch_forward<13, 10>(a, topology, fast, 0);
-#ifndef SAPR_ONLY_13_10
-  if (D == 13 && S == 18) return launch_forward<13, 18>(a, topology, fast, 0);
-  if (D == 39 && S == 10) return launch_forward<39, 10>(a, topology, fast, 0);
-  if (D == 39 && S == 18) return launch_forward<39, 18>(a, topology, fast, 0);
-#endif
-  return fail(SAPR_ERR_UNSUPPORTED, "trellis kernels are instantiated for (D,S) in {13,39}x{10,18}; got D=%d S=%d",
-              D, S);
+  return dispatch_ds(D, S, [&](auto d, auto s) {
+    return launch_score<decltype(d)::value, decltype(s)::value>(a, topology, fast);
+  });
 }
 
 // one E-step over a batch: stats[W][width], loglik[n_utts]
@@ -983,22 +927,12 @@ extern "C" int sapr_estep_diag(const float *feats, const int64_t *offsets, const
   a.staged = (fast_div & SAPR_ESTEP_STAGED) != 0;
   a.loglik = loglik;
   a.stream = as_stream(stream);
-  const int fast = (fast_div & SAPR_PACK_FAST_DIV) ? 1 : 0;
   int rc = 0, sub = 1;  // partial rows per tile handed to the last reduction
   if (n_tiles > 0) {
-    if (D == 13 && S == 10)
-      rc = launch_forward<13, 10>(a, topology, fast, max_T);
-#ifndef SAPR_ONLY_13_10
-    else if (D == 13 && S == 18)
-      rc = launch_forward<13, 18>(a, topology, fast, max_T);
-    else if (D == 39 && S == 10)
-      rc = launch_forward<39, 10>(a, topology, fast, max_T);
-    else if (D == 39 && S == 18)
-      rc = launch_forward<39, 18>(a, topology, fast, max_T);
-#endif
-    else
-      rc = fail(SAPR_ERR_UNSUPPORTED,
-                "trellis kernels are instantiated for (D,S) in {13,39}x{10,18}; got D=%d S=%d", D, S);
+    // (the quick emission form has one division-free arithmetic: the pack's fast_div flavour changes nothing here)
+    rc = dispatch_ds(D, S, [&](auto d, auto s) {
+      return launch_forward<decltype(d)::value, decltype(s)::value>(a, topology, max_T);
+    });
     if (rc) return rc;
     static const bool split = [] {  // SAPR_ESTEP_OBS=split: round 3's smoothing pass + fb_obs_kernel over its lattice
       const char *e = getenv("SAPR_ESTEP_OBS");
@@ -1006,16 +940,9 @@ extern "C" int sapr_estep_diag(const float *feats, const int64_t *offsets, const
     }();
     if (topology == SAPR_TOPO_BIDIAG && !split) {
       sub = kBlock / 64;
-      if (D == 13 && S == 10)
-        rc = launch_smooth_obs<13, 10>(a, tile_stats, tile_obs);
-#ifndef SAPR_ONLY_13_10
-      else if (D == 13)
-        rc = launch_smooth_obs<13, 18>(a, tile_stats, tile_obs);
-      else if (S == 10)
-        rc = launch_smooth_obs<39, 10>(a, tile_stats, tile_obs);
-      else
-        rc = launch_smooth_obs<39, 18>(a, tile_stats, tile_obs);
-#endif
+      rc = dispatch_ds(D, S, [&](auto d, auto s) {
+        return launch_smooth_obs<decltype(d)::value, decltype(s)::value>(a, tile_stats, tile_obs);
+      });
       if (rc) return rc;
     } else {
       rc = S == 10 ? launch_backward<10>(a, topology, utt_stats) : launch_backward<18>(a, topology, utt_stats);

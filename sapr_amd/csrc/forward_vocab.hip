@@ -6,10 +6,11 @@
 // utterance under the one model of its tile.  CPU restatement: oracle/c_oracle.decode_batch(which=1).
 //
 // Mapping: the (utterance tile, word) grid of the Viterbi kernels (viterbi_shared.h decode_block: the W workgroups
-// that read the same 256 utterances sit on one XCD, so the features cross HBM once) around the forward recursion of
-// fb_forward_kernel<..., QEMIT> — one lane per utterance, the model wavefront-uniform in SGPRs, log-densities in the
-// quick form of emission_quick.h (three float64 instructions per state, dimension and frame; only the exact-kernel
-// operands of the pack are read), NF frames per walk over the parameters.  The recursion's state is S registers per
+// that read the same 256 utterances sit on one XCD, so the features cross HBM once) around quick_forward_walk of
+// diag_forward.h, the recursion of the E-step's fb_forward_kernel without the share stores — one lane per utterance, the
+// model wavefront-uniform in SGPRs, log-densities in the quick form of emission_quick.h (three float64 instructions
+// per state, dimension and frame; only the exact-kernel operands of the pack are read), NF frames per walk over the
+// parameters.  The recursion's state is S registers per
 // lane: no lattice reaches HBM, there is no workspace, and the grid is W times the single-model forward grid.
 // Features are read from the frame-major batch itself (a lane's frame is 4 D contiguous bytes, re-read by the other
 // W - 1 models from the XCD's L2), not from a slot-major copy.
@@ -24,6 +25,7 @@ namespace sapr {
 namespace {
 
 #include "lse_ops.h"
+#include "diag_forward.h"
 #include "vocab_epilogue.h"
 
 using namespace emission;
@@ -40,71 +42,15 @@ __global__ __launch_bounds__(kBlock) void forward_vocab_kernel(
   if (tile >= n_tiles) return;  // grid padding (whole block leaves together)
 
   const int64_t slot = tile * kBlock + threadIdx.x;
-  const bool live = slot < n_utts;
-  const int64_t u = live ? (order ? static_cast<int64_t>(order[slot]) : slot) : 0;
-  const int64_t beg = live ? offsets[u] : 0;
-  const int T = live ? static_cast<int>(offsets[u + 1] - beg) : 0;
-  const int Tw = wave_max_i32(T);
-
-  // wavefront-uniform model pointers -> scalar loads
-  const double4 *__restrict__ prm = prm_all + static_cast<int64_t>(w) * S * D;
-  const double *__restrict__ gc = gconst + static_cast<int64_t>(w) * S;
-  const double *__restrict__ ls = log_start + static_cast<int64_t>(w) * S;
-  const double *__restrict__ lt = log_trans + static_cast<int64_t>(w) * S * S;
-  const float *__restrict__ xp = feats + beg * D;
+  const Lane ln = lane_of(offsets, slot < n_utts ? (order ? static_cast<int64_t>(order[slot]) : slot) : -1);
+  const DiagModel m = diag_model<D, S>(prm_all, gconst, log_start, log_trans, w);
+  const float *__restrict__ xp = feats + ln.beg * D;
 
   double fwd[S];
-#pragma unroll
-  for (int s = 0; s < S; ++s) fwd[s] = ls[s];
-
-  // one frame of _hmmc.cpp forward_log from its log-densities (fb_forward_kernel's recursion without the share stores)
-  auto step = [&](int t, const double (&b)[S]) {
-    if (t == 0) {
-#pragma unroll
-      for (int j = 0; j < S; ++j) fwd[j] += b[j];
-    } else if constexpr (BIDIAG) {
-      // descending j: fwd[j - 1] is still the previous frame's value when state j reads it
-#pragma unroll
-      for (int j = S - 1; j >= 1; --j)
-        fwd[j] = lse2(fwd[j - 1] + lt[(j - 1) * S + j], fwd[j] + lt[j * S + j]) + b[j];
-      fwd[0] = (fwd[0] + lt[0]) + b[0];
-    } else {
-      double prev[S], work[S];
-#pragma unroll
-      for (int s = 0; s < S; ++s) prev[s] = fwd[s];
-#pragma unroll
-      for (int j = 0; j < S; ++j) {
-#pragma unroll
-        for (int i = 0; i < S; ++i) work[i] = prev[i] + lt[i * S + j];
-        fwd[j] = lse_all<S>(work) + b[j];
-      }
-    }
-  };
-
-  // 39-dimensional frames stay float32 in registers and are promoted inside the chain (emission_quick.h)
-  using XT = std::conditional_t<(D >= 39), float, double>;
-  constexpr int NF = (D >= 39 || S > 10) ? 2 : 4;
-  for (int t0 = 0; t0 < Tw; t0 += NF) {
-    if (t0 < T) {
-      XT xq[NF][D];
-#pragma unroll
-      for (int f = 0; f < NF; ++f) {
-        const int t = t0 + f < T ? t0 + f : T - 1;  // frames past the end: evaluated, not used
-        if constexpr (D >= 39)
-          load_frame_f32<D>(xp + static_cast<int64_t>(t) * D, xq[f]);
-        else
-          load_frame<D>(xp + static_cast<int64_t>(t) * D, xq[f]);
-      }
-      double bq[NF][S];
-      frame_log_densities_quick<D, S, NF>(xq, prm, gc,
-                                          [&](auto jc, int f, double bv) { bq[f][decltype(jc)::value] = bv; });
-#pragma unroll
-      for (int f = 0; f < NF; ++f)
-        if (t0 + f < T) step(t0 + f, bq[f]);
-    }
-  }
+  quick_forward_walk<D, S, BIDIAG>(
+      ln, m, fwd, [&](int t, auto &x) { load_quick_frame<D>(xp + static_cast<int64_t>(t) * D, x); });
   // logsumexp over the last row (unreachable padding states add exp(-inf) = 0); no frames: the C oracle's -inf
-  if (live) loglik[u * W + w] = T > 0 ? lse_all<S>(fwd) : neg_inf();
+  if (ln.live) loglik[ln.u * W + w] = ln.T > 0 ? lse_all<S>(fwd) : neg_inf();
 }
 
 struct VocabArgs {
@@ -155,16 +101,9 @@ extern "C" int sapr_forward_vocab(const float *feats, const int64_t *offsets, co
   a.pv = pack_view(pack, W, S, D);
   a.loglik = loglik;
   a.stream = as_stream(stream);
-  int rc;
-  if (D == 13 && S == 10) rc = launch_forward_vocab<13, 10>(a, topology);
-#ifndef SAPR_ONLY_13_10
-  else if (D == 13 && S == 18) rc = launch_forward_vocab<13, 18>(a, topology);
-  else if (D == 39 && S == 10) rc = launch_forward_vocab<39, 10>(a, topology);
-  else if (D == 39 && S == 18) rc = launch_forward_vocab<39, 18>(a, topology);
-#endif
-  else
-    rc = fail(SAPR_ERR_UNSUPPORTED, "trellis kernels are instantiated for (D,S) in {13,39}x{10,18}; got D=%d S=%d", D,
-              S);
+  const int rc = dispatch_ds(D, S, [&](auto d, auto s) {
+    return launch_forward_vocab<decltype(d)::value, decltype(s)::value>(a, topology);
+  });
   if (rc) return rc;
   if (best_word || word_post) return launch_vocab_epilogue(n_utts, W, loglik, best_word, word_post, a.stream);
   return 0;

@@ -1,26 +1,48 @@
-// The two helpers of the bidiagonal smoothing recursion (estep.hip: fb_smooth_kernel, fb_smooth_obs_kernel), shared with
-// the posterior lattice of state_posteriors.hip.  Like lse_ops.h this header is included INSIDE the unit's
-// `namespace sapr { namespace {`, after lse_ops.h (exp_unit).
+// The rows of the backward half — the posterior soft-max, the dense backward_log row and the bidiagonal smoothing step —
+// shared by estep.hip (fb_smooth_kernel, fb_smooth_obs_kernel, fb_backward_dense_kernel) and the posterior lattice of
+// state_posteriors.hip.  Like lse_ops.h this header is included INSIDE the unit's `namespace sapr { namespace {`, after
+// lse_ops.h (exp_unit, lse_all).
 #pragma once
 
+// base.py _compute_posteriors_log, one row: g = exp(lg - logsumexp(lg)), evaluated as exp(lg - max) / sum — the S
+// exponentials of the logsumexp are the numerators
+template <int S>
+__device__ __forceinline__ void softmax_row(const double (&lg)[S], double (&g)[S]) {
+  double mx = lg[0];
+#pragma unroll
+  for (int s = 1; s < S; ++s) mx = lg[s] > mx ? lg[s] : mx;
+  double e[S], den = 0.0;
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    e[s] = exp_unit(lg[s] - mx);  // all -inf: NaN, as exp(lg - (-inf)) is in the reference
+    den += e[s];
+  }
+  const double inv = 1.0 / den;
+#pragma unroll
+  for (int s = 0; s < S; ++s) g[s] = e[s] * inv;
+}
+
+// the posteriors of an utterance's last frame: the soft-max of row T - 1 of a [t][s][slot] lattice of forward values
 template <int S>
 __device__ __forceinline__ void softmax_last_row(const double *__restrict__ lat_b, int64_t n_slots, int64_t slot, int T,
                                                  double (&g)[S]) {
   double lg[S];
 #pragma unroll
   for (int s = 0; s < S; ++s) lg[s] = lat_b[(static_cast<int64_t>(T - 1) * S + s) * n_slots + slot];
-  double mx = lg[0];
+  softmax_row<S>(lg, g);
+}
+
+// _hmmc.cpp backward_log, one row of a dense model: nb[i] = logsumexp_j(log a_ij + b_t[j] + bwd_t[j]) = bwd_(t-1)[i]
+template <int S>
+__device__ __forceinline__ void dense_backward_row(const double *__restrict__ lt, const double *b_t,
+                                                   const double (&bwd)[S], double (&nb)[S]) {
 #pragma unroll
-  for (int s = 1; s < S; ++s) mx = lg[s] > mx ? lg[s] : mx;
-  double den = 0.0;
+  for (int i = 0; i < S; ++i) {
+    double work[S];
 #pragma unroll
-  for (int s = 0; s < S; ++s) {
-    lg[s] = exp_unit(lg[s] - mx);  // all -inf: NaN, as exp(lg - (-inf)) is in the reference
-    den += lg[s];
+    for (int j = 0; j < S; ++j) work[j] = lt[i * S + j] + b_t[j] + bwd[j];
+    nb[i] = lse_all<S>(work);
   }
-  const double inv = 1.0 / den;
-#pragma unroll
-  for (int s = 0; s < S; ++s) g[s] = lg[s] * inv;
 }
 
 // one step t -> t-1 of the smoothing recursion: g = gamma_t on entry, gamma_(t-1) on exit; xs += the xi terms of the step

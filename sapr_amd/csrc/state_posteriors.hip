@@ -7,13 +7,14 @@
 // (log_density_diag, forward_log, backward_log, posteriors).
 //
 // Two passes over a slot-major workspace, one lane per utterance, the model wavefront-uniform in SGPRs:
-//   pass 1 (sp_forward_kernel)  forward_vocab_kernel's recursion with one model per tile: features from the frame-major
-//          batch itself (one-shot call: no slot-major staging copy to amortise), log-densities in the quick form of
-//          emission_quick.h.  Bidiagonal models keep the STAY SHARES of fb_forward_kernel, stay[t][s][slot], and the
-//          last forward row; dense models keep the forward lattice and the log-densities (stored, not recomputed:
-//          pass 2 would otherwise walk the S D parameters again for every frame, and the dense path is the rare one).
-//   pass 2 (sp_smooth_kernel)   bidiagonal: smooth_step of estep.hip from softmax(last forward row) backwards; dense:
-//          the log-domain backward recursion of fb_backward_dense_kernel and the row soft-max of fwd + bwd.
+//   pass 1 (sp_forward_kernel)  quick_forward_walk of diag_forward.h (the body of forward_vocab_kernel, the
+//          recursion of the E-step's fb_forward_kernel) with one model per tile: features from the frame-major batch itself (one-shot call: no
+//          slot-major staging copy to amortise), log-densities in the quick form of emission_quick.h.  Bidiagonal models
+//          keep the STAY SHARES, stay[t][s][slot], and the last forward row; dense models keep the forward lattice and
+//          the log-densities (stored, not recomputed: pass 2 would otherwise walk the S D parameters again for every
+//          frame, and the dense path is the rare one).
+//   pass 2 (sp_smooth_kernel)   smooth_ops.h, as the E-step: bidiagonal, smooth_step from softmax(last forward row)
+//          backwards; dense, dense_backward_row and softmax_row of fwd + bwd.
 //
 // The store is the new part.  A lane owns an utterance, so a direct write of post would put 64 rows of 8 n_out_states
 // bytes at 64 unrelated addresses every frame.  Pass 2 runs ONE wavefront per workgroup (no workgroup barrier, 4 x the
@@ -33,6 +34,7 @@ namespace sapr {
 namespace {
 
 #include "lse_ops.h"
+#include "diag_forward.h"
 #include "smooth_ops.h"
 
 using namespace emission;
@@ -62,91 +64,36 @@ __global__ __launch_bounds__(kBlock) void sp_forward_kernel(
     const double *__restrict__ gconst, const double *__restrict__ log_start, const double *__restrict__ log_trans,
     double *__restrict__ lat_a, double *__restrict__ lat_c, double *__restrict__ loglik) {
   const int64_t tile = blockIdx.x;
-  const int w = tile_model[tile];
   const int64_t slot = tile * kBlock + threadIdx.x;
-  const int64_t u = slot_utt[slot];
-  const bool live = u >= 0;
-  const int64_t beg = live ? offsets[u] : 0;
-  const int T = live ? static_cast<int>(offsets[u + 1] - beg) : 0;
-  const int Tw = wave_max_i32(T);
-
-  // wavefront-uniform model pointers -> scalar loads
-  const double4 *__restrict__ prm = prm_all + static_cast<int64_t>(w) * S * D;
-  const double *__restrict__ gc = gconst + static_cast<int64_t>(w) * S;
-  const double *__restrict__ ls = log_start + static_cast<int64_t>(w) * S;
-  const double *__restrict__ lt = log_trans + static_cast<int64_t>(w) * S * S;
-  const float *__restrict__ xp = feats + beg * D;
+  const Lane ln = lane_of(offsets, slot_utt[slot]);
+  const DiagModel m = diag_model<D, S>(prm_all, gconst, log_start, log_trans, tile_model[tile]);
+  const float *__restrict__ xp = feats + ln.beg * D;
+  auto load = [&](int t, auto &x) { load_quick_frame<D>(xp + static_cast<int64_t>(t) * D, x); };
 
   double fwd[S];
-#pragma unroll
-  for (int s = 0; s < S; ++s) fwd[s] = ls[s];
-
-  // one frame of _hmmc.cpp forward_log from its log-densities
-  auto step = [&](int t, const double (&b)[S]) {
-    const int64_t row = static_cast<int64_t>(t) * S;
-    if (t == 0) {
-#pragma unroll
-      for (int j = 0; j < S; ++j) fwd[j] += b[j];
-    } else if constexpr (BIDIAG) {
-      // the share of each state's mass that STAYED (the rest came from j - 1); descending j: fwd[j - 1] is still the
-      // previous frame's value when state j reads it.  State 0 has no predecessor: constant 1, not stored
-#pragma unroll
-      for (int j = S - 1; j >= 1; --j) {
-        double stay;
-        fwd[j] = lse2_share(fwd[j - 1] + lt[(j - 1) * S + j], fwd[j] + lt[j * S + j], stay) + b[j];
-        lat_a[(row + j) * n_slots + slot] = stay;
-      }
-      fwd[0] = (fwd[0] + lt[0]) + b[0];
-    } else {
-      double prev[S], work[S];
-#pragma unroll
-      for (int s = 0; s < S; ++s) prev[s] = fwd[s];
-#pragma unroll
-      for (int j = 0; j < S; ++j) {
-#pragma unroll
-        for (int i = 0; i < S; ++i) work[i] = prev[i] + lt[i * S + j];
-        fwd[j] = lse_all<S>(work) + b[j];
-      }
-    }
-    if constexpr (!BIDIAG) {
-#pragma unroll
-      for (int j = 0; j < S; ++j) {
-        lat_a[(row + j) * n_slots + slot] = fwd[j];
-        lat_c[(row + j) * n_slots + slot] = b[j];
-      }
-    }
-  };
-
-  // 39-dimensional frames stay float32 in registers and are promoted inside the chain (emission_quick.h)
-  using XT = std::conditional_t<(D >= 39), float, double>;
-  constexpr int NF = (D >= 39 || S > 10) ? 2 : 4;
-  for (int t0 = 0; t0 < Tw; t0 += NF) {
-    if (t0 < T) {
-      XT xq[NF][D];
-#pragma unroll
-      for (int f = 0; f < NF; ++f) {
-        const int t = t0 + f < T ? t0 + f : T - 1;  // frames past the end: evaluated, not used
-        if constexpr (D >= 39)
-          load_frame_f32<D>(xp + static_cast<int64_t>(t) * D, xq[f]);
-        else
-          load_frame<D>(xp + static_cast<int64_t>(t) * D, xq[f]);
-      }
-      double bq[NF][S];
-      frame_log_densities_quick<D, S, NF>(xq, prm, gc,
-                                          [&](auto jc, int f, double bv) { bq[f][decltype(jc)::value] = bv; });
-#pragma unroll
-      for (int f = 0; f < NF; ++f)
-        if (t0 + f < T) step(t0 + f, bq[f]);
-    }
-  }
-  if constexpr (BIDIAG) {  // the posteriors of the last frame start from the last forward row
-    if (T > 0) {
+  if constexpr (BIDIAG) {
+    // the stay shares, and the last forward row: the posteriors of the last frame start from it
+    quick_forward_walk<D, S, true>(ln, m, fwd, load, [&](int t, int j, double stay) {
+      lat_a[(static_cast<int64_t>(t) * S + j) * n_slots + slot] = stay;
+    });
+    if (ln.T > 0) {
 #pragma unroll
       for (int j = 0; j < S; ++j) lat_c[static_cast<int64_t>(j) * n_slots + slot] = fwd[j];
     }
+  } else {
+    // the forward lattice and the log-densities
+    auto rows = [&](int t, const double (&b)[S], const double (&f)[S]) {
+      const int64_t row = static_cast<int64_t>(t) * S;
+#pragma unroll
+      for (int j = 0; j < S; ++j) {
+        lat_a[(row + j) * n_slots + slot] = f[j];
+        lat_c[(row + j) * n_slots + slot] = b[j];
+      }
+    };
+    quick_forward_walk<D, S, false>(ln, m, fwd, load, NoShares{}, rows);
   }
   // logsumexp over the last row (unreachable padding states add exp(-inf) = 0); no frames: -inf
-  if (live) loglik[u] = T > 0 ? lse_all<S>(fwd) : neg_inf();
+  if (ln.live) loglik[ln.u] = ln.T > 0 ? lse_all<S>(fwd) : neg_inf();
 }
 
 // -------------------------------------------------------------------------------------------
@@ -211,10 +158,9 @@ __global__ __launch_bounds__(64) void sp_smooth_kernel(
   const int lane = threadIdx.x;
   const int64_t wq = blockIdx.x;
   const int64_t slot = wq * 64 + lane;
-  const int64_t u = slot_utt[slot];
-  const int64_t beg = u >= 0 ? offsets[u] : 0;
-  const int T = u >= 0 ? static_cast<int>(offsets[u + 1] - beg) : 0;
-  const int Tw = wave_max_i32(T);
+  const Lane ln = lane_of(offsets, slot_utt[slot]);
+  const int64_t beg = ln.beg;
+  const int T = ln.T, Tw = ln.Tw;
 
   double g[S];
 #pragma unroll
@@ -258,22 +204,10 @@ __global__ __launch_bounds__(64) void sp_smooth_kernel(
         for (int s = 0; s < S; ++s) bwd[s] = 0.0;
       }
       if (active) {
-        // base.py _compute_posteriors_log: row soft-max of fwd + bwd, exp(lg - max) / sum as in fb_backward_dense_kernel
-        double lg[S];
+        double lg[S];  // base.py _compute_posteriors_log: row soft-max of fwd + bwd
 #pragma unroll
         for (int s = 0; s < S; ++s) lg[s] = r0[s] + bwd[s];
-        double mx = lg[0];
-#pragma unroll
-        for (int s = 1; s < S; ++s) mx = lg[s] > mx ? lg[s] : mx;
-        double den = 0.0;
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-          lg[s] = exp_unit(lg[s] - mx);  // all -inf: NaN, as exp(lg - (-inf)) is in the reference
-          den += lg[s];
-        }
-        const double inv = 1.0 / den;
-#pragma unroll
-        for (int s = 0; s < S; ++s) g[s] = lg[s] * inv;
+        softmax_row<S>(lg, g);
       }
     }
 
@@ -297,14 +231,8 @@ __global__ __launch_bounds__(64) void sp_smooth_kernel(
         for (int i = 0; i < 2 * S; ++i) xs[i] = 0.0;
         smooth_step<S>(g, r0, xs);
       } else {
-        // _hmmc.cpp backward_log: bwd_(t-1)[i] = logsumexp_j(log a_ij + b_t[j] + bwd_t[j])
-        double nb[S], work[S];
-#pragma unroll
-        for (int i = 0; i < S; ++i) {
-#pragma unroll
-          for (int j = 0; j < S; ++j) work[j] = lt[i * S + j] + r0[S + j] + bwd[j];
-          nb[i] = lse_all<S>(work);
-        }
+        double nb[S];
+        dense_backward_row<S>(lt, r0 + S, bwd, nb);
 #pragma unroll
         for (int i = 0; i < S; ++i) bwd[i] = nb[i];
       }
@@ -390,12 +318,7 @@ extern "C" int sapr_state_posteriors_diag(const float *feats, const int64_t *off
   a.path = path;
   a.n_out = n_out_states;
   a.stream = as_stream(stream);
-  if (D == 13 && S == 10) return launch_sp<13, 10>(a, topology);
-#ifndef SAPR_ONLY_13_10
-  if (D == 13 && S == 18) return launch_sp<13, 18>(a, topology);
-  if (D == 39 && S == 10) return launch_sp<39, 10>(a, topology);
-  if (D == 39 && S == 18) return launch_sp<39, 18>(a, topology);
-#endif
-  return fail(SAPR_ERR_UNSUPPORTED, "trellis kernels are instantiated for (D,S) in {13,39}x{10,18}; got D=%d S=%d", D,
-              S);
+  return dispatch_ds(D, S, [&](auto d, auto s) {
+    return launch_sp<decltype(d)::value, decltype(s)::value>(a, topology);
+  });
 }

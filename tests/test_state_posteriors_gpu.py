@@ -189,6 +189,31 @@ def test_agreement_with_the_estep(dense):
         np.testing.assert_allclose(first, st["start"], rtol=1e-9, atol=1e-9)
 
 
+@pytest.mark.parametrize("dense", [False, True])
+@pytest.mark.parametrize("D,ns", [(13, 8), (39, 16)])
+def test_one_forward_recursion_behind_three_entry_points(D, ns, dense):
+    """The vocabulary scorer, the posteriors' first pass and the E-step's forward pass are one device body
+    (diag_forward.h) on the same values: the log-likelihood of utterance u under model u % 11 is the same float64 from
+    all three, bit for bit.  75 utterances (two wavefronts); the prefixes of 3 .. 9 frames, with the T = 1 and T = 2
+    of the case, end the two- and the four-frame walk on every remainder."""
+    from sapr_amd.trellis import DiagModelPack, EStep, forward_scores, state_posteriors
+    c = _case(D, ns, dense)
+    longest = max(c.utts, key=lambda a: a.shape[0])
+    utts = list(c.utts) + [np.ascontiguousarray(longest[:n]) for n in range(3, 10)]
+    assert len(utts) == 75 and {X.shape[0] for X in utts} >= set(range(1, 10))
+    utt_model = np.arange(len(utts)) % 11
+    batch = _batch(utts)
+    pack = DiagModelPack.from_params(c.sp, c.A, c.mu, c.cv)
+    vocab = forward_scores(batch, pack, want_post=False).loglik.cpu().numpy()[np.arange(len(utts)), utt_model]
+    posteriors = state_posteriors(batch, pack, utt_model, want_post=False).loglik.cpu().numpy()
+    es = EStep(batch, utt_model, 11, c.S)
+    es.run(pack)
+    estep = es.loglik.cpu().numpy()
+    assert np.isfinite(vocab).all()
+    assert np.array_equal(vocab, posteriors), f"{int((vocab != posteriors).sum())} of {len(utts)} utterances differ"
+    assert np.array_equal(vocab, estep), f"{int((vocab != estep).sum())} of {len(utts)} utterances differ"
+
+
 def _capi(batch, pack, layout, post, path, n_out=None, guard=0):
     """sapr_state_posteriors_diag on caller-owned buffers; ``guard`` elements in front of post / path are skipped."""
     import torch
