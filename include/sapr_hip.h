@@ -501,7 +501,7 @@ int sapr_colsum_f32(const float *x, int64_t n_rows, int32_t D, const float *cent
 
 /* ------------------------------------------------------------------------------------
  * The reference's from-scratch HMM (custom_hmm.py): non-emitting entry/exit states, full
- * covariances, the Gram-row-sum emission term — every quirk kept (see custom.hip).  Models are
+ * covariances, the Gram-row-sum emission term — every quirk kept (see custom_*.hip).  Models are
  * float64 arrays prepared on the host exactly as the reference prepares them per call:
  *   means[W][S][D], inv[W][S][D][D] = inv(cov + 1e-6 I), cterm[W][S] = D*log(2*pi) + logdet,
  *   A[W][S][S], logA[W][S][S] = log(A)   (custom_hmm.py:160-165, :191-205).
@@ -521,7 +521,7 @@ int sapr_colsum_f32(const float *x, int64_t n_rows, int32_t D, const float *cent
  * [max_T][S][lane_slots] with the utterance index fastest (coalesced; gamma then goes to the update_b
  * entry points with the same lane_slots).  In the lane_slots layout with xi == NULL (the batched training path) gamma
  * and utt_out are the outputs: E is filled, the alpha (unshifted) and beta lattices are scratch except for the
- * utterances whose backward half had to run in the reference's own order (custom.hip).
+ * utterances whose backward half had to run in the reference's own order (custom_estep.hip).
  * An utterance too short to reach the exit state (T < S - 1) has NaN posteriors in EVERY state of every frame and NaN
  * posterior sums, as in the reference (a soft-max over a row of -inf), and no transition counts; the batched path
  * used to return exact zeros for the exit state's posteriors of such an utterance.  An utterance of 0 frames gets a

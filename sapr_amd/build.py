@@ -20,7 +20,8 @@ SOURCES = ["viterbi_exact_39_18_t1s1.hip", "viterbi_exact_39_18_t1s0.hip", "vite
            "viterbi_exact_39_18_t0s0.hip", "estep.hip", "state_posteriors.hip", "forward_vocab.hip",
            "viterbi_exact_39_10_t1s1.hip", "viterbi_exact_39_10_t1s0.hip",
            "viterbi_exact_39_10_t0s1.hip", "viterbi_exact_39_10_t0s0.hip", "viterbi_exact_13_18.hip",
-           "viterbi_bound.hip", "mfcc.hip", "viterbi_exact_13_10.hip", "custom.hip", "viterbi.hip", "common.hip",
+           "viterbi_bound.hip", "mfcc.hip", "viterbi_exact_13_10.hip", "custom_estep.hip", "custom_emission.hip",
+           "custom_update.hip", "custom_decode.hip", "viterbi.hip", "common.hip",
            "resample.hip", "kmeans.hip", "gmm_hmm.hip", "gmm_vocab.hip", "full_vocab.hip",
            "connected.hip"]
 # -ffp-contract=off: the trellis kernels must perform the individually rounded IEEE

@@ -1,4 +1,4 @@
-"""Host-side mirror of ``assignment2/custom_hmm.py`` over the HIP kernels of ``custom.hip``.
+"""Host-side mirror of ``assignment2/custom_hmm.py`` over the HIP kernels of ``custom_*.hip``.
 
 Same class name, constructor, attributes (``A``, ``B["mean"]``, ``B["covariance"]``, ``pi``,
 ``global_mean``, ``global_covariance`` …) and method signatures as the reference ``HMM``; the
@@ -249,7 +249,7 @@ class HMM:
     def compute_emission_matrix(self, features):
         """(T, total_states) log "densities"; entry/exit columns are -inf (``:146-174``).  Evaluated in the
         reference's own order (two fused-multiply-add chains + numpy's pair-wise row sum of the (T,T) Gram
-        matrix, see custom.hip): bit-identical to the reference on the golden build."""
+        matrix, see custom_emission.hip): bit-identical to the reference on the golden build."""
         import torch
         features = np.asarray(features)
         if features.ndim != 2 or features.shape[0] != self.num_obs:

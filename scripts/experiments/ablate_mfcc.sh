@@ -11,6 +11,7 @@ done
 wait
 for n in "$@"; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC sapr_amd/csrc/common.o sapr_amd/csrc/viterbi.o sapr_amd/csrc/estep.o \
-     sapr_amd/csrc/custom.o sapr_amd/csrc/resample.o /tmp/mfcc_abl$n.o -o sapr_amd/libsapr_hip_abl$n.so
+     sapr_amd/csrc/custom_estep.o sapr_amd/csrc/custom_emission.o sapr_amd/csrc/custom_update.o \
+     sapr_amd/csrc/custom_decode.o sapr_amd/csrc/resample.o /tmp/mfcc_abl$n.o -o sapr_amd/libsapr_hip_abl$n.so
 done
 ls -la sapr_amd/libsapr_hip_abl*.so

@@ -86,7 +86,7 @@ def body(kind, n=64):
             out.append(f"v_mul_f64 v[{2 * (k % 8)}:{2 * (k % 8) + 1}], v[{2 * (k % 8)}:{2 * (k % 8) + 1}], v[{16 + 2 * (j % 8)}:{17 + 2 * (j % 8)}]")
         elif kind == "v_fma_f64_sgpr":   # one operand from the scalar file (the coefficient chains of lse_unit.h)
             out.append(f"v_fma_f64 v[{2 * (k % 8)}:{2 * (k % 8) + 1}], v[{2 * (k % 8)}:{2 * (k % 8) + 1}], v[{16 + 2 * (j % 8)}:{17 + 2 * (j % 8)}], s[22:23]")
-        elif kind == "v_fmac_f64_dpp":   # src0 from lane i % 13 of each row of 16 lanes (custom.hip emission rows)
+        elif kind == "v_fmac_f64_dpp":   # src0 from lane i % 13 of each row of 16 lanes (custom_emission.hip emission rows)
             out.append(f"v_fmac_f64_dpp v[{2 * (k % 8)}:{2 * (k % 8) + 1}], v[{16 + 2 * (j % 8)}:{17 + 2 * (j % 8)}], v[{16 + 2 * (k % 8)}:{17 + 2 * (k % 8)}] row_newbcast:{i % 13} row_mask:0xf bank_mask:0xf")
         elif kind == "v_fmac_f64":
             out.append(f"v_fmac_f64 v[{2 * (k % 8)}:{2 * (k % 8) + 1}], v[{16 + 2 * (j % 8)}:{17 + 2 * (j % 8)}], v[{16 + 2 * (k % 8)}:{17 + 2 * (k % 8)}]")

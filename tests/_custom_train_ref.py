@@ -1,4 +1,4 @@
-"""References and case builders for the training half of custom.hip (numpy only; no GPU, no torch).
+"""References and case builders for the training units custom_estep.hip and custom_update.hip (numpy only; no GPU, no torch).
 
 Parts 1-4 (folds, M-step accumulators, moments, flat-start statistics): plain ``np.longdouble`` accumulations of the
 definitions in the comments above each entry point.  Features are float32 and posteriors float64, both promoted

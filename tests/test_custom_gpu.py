@@ -1,4 +1,4 @@
-"""GPU parity of the custom-HMM mirror (sapr_amd.custom_hmm.HMM, kernels in custom.hip) against the
+"""GPU parity of the custom-HMM mirror (sapr_amd.custom_hmm.HMM, kernels in custom_*.hip) against the
 golden vectors produced by the IMPORTED reference (tests/golden/make_golden.py) and the oracle.
 
 Floating point: float64 on both sides.  The emission matrix (``compute_emission_matrix``) and ``decode``
@@ -388,7 +388,7 @@ def test_g5_flat_start_ties_and_quirk(golden, feature_set):
 
     At flat start every state has the same Gaussian, so all left-to-right paths into a cell tie
     mathematically and the reference's choice hangs on the last bit of its emission values.  The kernel
-    evaluates them in the reference's order (custom.hip, pinned in tests/test_oracle_custom.py), so paths
+    evaluates them in the reference's order (custom_emission.hip, pinned in tests/test_oracle_custom.py), so paths
     AND scores are the reference's, bit for bit, for all 66 utterances."""
     from sapr_amd.custom_hmm import decode_batch
     _, flat = feature_set

@@ -1,6 +1,6 @@
 """The conditions test_custom_train_gpu.py relies on, asserted from the references alone (no GPU): the E-step batches
 hold every class of c0 in the numbers the kernel's branches need, every tile / block / chunk / run / loop threshold of
-custom.hip's training half is straddled by the case sizes, the zero-occupancy state and the empty model exist, a plain
+custom_estep.hip and custom_update.hip is straddled by the case sizes, the zero-occupancy state and the empty model exist, a plain
 float64 evaluation stays under every pin (so the pin decides), and the long-double references agree with the oracle."""
 import numpy as np
 import pytest

@@ -1,5 +1,6 @@
-"""The training half of custom.hip at every dispatch branch and size, through the C ABI (references, case builders and
-the derivation of every tolerance: tests/_custom_train_ref.py; the conditions on the inputs: test_custom_train_cpu.py).
+"""The training units custom_estep.hip and custom_update.hip at every dispatch branch and size, through the C ABI
+(references, case builders and the derivation of every tolerance: tests/_custom_train_ref.py; the conditions on the
+inputs: test_custom_train_cpu.py).
 
 1. sapr_custom_fold_rows: tree (single- and two-level) within n 2^-53 sum|x| of the long-double sum per column — a
    bound that holds for any order of summation — and the same bits twice; SAPR_CUSTOM_FOLD=ordered bit-equal to the
