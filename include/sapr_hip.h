@@ -492,6 +492,52 @@ int sapr_connected_viterbi(const double *logb, const int64_t *offsets, int64_t n
                            int32_t *path_state /* may be NULL */, uint8_t *path_entry /* may be NULL */,
                            void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Forced alignment (csrc/connected_align.hip): Viterbi over the left-to-right chain of the K words an utterance is
+ * known to hold — where does each word begin and end, and which state explains each frame.  Word slot k is entered
+ * only from the exit of slot k - 1 and the score is read only at the exit of the last slot.  The definition is the CPU
+ * restatement tests/_align_ref.py; with the transcript w_0 .. w_{K-1} and b_t(k,s) = logb[t][w_k * SP + s]:
+ *     delta_0(0,j)   = log_start[w_0][j] + b_0(0,j)          delta_0(k>0,j) = -inf
+ *     X_{t-1}(k)     = max_s (delta_{t-1}(k,s) + log_exit[w_k][s])            s ascending, the first maximum
+ *     within         = max_i (delta_{t-1}(k,i) + log_trans[w_k][i][j])        i ascending, the first maximum
+ *     entry (k >= 1) = (X_{t-1}(k-1) + word_penalty) + log_start[w_k][j]      (k = 0: -inf)
+ *     delta_t(k,j)   = max(within, entry) + b_t(k,j)                          entry only where strictly greater
+ *     score          = X_{T-1}(K-1)
+ * The additions are made in the order written (the word loop's order): float64 adds and compares only, bit for bit
+ * numpy's, and aligning to the string sapr_connected_viterbi decoded gives that call's score bit for bit.
+ *   logb          [total_frames][R = W * SP], what the three sapr_connected_emit_* entry points write
+ *   offsets       [n_utts + 1] frames, word_offsets [n_utts + 1] transcript positions; a range that leaves its array is
+ *                 served as empty
+ *   words         [total_words] vocabulary indices, the transcripts one after the other (a word may follow itself)
+ *   max_words     the longest transcript the call is sized for: max_words * SP <= 256 chain positions lie along the
+ *                 lanes of one wavefront
+ *   log_start, log_trans, log_exit, word_penalty: as for sapr_connected_viterbi
+ *   workspace     sapr_connected_align_workspace_bytes: back-pointers, one byte per (frame, chain position) in rows of
+ *                 max_words * SP, rounded up to 16, then one byte per (frame, word slot) — the state that attained X —
+ *                 in rows of max_words, rounded up to 16
+ *   score         [n_utts]
+ *   path_word (vocabulary indices), path_state [total_frames] int32, path_entry [total_frames] uint8 (1 at frame 0 and
+ *                 wherever a word begins), word_start [total_words] int32 (the frame, counted from the utterance's
+ *                 start, at which transcript word k begins): each may be NULL
+ * An utterance without a path — no frames, no words, more than max_words words, a word index outside 0 .. W - 1, a
+ * score that is not finite — scores -inf (or the NaN that propagated); its path rows are -1, its entry flags 0, its
+ * word_start -1.  No atomics: outputs are bit-identical from run to run, and an utterance's outputs are a function of
+ * its own frames, its own transcript and the network.  Non-finite values propagate; every index of the walk is clamped
+ * into its row.
+ *
+ * Bad sizes, NULL required pointers and a workspace that is too small return SAPR_ERR_ARG, S > 18, W * SP > 256 or
+ * max_words * SP > 256 SAPR_ERR_UNSUPPORTED (from the size function too), all before any launch; n_utts == 0 returns 0
+ * after these checks. */
+int sapr_connected_align_workspace_bytes(int64_t total_frames, int64_t n_utts, int32_t max_words, int32_t S,
+                                         size_t *bytes);
+int sapr_connected_align(const double *logb, const int64_t *offsets, int64_t n_utts, int64_t total_frames,
+                         const int32_t *words /* [total_words] */, const int64_t *word_offsets /* [n_utts + 1] */,
+                         int64_t total_words, int32_t max_words, const double *log_start, const double *log_trans,
+                         const double *log_exit, double word_penalty, int32_t W, int32_t S, void *workspace,
+                         size_t workspace_bytes, double *score, int32_t *path_word /* may be NULL */,
+                         int32_t *path_state /* may be NULL */, uint8_t *path_entry /* may be NULL */,
+                         int32_t *word_start /* [total_words], may be NULL */, void *stream);
+
 /* Flat start of HMMLearnModel (hmmlearn_hmm.py:83-94: np.mean / np.var over axis 0 of the concatenated float32
  * features): numpy adds row after row in float32, so each column is one sequential float32 chain — reproduced
  * bit for bit.  center == NULL: out[d] = sum_r x[r][d]; else out[d] = sum_r RN32(RN32(x[r][d] - center[d])^2).

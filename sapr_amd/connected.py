@@ -8,6 +8,11 @@ family: ``sapr_connected_emit_diag`` for diagonal-Gaussian word models ("diag", 
 ``sapr_connected_emit_full`` for a vocabulary with a "full" or "tied" model over its ``full_cov.FullPack`` (both packs
 are read as they are).  Stage 2, ``sapr_connected_viterbi``, runs the recursion over any ``logb`` it is given.  The CPU
 restatement ``tests/_connected_ref.py`` is the definition; the recursion reproduces it bit for bit.
+
+Forced alignment is the inverse question — the words of a recording are known, where does each begin and end:
+``sapr_connected_align`` (``csrc/connected_align.hip``) runs the Viterbi recursion over the left-to-right chain of an
+utterance's own transcript, on the same ``logb`` (:func:`align_viterbi`, :func:`connected_align`; the definition is
+``tests/_align_ref.py``).
 """
 from __future__ import annotations
 
@@ -332,17 +337,12 @@ def _result(tensors, offs) -> ConnectedResult:
     return ConnectedResult(*host, offsets=offs)
 
 
-def connected_viterbi(logb, lengths, network: ConnectedNetwork) -> ConnectedResult:
-    """The recursion over a given ``logb``: float64 ``[total_frames, W, S]`` (the network's own S: padded here with
-    ``-inf``), ``[total_frames, W, SP]`` or ``[total_frames, W * SP]``, a host array or a device tensor; host
-    ``lengths``.  Any emission family may supply ``logb``."""
+def _flat_logb(logb, total, network, dev):
+    """A caller's ``logb`` (host array or device tensor, any of the three shapes) -> device ``[total_frames, R]``."""
     torch = _torch()
-    dev = _lib.require_gpu()
-    lengths, offs = _offsets(lengths)
     if not torch.is_tensor(logb):
         logb = torch.from_numpy(np.ascontiguousarray(logb, dtype=np.float64))
     logb = logb.to(dev)
-    total = int(offs[-1])
     if logb.dtype != torch.float64 or int(logb.shape[0]) != total:
         raise ValueError("logb must be float64 with sum(lengths) rows")
     W, S, SP, R = network.W, network.S, network.SP, network.R
@@ -353,31 +353,159 @@ def connected_viterbi(logb, lengths, network: ConnectedNetwork) -> ConnectedResu
     if tuple(logb.shape[1:]) not in ((W, SP), (R,)):
         raise ValueError(f"logb must be [total_frames, {W}, {S}], [total_frames, {W}, {SP}] or [total_frames, {R}]; "
                          f"got {tuple(logb.shape)}")
-    logb = logb.reshape(total, R).contiguous()
+    return logb.reshape(total, R).contiguous()
+
+
+def connected_viterbi(logb, lengths, network: ConnectedNetwork) -> ConnectedResult:
+    """The recursion over a given ``logb``: float64 ``[total_frames, W, S]`` (the network's own S: padded here with
+    ``-inf``), ``[total_frames, W, SP]`` or ``[total_frames, W * SP]``, a host array or a device tensor; host
+    ``lengths``.  Any emission family may supply ``logb``."""
+    torch = _torch()
+    dev = _lib.require_gpu()
+    lengths, offs = _offsets(lengths)
+    total = int(offs[-1])
+    logb = _flat_logb(logb, total, network, dev)
     offs_dev = torch.from_numpy(offs).to(dev)
     return _result(_run_viterbi(logb, offs_dev, int(lengths.size), total, network), offs)
 
 
-def connected_decode(batch_or_feature_list, network: ConnectedNetwork) -> ConnectedResult:
-    """Emission (by the network's family) and recursion: a ``trellis.FeatureBatch`` or a list of frame-major
-    ``(T, D)`` feature arrays -> :class:`ConnectedResult`."""
+def _features(batch_or_feature_list):
+    """A ``trellis.FeatureBatch`` or a list of frame-major ``(T, D)`` arrays -> ``(device feats [total_frames, D]
+    float32, device offsets, host offsets)``."""
     torch = _torch()
     from .tile_family import vocab_features
     b = batch_or_feature_list
     if hasattr(b, "offsets") and hasattr(b, "order"):
         feats, offs_dev, _, lengths, _ = vocab_features(b)
-        lengths, offs = _offsets(lengths)
-    else:
-        mats = [np.ascontiguousarray(np.asarray(f), dtype=np.float32) for f in b]
-        if len(mats) == 0:
-            raise ValueError("empty utterance list")
-        D = mats[0].shape[1] if mats[0].ndim == 2 else -1
-        if any(m.ndim != 2 or m.shape[1] != D for m in mats):
-            raise ValueError("all utterances must be (T, D) arrays that share the feature dimension")
-        lengths, offs = _offsets([m.shape[0] for m in mats])
-        dev = _lib.require_gpu()
-        packed = np.concatenate(mats, axis=0) if offs[-1] else np.zeros((0, D), np.float32)
-        feats = torch.from_numpy(packed).to(dev)
-        offs_dev = torch.from_numpy(offs).to(dev)
+        return feats, offs_dev, _offsets(lengths)[1]
+    mats = [np.ascontiguousarray(np.asarray(f), dtype=np.float32) for f in b]
+    if len(mats) == 0:
+        raise ValueError("empty utterance list")
+    D = mats[0].shape[1] if mats[0].ndim == 2 else -1
+    if any(m.ndim != 2 or m.shape[1] != D for m in mats):
+        raise ValueError("all utterances must be (T, D) arrays that share the feature dimension")
+    _, offs = _offsets([m.shape[0] for m in mats])
+    dev = _lib.require_gpu()
+    packed = np.concatenate(mats, axis=0) if offs[-1] else np.zeros((0, D), np.float32)
+    return torch.from_numpy(packed).to(dev), torch.from_numpy(offs).to(dev), offs
+
+
+def connected_decode(batch_or_feature_list, network: ConnectedNetwork) -> ConnectedResult:
+    """Emission (by the network's family) and recursion: a ``trellis.FeatureBatch`` or a list of frame-major
+    ``(T, D)`` feature arrays -> :class:`ConnectedResult`."""
+    feats, offs_dev, offs = _features(batch_or_feature_list)
     logb = _EMIT[network.family](feats, network)
-    return _result(_run_viterbi(logb, offs_dev, int(lengths.size), int(offs[-1]), network), offs)
+    return _result(_run_viterbi(logb, offs_dev, int(offs.size - 1), int(offs[-1]), network), offs)
+
+
+# ---- forced alignment ---------------------------------------------------------------------------
+def align_workspace_bytes(total_frames, n_utts, max_words, S) -> int:
+    n = C.c_size_t(0)
+    _lib.check(_lib.load().sapr_connected_align_workspace_bytes(total_frames, n_utts, max_words, S, C.byref(n)),
+               "sapr_connected_align_workspace_bytes")
+    return int(n.value)
+
+
+@dataclass
+class AlignResult:
+    score: np.ndarray         # [N] f64: the best path's log score through the transcript; -inf without a path
+    path_word: np.ndarray     # [total_frames] i32: vocabulary indices (-1 where there is no path)
+    path_state: np.ndarray    # [total_frames] i32 (-1 where there is no path)
+    path_entry: np.ndarray    # [total_frames] u8: 1 where a word begins
+    word_start: np.ndarray    # [total_words] i32: the frame, from the utterance's start, at which word k begins (-1)
+    word_offsets: np.ndarray  # [N + 1] i64: transcript k of utterance u is entry word_offsets[u] + k
+    offsets: np.ndarray       # [N + 1] i64
+    words: np.ndarray         # [total_words] i32: the transcripts, one after the other
+
+    def segments(self, u):
+        """``[(word_index, start, end_exclusive), ...]`` of utterance ``u``: one entry per transcript word, frames
+        counted from the utterance's own start; ``[]`` where there is no path."""
+        lo, hi = int(self.word_offsets[u]), int(self.word_offsets[u + 1])
+        if hi == lo or int(self.word_start[lo]) < 0:
+            return []
+        starts = [int(a) for a in self.word_start[lo:hi]]
+        ends = starts[1:] + [int(self.offsets[u + 1] - self.offsets[u])]
+        return [(int(w), a, b) for w, a, b in zip(self.words[lo:hi], starts, ends)]
+
+    def word_examples(self, features):
+        """Cut the utterances at the word boundaries: ``features`` are the frame-major ``(T, D)`` arrays that were
+        aligned; returns ``{word_index: [array, ...]}`` (views), the per-word training examples ``GaussianHMM.fit`` /
+        ``GMMHMM.fit`` take.  Utterances without a path contribute nothing."""
+        if len(features) != len(self.offsets) - 1:
+            raise ValueError(f"{len(features)} feature arrays for {len(self.offsets) - 1} aligned utterances")
+        out = {}
+        for u, x in enumerate(features):
+            x = np.asarray(x)
+            if x.shape[0] != int(self.offsets[u + 1] - self.offsets[u]):
+                raise ValueError(f"utterance {u} has {x.shape[0]} frames, the alignment "
+                                 f"{int(self.offsets[u + 1] - self.offsets[u])}")
+            for w, a, b in self.segments(u):
+                out.setdefault(w, []).append(x[a:b])
+        return out
+
+
+def _transcripts(transcripts, n_utts, network):
+    """Validated transcripts -> ``(words[total_words] i32, word_offsets[N + 1] i64, max_words)``."""
+    transcripts = [np.asarray(t, dtype=np.int64).reshape(-1) for t in transcripts]
+    if len(transcripts) != n_utts:
+        raise ValueError(f"{len(transcripts)} transcripts for {n_utts} utterances")
+    limit = MAX_FLAT // network.SP
+    for u, t in enumerate(transcripts):
+        if t.size == 0:
+            raise ValueError(f"the transcript of utterance {u} is empty")
+        if t.min() < 0 or t.max() >= network.W:
+            raise ValueError(f"the transcript of utterance {u} names a word outside the vocabulary 0..{network.W - 1}")
+        if t.size * network.SP > MAX_FLAT:
+            raise ValueError(f"the transcript of utterance {u} has {t.size} words: K * SP = {t.size * network.SP} "
+                             f"exceeds the limit of {MAX_FLAT} chain positions ({limit} words at SP = {network.SP})")
+    _, word_offs = _offsets([t.size for t in transcripts])
+    words = np.concatenate(transcripts).astype(np.int32) if transcripts else np.zeros(0, np.int32)
+    return words, word_offs, max((t.size for t in transcripts), default=1)
+
+
+def _run_align(logb, offs_dev, offs, transcripts, network) -> AlignResult:
+    """One ``sapr_connected_align`` over device ``logb[total_frames, R]``."""
+    torch = _torch()
+    dev = logb.device
+    n_utts, total = int(offs.size - 1), int(offs[-1])
+    words, word_offs, max_words = _transcripts(transcripts, n_utts, network)
+    total_words = int(word_offs[-1])
+    ls, lt, lx, _ = network.device(dev)
+    words_dev = torch.from_numpy(words).to(dev)
+    word_offs_dev = torch.from_numpy(word_offs).to(dev)
+    ws_bytes = align_workspace_bytes(total, n_utts, max_words, network.S)
+    workspace = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    score = torch.empty(n_utts, dtype=torch.float64, device=dev)
+    path_word = torch.empty(total, dtype=torch.int32, device=dev)
+    path_state = torch.empty(total, dtype=torch.int32, device=dev)
+    path_entry = torch.empty(total, dtype=torch.uint8, device=dev)
+    word_start = torch.empty(total_words, dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().sapr_connected_align(
+        _lib.ptr(logb), _lib.ptr(offs_dev), n_utts, total, _lib.ptr(words_dev), _lib.ptr(word_offs_dev), total_words,
+        max_words, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx), network.word_penalty, network.W, network.S,
+        _lib.ptr(workspace), ws_bytes, _lib.ptr(score), _lib.ptr(path_word), _lib.ptr(path_state),
+        _lib.ptr(path_entry), _lib.ptr(word_start), _lib.current_stream()), "sapr_connected_align")
+    host = [a.copy() for a in _lib.to_host(score, path_word, path_state, path_entry, word_start)]
+    return AlignResult(*host, word_offsets=word_offs, offsets=offs, words=words)
+
+
+def align_viterbi(logb, lengths, transcripts, network: ConnectedNetwork) -> AlignResult:
+    """Forced alignment over a given ``logb`` (the shapes :func:`connected_viterbi` takes): ``transcripts`` is one
+    sequence of vocabulary indices per utterance, the words the utterance is known to hold, in order."""
+    torch = _torch()
+    lengths, offs = _offsets(lengths)
+    _transcripts(transcripts, int(lengths.size), network)  # (refused before a device is asked for)
+    dev = _lib.require_gpu()
+    logb = _flat_logb(logb, int(offs[-1]), network, dev)
+    return _run_align(logb, torch.from_numpy(offs).to(dev), offs, transcripts, network)
+
+
+def connected_align(batch_or_feature_list, transcripts, network: ConnectedNetwork) -> AlignResult:
+    """Emission (by the network's family) and the alignment recursion: a ``trellis.FeatureBatch`` or a list of
+    frame-major ``(T, D)`` feature arrays, with one transcript of vocabulary indices per utterance."""
+    b = batch_or_feature_list
+    n_utts = len(b.lengths) if hasattr(b, "offsets") and hasattr(b, "order") else len(b)
+    _transcripts(transcripts, n_utts, network)  # (refused before a device is asked for)
+    feats, offs_dev, offs = _features(b)
+    logb = _EMIT[network.family](feats, network)
+    return _run_align(logb, offs_dev, offs, transcripts, network)

@@ -124,16 +124,60 @@ class Decoder:
         if self.implementation not in ("hmmlearn", "gmmhmm"):
             raise ValueError(f"connected-word decoding needs implementation='hmmlearn' with 'diag' or 'spherical' "
                              f"models: it has no emission stage for implementation={self.implementation!r}")
-        from .connected import ConnectedNetwork, connected_decode, vocabulary_family
+        from .connected import connected_decode
         if len(feature_list) == 0:
             raise ValueError("empty utterance list")
         words = list(self.models)
+        net = self._connected_network(exit_states, word_penalty)
+        res = connected_decode([np.asarray(f).T for f in feature_list], net)
+        out = []
+        for u in range(len(feature_list)):
+            segs = res.segments(u)
+            lo, hi = int(res.offsets[u]), int(res.offsets[u + 1])
+            out.append({"words": [words[w] for w, _, _ in segs], "log_likelihood": float(res.score[u]),
+                        "segments": [(words[w], a, b) for w, a, b in segs],
+                        "state_sequence": res.path_state[lo:hi].astype(np.int64)})
+        return out
+
+    def _connected_network(self, exit_states, word_penalty):
+        """The vocabulary as a ``ConnectedNetwork`` of its emission family, over the decoder's own pack."""
+        from .connected import ConnectedNetwork, vocabulary_family
+        words = list(self.models)
         # (validated before the pack is built: packing reads the fitted attributes)
         family = vocabulary_family(self._model_list(), words, self.implementation)
-        net = ConnectedNetwork.from_models(self._model_list(), exit_states=exit_states, word_penalty=word_penalty,
-                                           names=words, implementation=self.implementation,
-                                           pack=None if family == "diag" else self._vocab_pack())
-        res = connected_decode([np.asarray(f).T for f in feature_list], net)
+        return ConnectedNetwork.from_models(self._model_list(), exit_states=exit_states, word_penalty=word_penalty,
+                                            names=words, implementation=self.implementation,
+                                            pack=None if family == "diag" else self._vocab_pack())
+
+    def align(self, feature_list: List[np.ndarray], transcripts, word_penalty: float = 0.0,
+              exit_states="last") -> List[Dict]:
+        """Forced alignment: the words of every recording are known (``transcripts``: one list of word names per
+        utterance, in spoken order; a word may follow itself), where does each begin and end.  Viterbi over the chain
+        of the transcript's word models (``sapr_amd.connected.connected_align``: the emission stage of the vocabulary's
+        family, then ``sapr_connected_align``).  ``feature_list``: (D, T) arrays as in ``decode_connected``.  Per
+        utterance ``{"words": [...], "log_likelihood": float, "segments": [(word, start, end_exclusive), ...],
+        "state_sequence": ndarray}`` with one segment per transcript word; an utterance its transcript cannot explain
+        (too few frames, no path) has no words, no segments, ``-inf`` and states of -1.
+
+        Served for the implementations and families ``decode_connected`` serves.  A word that is not in the
+        vocabulary is refused with a ``ValueError`` that names it."""
+        if self.implementation not in ("hmmlearn", "gmmhmm"):
+            raise ValueError(f"forced alignment needs implementation='hmmlearn' or 'gmmhmm': it has no emission stage "
+                             f"for implementation={self.implementation!r}")
+        from .connected import connected_align
+        if len(feature_list) == 0:
+            raise ValueError("empty utterance list")
+        words = list(self.models)
+        index = {w: i for i, w in enumerate(words)}
+        rows = []
+        for u, names in enumerate(transcripts):
+            for name in names:
+                if name not in index:
+                    raise ValueError(f"the transcript of utterance {u} names {name!r}, which is not in the vocabulary "
+                                     f"({', '.join(words)})")
+            rows.append([index[name] for name in names])
+        net = self._connected_network(exit_states, word_penalty)
+        res = connected_align([np.asarray(f).T for f in feature_list], rows, net)
         out = []
         for u in range(len(feature_list)):
             segs = res.segments(u)
