@@ -538,6 +538,55 @@ int sapr_connected_align(const double *logb, const int64_t *offsets, int64_t n_u
                          int32_t *path_state /* may be NULL */, uint8_t *path_entry /* may be NULL */,
                          int32_t *word_start /* [total_words], may be NULL */, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Embedded Baum-Welch (csrc/connected_embed.hip): forward-backward over the same chain of an utterance's transcript
+ * words, and its posteriors reduced to per-word sufficient statistics — training from recordings of several words
+ * without cutting them.  The definition is the CPU restatement tests/_embedded_ref.py; with lse the log-sum-exp:
+ *     alpha_0(0,j)  = log_start[w_0][j] + b_0(0,j)             alpha_0(k>0,j) = -inf
+ *     X_{t-1}(k)    = lse_s (alpha_{t-1}(k,s) + log_exit[w_k][s])
+ *     alpha_t(k,j)  = lse( lse_i (alpha_{t-1}(k,i) + log_trans[w_k][i][j]),
+ *                          (X_{t-1}(k-1) + word_penalty) + log_start[w_k][j] ) + b_t(k,j)   (k = 0: no entry term)
+ *     loglik        = X_{T-1}(K-1)
+ *     beta_{T-1}(K-1,s) = log_exit[w_{K-1}][s]                 beta_{T-1}(k<K-1,s) = -inf
+ *     E_t(k)        = word_penalty + lse_j (log_start[w_k][j] + b_t(k,j) + beta_t(k,j))     (k >= 1)
+ *     beta_t(k,i)   = lse( lse_j (log_trans[w_k][i][j] + b_{t+1}(k,j) + beta_{t+1}(k,j)),
+ *                          log_exit[w_k][i] + E_{t+1}(k+1) )                                (k = K-1: no exit term)
+ *     gamma_t(k,s)  = exp(alpha_t(k,s) + beta_t(k,s) - loglik)
+ * Statistics are kept per word model w and sum over every slot k with w_k = w of every utterance whose loglik is
+ * finite: post = sum_t gamma, obs = sum_t gamma x_t, obs2 = sum_t gamma x_t^2 (float64 sums; x_t^2 is the float32
+ * square, as in sapr_estep_diag), trans[i][j] = sum_{t>=1}
+ * exp(alpha_{t-1}(k,i) + log_trans + b_t(k,j) + beta_t(k,j) - loglik), start[j] = gamma_0(0,j) for slot 0 plus, for
+ * k >= 1, sum_{t>=1} exp((X_{t-1}(k-1) + word_penalty) + log_start[w_k][j] + b_t(k,j) + beta_t(k,j) - loglik),
+ * nobs = the number of such slots.
+ *   logb, offsets, words, word_offsets, max_words, log_start, log_trans, log_exit, word_penalty, W, S: as for
+ *                 sapr_connected_align
+ *   feats         [total_frames][D] float32, the frames logb was evaluated on; NULL iff D == 0 (the obs blocks then
+ *                 have width 0).  D <= 39
+ *   workspace     sapr_connected_embed_workspace_bytes: alpha [total_frames][max_words * SP] and X
+ *                 [total_frames][max_words] float64, one partial statistics row per transcript word
+ *                 (SP * (2 + SP + 2 D) float64), one byte per transcript word, and per 256 transcript words 256 / SP
+ *                 statistics rows (the first level of the fold), each block rounded up to 16
+ *   loglik        [n_utts]
+ *   stats         [W][width], width = sapr_connected_embed_stats_width(S, D) = 2 + S + S*S + S + 2*S*D:
+ *                 {nobs, reserved 0.0, start[S], trans[S][S], post[S], obs[S][D], obs2[S][D]} per word model; or NULL
+ *   post          [total_frames][max_words * SP]: gamma_t at chain position k * SP + s, 0 behind the utterance's own
+ *                 K * SP positions; or NULL.  Frames that belong to no utterance are not written
+ * An utterance without a path — no frames, no words, more words than frames or than max_words, a word index outside
+ * 0 .. W - 1, a likelihood that is not finite (-inf, or NaN wherever a NaN was met) — contributes exact zeros to every
+ * statistic and its posterior rows are 0: one bad recording does not poison a word's statistics (sapr_estep_diag
+ * propagates instead).  No atomics: the per-slot sums are folded in slot order, outputs are bit-identical from run to
+ * run.  The argument checks, limits and error codes are those of sapr_connected_align, with D > 39 unsupported. */
+int sapr_connected_embed_stats_width(int32_t S, int32_t D, int32_t *width);
+int sapr_connected_embed_workspace_bytes(int64_t total_frames, int64_t n_utts, int64_t total_words,
+                                         int32_t max_words, int32_t S, int32_t D, size_t *bytes);
+int sapr_connected_embed(const double *logb, const float *feats /* [total_frames][D]; NULL iff D == 0 */, int32_t D,
+                         const int64_t *offsets, int64_t n_utts, int64_t total_frames, const int32_t *words,
+                         const int64_t *word_offsets, int64_t total_words, int32_t max_words,
+                         const double *log_start, const double *log_trans, const double *log_exit,
+                         double word_penalty, int32_t W, int32_t S, void *workspace, size_t workspace_bytes,
+                         double *loglik /* [n_utts] */, double *stats /* [W][width] or NULL */,
+                         double *post /* [total_frames][max_words*SP] or NULL */, void *stream);
+
 /* Flat start of HMMLearnModel (hmmlearn_hmm.py:83-94: np.mean / np.var over axis 0 of the concatenated float32
  * features): numpy adds row after row in float32, so each column is one sequential float32 chain — reproduced
  * bit for bit.  center == NULL: out[d] = sum_r x[r][d]; else out[d] = sum_r RN32(RN32(x[r][d] - center[d])^2).

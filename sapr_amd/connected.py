@@ -509,3 +509,154 @@ def connected_align(batch_or_feature_list, transcripts, network: ConnectedNetwor
     feats, offs_dev, offs = _features(b)
     logb = _EMIT[network.family](feats, network)
     return _run_align(logb, offs_dev, offs, transcripts, network)
+
+
+# ---- embedded Baum-Welch --------------------------------------------------------------------------
+def embed_stats_width(S, D) -> int:
+    n = C.c_int32(0)
+    _lib.check(_lib.load().sapr_connected_embed_stats_width(S, D, C.byref(n)), "sapr_connected_embed_stats_width")
+    return int(n.value)
+
+
+def embed_workspace_bytes(total_frames, n_utts, total_words, max_words, S, D) -> int:
+    n = C.c_size_t(0)
+    _lib.check(_lib.load().sapr_connected_embed_workspace_bytes(total_frames, n_utts, total_words, max_words, S, D,
+                                                                C.byref(n)), "sapr_connected_embed_workspace_bytes")
+    return int(n.value)
+
+
+@dataclass
+class EmbeddedStats:
+    loglik: np.ndarray        # [N] f64: log P(utterance | its transcript's chain); -inf (or NaN) without a path
+    stats: np.ndarray         # [W, width] f64 (sapr_connected_embed_stats_width), or None
+    post: np.ndarray          # [total_frames, max_words * SP] f64: gamma_t at chain position k * SP + s, or None
+    offsets: np.ndarray       # [N + 1] i64
+    word_offsets: np.ndarray  # [N + 1] i64
+    words: np.ndarray         # [total_words] i32: the transcripts, one after the other
+    S: int = 0                # the network's states (the layout of a statistics row) ...
+    SP: int = 0               # ... and the padded states of a chain position
+    D: int = 0                # feature width of the obs blocks (0: none)
+    n_states: tuple = ()      # every word model's own states
+
+    def split(self, w):
+        """hmmlearn's statistics dict of word model ``w`` (``trellis.split_stats``), cut to the model's own states;
+        ``logprob`` is the row's reserved 0.0."""
+        from .trellis import split_stats
+        if self.stats is None:
+            raise ValueError("the statistics were not asked for")
+        return split_stats(self.stats[w], self.S, self.D, self.n_states[w] if self.n_states else None, self.D)
+
+    def posteriors(self, u):
+        """``gamma[T, K, SP]`` of utterance ``u`` (zeros where it has no path)."""
+        if self.post is None:
+            raise ValueError("the posteriors were not asked for (want_post=True)")
+        lo, hi = int(self.offsets[u]), int(self.offsets[u + 1])
+        K = int(self.word_offsets[u + 1] - self.word_offsets[u])
+        return self.post[lo:hi].reshape(hi - lo, -1, self.SP)[:, :K]
+
+
+def _run_embed(logb, feats, offs_dev, offs, transcripts, network, want_stats, want_post) -> EmbeddedStats:
+    """One ``sapr_connected_embed`` over device ``logb[total_frames, R]`` (and device ``feats`` or ``None``)."""
+    torch = _torch()
+    dev = logb.device
+    n_utts, total = int(offs.size - 1), int(offs[-1])
+    words, word_offs, max_words = _transcripts(transcripts, n_utts, network)
+    total_words = int(word_offs[-1])
+    D = 0 if feats is None else int(feats.shape[1])
+    ls, lt, lx, _ = network.device(dev)
+    words_dev = torch.from_numpy(words).to(dev)
+    word_offs_dev = torch.from_numpy(word_offs).to(dev)
+    ws_bytes = embed_workspace_bytes(total, n_utts, total_words, max_words, network.S, D)
+    workspace = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    loglik = torch.empty(n_utts, dtype=torch.float64, device=dev)
+    stats = torch.empty((network.W, embed_stats_width(network.S, D)), dtype=torch.float64, device=dev) \
+        if want_stats else None
+    post = torch.zeros((total, max_words * network.SP), dtype=torch.float64, device=dev) if want_post else None
+    _lib.check(_lib.load().sapr_connected_embed(
+        _lib.ptr(logb), _lib.ptr(feats), D, _lib.ptr(offs_dev), n_utts, total, _lib.ptr(words_dev),
+        _lib.ptr(word_offs_dev), total_words, max_words, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx),
+        network.word_penalty, network.W, network.S, _lib.ptr(workspace), ws_bytes, _lib.ptr(loglik), _lib.ptr(stats),
+        _lib.ptr(post), _lib.current_stream()), "sapr_connected_embed")
+    host = [None if a is None else a.cpu().numpy() for a in (loglik, stats, post)]
+    return EmbeddedStats(*host, offsets=offs, word_offsets=word_offs, words=words, S=network.S, SP=network.SP, D=D,
+                         n_states=tuple(network.n_states))
+
+
+def _refuse_stats(network):
+    if network.family != "diag":
+        raise NotImplementedError(
+            f"embedded statistics are served for the 'diag' family; the {network.family!r} family needs "
+            f"{'mixture responsibilities' if network.family == 'gmm' else 'second-moment matrices'} "
+            f"(loglik and post are served: want_stats=False)")
+
+
+def embedded_forward_backward(logb, lengths, transcripts, network: ConnectedNetwork, feats=None,
+                              want_post=False) -> EmbeddedStats:
+    """Forward-backward over every utterance's transcript chain on a given ``logb`` (the shapes
+    :func:`connected_viterbi` takes) — the counterpart of :func:`align_viterbi`.  ``feats``: the float32 frames
+    ``[total_frames, D]`` (host array or device tensor) for the ``obs`` blocks of the statistics; without them the
+    statistics carry ``start``, ``trans``, ``post`` and ``nobs`` only.  The definition is ``tests/_embedded_ref.py``."""
+    torch = _torch()
+    lengths, offs = _offsets(lengths)
+    _transcripts(transcripts, int(lengths.size), network)  # (refused before a device is asked for)
+    dev = _lib.require_gpu()
+    total = int(offs[-1])
+    logb = _flat_logb(logb, total, network, dev)
+    if feats is not None:
+        if not torch.is_tensor(feats):
+            feats = torch.from_numpy(np.ascontiguousarray(feats, dtype=np.float32))
+        feats = feats.to(dev).contiguous()
+        if feats.dtype != torch.float32 or feats.dim() != 2 or int(feats.shape[0]) != total:
+            raise ValueError("feats must be float32 [sum(lengths), D]")
+        if int(feats.shape[1]) == 0:
+            feats = None
+    return _run_embed(logb, feats, torch.from_numpy(offs).to(dev), offs, transcripts, network, True, want_post)
+
+
+def embedded_estep(batch_or_feature_list, transcripts, network: ConnectedNetwork, want_post=False,
+                   want_stats=True) -> EmbeddedStats:
+    """Emission (by the network's family) and forward-backward over the transcript chains — the counterpart of
+    :func:`connected_align`.  ``loglik`` and ``post`` are served for all three families; the statistics for "diag"
+    (for "gmm" and "full" asking for them raises ``NotImplementedError``: pass ``want_stats=False``)."""
+    b = batch_or_feature_list
+    n_utts = len(b.lengths) if hasattr(b, "offsets") and hasattr(b, "order") else len(b)
+    _transcripts(transcripts, n_utts, network)  # (refused before a device is asked for)
+    if want_stats:
+        _refuse_stats(network)
+    feats, offs_dev, offs = _features(b)
+    logb = _EMIT[network.family](feats, network)
+    return _run_embed(logb, feats if want_stats else None, offs_dev, offs, transcripts, network, want_stats, want_post)
+
+
+def embedded_fit(models, features, transcripts, n_iter=10, tol=1e-2, exit_states="last", word_penalty=0.0,
+                 names=None):
+    """Embedded Baum-Welch: train the word models of a "diag" / "spherical" ``GaussianHMM`` vocabulary in place from
+    recordings of several words (``features``: frame-major ``(T, D)`` arrays) and their transcripts (vocabulary
+    indices), without cutting the recordings.  Each iteration: ``ConnectedNetwork.from_models``, the emission, the
+    E-step, then ``hmmlearn_hmm.m_step_typed`` per model with the model's own hyper-parameters; a word that never
+    occurs (in an utterance with a path) stays untouched.  One ``ConvergenceMonitor`` runs on the sum of ``loglik``
+    over the utterances with a path; returns its history as a list."""
+    from .hmmlearn_hmm import ConvergenceMonitor, m_step_typed
+    models = list(models)
+    if vocabulary_family(models, names, "hmmlearn") != "diag":
+        raise ValueError("embedded_fit serves 'diag' and 'spherical' GaussianHMM vocabularies: a 'full' or 'tied' "
+                         "model needs second-moment matrices the embedded E-step does not accumulate")
+    net = ConnectedNetwork.from_models(models, exit_states, word_penalty, names, "hmmlearn")
+    _transcripts(transcripts, len(features), net)  # (refused before a device is asked for)
+    feats, offs_dev, offs = _features(features)
+    monitor = ConvergenceMonitor(tol, n_iter)
+    for _ in range(n_iter):
+        net = ConnectedNetwork.from_models(models, exit_states, word_penalty, names, "hmmlearn")
+        res = _run_embed(emit_diag(feats, net), feats, offs_dev, offs, transcripts, net, True, False)
+        for w, m in enumerate(models):
+            st = res.split(w)
+            if st["nobs"] == 0:
+                continue
+            m.startprob_, m.transmat_, m.means_, m._covars_ = m_step_typed(
+                st, m.covariance_type, m.startprob_, m.transmat_, m.params, m.startprob_prior, m.transmat_prior,
+                m.means_prior, m.means_weight, m.covars_prior, m.covars_weight, np.asarray(m.means_, dtype=np.float64),
+                np.asarray(m._covars_, dtype=np.float64))
+        monitor.report(float(res.loglik[np.isfinite(res.loglik)].sum()))
+        if monitor.converged:
+            break
+    return list(monitor.history)

@@ -1,0 +1,747 @@
+// Embedded Baum-Welch on gfx950: forward-backward over the left-to-right chain of an utterance's K transcript words and
+// the reduction of its posteriors into per-word sufficient statistics.  CPU restatement, which is the
+// definition: tests/_embedded_ref.py.  The input logb[total_frames][R = W * SP] is what the three emission stages of
+// connected.hip write; the recursion knows nothing about the emission family.
+//
+// The layout is that of connected_align.hip: one wavefront serves one utterance, chain position p = k * 64 + lane sits
+// in register k of its lane (RL in {1, 2, 4}) and belongs to word slot p / SP, state p % SP; the vocabulary's table lies
+// in LDS by diagonals, tab[w][(j - i) mod SP][j]; rotations run only at the distances d = j - i at which some
+// transition of the vocabulary is finite; the coupling between the slots goes through a per-wavefront LDS row.
+//
+// embed_forward_kernel<RL, SP>  (four wavefronts per workgroup): the alignment recursion with the two-term log-sum-exp
+//   of lse_ops.h in place of the strict maximum and a segmented log-sum-exp (slot_lse: the lanes of slot q evaluate
+//   its SP exponentials, lane q takes the maximum before and the sum after) in place of the segmented maximum.  Per
+//   frame it writes alpha[t][max_words * SP] and X[t][max_words] into the workspace; at the end loglik[u].  A NaN met
+//   anywhere (lse2 would drop it) makes the likelihood NaN.
+// embed_backward_kernel<RL, SP>  (as many wavefronts per workgroup as the LDS holds, at most four): walks t downwards
+//   with beta in registers.  c_t(p) = b_t(p) + beta_t(p) is rotated to the lane of position p - d — the lane of state i
+//   reads its successor j = i + d at position p + d, with the transposed diagonal tab[w][d mod SP][i + d] — and one
+//   rotation serves both the recursion and the transition share exp(alpha_{t-1}(i) + lt(i,j) + c_t(j) - loglik).
+//   The shares are accumulated where they are formed: lane (slot, i) owns trans[slot][i][*], one double per
+//   (d mod SP, position) in a per-wavefront LDS block of SP * 64 * RL doubles that only its own lane touches.
+//   gamma_t overwrites alpha_t in the workspace (alpha_t is dead once frame t is done) and goes to post[] when asked;
+//   the per-position sums of gamma and of the entry shares stay in registers.  At the end the wavefront writes its
+//   slots' {start[SP], trans[SP][SP], post[SP]} into the per-slot partial rows and marks the slots as counted.
+// embed_obs_kernel: one workgroup per utterance, sum_t gamma_t(p) [x, x^2] in float64 over the float32 features (x^2
+//   is the float32 square, as in estep.hip), t ascending, into the per-slot partial rows.
+// embed_fold_chunk_kernel, embed_fold_kernel: stats[w][e] = the sum over the counted slots n with words[n] == w, in two
+//   levels with fixed boundaries (chunks of 256 slots, n ascending; then the chunks, ascending).
+//
+// No atomics anywhere; an utterance's outputs are a function of its own frames, its own transcript and the network, and
+// the fold adds in slot order: two calls return the same bytes.  Every index is clamped into its row and offsets that
+// leave the batch are served as empty.
+#include "sapr_common.h"
+
+namespace sapr {
+namespace {
+
+#include "lse_ops.h"
+#include "gmm_ops.h"
+
+constexpr int kEmMaxP = 256;          // chain positions (and flat states of the vocabulary) one wavefront holds
+constexpr int kEmBlock = 256;         // forward: 4 wavefronts per workgroup
+constexpr int kEmWaves = kEmBlock / kWave;
+constexpr int kEmXRow = kWave + 2;    // coupling row of one wavefront: [0] = -inf (nothing enters slot 0), [q + 1]
+constexpr int kEmRows = kEmXRow + kWave;  // ... and the row of the slots' maxima behind it
+constexpr int kEmMaxD = 39;
+constexpr int kEmFoldChunk = 256;     // slots one block of the first fold level adds up (fixed: it fixes the order)
+
+inline int em_check_shape(int32_t W, int32_t S, int32_t max_words) {
+  if (S > kMaxS || static_cast<int64_t>(W) * sp_of(S) > kEmMaxP || static_cast<int64_t>(max_words) * sp_of(S) > kEmMaxP)
+    return fail(SAPR_ERR_UNSUPPORTED,
+                "the embedded Baum-Welch kernels serve S in 1..%d, W * SP <= %d and max_words * SP <= %d; got W=%d "
+                "S=%d max_words=%d (SP=%d)",
+                kMaxS, kEmMaxP, kEmMaxP, W, S, max_words, sp_of(S));
+  return 0;
+}
+
+inline int em_check_dims(int32_t D) {
+  if (D > kEmMaxD)
+    return fail(SAPR_ERR_UNSUPPORTED, "the embedded Baum-Welch kernels serve D in 0..%d; got D=%d", kEmMaxD, D);
+  return 0;
+}
+
+inline size_t em_align16(size_t x) { return (x + 15) / 16 * 16; }
+
+// doubles of one slot's partial row: {start[SP], trans[SP][SP], post[SP], obs[SP][D], obs2[SP][D]}
+inline size_t em_part_width(int SP, int D) { return static_cast<size_t>(SP) * (2 + SP + 2 * D); }
+
+struct EmWorkspace {
+  double *alpha;     // [total_frames][max_words * SP]; gamma after the backward pass
+  double *X;         // [total_frames][max_words]
+  double *part;      // [total_words][em_part_width]
+  uint8_t *slot_ok;  // [total_words]: the slot belongs to an utterance with a path
+  double *fold;      // [chunks of kEmFoldChunk slots][W <= 256 / SP][stats width]: the first fold level
+  size_t bytes;
+};
+
+inline int64_t em_chunks(int64_t total_words) { return (total_words + kEmFoldChunk - 1) / kEmFoldChunk; }
+
+inline EmWorkspace em_carve(void *base, int64_t total_frames, int64_t total_words, int32_t max_words, int S, int D) {
+  const int SP = sp_of(S);
+  EmWorkspace w;
+  uint8_t *p = static_cast<uint8_t *>(base);
+  const size_t a = em_align16(static_cast<size_t>(total_frames) * max_words * SP * sizeof(double));
+  const size_t x = em_align16(static_cast<size_t>(total_frames) * max_words * sizeof(double));
+  const size_t s = em_align16(static_cast<size_t>(total_words) * em_part_width(SP, D) * sizeof(double));
+  const size_t o = em_align16(static_cast<size_t>(total_words));
+  const size_t f = em_align16(static_cast<size_t>(em_chunks(total_words)) * (kEmMaxP / SP) *
+                              (2 + S + S * S + S + 2 * S * D) * sizeof(double));
+  w.alpha = reinterpret_cast<double *>(p);
+  w.X = reinterpret_cast<double *>(p + a);
+  w.part = reinterpret_cast<double *>(p + a + x);
+  w.slot_ok = p + a + x + s;
+  w.fold = reinterpret_cast<double *>(p + a + x + s + o);
+  w.bytes = a + x + s + o + f;
+  return w;
+}
+
+// between the lanes of ONE wavefront: what the lanes wrote to LDS before is what they read after (connected_align.hip)
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ bool finite_f64(double v) { return v - v == 0.0; }
+
+// The segmented log-sum-exp: val[k] is the term of the lane's position in register k (in[k]: inside the chain); lane
+// q < K returns the log-sum-exp over the SP terms of slot q — the operations of lse_all<SP> over them in its order (the
+// first maximum by strict compares, the exponentials added s ascending, log(sum) + max; an infinite maximum is the
+// result), but with the SP exponentials of a slot evaluated by the SP lanes that hold its positions instead of by lane
+// q alone: lse_all on K lanes costs the whole wavefront SP exponentials per frame, this costs RL.  Three hand-overs
+// through the wavefront's own LDS rows; the caller synchronises before it writes cbuf again.
+template <int RL, int SP>
+__device__ __forceinline__ double slot_lse(double *cbuf, double *mbuf, const double (&val)[RL], const bool (&in)[RL],
+                                           const int (&qk)[RL], int lane, int K) {
+#pragma unroll
+  for (int k = 0; k < RL; ++k)
+    if (in[k]) cbuf[k * kWave + lane] = val[k];
+  wave_lds_sync();
+  double m = neg_inf();
+  if (lane < K) {
+    m = cbuf[lane * SP];
+#pragma unroll
+    for (int s = 1; s < SP; ++s) {
+      const double v = cbuf[lane * SP + s];
+      m = v > m ? v : m;
+    }
+    mbuf[lane] = m;
+  }
+  wave_lds_sync();
+#pragma unroll
+  for (int k = 0; k < RL; ++k)
+    if (in[k]) cbuf[k * kWave + lane] = exp_unit(val[k] - mbuf[qk[k]]);  // (an infinite maximum: selected away below)
+  wave_lds_sync();
+  double r = m;
+  if (lane < K) {
+    double acc = 0.0;
+#pragma unroll
+    for (int s = 0; s < SP; ++s) acc += cbuf[lane * SP + s];
+    r = isinf(m) ? m : log(acc) + m;
+  }
+  return r;
+}
+
+// the part every kernel of this unit starts with: the utterance's frames, transcript and whether the chain can be laid
+// out at all (the likelihood decides the rest)
+struct EmUtt {
+  int64_t beg, T, wbeg;
+  int K;
+  bool path;
+};
+
+__device__ __forceinline__ EmUtt em_utt(const int64_t *__restrict__ offsets, int64_t total_frames,
+                                        const int64_t *__restrict__ word_offsets, int64_t total_words,
+                                        int32_t max_words, int64_t u) {
+  EmUtt r;
+  int64_t beg = offsets[u], end = offsets[u + 1];
+  if (beg < 0 || end < beg || end > total_frames) end = beg = 0;  // offsets that leave the batch: served as empty
+  int64_t wbeg = word_offsets[u], wend = word_offsets[u + 1];
+  if (wbeg < 0 || wend < wbeg || wend > total_words) wend = wbeg = 0;
+  const int64_t K64 = wend - wbeg;
+  r.beg = beg;
+  r.T = end - beg;
+  r.wbeg = wbeg;
+  r.path = r.T > 0 && K64 > 0 && K64 <= max_words;  // (max_words <= 64: a slot per lane in the coupling step)
+  r.K = r.path ? static_cast<int>(K64) : 0;
+  return r;
+}
+
+// tab[w][dd][j] = log_trans[w][i][j] with i = (j - dd) mod SP (all threads of the workgroup; followed by a barrier)
+template <int SP>
+__device__ __forceinline__ void em_load_table(double *tab, const double *__restrict__ log_trans, int W, int S) {
+  const int n_tab = W * SP * SP;
+  for (int n = threadIdx.x; n < n_tab; n += blockDim.x) {
+    const int w = n / (SP * SP), rem = n - w * (SP * SP);
+    const int dd = rem / SP, j = rem - dd * SP;
+    const int i = j >= dd ? j - dd : j - dd + SP;
+    tab[n] = (i < S && j < S) ? log_trans[(static_cast<int64_t>(w) * S + i) * S + j] : neg_inf();
+  }
+  __syncthreads();
+}
+
+// the distances d = j - i in -(SP - 1) .. SP - 1 at which some transition of the vocabulary is finite (bit d + SP - 1),
+// wavefront-uniform; *nan: the table holds a NaN
+template <int SP>
+__device__ __forceinline__ uint64_t em_distance_mask(const double *tab, int n_tab, int lane, bool *nan) {
+  uint64_t dmask = 0;
+  unsigned bad = 0;
+  for (int n = lane; n < n_tab; n += kWave) {
+    const int rem = n % (SP * SP);
+    const int dd = rem / SP, j = rem - dd * SP;
+    const int d = j >= dd ? dd : dd - SP;
+    const double v = tab[n];
+    if (!(v == neg_inf())) dmask |= 1ull << (d + SP - 1);
+    if (v != v) bad = 1;
+  }
+  unsigned lo = static_cast<unsigned>(dmask), hi = static_cast<unsigned>(dmask >> 32);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    lo |= __shfl_xor(lo, o, kWave);
+    hi |= __shfl_xor(hi, o, kWave);
+    bad |= __shfl_xor(bad, o, kWave);
+  }
+  *nan = __builtin_amdgcn_readfirstlane(bad) != 0;
+  return (static_cast<uint64_t>(__builtin_amdgcn_readfirstlane(hi)) << 32) | __builtin_amdgcn_readfirstlane(lo);
+}
+
+template <int RL, int SP>
+__global__ __launch_bounds__(kEmBlock) void embed_forward_kernel(
+    const double *__restrict__ logb, const int64_t *__restrict__ offsets, int64_t n_utts, int64_t total_frames,
+    const int32_t *__restrict__ words, const int64_t *__restrict__ word_offsets, int64_t total_words, int32_t max_words,
+    const double *__restrict__ log_start, const double *__restrict__ log_trans, const double *__restrict__ log_exit,
+    double word_penalty, int32_t W, int32_t S, double *__restrict__ alpha_ws, double *__restrict__ x_ws,
+    double *__restrict__ loglik) {
+  constexpr int PP = kWave * RL;
+  extern __shared__ double smem[];
+  double *tab = smem;
+  const int n_tab = W * SP * SP;
+  em_load_table<SP>(tab, log_trans, W, S);
+
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = threadIdx.x / kWave;
+  double *cbuf = smem + n_tab + wave * (PP + kEmRows);
+  double *xbuf = cbuf + PP;
+  double *mbuf = xbuf + kEmXRow;
+  const int64_t u = static_cast<int64_t>(blockIdx.x) * kEmWaves + wave;
+  if (u >= n_utts) return;  // (after the only barrier; a whole wavefront leaves)
+  const EmUtt ut = em_utt(offsets, total_frames, word_offsets, total_words, max_words, u);
+  bool path = ut.path;
+  const int K = ut.K;
+  {  // a word outside the vocabulary: no path, and nothing of it is used as an index
+    const int w = lane < K ? words[ut.wbeg + lane] : 0;
+    if (__ballot(w < 0 || w >= W)) path = false;
+  }
+  if (!path) {
+    if (lane == 0) loglik[u] = neg_inf();
+    return;
+  }
+  const int64_t beg = ut.beg, T = ut.T;
+  const int P = K * SP;
+  const int R = W * SP;
+  const int MP = max_words * SP;
+
+  bool tab_nan;
+  const uint64_t dmask = em_distance_mask<SP>(tab, n_tab, lane, &tab_nan);
+
+  double ls[RL], lx[RL], alpha[RL], bn[RL];
+  int sk[RL], qk[RL], col[RL], tb[RL];
+  bool ok[RL], real[RL];
+  bool bad = tab_nan || word_penalty != word_penalty;
+#pragma unroll
+  for (int k = 0; k < RL; ++k) {
+    const int p = k * kWave + lane;
+    const int q = p / SP, s = p - q * SP;
+    ok[k] = p < P;
+    const int w = ok[k] ? words[ut.wbeg + q] : 0;  // (checked above: 0 .. W - 1)
+    sk[k] = s;
+    qk[k] = ok[k] ? q : 0;
+    col[k] = w * SP + s;
+    tb[k] = w * (SP * SP) + s;
+    real[k] = ok[k] && s < S;
+    ls[k] = real[k] ? log_start[w * S + s] : neg_inf();
+    lx[k] = real[k] ? log_exit[w * S + s] : neg_inf();
+    bad = bad || ls[k] != ls[k] || lx[k] != lx[k];
+    alpha[k] = neg_inf();
+  }
+
+  const double *__restrict__ brow = logb + beg * R;
+#pragma unroll
+  for (int k = 0; k < RL; ++k) bn[k] = ok[k] ? brow[col[k]] : neg_inf();
+  if (lane == 0) xbuf[0] = neg_inf();
+
+  double xv = neg_inf();  // lane q: X(q) of the frame just finished
+  for (int64_t t = 0; t < T; ++t) {
+    double b[RL];
+#pragma unroll
+    for (int k = 0; k < RL; ++k) b[k] = bn[k];
+    {  // the next frame's values in flight under this frame's chain
+      const int64_t tn = t + 1 < T ? t + 1 : t;
+#pragma unroll
+      for (int k = 0; k < RL; ++k) bn[k] = ok[k] ? brow[tn * R + col[k]] : neg_inf();
+    }
+    double v[RL];
+    if (t == 0) {
+#pragma unroll
+      for (int k = 0; k < RL; ++k) v[k] = qk[k] == 0 ? ls[k] : neg_inf();
+    } else {
+      double xe[RL];  // X_{t-1} of the slot before the lane's own (-inf in front of slot 0)
+#pragma unroll
+      for (int k = 0; k < RL; ++k) {
+        xe[k] = xbuf[qk[k]];
+        v[k] = neg_inf();
+      }
+#pragma unroll 1
+      for (int d = SP - 1; d > -SP; --d) {
+        if (!((dmask >> (d + SP - 1)) & 1ull)) continue;  // (uniform)
+        // position p - d: lane (lane - d) & 63 of register k, of k - 1 where lane < d, of k + 1 where lane - d >= 64
+        const int off = lane - d;
+        const int src = off & (kWave - 1);
+        const int drow = (d >= 0 ? d : d + SP) * SP;
+        double rot[RL];
+#pragma unroll
+        for (int k = 0; k < RL; ++k) rot[k] = __shfl(alpha[k], src, kWave);
+#pragma unroll
+        for (int k = 0; k < RL; ++k) {
+          const double below = k > 0 ? rot[k > 0 ? k - 1 : 0] : neg_inf();
+          const double above = k + 1 < RL ? rot[k + 1 < RL ? k + 1 : k] : neg_inf();
+          const double prev = off < 0 ? below : (off >= kWave ? above : rot[k]);
+          const int i = sk[k] - d;
+          const bool in = i >= 0 && i < SP;  // (outside the word: no such predecessor)
+          const double lt = tab[tb[k] + drow];
+          v[k] = lse2(v[k], prev + (in ? lt : neg_inf()));
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < RL; ++k) v[k] = lse2(v[k], (xe[k] + word_penalty) + ls[k]);
+    }
+    double *__restrict__ arow = alpha_ws + (beg + t) * MP;
+    double ex[RL];
+#pragma unroll
+    for (int k = 0; k < RL; ++k) {
+      alpha[k] = real[k] ? v[k] + b[k] : neg_inf();
+      bad = bad || alpha[k] != alpha[k];
+      if (ok[k]) arow[k * kWave + lane] = alpha[k];
+      ex[k] = alpha[k] + lx[k];
+    }
+    xv = slot_lse<RL, SP>(cbuf, mbuf, ex, ok, qk, lane, K);  // the log-sum-exp over the slot's states
+    if (lane < K) {
+      xbuf[lane + 1] = xv;
+      x_ws[(beg + t) * max_words + lane] = xv;
+    }
+    wave_lds_sync();
+  }
+  const bool any_bad = __ballot(bad) != 0;
+  if (lane == K - 1) loglik[u] = any_bad ? __builtin_nan("") : xv;
+}
+
+template <int RL, int SP>
+__global__ __launch_bounds__(kEmBlock) void embed_backward_kernel(
+    const double *__restrict__ logb, const int64_t *__restrict__ offsets, int64_t n_utts, int64_t total_frames,
+    const int32_t *__restrict__ words, const int64_t *__restrict__ word_offsets, int64_t total_words, int32_t max_words,
+    const double *__restrict__ log_start, const double *__restrict__ log_trans, const double *__restrict__ log_exit,
+    double word_penalty, int32_t W, int32_t S, int32_t part_width, double *__restrict__ alpha_ws,
+    const double *__restrict__ x_ws, const double *__restrict__ loglik, double *__restrict__ part,
+    uint8_t *__restrict__ slot_ok, double *__restrict__ post) {
+  constexpr int PP = kWave * RL;
+  constexpr int kPerWave = PP + kEmRows + SP * PP;  // cbuf, ebuf, mbuf, the transition accumulators [SP][PP]
+  extern __shared__ double smem[];
+  double *tab = smem;
+  const int n_tab = W * SP * SP;
+  em_load_table<SP>(tab, log_trans, W, S);
+
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = threadIdx.x / kWave;
+  const int waves = blockDim.x / kWave;
+  double *cbuf = smem + n_tab + static_cast<size_t>(wave) * kPerWave;
+  double *ebuf = cbuf + PP;
+  double *mbuf = ebuf + kEmXRow;
+  double *acc = mbuf + kWave;
+  const int64_t u = static_cast<int64_t>(blockIdx.x) * waves + wave;
+  if (u >= n_utts) return;  // (after the only barrier; a whole wavefront leaves)
+  const EmUtt ut = em_utt(offsets, total_frames, word_offsets, total_words, max_words, u);
+  const int64_t beg = ut.beg, T = ut.T;
+  const int MP = max_words * SP;
+  const double ll = loglik[u];
+  // (a finite likelihood was written only for 0 < K <= max_words, T > 0 and words inside the vocabulary)
+  bool path = ut.path && finite_f64(ll);
+  const int K = ut.K;
+  {
+    const int w = lane < K ? words[ut.wbeg + lane] : 0;
+    if (__ballot(w < 0 || w >= W)) path = false;
+  }
+  if (!path) {  // zero posterior rows; the slots stay uncounted
+    if (post)
+      for (int64_t t = 0; t < T; ++t)
+        for (int p = lane; p < MP; p += kWave) post[(beg + t) * MP + p] = 0.0;
+    return;
+  }
+  const int P = K * SP;
+  const int R = W * SP;
+
+  bool tab_nan;  // (a NaN in the table made the likelihood NaN: not reached)
+  const uint64_t dmask = em_distance_mask<SP>(tab, n_tab, lane, &tab_nan);
+  (void)tab_nan;
+
+  double ls[RL], lx[RL], beta[RL], acur[RL], bcur[RL], gsum[RL], sacc[RL];
+  int sk[RL], qk[RL], col[RL], tb[RL];
+  bool ok[RL], real[RL];
+#pragma unroll
+  for (int k = 0; k < RL; ++k) {
+    const int p = k * kWave + lane;
+    const int q = p / SP, s = p - q * SP;
+    ok[k] = p < P;
+    const int w = ok[k] ? words[ut.wbeg + q] : 0;
+    sk[k] = s;
+    qk[k] = ok[k] ? q : 0;
+    col[k] = w * SP + s;
+    tb[k] = w * (SP * SP) + s;
+    real[k] = ok[k] && s < S;  // (a padded state carries nothing, whatever its column of logb holds)
+    ls[k] = real[k] ? log_start[w * S + s] : neg_inf();
+    lx[k] = real[k] ? log_exit[w * S + s] : neg_inf();
+    beta[k] = (ok[k] && q == K - 1) ? lx[k] : neg_inf();
+    gsum[k] = 0.0;
+    sacc[k] = 0.0;
+#pragma unroll 1
+    for (int dd = 0; dd < SP; ++dd) acc[dd * PP + p] = 0.0;
+  }
+  ebuf[lane] = neg_inf();
+  if (lane + kWave < kEmXRow) ebuf[lane + kWave] = neg_inf();
+
+  const double *__restrict__ brow = logb + beg * R;
+  double *__restrict__ abase = alpha_ws + beg * MP;
+  const double *__restrict__ xbase = x_ws + beg * max_words;
+#pragma unroll
+  for (int k = 0; k < RL; ++k) {
+    acur[k] = ok[k] ? abase[(T - 1) * MP + k * kWave + lane] : neg_inf();
+    bcur[k] = real[k] ? brow[(T - 1) * R + col[k]] : neg_inf();
+  }
+
+  for (int64_t t = T - 1; t >= 0; --t) {
+    double c[RL], g[RL];
+#pragma unroll
+    for (int k = 0; k < RL; ++k) {
+      const int p = k * kWave + lane;
+      c[k] = bcur[k] + beta[k];
+      g[k] = ok[k] ? exp_unit((acur[k] + beta[k]) - ll) : 0.0;
+      gsum[k] += g[k];
+      if (ok[k]) abase[t * MP + p] = g[k];  // alpha_t is dead from here on: the observation sums read gamma_t
+      if (post && p < MP) post[(beg + t) * MP + p] = g[k];
+    }
+    if (t == 0) {
+#pragma unroll
+      for (int k = 0; k < RL; ++k) sacc[k] += (ok[k] && qk[k] == 0) ? g[k] : 0.0;
+      break;
+    }
+    double ap[RL], bn[RL], xe[RL];
+#pragma unroll
+    for (int k = 0; k < RL; ++k) {
+      ap[k] = ok[k] ? abase[(t - 1) * MP + k * kWave + lane] : neg_inf();
+      bn[k] = real[k] ? brow[(t - 1) * R + col[k]] : neg_inf();
+      xe[k] = (ok[k] && qk[k] > 0) ? xbase[(t - 1) * max_words + qk[k] - 1] : neg_inf();
+    }
+    // the entry share of slot q >= 1 at frame t, and E_t(q) through the coupling row
+    double en[RL];
+#pragma unroll
+    for (int k = 0; k < RL; ++k) {
+      en[k] = ls[k] + c[k];
+      sacc[k] += exp_unit(((xe[k] + word_penalty) + en[k]) - ll);
+    }
+    {
+      const double e = slot_lse<RL, SP>(cbuf, mbuf, en, ok, qk, lane, K);
+      if (lane >= 1 && lane < K) ebuf[lane] = word_penalty + e;
+    }
+    wave_lds_sync();
+    double nb[RL];
+#pragma unroll
+    for (int k = 0; k < RL; ++k) nb[k] = lx[k] + ebuf[qk[k] + 1];  // (ebuf[K] stays -inf: nothing follows the last slot)
+#pragma unroll 1
+    for (int d = SP - 1; d > -SP; --d) {
+      if (!((dmask >> (d + SP - 1)) & 1ull)) continue;  // (uniform)
+      // position p + d: lane (lane + d) & 63 of register k, of k + 1 where lane + d >= 64, of k - 1 where lane + d < 0
+      const int off = lane + d;
+      const int src = off & (kWave - 1);
+      const int dd = d >= 0 ? d : d + SP;
+      double rot[RL];
+#pragma unroll
+      for (int k = 0; k < RL; ++k) rot[k] = __shfl(c[k], src, kWave);
+#pragma unroll
+      for (int k = 0; k < RL; ++k) {
+        const double below = k > 0 ? rot[k > 0 ? k - 1 : 0] : neg_inf();
+        const double above = k + 1 < RL ? rot[k + 1 < RL ? k + 1 : k] : neg_inf();
+        const double next = off < 0 ? below : (off >= kWave ? above : rot[k]);
+        const int j = sk[k] + d;
+        const bool in = j >= 0 && j < SP;  // (outside the word: no such successor)
+        const double lt = tab[in ? tb[k] + dd * SP + d : 0];
+        const double term = in ? lt + next : neg_inf();
+        nb[k] = lse2(nb[k], term);
+        double *a = acc + dd * PP + k * kWave + lane;
+        *a += exp_unit((ap[k] + term) - ll);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < RL; ++k) {
+      beta[k] = nb[k];
+      acur[k] = ap[k];
+      bcur[k] = bn[k];
+    }
+  }
+
+  if (lane < K) slot_ok[ut.wbeg + lane] = 1;
+#pragma unroll
+  for (int k = 0; k < RL; ++k) {
+    if (!ok[k]) continue;
+    const int p = k * kWave + lane;
+    double *__restrict__ row = part + (ut.wbeg + qk[k]) * static_cast<int64_t>(part_width);
+    const int s = sk[k];
+    row[s] = sacc[k];
+    row[SP + SP * SP + s] = gsum[k];
+#pragma unroll 1
+    for (int dd = 0; dd < SP; ++dd) {
+      const int j = s + dd < SP ? s + dd : s + dd - SP;
+      row[SP + s * SP + j] = acc[dd * PP + p];
+    }
+  }
+}
+
+// sum_t gamma_t(p) [x_t, x_t^2]: one workgroup per utterance, thread (p, d) with d fastest
+__global__ __launch_bounds__(kEmBlock) void embed_obs_kernel(
+    const double *__restrict__ gamma, const float *__restrict__ feats, int32_t D, const int64_t *__restrict__ offsets,
+    int64_t n_utts, int64_t total_frames, const int64_t *__restrict__ word_offsets, int64_t total_words,
+    int32_t max_words, int32_t SP, int32_t part_width, const double *__restrict__ loglik, double *__restrict__ part) {
+  const int64_t u = blockIdx.x;
+  if (u >= n_utts) return;
+  const EmUtt ut = em_utt(offsets, total_frames, word_offsets, total_words, max_words, u);
+  if (!ut.path || !finite_f64(loglik[u])) return;
+  const int MP = max_words * SP;
+  const int n = ut.K * SP * D;
+  const double *__restrict__ g = gamma + ut.beg * MP;
+  const float *__restrict__ x = feats + ut.beg * D;
+  constexpr int NP = 4;  // (position, feature) pairs a thread carries at once: independent chains, each t ascending
+  for (int base = threadIdx.x; base < n; base += kEmBlock * NP) {
+    int p[NP], d[NP];
+    double a1[NP], a2[NP];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      const int idx = base + j * kEmBlock < n ? base + j * kEmBlock : n - 1;  // (behind the end: computed, not stored)
+      p[j] = idx / D;
+      d[j] = idx - p[j] * D;
+      a1[j] = a2[j] = 0.0;
+    }
+    for (int64_t t = 0; t < ut.T; ++t) {
+#pragma unroll
+      for (int j = 0; j < NP; ++j) {
+        const double gt = g[t * MP + p[j]];
+        const float xf = x[t * D + d[j]];
+        a1[j] += gt * static_cast<double>(xf);
+        a2[j] += gt * static_cast<double>(xf * xf);  // float32 square, then widened (estep.hip, hmmlearn's X**2)
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      if (base + j * kEmBlock >= n) continue;
+      const int q = p[j] / SP, s = p[j] - q * SP;
+      double *__restrict__ row = part + (ut.wbeg + q) * static_cast<int64_t>(part_width) + SP * (2 + SP);
+      row[s * D + d[j]] = a1[j];
+      row[SP * D + s * D + d[j]] = a2[j];
+    }
+  }
+}
+
+// stats[w][e]: {nobs, 0.0, start[S], trans[S][S], post[S], obs[S][D], obs2[S][D]} over the counted slots of word w, in
+// two levels with fixed boundaries: fold[c][w][e] = the sum over the slots n of chunk c (kEmFoldChunk of them), n
+// ascending; then stats[w][e] = the sum over the chunks, c ascending
+__global__ __launch_bounds__(kEmBlock) void embed_fold_chunk_kernel(const double *__restrict__ part,
+                                                                    const uint8_t *__restrict__ slot_ok,
+                                                                    const int32_t *__restrict__ words,
+                                                                    int64_t total_words, int32_t W, int32_t S,
+                                                                    int32_t SP, int32_t D, int32_t part_width,
+                                                                    int32_t width, double *__restrict__ fold) {
+  const int e = blockIdx.x * kEmBlock + threadIdx.x;
+  const int w = blockIdx.y;
+  const int64_t c = blockIdx.z;
+  if (e >= width) return;
+  int po = -1;  // the element's place in a slot's partial row
+  int r = e - 2;
+  if (r >= 0) {
+    if (r < S) {
+      po = r;
+    } else if ((r -= S) < S * S) {
+      po = SP + (r / S) * SP + r % S;
+    } else if ((r -= S * S) < S) {
+      po = SP + SP * SP + r;
+    } else if ((r -= S) < S * D) {
+      po = SP * (2 + SP) + r;  // (s * D + d in both layouts)
+    } else {
+      r -= S * D;
+      po = SP * (2 + SP) + SP * D + r;
+    }
+  }
+  const int64_t lo = c * kEmFoldChunk;
+  const int64_t hi = lo + kEmFoldChunk < total_words ? lo + kEmFoldChunk : total_words;
+  double sum = 0.0;
+  for (int64_t n = lo; n < hi; ++n) {
+    if (!slot_ok[n] || words[n] != w) continue;  // (uniform)
+    sum += e == 0 ? 1.0 : (po >= 0 ? part[n * part_width + po] : 0.0);
+  }
+  fold[(c * W + w) * width + e] = sum;
+}
+
+__global__ __launch_bounds__(kEmBlock) void embed_fold_kernel(const double *__restrict__ fold, int64_t chunks,
+                                                              int32_t W, int32_t width, double *__restrict__ stats) {
+  const int e = blockIdx.x * kEmBlock + threadIdx.x;
+  const int w = blockIdx.y;
+  if (e >= width) return;
+  double sum = 0.0;
+  for (int64_t c = 0; c < chunks; ++c) sum += fold[(c * W + w) * width + e];
+  stats[static_cast<int64_t>(w) * width + e] = sum;
+}
+
+struct EmArgs {
+  const double *logb;
+  const int64_t *offsets;
+  int64_t n_utts, total_frames;
+  const int32_t *words;
+  const int64_t *word_offsets;
+  int64_t total_words;
+  int32_t max_words;
+  const double *log_start, *log_trans, *log_exit;
+  double word_penalty;
+  int32_t W, S;
+};
+
+template <int RL, int SP>
+int launch_forward(const EmArgs &a, const EmWorkspace &ws, double *loglik, hipStream_t stream) {
+  const size_t lds =
+      (static_cast<size_t>(a.W) * SP * SP + static_cast<size_t>(kEmWaves) * (kWave * RL + kEmRows)) * sizeof(double);
+  const int64_t blocks = (a.n_utts + kEmWaves - 1) / kEmWaves;
+  SAPR_LAUNCH((embed_forward_kernel<RL, SP>), dim3(static_cast<unsigned>(blocks)), dim3(kEmBlock), lds, stream, a.logb,
+              a.offsets, a.n_utts, a.total_frames, a.words, a.word_offsets, a.total_words, a.max_words, a.log_start,
+              a.log_trans, a.log_exit, a.word_penalty, a.W, a.S, ws.alpha, ws.X, loglik);
+  SAPR_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+template <int RL, int SP>
+int launch_backward(const EmArgs &a, const EmWorkspace &ws, int32_t part_width, const double *loglik, double *post,
+                    hipStream_t stream) {
+  // as many wavefronts per workgroup as the LDS holds next to the vocabulary's table: the transition accumulators take
+  // SP * 64 * RL doubles per wavefront (36 KB at SP = 18, RL = 4)
+  constexpr int lds_max = 160 * 1024;  // a gfx950 workgroup's LDS
+  const size_t tab = static_cast<size_t>(a.W) * SP * SP * sizeof(double);
+  const size_t per_wave = static_cast<size_t>(kWave * RL + kEmRows + SP * kWave * RL) * sizeof(double);
+  int waves = kEmWaves;
+  while (waves > 1 && tab + waves * per_wave > static_cast<size_t>(lds_max)) --waves;
+  const size_t lds = tab + waves * per_wave;
+  if (lds > static_cast<size_t>(lds_max))
+    return fail(SAPR_ERR_UNSUPPORTED, "the backward kernel needs %zu bytes of LDS, the device offers %d", lds, lds_max);
+  const auto kern = embed_backward_kernel<RL, SP>;
+  if (lds > 64 * 1024)  // per launch, not once: the attribute belongs to the current device's copy of the kernel
+    SAPR_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     static_cast<int>(lds)));
+  const int64_t blocks = (a.n_utts + waves - 1) / waves;
+  SAPR_LAUNCH(kern, dim3(static_cast<unsigned>(blocks)), dim3(waves * kWave), lds, stream, a.logb, a.offsets, a.n_utts,
+              a.total_frames, a.words, a.word_offsets, a.total_words, a.max_words, a.log_start, a.log_trans,
+              a.log_exit, a.word_penalty, a.W, a.S, part_width, ws.alpha, ws.X, loglik, ws.part, ws.slot_ok, post);
+  SAPR_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+template <int SP>
+int launch_recursions(const EmArgs &a, const EmWorkspace &ws, int32_t part_width, double *loglik, double *post,
+                      bool backward, hipStream_t stream) {
+  const int positions = a.max_words * SP;
+  if (positions <= kWave) {
+    if (int rc = launch_forward<1, SP>(a, ws, loglik, stream)) return rc;
+    return backward ? launch_backward<1, SP>(a, ws, part_width, loglik, post, stream) : 0;
+  }
+  if (positions <= 2 * kWave) {
+    if (int rc = launch_forward<2, SP>(a, ws, loglik, stream)) return rc;
+    return backward ? launch_backward<2, SP>(a, ws, part_width, loglik, post, stream) : 0;
+  }
+  if (int rc = launch_forward<4, SP>(a, ws, loglik, stream)) return rc;
+  return backward ? launch_backward<4, SP>(a, ws, part_width, loglik, post, stream) : 0;
+}
+
+}  // namespace
+}  // namespace sapr
+
+using namespace sapr;
+
+extern "C" int sapr_connected_embed_stats_width(int32_t S, int32_t D, int32_t *width) {
+  SAPR_REQUIRE(width && S > 0 && D >= 0, "bad sizes (S=%d D=%d)", S, D);
+  if (int rc = em_check_shape(1, S, 1)) return rc;
+  if (int rc = em_check_dims(D)) return rc;
+  *width = 2 + S + S * S + S + 2 * S * D;
+  return 0;
+}
+
+extern "C" int sapr_connected_embed_workspace_bytes(int64_t total_frames, int64_t n_utts, int64_t total_words,
+                                                    int32_t max_words, int32_t S, int32_t D, size_t *bytes) {
+  SAPR_REQUIRE(bytes && total_frames >= 0 && n_utts >= 0 && total_words >= 0 && max_words > 0 && S > 0 && D >= 0,
+               "bad sizes (total_frames=%lld n_utts=%lld total_words=%lld max_words=%d S=%d D=%d)",
+               (long long)total_frames, (long long)n_utts, (long long)total_words, max_words, S, D);
+  if (int rc = em_check_shape(1, S, max_words)) return rc;
+  if (int rc = em_check_dims(D)) return rc;
+  *bytes = em_carve(nullptr, total_frames, total_words, max_words, S, D).bytes;
+  return 0;
+}
+
+extern "C" int sapr_connected_embed(const double *logb, const float *feats, int32_t D, const int64_t *offsets,
+                                    int64_t n_utts, int64_t total_frames, const int32_t *words,
+                                    const int64_t *word_offsets, int64_t total_words, int32_t max_words,
+                                    const double *log_start, const double *log_trans, const double *log_exit,
+                                    double word_penalty, int32_t W, int32_t S, void *workspace, size_t workspace_bytes,
+                                    double *loglik, double *stats, double *post, void *stream) {
+  SAPR_REQUIRE(n_utts >= 0 && total_frames >= 0 && total_words >= 0 && max_words > 0 && W > 0 && S > 0 && D >= 0,
+               "bad sizes (n_utts=%lld total_frames=%lld total_words=%lld max_words=%d W=%d S=%d D=%d)",
+               (long long)n_utts, (long long)total_frames, (long long)total_words, max_words, W, S, D);
+  if (int rc = em_check_shape(W, S, max_words)) return rc;
+  if (int rc = em_check_dims(D)) return rc;
+  size_t need = 0;
+  if (int rc = sapr_connected_embed_workspace_bytes(total_frames, n_utts, total_words, max_words, S, D, &need))
+    return rc;
+  SAPR_REQUIRE(workspace_bytes >= need && (need == 0 || workspace), "workspace too small: %zu < %zu", workspace_bytes,
+               need);
+  SAPR_REQUIRE((n_utts + 0) <= 0x7fffffffLL, "grid too large (%lld utterances)", (long long)n_utts);
+  SAPR_REQUIRE(em_chunks(total_words) <= 65535, "too many transcript words for one call (%lld; at most %d)",
+               (long long)total_words, 65535 * kEmFoldChunk);
+  if (n_utts == 0) return 0;
+  SAPR_REQUIRE(offsets && word_offsets && log_start && log_trans && log_exit && loglik && (total_frames == 0 || logb) &&
+                   (total_words == 0 || words) && (D == 0 || total_frames == 0 || !stats || feats),
+               "NULL pointer argument");
+  const int32_t SP = sp_of(S);
+  const EmWorkspace ws = em_carve(workspace, total_frames, total_words, max_words, S, D);
+  const int32_t part_width = static_cast<int32_t>(em_part_width(SP, D));
+  hipStream_t st = as_stream(stream);
+  const EmArgs a{logb, offsets, n_utts, total_frames, words, word_offsets, total_words, max_words,
+                 log_start, log_trans, log_exit, word_penalty, W, S};
+  const bool backward = stats || post;
+  if (backward && total_words > 0) SAPR_HIP_TRY(hipMemsetAsync(ws.slot_ok, 0, static_cast<size_t>(total_words), st));
+  int rc;
+  if (SP == 4)
+    rc = launch_recursions<4>(a, ws, part_width, loglik, post, backward, st);
+  else if (SP == 10)
+    rc = launch_recursions<10>(a, ws, part_width, loglik, post, backward, st);
+  else
+    rc = launch_recursions<18>(a, ws, part_width, loglik, post, backward, st);
+  if (rc || !stats) return rc;
+  if (D > 0 && total_frames > 0) {
+    SAPR_LAUNCH(embed_obs_kernel, dim3(static_cast<unsigned>(n_utts)), dim3(kEmBlock), 0, st, ws.alpha, feats, D,
+                offsets, n_utts, total_frames, word_offsets, total_words, max_words, SP, part_width, loglik, ws.part);
+    SAPR_HIP_TRY(hipGetLastError());
+  }
+  const int32_t width = 2 + S + S * S + S + 2 * S * D;
+  const int64_t chunks = em_chunks(total_words);
+  const unsigned tiles = static_cast<unsigned>((width + kEmBlock - 1) / kEmBlock);
+  if (chunks > 0) {
+    SAPR_LAUNCH(embed_fold_chunk_kernel, dim3(tiles, static_cast<unsigned>(W), static_cast<unsigned>(chunks)),
+                dim3(kEmBlock), 0, st, ws.part, ws.slot_ok, words, total_words, W, S, SP, D, part_width, width, ws.fold);
+    SAPR_HIP_TRY(hipGetLastError());
+  }
+  SAPR_LAUNCH(embed_fold_kernel, dim3(tiles, static_cast<unsigned>(W)), dim3(kEmBlock), 0, st, ws.fold, chunks, W,
+              width, stats);
+  SAPR_HIP_TRY(hipGetLastError());
+  return 0;
+}

@@ -187,6 +187,42 @@ class Decoder:
                         "state_sequence": res.path_state[lo:hi].astype(np.int64)})
         return out
 
+    def train_embedded(self, feature_list: List[np.ndarray], transcripts, n_iter: int = 10, tol: float = 1e-2,
+                       word_penalty: float = 0.0, exit_states="last") -> List[float]:
+        """Embedded Baum-Welch over recordings of several words: the loaded word models are re-estimated IN PLACE from
+        ``feature_list`` ((D, T) arrays as in ``align``) and ``transcripts`` (one list of word names per utterance, in
+        spoken order), without cutting the recordings at word boundaries (``sapr_amd.connected.embedded_fit``:
+        forward-backward over the chain of each transcript's word models, ``sapr_connected_embed``).  Returns the
+        history of the summed log-likelihood, one entry per iteration.  A word that is in no transcript keeps its
+        parameters.
+
+        Served for ``implementation="hmmlearn"`` over "diag" / "spherical" models; anything else is refused with a
+        ``ValueError`` that says why.  A word that is not in the vocabulary is refused with a ``ValueError`` that
+        names it."""
+        if self.implementation != "hmmlearn":
+            raise ValueError(f"embedded training needs implementation='hmmlearn' with 'diag' or 'spherical' models: "
+                             f"the embedded E-step accumulates single-Gaussian diagonal statistics, not those of "
+                             f"implementation={self.implementation!r}")
+        if self._is_full():
+            raise ValueError("embedded training serves 'diag' and 'spherical' models: this vocabulary holds a 'full' "
+                             "or 'tied' model, whose M-step needs second-moment matrices")
+        from .connected import embedded_fit
+        if len(feature_list) == 0:
+            raise ValueError("empty utterance list")
+        words = list(self.models)
+        index = {w: i for i, w in enumerate(words)}
+        rows = []
+        for u, names in enumerate(transcripts):
+            for name in names:
+                if name not in index:
+                    raise ValueError(f"the transcript of utterance {u} names {name!r}, which is not in the vocabulary "
+                                     f"({', '.join(words)})")
+            rows.append([index[name] for name in names])
+        history = embedded_fit(self._model_list(), [np.asarray(f).T for f in feature_list], rows, n_iter=n_iter,
+                               tol=tol, exit_states=exit_states, word_penalty=word_penalty, names=words)
+        self._pack = self._vocab = None  # (packed from the old parameters)
+        return history
+
     def _decode_custom(self, features) -> List[Tuple[str, float, object]]:
         """The reference's from-scratch models: emission rows, trellis and the arg-max over the models
         (decoder.py:42-47, first strict maximum in load order) all on the device."""
