@@ -587,6 +587,36 @@ int sapr_connected_embed(const double *logb, const float *feats /* [total_frames
                          double *loglik /* [n_utts] */, double *stats /* [W][width] or NULL */,
                          double *post /* [total_frames][max_words*SP] or NULL */, void *stream);
 
+/* The same E-step with second-moment matrices, for word models with "full" or "tied" covariances (definition:
+ * tests/_embedded_full_ref.py): in place of obs2 the row carries, with x_t the float32 frame widened to float64,
+ *     oo[w][s] = sum over the utterances with a finite loglik, the slots k with w_k = w and t of
+ *                gamma_t(k,s) x_t x_t^T        (float64 products, as sapr_full_estep)
+ * The arguments are those of sapr_connected_embed, in its order; loglik and post are exactly its results, and so is
+ * the head of a statistics row, byte for byte (the recursions and their two-level fold are the same launches).
+ *   workspace     sapr_connected_embed_full_workspace_bytes: what sapr_connected_embed takes at D = 0, W heads of
+ *                 2 + S + S*S + S float64, and one partial row of S*D + S*D*D float64 per (utterance group, word);
+ *                 the number of groups is a function of n_utts only (8 utterances each, at most 96 groups, beyond
+ *                 which the groups grow), each block rounded up to 16
+ *   stats         [W][width], width = sapr_connected_embed_full_stats_width(S, D) = 2 + S + S*S + S + S*D + S*D*D
+ *                 (== sapr_full_stats_width): {nobs, reserved 0.0, start[S], trans[S][S], post[S], obs[S][D],
+ *                 oo[S][D][D]} per word model, the row of sapr_full_estep; or NULL.  stats != NULL needs D >= 1 and
+ *                 feats.  Every oo[w][s] is exactly symmetric (both halves are written from the upper one)
+ * The gamma of the slots of one word are added (k ascending) into one weight per frame and state, and sum g x x^T runs
+ * as weighted Gram products on the float64 matrix cores, utterances ascending inside a group; the groups' partial rows
+ * are added in ascending order.  No atomics: outputs are bit-identical from run to run.  An utterance without a path
+ * contributes exact zeros — its posterior rows in the workspace are never read.  Argument checks, limits and error
+ * codes are those of sapr_connected_embed. */
+int sapr_connected_embed_full_stats_width(int32_t S, int32_t D, int32_t *width);
+int sapr_connected_embed_full_workspace_bytes(int64_t total_frames, int64_t n_utts, int64_t total_words,
+                                              int32_t max_words, int32_t W, int32_t S, int32_t D, size_t *bytes);
+int sapr_connected_embed_full(const double *logb, const float *feats /* [total_frames][D] */, int32_t D,
+                              const int64_t *offsets, int64_t n_utts, int64_t total_frames, const int32_t *words,
+                              const int64_t *word_offsets, int64_t total_words, int32_t max_words,
+                              const double *log_start, const double *log_trans, const double *log_exit,
+                              double word_penalty, int32_t W, int32_t S, void *workspace, size_t workspace_bytes,
+                              double *loglik /* [n_utts] */, double *stats /* [W][width] or NULL */,
+                              double *post /* [total_frames][max_words*SP] or NULL */, void *stream);
+
 /* Flat start of HMMLearnModel (hmmlearn_hmm.py:83-94: np.mean / np.var over axis 0 of the concatenated float32
  * features): numpy adds row after row in float32, so each column is one sequential float32 chain — reproduced
  * bit for bit.  center == NULL: out[d] = sum_r x[r][d]; else out[d] = sum_r RN32(RN32(x[r][d] - center[d])^2).

@@ -16,6 +16,7 @@ utterance's own transcript, on the same ``logb`` (:func:`align_viterbi`, :func:`
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
 from dataclasses import dataclass
 
@@ -525,10 +526,25 @@ def embed_workspace_bytes(total_frames, n_utts, total_words, max_words, S, D) ->
     return int(n.value)
 
 
+def embed_full_stats_width(S, D) -> int:
+    n = C.c_int32(0)
+    _lib.check(_lib.load().sapr_connected_embed_full_stats_width(S, D, C.byref(n)),
+               "sapr_connected_embed_full_stats_width")
+    return int(n.value)
+
+
+def embed_full_workspace_bytes(total_frames, n_utts, total_words, max_words, W, S, D) -> int:
+    n = C.c_size_t(0)
+    _lib.check(_lib.load().sapr_connected_embed_full_workspace_bytes(total_frames, n_utts, total_words, max_words, W,
+                                                                     S, D, C.byref(n)),
+               "sapr_connected_embed_full_workspace_bytes")
+    return int(n.value)
+
+
 @dataclass
 class EmbeddedStats:
     loglik: np.ndarray        # [N] f64: log P(utterance | its transcript's chain); -inf (or NaN) without a path
-    stats: np.ndarray         # [W, width] f64 (sapr_connected_embed_stats_width), or None
+    stats: np.ndarray         # [W, width] f64 (sapr_connected_embed[_full]_stats_width), or None
     post: np.ndarray          # [total_frames, max_words * SP] f64: gamma_t at chain position k * SP + s, or None
     offsets: np.ndarray       # [N + 1] i64
     word_offsets: np.ndarray  # [N + 1] i64
@@ -537,13 +553,18 @@ class EmbeddedStats:
     SP: int = 0               # ... and the padded states of a chain position
     D: int = 0                # feature width of the obs blocks (0: none)
     n_states: tuple = ()      # every word model's own states
+    layout: str = "diag"      # the row's observation blocks: "diag" {obs, obs**2} or "full" {obs, obs*obs.T}
 
     def split(self, w):
-        """hmmlearn's statistics dict of word model ``w`` (``trellis.split_stats``), cut to the model's own states;
-        ``logprob`` is the row's reserved 0.0."""
+        """hmmlearn's statistics dict of word model ``w``, cut to the model's own states; ``logprob`` is the row's
+        reserved 0.0.  A "diag" row gives ``trellis.split_stats``' dict (``obs**2``), a "full" row
+        ``full_cov.split_stats``' (``obs*obs.T``)."""
         from .trellis import split_stats
         if self.stats is None:
             raise ValueError("the statistics were not asked for")
+        if self.layout == "full":
+            from .full_cov import split_stats as split_full
+            return split_full(self.stats[w], self.S, self.D, self.n_states[w] if self.n_states else None)
         return split_stats(self.stats[w], self.S, self.D, self.n_states[w] if self.n_states else None, self.D)
 
     def posteriors(self, u):
@@ -555,9 +576,15 @@ class EmbeddedStats:
         return self.post[lo:hi].reshape(hi - lo, -1, self.SP)[:, :K]
 
 
-def _run_embed(logb, feats, offs_dev, offs, transcripts, network, want_stats, want_post) -> EmbeddedStats:
-    """One ``sapr_connected_embed`` over device ``logb[total_frames, R]`` (and device ``feats`` or ``None``)."""
+def _run_embed(logb, feats, offs_dev, offs, transcripts, network, want_stats, want_post,
+               second_moments=False) -> EmbeddedStats:
+    """One ``sapr_connected_embed`` over device ``logb[total_frames, R]`` (and device ``feats`` or ``None``);
+    ``second_moments``: one ``sapr_connected_embed_full`` instead, whose rows carry ``obs*obs.T``."""
     torch = _torch()
+    if second_moments and want_stats:
+        if feats is None or int(feats.shape[1]) == 0:
+            raise ValueError("the second moments need the frames: feats [total_frames, D] with D >= 1")
+        return _run_embed_full(logb, feats, offs_dev, offs, transcripts, network, want_post)
     dev = logb.device
     n_utts, total = int(offs.size - 1), int(offs[-1])
     words, word_offs, max_words = _transcripts(transcripts, n_utts, network)
@@ -582,7 +609,39 @@ def _run_embed(logb, feats, offs_dev, offs, transcripts, network, want_stats, wa
                          n_states=tuple(network.n_states))
 
 
-def _refuse_stats(network):
+def _run_embed_full(logb, feats, offs_dev, offs, transcripts, network, want_post) -> EmbeddedStats:
+    """One ``sapr_connected_embed_full`` over device ``logb[total_frames, R]`` and device ``feats``."""
+    torch = _torch()
+    dev = logb.device
+    n_utts, total = int(offs.size - 1), int(offs[-1])
+    words, word_offs, max_words = _transcripts(transcripts, n_utts, network)
+    total_words = int(word_offs[-1])
+    D = int(feats.shape[1])
+    ls, lt, lx, _ = network.device(dev)
+    words_dev = torch.from_numpy(words).to(dev)
+    word_offs_dev = torch.from_numpy(word_offs).to(dev)
+    ws_bytes = embed_full_workspace_bytes(total, n_utts, total_words, max_words, network.W, network.S, D)
+    workspace = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    loglik = torch.empty(n_utts, dtype=torch.float64, device=dev)
+    stats = torch.empty((network.W, embed_full_stats_width(network.S, D)), dtype=torch.float64, device=dev)
+    post = torch.zeros((total, max_words * network.SP), dtype=torch.float64, device=dev) if want_post else None
+    _lib.check(_lib.load().sapr_connected_embed_full(
+        _lib.ptr(logb), _lib.ptr(feats), D, _lib.ptr(offs_dev), n_utts, total, _lib.ptr(words_dev),
+        _lib.ptr(word_offs_dev), total_words, max_words, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx),
+        network.word_penalty, network.W, network.S, _lib.ptr(workspace), ws_bytes, _lib.ptr(loglik), _lib.ptr(stats),
+        _lib.ptr(post), _lib.current_stream()), "sapr_connected_embed_full")
+    host = [None if a is None else a.cpu().numpy() for a in (loglik, stats, post)]
+    return EmbeddedStats(*host, offsets=offs, word_offsets=word_offs, words=words, S=network.S, SP=network.SP, D=D,
+                         n_states=tuple(network.n_states), layout="full")
+
+
+def _refuse_stats(network, second_moments=False):
+    if second_moments:
+        if network.family == "gmm":
+            raise NotImplementedError(
+                "embedded statistics with second_moments=True are served for the 'diag' and 'full' families; the "
+                "'gmm' family needs mixture responsibilities (loglik and post are served: want_stats=False)")
+        return
     if network.family != "diag":
         raise NotImplementedError(
             f"embedded statistics are served for the 'diag' family; the {network.family!r} family needs "
@@ -591,14 +650,18 @@ def _refuse_stats(network):
 
 
 def embedded_forward_backward(logb, lengths, transcripts, network: ConnectedNetwork, feats=None,
-                              want_post=False) -> EmbeddedStats:
+                              want_post=False, second_moments=False) -> EmbeddedStats:
     """Forward-backward over every utterance's transcript chain on a given ``logb`` (the shapes
     :func:`connected_viterbi` takes) — the counterpart of :func:`align_viterbi`.  ``feats``: the float32 frames
     ``[total_frames, D]`` (host array or device tensor) for the ``obs`` blocks of the statistics; without them the
-    statistics carry ``start``, ``trans``, ``post`` and ``nobs`` only.  The definition is ``tests/_embedded_ref.py``."""
+    statistics carry ``start``, ``trans``, ``post`` and ``nobs`` only.  The definition is ``tests/_embedded_ref.py``.
+    ``second_moments=True`` (needs ``feats``): the rows carry ``obs*obs.T`` in place of ``obs**2``
+    (``sapr_connected_embed_full``; definition ``tests/_embedded_full_ref.py``)."""
     torch = _torch()
     lengths, offs = _offsets(lengths)
     _transcripts(transcripts, int(lengths.size), network)  # (refused before a device is asked for)
+    if second_moments and (feats is None or np.ndim(feats) != 2 or int(np.shape(feats)[1]) == 0):
+        raise ValueError("second_moments=True needs the frames: feats [sum(lengths), D] with D >= 1")
     dev = _lib.require_gpu()
     total = int(offs[-1])
     logb = _flat_logb(logb, total, network, dev)
@@ -610,46 +673,76 @@ def embedded_forward_backward(logb, lengths, transcripts, network: ConnectedNetw
             raise ValueError("feats must be float32 [sum(lengths), D]")
         if int(feats.shape[1]) == 0:
             feats = None
-    return _run_embed(logb, feats, torch.from_numpy(offs).to(dev), offs, transcripts, network, True, want_post)
+    return _run_embed(logb, feats, torch.from_numpy(offs).to(dev), offs, transcripts, network, True, want_post,
+                      second_moments)
 
 
 def embedded_estep(batch_or_feature_list, transcripts, network: ConnectedNetwork, want_post=False,
-                   want_stats=True) -> EmbeddedStats:
+                   want_stats=True, second_moments=False) -> EmbeddedStats:
     """Emission (by the network's family) and forward-backward over the transcript chains — the counterpart of
     :func:`connected_align`.  ``loglik`` and ``post`` are served for all three families; the statistics for "diag"
-    (for "gmm" and "full" asking for them raises ``NotImplementedError``: pass ``want_stats=False``)."""
+    (for "gmm" and "full" asking for them raises ``NotImplementedError``: pass ``want_stats=False``).  With
+    ``second_moments=True`` the statistics of a "diag" or "full" network carry ``obs*obs.T``
+    (``sapr_connected_embed_full``), what the M-step of a "full" or "tied" model reads; a "gmm" network is still
+    refused: its statistics need mixture responsibilities."""
     b = batch_or_feature_list
     n_utts = len(b.lengths) if hasattr(b, "offsets") and hasattr(b, "order") else len(b)
     _transcripts(transcripts, n_utts, network)  # (refused before a device is asked for)
     if want_stats:
-        _refuse_stats(network)
+        _refuse_stats(network, second_moments)
     feats, offs_dev, offs = _features(b)
     logb = _EMIT[network.family](feats, network)
-    return _run_embed(logb, feats if want_stats else None, offs_dev, offs, transcripts, network, want_stats, want_post)
+    return _run_embed(logb, feats if want_stats else None, offs_dev, offs, transcripts, network, want_stats, want_post,
+                      second_moments)
+
+
+def _diag_of_moments(st, covariance_type):
+    """The statistics dict the M-step of ``covariance_type`` reads, from a row with ``obs*obs.T``: a "diag" or
+    "spherical" member of a mixed vocabulary takes ``obs**2`` = the diagonal of each matrix (the float64 square of
+    the widened frame, where the all-diagonal route adds the float32 square: one ulp of float32 per term)."""
+    if covariance_type in ("diag", "spherical"):
+        st = dict(st)
+        st["obs**2"] = np.ascontiguousarray(np.diagonal(st["obs*obs.T"], axis1=1, axis2=2))
+    return st
 
 
 def embedded_fit(models, features, transcripts, n_iter=10, tol=1e-2, exit_states="last", word_penalty=0.0,
-                 names=None):
-    """Embedded Baum-Welch: train the word models of a "diag" / "spherical" ``GaussianHMM`` vocabulary in place from
-    recordings of several words (``features``: frame-major ``(T, D)`` arrays) and their transcripts (vocabulary
-    indices), without cutting the recordings.  Each iteration: ``ConnectedNetwork.from_models``, the emission, the
-    E-step, then ``hmmlearn_hmm.m_step_typed`` per model with the model's own hyper-parameters; a word that never
-    occurs (in an utterance with a path) stays untouched.  One ``ConvergenceMonitor`` runs on the sum of ``loglik``
-    over the utterances with a path; returns its history as a list."""
+                 names=None, second_moments=False):
+    """Embedded Baum-Welch: train the word models of a ``GaussianHMM`` vocabulary in place from recordings of several
+    words (``features``: frame-major ``(T, D)`` arrays) and their transcripts (vocabulary indices), without cutting
+    the recordings.  Each iteration: ``ConnectedNetwork.from_models``, the emission, the E-step, then
+    ``hmmlearn_hmm.m_step_typed`` per model with the model's own covariance type and hyper-parameters; a word that
+    never occurs (in an utterance with a path) stays untouched.  One ``ConvergenceMonitor`` runs on the sum of
+    ``loglik`` over the utterances with a path; returns its history as a list.
+
+    ``second_moments=False`` serves "diag" / "spherical" vocabularies (``sapr_connected_embed``).  With
+    ``second_moments=True`` any ``GaussianHMM`` vocabulary trains, "full" and "tied" members included: the E-step is
+    ``sapr_connected_embed_full``, a "tied" model ends with one ``(D, D)`` matrix, and a "diag" / "spherical" member
+    reads the diagonal of its second-moment matrices."""
     from .hmmlearn_hmm import ConvergenceMonitor, m_step_typed
     models = list(models)
-    if vocabulary_family(models, names, "hmmlearn") != "diag":
-        raise ValueError("embedded_fit serves 'diag' and 'spherical' GaussianHMM vocabularies: a 'full' or 'tied' "
-                         "model needs second-moment matrices the embedded E-step does not accumulate")
-    net = ConnectedNetwork.from_models(models, exit_states, word_penalty, names, "hmmlearn")
+    family = vocabulary_family(models, names, "hmmlearn")
+    if family != "diag" and not second_moments:
+        raise ValueError("embedded_fit serves 'diag' and 'spherical' GaussianHMM vocabularies by default: a 'full' or "
+                         "'tied' model needs second-moment matrices, which second_moments=True accumulates")
+    def network():
+        # (packing a 'full' vocabulary validates every model and notes what it found on the object: done on shallow
+        # copies, so that a word that is never trained keeps its bytes)
+        return ConnectedNetwork.from_models(models if family == "diag" else [copy.copy(m) for m in models],
+                                            exit_states, word_penalty, names, "hmmlearn")
+
+    net = network()
     _transcripts(transcripts, len(features), net)  # (refused before a device is asked for)
     feats, offs_dev, offs = _features(features)
     monitor = ConvergenceMonitor(tol, n_iter)
     for _ in range(n_iter):
-        net = ConnectedNetwork.from_models(models, exit_states, word_penalty, names, "hmmlearn")
-        res = _run_embed(emit_diag(feats, net), feats, offs_dev, offs, transcripts, net, True, False)
+        net = network()
+        res = _run_embed(_EMIT[net.family](feats, net), feats, offs_dev, offs, transcripts, net, True, False,
+                         second_moments)
         for w, m in enumerate(models):
             st = res.split(w)
+            if second_moments:
+                st = _diag_of_moments(st, m.covariance_type)
             if st["nobs"] == 0:
                 continue
             m.startprob_, m.transmat_, m.means_, m._covars_ = m_step_typed(

@@ -26,6 +26,8 @@
 //   is the float32 square, as in estep.hip), t ascending, into the per-slot partial rows.
 // embed_fold_chunk_kernel, embed_fold_kernel: stats[w][e] = the sum over the counted slots n with words[n] == w, in two
 //   levels with fixed boundaries (chunks of 256 slots, n ascending; then the chunks, ascending).
+// embed_full_accum_kernel<DP>, embed_full_fold_kernel (sapr_connected_embed_full): the second moments sum gamma x x^T
+//   per word model on the float64 matrix cores, behind the same recursions; described where they stand.
 //
 // No atomics anywhere; an utterance's outputs are a function of its own frames, its own transcript and the network, and
 // the fold adds in slot order: two calls return the same bytes.  Every index is clamped into its row and offsets that
@@ -664,6 +666,199 @@ int launch_recursions(const EmArgs &a, const EmWorkspace &ws, int32_t part_width
   return backward ? launch_backward<4, SP>(a, ws, part_width, loglik, post, stream) : 0;
 }
 
+// ---- second moments over the chain posteriors (sapr_connected_embed_full) ----------------------------------------
+// embed_full_accum_kernel<DP>: obs[w][s] = sum gamma_t(k, s) x_t and oo[w][s] = sum gamma_t(k, s) x_t x_t^T over the
+//   slots k with w_k = w, as the weighted Gram products of full_accum_kernel (fullcov_ops.h) on the float64 matrix
+//   cores: four frames per v_mfma_f64_16x16x4_f64, A = g x[a], B = x[b], the constant 1 in column DP of B carries obs;
+//   only the 16 x 16 tiles on or above the diagonal.  Grid (utterance group, word w); the workgroup walks its group's
+//   utterances in ascending order and leaves out, uniformly, those without a path, with a likelihood that is not
+//   finite (their gamma rows were never written: nothing of them is read) and those whose transcript lacks w.  Four
+//   states per pass, one per wavefront; per chunk of 64 frames the weights g_t(w, s) = sum_{k: w_k = w, k ascending}
+//   gamma_t(k, s) of the pass's four states are collapsed while they are staged into LDS; a chunk, and inside it a
+//   4-frame step, whose weights are all exactly 0.0 is skipped (adding +0.0 changes no bit of a sum that started at
+//   +0.0) — slot k's posterior mass sits in its own stretch of the recording.  One partial row {obs[S][D],
+//   oo[S][D][D]} per (group, w), every element of it written.
+// embed_full_fold_kernel: stats[w] = {the head sapr_connected_embed folded, the partial rows added group ascending}.
+constexpr int kEmFullGroupUtts = 8;    // utterances of one group (fixed: with kEmFullMaxGroups it fixes the order)
+constexpr int kEmFullMaxGroups = 96;   // beyond 8 * 96 utterances the groups grow instead of their number
+constexpr int kEmFullChunk = 64;       // frames staged at once
+constexpr int kEmFullGS = 5;           // LDS row stride of the staged weights (doubles), odd
+
+typedef double f64x4_em __attribute__((ext_vector_type(4)));
+
+inline int64_t em_full_group_utts(int64_t n_utts) {
+  const int64_t spread = (n_utts + kEmFullMaxGroups - 1) / kEmFullMaxGroups;
+  return spread > kEmFullGroupUtts ? spread : kEmFullGroupUtts;
+}
+
+inline int64_t em_full_groups(int64_t n_utts) {
+  const int64_t per = em_full_group_utts(n_utts);
+  return (n_utts + per - 1) / per;
+}
+
+inline size_t em_head_width(int S) { return static_cast<size_t>(2 + S + S * S + S); }
+inline size_t em_full_p(int S, int D) { return static_cast<size_t>(S) * D + static_cast<size_t>(S) * D * D; }
+
+struct EmFullWorkspace {
+  size_t base_bytes;  // what sapr_connected_embed takes at D = 0 (alpha / gamma first)
+  double *head;       // [W][2 + S + S * S + S]
+  double *part;       // [groups][W][S * D + S * D * D]
+  size_t bytes;
+};
+
+inline EmFullWorkspace em_full_carve(void *base, int64_t total_frames, int64_t n_utts, int64_t total_words,
+                                     int32_t max_words, int W, int S, int D) {
+  EmFullWorkspace w;
+  uint8_t *p = static_cast<uint8_t *>(base);
+  w.base_bytes = em_carve(nullptr, total_frames, total_words, max_words, S, 0).bytes;
+  const size_t h = em_align16(static_cast<size_t>(W) * em_head_width(S) * sizeof(double));
+  const size_t f = em_align16(static_cast<size_t>(em_full_groups(n_utts)) * W * em_full_p(S, D) * sizeof(double));
+  w.head = reinterpret_cast<double *>(p + w.base_bytes);
+  w.part = reinterpret_cast<double *>(p + w.base_bytes + h);
+  w.bytes = w.base_bytes + h + f;
+  return w;
+}
+
+template <int DP>
+__global__ __launch_bounds__(kEmBlock) void embed_full_accum_kernel(
+    const double *__restrict__ gamma, const float *__restrict__ feats, int32_t D, const int64_t *__restrict__ offsets,
+    int64_t n_utts, int64_t total_frames, const int32_t *__restrict__ words, const int64_t *__restrict__ word_offsets,
+    int64_t total_words, int32_t max_words, int32_t W, int32_t S, int32_t SP, int64_t group_utts,
+    const double *__restrict__ loglik, double *__restrict__ part) {
+  constexpr int NT = (DP + 1 + 15) / 16;       // 16-wide tiles per side: x[0..DP) and the constant 1 at column DP
+  constexpr int NTU = NT * (NT + 1) / 2;       // tiles on or above the diagonal
+  constexpr int XS = NT == 2 ? 48 : 16 * NT;   // LDS row stride (doubles): four consecutive rows on distinct banks
+  constexpr int GS = kEmFullGS;
+  constexpr int T1 = DP / 16, N1 = DP % 16;    // where the constant 1 sits
+  constexpr int NI = kEmFullChunk * XS / kEmBlock;  // staged features per thread and chunk
+  static_assert(NI * kEmBlock == kEmFullChunk * XS, "the staging loop covers the chunk exactly");
+  static_assert(kEmFullChunk * 4 == kEmBlock, "one staged weight per thread: 64 frames x the pass's four states");
+  __shared__ double s_x[kEmFullChunk * XS];
+  __shared__ double s_g[kEmFullChunk * GS];
+
+  const int tid = threadIdx.x, lane = tid & 63, n = lane & 15, k = lane >> 4;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int64_t grp = blockIdx.x;
+  const int w = blockIdx.y;
+  const int64_t u_lo = grp * group_utts;
+  const int64_t u_hi = u_lo + group_utts < n_utts ? u_lo + group_utts : n_utts;
+  const int MP = max_words * SP;
+  const int sf = tid >> 2, sj = tid & 3;  // the weight this thread stages: frame of the chunk, state of the pass
+  double *__restrict__ out = part + (grp * W + w) * static_cast<int64_t>(S * D + S * D * D);
+  double *__restrict__ out_oo = out + S * D;
+
+  // four states at a time, one per wavefront, over all of the group's utterances: the accumulators of ONE state live
+  // in a wavefront's registers (the features are staged again for every pass, from L2)
+  for (int g = 0; g * 4 < S; ++g) {  // (uniform trip counts: every thread reaches the barriers)
+    const int s = g * 4 + wv;
+    f64x4_em acc[NTU];
+#pragma unroll
+    for (int tau = 0; tau < NTU; ++tau) acc[tau] = f64x4_em{0.0, 0.0, 0.0, 0.0};
+    for (int64_t u = u_lo; u < u_hi; ++u) {
+      const EmUtt ut = em_utt(offsets, total_frames, word_offsets, total_words, max_words, u);
+      // (a finite likelihood was written only for 0 < K <= max_words, T > 0 and words inside the vocabulary; the
+      // gamma rows of every other utterance hold whatever the workspace held: left out, not multiplied by zero)
+      if (!ut.path || !finite_f64(loglik[u])) continue;  // (uniform)
+      const int wd = lane < ut.K ? words[ut.wbeg + lane] : -1;
+      const uint64_t slots = __ballot(wd == w);  // the slots of word w (the same in every wavefront)
+      if (slots == 0) continue;
+      const double *__restrict__ gu = gamma + ut.beg * MP;
+      const float *__restrict__ xu = feats + ut.beg * D;
+      for (int64_t c0 = 0; c0 < ut.T; c0 += kEmFullChunk) {
+        {  // g_t(w, s) of the pass's states, the slots collapsed k ascending; 0.0 selected behind the utterance's end
+          const int64_t t = c0 + sf;
+          const int st = g * 4 + sj;
+          const bool live = t < ut.T && st < S;
+          const double *__restrict__ src = gu + (live ? t : 0) * MP + (live ? st : 0);  // (dead: a valid address)
+          double gw = 0.0;
+          for (uint64_t m = slots; m; m &= m - 1) gw += src[__builtin_ctzll(m) * SP];
+          gw = live ? gw : 0.0;
+          s_g[sf * GS + sj] = gw;
+          if (!__syncthreads_or(gw != 0.0)) continue;  // (uniform) nothing of word w in these frames
+        }
+        // the chunk's frames into LDS as float64: columns [0, D) the features, column DP the ones behind obs, zeros
+        // elsewhere and in the rows past the utterance's last frame; every load is issued before the first is used
+        float xv[NI];
+#pragma unroll
+        for (int q = 0; q < NI; ++q) {
+          const int item = tid + q * kEmBlock, f = item / XS, col = item - f * XS;
+          const int64_t t = c0 + f;
+          xv[q] = xu[(t < ut.T && col < D) ? t * D + col : 0];
+        }
+#pragma unroll
+        for (int q = 0; q < NI; ++q) {
+          const int item = tid + q * kEmBlock, f = item / XS, col = item - f * XS;
+          const bool live = c0 + f < ut.T;
+          s_x[item] = live ? (col < D ? static_cast<double>(xv[q]) : (col == DP ? 1.0 : 0.0)) : 0.0;
+        }
+        __syncthreads();
+        if (s < S) {  // (uniform)
+          for (int step = 0; step < kEmFullChunk / 4; ++step) {
+            // A and B of the float64 MFMA: lane & 15 = row (column), lane >> 4 = the K index, here the frame
+            const int f = 4 * step + k;
+            const double gm = s_g[f * GS + wv];
+            if (__ballot(gm != 0.0) == 0) continue;  // (wavefront-uniform) four frames that add exact zeros
+            double xa[NT], xb[NT];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+              xb[t] = s_x[f * XS + 16 * t + n];
+              xa[t] = gm * xb[t];
+            }
+            int tau = 0;
+#pragma unroll
+            for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+              for (int tj = ti; tj < NT; ++tj, ++tau)
+                acc[tau] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[ti], xb[tj], acc[tau], 0, 0, 0);
+          }
+        }
+        __syncthreads();
+      }
+    }
+    if (s < S) {
+      // C of the float64 MFMA: column = lane & 15, row = (lane >> 4) + 4 * register.  The entries on or above the
+      // diagonal go to both halves of oo[s]; column DP of the last tile column is obs[s]
+      int tau = 0;
+#pragma unroll
+      for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+        for (int tj = ti; tj < NT; ++tj, ++tau)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int a = 16 * ti + k + 4 * r, bc = 16 * tj + n;
+            const double v = acc[tau][r];
+            if (a < D) {
+              if (bc < D && a <= bc) {
+                out_oo[(static_cast<int64_t>(s) * D + a) * D + bc] = v;
+                out_oo[(static_cast<int64_t>(s) * D + bc) * D + a] = v;
+              }
+              if (tj == T1 && n == N1) out[s * D + a] = v;
+            }
+          }
+    }
+  }
+}
+
+// stats[w][e]: the head as sapr_connected_embed folded it, then {obs[S][D], oo[S][D][D]} = the sum over the groups'
+// partial rows, group ascending; one thread per element
+__global__ __launch_bounds__(kEmBlock) void embed_full_fold_kernel(const double *__restrict__ head,
+                                                                   const double *__restrict__ part, int64_t groups,
+                                                                   int32_t W, int32_t head_width, int32_t P,
+                                                                   double *__restrict__ stats) {
+  const int e = blockIdx.x * kEmBlock + threadIdx.x;
+  const int w = blockIdx.y;
+  const int width = head_width + P;
+  if (e >= width) return;
+  double sum;
+  if (e < head_width) {
+    sum = head[static_cast<int64_t>(w) * head_width + e];
+  } else {
+    sum = 0.0;
+    for (int64_t g = 0; g < groups; ++g) sum += part[(g * W + w) * static_cast<int64_t>(P) + (e - head_width)];
+  }
+  stats[static_cast<int64_t>(w) * width + e] = sum;
+}
+
 }  // namespace
 }  // namespace sapr
 
@@ -742,6 +937,77 @@ extern "C" int sapr_connected_embed(const double *logb, const float *feats, int3
   }
   SAPR_LAUNCH(embed_fold_kernel, dim3(tiles, static_cast<unsigned>(W)), dim3(kEmBlock), 0, st, ws.fold, chunks, W,
               width, stats);
+  SAPR_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int sapr_connected_embed_full_stats_width(int32_t S, int32_t D, int32_t *width) {
+  SAPR_REQUIRE(width && S > 0 && D >= 0, "bad sizes (S=%d D=%d)", S, D);
+  if (int rc = em_check_shape(1, S, 1)) return rc;
+  if (int rc = em_check_dims(D)) return rc;
+  *width = static_cast<int32_t>(em_head_width(S) + em_full_p(S, D));
+  return 0;
+}
+
+extern "C" int sapr_connected_embed_full_workspace_bytes(int64_t total_frames, int64_t n_utts, int64_t total_words,
+                                                         int32_t max_words, int32_t W, int32_t S, int32_t D,
+                                                         size_t *bytes) {
+  SAPR_REQUIRE(bytes && total_frames >= 0 && n_utts >= 0 && total_words >= 0 && max_words > 0 && W > 0 && S > 0 &&
+                   D >= 0,
+               "bad sizes (total_frames=%lld n_utts=%lld total_words=%lld max_words=%d W=%d S=%d D=%d)",
+               (long long)total_frames, (long long)n_utts, (long long)total_words, max_words, W, S, D);
+  if (int rc = em_check_shape(W, S, max_words)) return rc;
+  if (int rc = em_check_dims(D)) return rc;
+  *bytes = em_full_carve(nullptr, total_frames, n_utts, total_words, max_words, W, S, D).bytes;
+  return 0;
+}
+
+extern "C" int sapr_connected_embed_full(const double *logb, const float *feats, int32_t D, const int64_t *offsets,
+                                         int64_t n_utts, int64_t total_frames, const int32_t *words,
+                                         const int64_t *word_offsets, int64_t total_words, int32_t max_words,
+                                         const double *log_start, const double *log_trans, const double *log_exit,
+                                         double word_penalty, int32_t W, int32_t S, void *workspace,
+                                         size_t workspace_bytes, double *loglik, double *stats, double *post,
+                                         void *stream) {
+  SAPR_REQUIRE(n_utts >= 0 && total_frames >= 0 && total_words >= 0 && max_words > 0 && W > 0 && S > 0 && D >= 0,
+               "bad sizes (n_utts=%lld total_frames=%lld total_words=%lld max_words=%d W=%d S=%d D=%d)",
+               (long long)n_utts, (long long)total_frames, (long long)total_words, max_words, W, S, D);
+  if (int rc = em_check_shape(W, S, max_words)) return rc;
+  if (int rc = em_check_dims(D)) return rc;
+  size_t need = 0;
+  if (int rc = sapr_connected_embed_full_workspace_bytes(total_frames, n_utts, total_words, max_words, W, S, D, &need))
+    return rc;
+  SAPR_REQUIRE(workspace_bytes >= need && (need == 0 || workspace), "workspace too small: %zu < %zu", workspace_bytes,
+               need);
+  SAPR_REQUIRE(!stats || D >= 1, "the second moments need D >= 1 (got D=%d)", D);
+  SAPR_REQUIRE(!stats || n_utts == 0 || total_frames == 0 || feats, "NULL pointer argument");
+  const EmFullWorkspace ws = em_full_carve(workspace, total_frames, n_utts, total_words, max_words, W, S, D);
+  // the recursions, loglik, post and the head of the row: sapr_connected_embed itself on the front of the workspace,
+  // without features (the head does not depend on them); gamma stays behind in the workspace
+  if (int rc = sapr_connected_embed(logb, nullptr, 0, offsets, n_utts, total_frames, words, word_offsets, total_words,
+                                    max_words, log_start, log_trans, log_exit, word_penalty, W, S, workspace,
+                                    ws.base_bytes, loglik, stats ? ws.head : nullptr, post, stream))
+    return rc;
+  if (n_utts == 0 || !stats) return 0;
+  hipStream_t st = as_stream(stream);
+  const int32_t SP = sp_of(S);
+  const int64_t groups = em_full_groups(n_utts), per = em_full_group_utts(n_utts);
+  const double *gamma = static_cast<const double *>(workspace);
+  const dim3 grid(static_cast<unsigned>(groups), static_cast<unsigned>(W));
+#define SAPR_EM_FULL_ACCUM(DP)                                                                                        \
+  SAPR_LAUNCH(embed_full_accum_kernel<DP>, grid, dim3(kEmBlock), 0, st, gamma, feats, D, offsets, n_utts,            \
+              total_frames, words, word_offsets, total_words, max_words, W, S, SP, per, loglik, ws.part)
+  switch (dp_of(D)) {
+    case 13: SAPR_EM_FULL_ACCUM(13); break;
+    case 26: SAPR_EM_FULL_ACCUM(26); break;
+    default: SAPR_EM_FULL_ACCUM(39); break;
+  }
+#undef SAPR_EM_FULL_ACCUM
+  SAPR_HIP_TRY(hipGetLastError());
+  const int32_t hw = static_cast<int32_t>(em_head_width(S)), P = static_cast<int32_t>(em_full_p(S, D));
+  const unsigned tiles = static_cast<unsigned>((hw + P + kEmBlock - 1) / kEmBlock);
+  SAPR_LAUNCH(embed_full_fold_kernel, dim3(tiles, static_cast<unsigned>(W)), dim3(kEmBlock), 0, st, ws.head, ws.part,
+              groups, W, hw, P, stats);
   SAPR_HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -196,16 +196,15 @@ class Decoder:
         history of the summed log-likelihood, one entry per iteration.  A word that is in no transcript keeps its
         parameters.
 
-        Served for ``implementation="hmmlearn"`` over "diag" / "spherical" models; anything else is refused with a
+        Served for ``implementation="hmmlearn"``: "diag" / "spherical" vocabularies through ``sapr_connected_embed``,
+        a vocabulary that holds a "full" or "tied" model through ``sapr_connected_embed_full`` (second-moment
+        matrices; ``embedded_fit(..., second_moments=True)``).  Another implementation is refused with a
         ``ValueError`` that says why.  A word that is not in the vocabulary is refused with a ``ValueError`` that
         names it."""
         if self.implementation != "hmmlearn":
-            raise ValueError(f"embedded training needs implementation='hmmlearn' with 'diag' or 'spherical' models: "
-                             f"the embedded E-step accumulates single-Gaussian diagonal statistics, not those of "
+            raise ValueError(f"embedded training needs implementation='hmmlearn' (GaussianHMM word models): "
+                             f"the embedded E-step accumulates single-Gaussian statistics, not those of "
                              f"implementation={self.implementation!r}")
-        if self._is_full():
-            raise ValueError("embedded training serves 'diag' and 'spherical' models: this vocabulary holds a 'full' "
-                             "or 'tied' model, whose M-step needs second-moment matrices")
         from .connected import embedded_fit
         if len(feature_list) == 0:
             raise ValueError("empty utterance list")
@@ -219,7 +218,8 @@ class Decoder:
                                      f"({', '.join(words)})")
             rows.append([index[name] for name in names])
         history = embedded_fit(self._model_list(), [np.asarray(f).T for f in feature_list], rows, n_iter=n_iter,
-                               tol=tol, exit_states=exit_states, word_penalty=word_penalty, names=words)
+                               tol=tol, exit_states=exit_states, word_penalty=word_penalty, names=words,
+                               second_moments=self._is_full())
         self._pack = self._vocab = None  # (packed from the old parameters)
         return history
 
