@@ -181,13 +181,22 @@ struct MfccDev {
 };
 
 constexpr int kMaxSlices = 32;  // utterance slices of one batch (SAPR_MFCC_SLICES is clamped to it)
+// Default slice count (a power of two, halved until a batch is large enough).  Every slice but the last hides its finish
+// pass, so the exposed one shrinks with the slice count (0.20 ms of two, 0.10 ms of four, 0.05 ms of eight at 100 000
+// utterances), while every further spectral launch costs 0.01 ms of kernel time and a 7-us gap: four is where the sum is
+// least for the <10, false> finish body.  The body with deltas runs three wavefronts per SIMD for longer beside a
+// spectral launch and loses 0.1 ms with four; it and the generic body, which was not measured with four, keep two
+// (the tables the defaults were set from).
 #ifndef SAPR_MFCC_DEFAULT_SLICES
 #define SAPR_MFCC_DEFAULT_SLICES 2
+#endif
+#ifndef SAPR_MFCC_DEFAULT_SLICES_S
+#define SAPR_MFCC_DEFAULT_SLICES_S 4  // plans whose finish body is <10, false>
 #endif
 #ifndef SAPR_MFCC_SLICE_MIN_SETS
 #define SAPR_MFCC_SLICE_MIN_SETS 64
 #endif
-constexpr int kDefaultSlices = SAPR_MFCC_DEFAULT_SLICES;  // power of two (halved until a batch is large enough)
+constexpr int kDefaultSlices = SAPR_MFCC_DEFAULT_SLICES, kDefaultSlicesS = SAPR_MFCC_DEFAULT_SLICES_S;
 constexpr int kSliceMinSets = SAPR_MFCC_SLICE_MIN_SETS;   // 4-frame sets per spectral wavefront and slice
 #ifndef SAPR_FINISH_BESIDE_MAX
 #define SAPR_FINISH_BESIDE_MAX 8
@@ -212,6 +221,7 @@ struct MfccPlan {
   // and under SAPR_FINISH_GENERIC=1 at plan creation; finish_occ = its wavefronts per SIMD = workgroups per CU
   FinishKernel finish_kernel = nullptr;
   int finish_occ = 0;
+  int default_slices = kDefaultSlices;  // slices of a large batch where SAPR_MFCC_SLICES does not say
   mutable std::mutex side_mu;       // the stream and the events below serve one sapr_mfcc_batch call at a time
   mutable bool side_tried = false;  // created on the first call that cuts a batch
   mutable hipStream_t side = nullptr;
@@ -1485,6 +1495,7 @@ extern "C" int sapr_mfcc_plan_create(double sr, int32_t n_fft, int32_t win_lengt
     if (!finish_generic && d.n_mels == 40) {
       pl->finish_kernel = d.deltas ? &mfcc_wave_finish_kernel<10, true> : &mfcc_wave_finish_kernel<10, false>;
       pl->finish_occ = finish_occ(10, d.deltas != 0);
+      if (!d.deltas) pl->default_slices = kDefaultSlicesS;
     }
     // finish workgroups per CU of a launch beside a spectral grid: what fits into the LDS the resident spectral
     // workgroups leave free (both rounded up to the allocation granule, 320 dwords on gfx950), at least 1, at most the
@@ -1639,7 +1650,7 @@ extern "C" int sapr_mfcc_batch(const void *plan, const float *pcm, const int64_t
       } else {
         // default: every slice keeps the finish pass at one wavefront per utterance (fsplit == 1, as in the single
         // launch of a batch this size) and gives each spectral wavefront at least kSliceMinSets sets per launch
-        n_slices = kDefaultSlices;
+        n_slices = pl->default_slices;
         const int64_t fwaves = static_cast<int64_t>(finish_grid) * kWaves;
         while (n_slices > 1 && (n_utts / n_slices < fwaves || total_frames / n_slices < 4 * kSliceMinSets * n_waves_full))
           n_slices >>= 1;
