@@ -617,6 +617,37 @@ int sapr_connected_embed_full(const double *logb, const float *feats /* [total_f
                               double *loglik /* [n_utts] */, double *stats /* [W][width] or NULL */,
                               double *post /* [total_frames][max_words*SP] or NULL */, void *stream);
 
+/* The same E-step with mixture responsibilities, for Gaussian-mixture word models (GMMHMM; definition:
+ * tests/_embedded_gmm_ref.py).  With x_t the float32 frame widened to float64, lc[t][w][s][m] the component log-terms
+ * of word w (the formula of sapr_gmm_estep_diag) and g_t(w,s) = sum over the slots k with w_k = w of gamma_t(k,s),
+ *     r_t(w,s,m)        = g_t(w,s) exp(lc - max_m lc) / sum_m exp(lc - max_m lc)   (0 where every component is off)
+ *     post_mix[w][s][m] = sum r     obs[w][s][m] = sum r x_t     obs2[w][s][m] = sum r f64(RN32(x_t x_t))
+ * over the utterances with a finite loglik and all their frames.  pack is the [W][sapr_gmm_pack_layout(S, M, D)] block
+ * sapr_connected_emit_gmm read, in place; the other arguments are those of sapr_connected_embed, in its order; loglik
+ * and post are exactly its results, and so is the head of a statistics row, byte for byte.
+ *   workspace     sapr_connected_embed_gmm_workspace_bytes: what sapr_connected_embed takes at D = 0, W heads of
+ *                 2 + S + S*S + S float64, and one partial row of S*M*(2 D + 1) float64 per (utterance group, word),
+ *                 the groups being those of sapr_connected_embed_full; each block rounded up to 16
+ *   stats         [W][width], width = sapr_connected_embed_gmm_stats_width(S, M, D) (== sapr_gmm_stats_width):
+ *                 {nobs, reserved 0.0, start[S], trans[S][S], post[S], post_mix[S][M], obs[S][M][D], obs2[S][M][D]}
+ *                 per word model, the row of sapr_gmm_estep_diag; or NULL.  stats != NULL needs D >= 1, feats and pack
+ * The sums r^T [x, x^2, 1] run on the float64 matrix cores, utterances ascending inside a group; the groups' partial
+ * rows are added in ascending order.  No atomics: outputs are bit-identical from run to run.  An utterance without a
+ * path contributes exact zeros — its posterior rows in the workspace are never read.  Argument checks, limits and error
+ * codes are those of sapr_connected_embed, with M > 8 unsupported. */
+int sapr_connected_embed_gmm_stats_width(int32_t S, int32_t M, int32_t D, int32_t *width);
+int sapr_connected_embed_gmm_workspace_bytes(int64_t total_frames, int64_t n_utts, int64_t total_words,
+                                             int32_t max_words, int32_t W, int32_t S, int32_t M, int32_t D,
+                                             size_t *bytes);
+int sapr_connected_embed_gmm(const double *logb, const float *feats /* [total_frames][D] */, int32_t D,
+                             const double *pack /* [W][sapr_gmm_pack_layout(S, M, D)] */, int32_t M,
+                             const int64_t *offsets, int64_t n_utts, int64_t total_frames, const int32_t *words,
+                             const int64_t *word_offsets, int64_t total_words, int32_t max_words,
+                             const double *log_start, const double *log_trans, const double *log_exit,
+                             double word_penalty, int32_t W, int32_t S, void *workspace, size_t workspace_bytes,
+                             double *loglik /* [n_utts] */, double *stats /* [W][width] or NULL */,
+                             double *post /* [total_frames][max_words*SP] or NULL */, void *stream);
+
 /* Flat start of HMMLearnModel (hmmlearn_hmm.py:83-94: np.mean / np.var over axis 0 of the concatenated float32
  * features): numpy adds row after row in float32, so each column is one sequential float32 chain — reproduced
  * bit for bit.  center == NULL: out[d] = sum_r x[r][d]; else out[d] = sum_r RN32(RN32(x[r][d] - center[d])^2).

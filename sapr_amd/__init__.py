@@ -25,14 +25,16 @@ def __getattr__(name):
     / ``sapr_amd.ConnectedNetwork`` / ``sapr_amd.connected_viterbi`` / ``sapr_amd.connected_decode`` /
     ``sapr_amd.AlignResult`` / ``sapr_amd.align_viterbi`` / ``sapr_amd.connected_align`` /
     ``sapr_amd.EmbeddedStats`` / ``sapr_amd.embedded_forward_backward`` / ``sapr_amd.embedded_estep`` /
-    ``sapr_amd.embedded_fit`` / ``sapr_amd.embed_full_stats_width`` / ``sapr_amd.embed_full_workspace_bytes``
+    ``sapr_amd.embedded_fit`` / ``sapr_amd.embed_full_stats_width`` / ``sapr_amd.embed_full_workspace_bytes`` /
+    ``sapr_amd.embed_gmm_stats_width`` / ``sapr_amd.embed_gmm_workspace_bytes``
     (resolved on first use: importing the package stays light)."""
     if name in ("GMMHMM", "fit_gmm_models", "vocab_scores"):
         from . import gmm_hmm
         return getattr(gmm_hmm, name)
     if name in ("ConnectedNetwork", "ConnectedResult", "connected_viterbi", "connected_decode", "AlignResult",
                 "align_viterbi", "connected_align", "EmbeddedStats", "embedded_forward_backward", "embedded_estep",
-                "embedded_fit", "embed_full_stats_width", "embed_full_workspace_bytes"):
+                "embedded_fit", "embed_full_stats_width", "embed_full_workspace_bytes", "embed_gmm_stats_width",
+                "embed_gmm_workspace_bytes"):
         from . import connected
         return getattr(connected, name)
     if name == "full_vocab_scores":

@@ -108,6 +108,13 @@ SIGNATURES = {
     "sapr_connected_embed_full": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
                                           c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_double, c_int32, c_int32,
                                           c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sapr_connected_embed_gmm_stats_width": (c_int, [c_int32, c_int32, c_int32, C.POINTER(c_int32)]),
+    "sapr_connected_embed_gmm_workspace_bytes": (c_int, [c_int64, c_int64, c_int64, c_int32, c_int32, c_int32,
+                                                         c_int32, c_int32, C.POINTER(c_size_t)]),
+    "sapr_connected_embed_gmm": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_int64,
+                                         c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_double,
+                                         c_int32, c_int32, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+                                         c_void_p]),
     "sapr_colsum_f32":(c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     "sapr_custom_estep": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32] + [c_void_p] * 5
                           + [c_int64] + [c_void_p] * 6 + [c_void_p]),

@@ -541,10 +541,25 @@ def embed_full_workspace_bytes(total_frames, n_utts, total_words, max_words, W, 
     return int(n.value)
 
 
+def embed_gmm_stats_width(S, M, D) -> int:
+    n = C.c_int32(0)
+    _lib.check(_lib.load().sapr_connected_embed_gmm_stats_width(S, M, D, C.byref(n)),
+               "sapr_connected_embed_gmm_stats_width")
+    return int(n.value)
+
+
+def embed_gmm_workspace_bytes(total_frames, n_utts, total_words, max_words, W, S, M, D) -> int:
+    n = C.c_size_t(0)
+    _lib.check(_lib.load().sapr_connected_embed_gmm_workspace_bytes(total_frames, n_utts, total_words, max_words, W,
+                                                                    S, M, D, C.byref(n)),
+               "sapr_connected_embed_gmm_workspace_bytes")
+    return int(n.value)
+
+
 @dataclass
 class EmbeddedStats:
     loglik: np.ndarray        # [N] f64: log P(utterance | its transcript's chain); -inf (or NaN) without a path
-    stats: np.ndarray         # [W, width] f64 (sapr_connected_embed[_full]_stats_width), or None
+    stats: np.ndarray         # [W, width] f64 (sapr_connected_embed[_full | _gmm]_stats_width), or None
     post: np.ndarray          # [total_frames, max_words * SP] f64: gamma_t at chain position k * SP + s, or None
     offsets: np.ndarray       # [N + 1] i64
     word_offsets: np.ndarray  # [N + 1] i64
@@ -553,15 +568,20 @@ class EmbeddedStats:
     SP: int = 0               # ... and the padded states of a chain position
     D: int = 0                # feature width of the obs blocks (0: none)
     n_states: tuple = ()      # every word model's own states
-    layout: str = "diag"      # the row's observation blocks: "diag" {obs, obs**2} or "full" {obs, obs*obs.T}
+    layout: str = "diag"      # the row's observation blocks: "diag" {obs, obs**2}, "full" {obs, obs*obs.T} or "gmm"
+    M: int = 0                # ... {post_mix, obs, obs**2} per component, M of them per state (0: no mixtures)
 
     def split(self, w):
         """hmmlearn's statistics dict of word model ``w``, cut to the model's own states; ``logprob`` is the row's
         reserved 0.0.  A "diag" row gives ``trellis.split_stats``' dict (``obs**2``), a "full" row
-        ``full_cov.split_stats``' (``obs*obs.T``)."""
+        ``full_cov.split_stats``' (``obs*obs.T``), a "gmm" row ``gmm_hmm.split_stats``' (``post_mix`` and the
+        per-component ``obs`` / ``obs**2``)."""
         from .trellis import split_stats
         if self.stats is None:
             raise ValueError("the statistics were not asked for")
+        if self.layout == "gmm":
+            from .gmm_hmm import split_stats as split_gmm
+            return split_gmm(self.stats[w], self.S, self.M, self.D, self.n_states[w] if self.n_states else None)
         if self.layout == "full":
             from .full_cov import split_stats as split_full
             return split_full(self.stats[w], self.S, self.D, self.n_states[w] if self.n_states else None)
@@ -577,10 +597,15 @@ class EmbeddedStats:
 
 
 def _run_embed(logb, feats, offs_dev, offs, transcripts, network, want_stats, want_post,
-               second_moments=False) -> EmbeddedStats:
+               second_moments=False, mixtures=False) -> EmbeddedStats:
     """One ``sapr_connected_embed`` over device ``logb[total_frames, R]`` (and device ``feats`` or ``None``);
-    ``second_moments``: one ``sapr_connected_embed_full`` instead, whose rows carry ``obs*obs.T``."""
+    ``second_moments``: one ``sapr_connected_embed_full`` instead, whose rows carry ``obs*obs.T``; ``mixtures``: one
+    ``sapr_connected_embed_gmm``, whose rows carry the statistics per mixture component."""
     torch = _torch()
+    if mixtures and want_stats:
+        if feats is None or int(feats.shape[1]) == 0:
+            raise ValueError("the mixture statistics need the frames: feats [total_frames, D] with D >= 1")
+        return _run_embed_gmm(logb, feats, offs_dev, offs, transcripts, network, want_post)
     if second_moments and want_stats:
         if feats is None or int(feats.shape[1]) == 0:
             raise ValueError("the second moments need the frames: feats [total_frames, D] with D >= 1")
@@ -635,33 +660,78 @@ def _run_embed_full(logb, feats, offs_dev, offs, transcripts, network, want_post
                          n_states=tuple(network.n_states), layout="full")
 
 
-def _refuse_stats(network, second_moments=False):
+def _run_embed_gmm(logb, feats, offs_dev, offs, transcripts, network, want_post) -> EmbeddedStats:
+    """One ``sapr_connected_embed_gmm`` over device ``logb[total_frames, R]``, device ``feats`` and the network's
+    ``GmmPack`` as the emission read it."""
+    torch = _torch()
+    dev = logb.device
+    n_utts, total = int(offs.size - 1), int(offs[-1])
+    words, word_offs, max_words = _transcripts(transcripts, n_utts, network)
+    total_words = int(word_offs[-1])
+    D, M = int(feats.shape[1]), int(network.pack.M)
+    if D != network.D:
+        raise ValueError(f"the utterances have {D} features, the models {network.D}")
+    ls, lt, lx, pack = network.device(dev)
+    words_dev = torch.from_numpy(words).to(dev)
+    word_offs_dev = torch.from_numpy(word_offs).to(dev)
+    ws_bytes = embed_gmm_workspace_bytes(total, n_utts, total_words, max_words, network.W, network.S, M, D)
+    workspace = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    loglik = torch.empty(n_utts, dtype=torch.float64, device=dev)
+    stats = torch.empty((network.W, embed_gmm_stats_width(network.S, M, D)), dtype=torch.float64, device=dev)
+    post = torch.zeros((total, max_words * network.SP), dtype=torch.float64, device=dev) if want_post else None
+    _lib.check(_lib.load().sapr_connected_embed_gmm(
+        _lib.ptr(logb), _lib.ptr(feats), D, _lib.ptr(pack), M, _lib.ptr(offs_dev), n_utts, total, _lib.ptr(words_dev),
+        _lib.ptr(word_offs_dev), total_words, max_words, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx),
+        network.word_penalty, network.W, network.S, _lib.ptr(workspace), ws_bytes, _lib.ptr(loglik), _lib.ptr(stats),
+        _lib.ptr(post), _lib.current_stream()), "sapr_connected_embed_gmm")
+    host = [None if a is None else a.cpu().numpy() for a in (loglik, stats, post)]
+    return EmbeddedStats(*host, offsets=offs, word_offsets=word_offs, words=words, S=network.S, SP=network.SP, D=D,
+                         n_states=tuple(network.n_states), layout="gmm", M=M)
+
+
+def _refuse_stats(network, second_moments=False, mixtures=False):
+    if mixtures:
+        if second_moments:
+            raise ValueError("mixtures=True and second_moments=True exclude each other: a statistics row carries "
+                             "either the per-component sums of a 'gmm' network or the second-moment matrices")
+        if network.family != "gmm":
+            raise ValueError(f"mixtures=True serves a network of the 'gmm' family (GMMHMM word models with their "
+                             f"GmmPack); this one is {network.family!r}")
+        return
     if second_moments:
         if network.family == "gmm":
             raise NotImplementedError(
                 "embedded statistics with second_moments=True are served for the 'diag' and 'full' families; the "
-                "'gmm' family needs mixture responsibilities (loglik and post are served: want_stats=False)")
+                "'gmm' family needs mixture responsibilities, which mixtures=True accumulates (loglik and post are "
+                "served either way: want_stats=False)")
         return
     if network.family != "diag":
         raise NotImplementedError(
-            f"embedded statistics are served for the 'diag' family; the {network.family!r} family needs "
-            f"{'mixture responsibilities' if network.family == 'gmm' else 'second-moment matrices'} "
+            f"embedded statistics are served for the 'diag' family by default; the {network.family!r} family needs "
+            f"{'mixture responsibilities (mixtures=True)' if network.family == 'gmm' else 'second-moment matrices'} "
             f"(loglik and post are served: want_stats=False)")
 
 
 def embedded_forward_backward(logb, lengths, transcripts, network: ConnectedNetwork, feats=None,
-                              want_post=False, second_moments=False) -> EmbeddedStats:
+                              want_post=False, second_moments=False, mixtures=False) -> EmbeddedStats:
     """Forward-backward over every utterance's transcript chain on a given ``logb`` (the shapes
     :func:`connected_viterbi` takes) — the counterpart of :func:`align_viterbi`.  ``feats``: the float32 frames
     ``[total_frames, D]`` (host array or device tensor) for the ``obs`` blocks of the statistics; without them the
     statistics carry ``start``, ``trans``, ``post`` and ``nobs`` only.  The definition is ``tests/_embedded_ref.py``.
     ``second_moments=True`` (needs ``feats``): the rows carry ``obs*obs.T`` in place of ``obs**2``
-    (``sapr_connected_embed_full``; definition ``tests/_embedded_full_ref.py``)."""
+    (``sapr_connected_embed_full``; definition ``tests/_embedded_full_ref.py``).  ``mixtures=True`` (needs ``feats``
+    and a "gmm" network, whose ``GmmPack`` supplies the components): the rows carry ``post_mix`` and the per-component
+    ``obs`` / ``obs**2`` (``sapr_connected_embed_gmm``; definition ``tests/_embedded_gmm_ref.py``)."""
     torch = _torch()
     lengths, offs = _offsets(lengths)
     _transcripts(transcripts, int(lengths.size), network)  # (refused before a device is asked for)
-    if second_moments and (feats is None or np.ndim(feats) != 2 or int(np.shape(feats)[1]) == 0):
-        raise ValueError("second_moments=True needs the frames: feats [sum(lengths), D] with D >= 1")
+    if mixtures:
+        _refuse_stats(network, second_moments, mixtures)
+        if network.pack is None or not hasattr(network.pack, "M"):
+            raise ValueError("mixtures=True needs the network's GmmPack (ConnectedNetwork.from_models)")
+    if (second_moments or mixtures) and (feats is None or np.ndim(feats) != 2 or int(np.shape(feats)[1]) == 0):
+        raise ValueError(f"{'mixtures' if mixtures else 'second_moments'}=True needs the frames: feats "
+                         f"[sum(lengths), D] with D >= 1")
     dev = _lib.require_gpu()
     total = int(offs[-1])
     logb = _flat_logb(logb, total, network, dev)
@@ -674,26 +744,28 @@ def embedded_forward_backward(logb, lengths, transcripts, network: ConnectedNetw
         if int(feats.shape[1]) == 0:
             feats = None
     return _run_embed(logb, feats, torch.from_numpy(offs).to(dev), offs, transcripts, network, True, want_post,
-                      second_moments)
+                      second_moments, mixtures)
 
 
 def embedded_estep(batch_or_feature_list, transcripts, network: ConnectedNetwork, want_post=False,
-                   want_stats=True, second_moments=False) -> EmbeddedStats:
+                   want_stats=True, second_moments=False, mixtures=False) -> EmbeddedStats:
     """Emission (by the network's family) and forward-backward over the transcript chains — the counterpart of
     :func:`connected_align`.  ``loglik`` and ``post`` are served for all three families; the statistics for "diag"
-    (for "gmm" and "full" asking for them raises ``NotImplementedError``: pass ``want_stats=False``).  With
+    by default (for "gmm" and "full" asking for them without their switch raises ``NotImplementedError``).  With
     ``second_moments=True`` the statistics of a "diag" or "full" network carry ``obs*obs.T``
-    (``sapr_connected_embed_full``), what the M-step of a "full" or "tied" model reads; a "gmm" network is still
-    refused: its statistics need mixture responsibilities."""
+    (``sapr_connected_embed_full``), what the M-step of a "full" or "tied" model reads.  With ``mixtures=True`` the
+    statistics of a "gmm" network carry ``post_mix`` and the per-component ``obs`` / ``obs**2``
+    (``sapr_connected_embed_gmm``), what ``gmm_hmm.gmm_m_step`` reads; on another family, or together with
+    ``second_moments=True``, the switch is a ``ValueError``."""
     b = batch_or_feature_list
     n_utts = len(b.lengths) if hasattr(b, "offsets") and hasattr(b, "order") else len(b)
     _transcripts(transcripts, n_utts, network)  # (refused before a device is asked for)
-    if want_stats:
-        _refuse_stats(network, second_moments)
+    if want_stats or mixtures:
+        _refuse_stats(network, second_moments, mixtures)
     feats, offs_dev, offs = _features(b)
     logb = _EMIT[network.family](feats, network)
     return _run_embed(logb, feats if want_stats else None, offs_dev, offs, transcripts, network, want_stats, want_post,
-                      second_moments)
+                      second_moments, mixtures)
 
 
 def _diag_of_moments(st, covariance_type):
@@ -704,6 +776,37 @@ def _diag_of_moments(st, covariance_type):
         st = dict(st)
         st["obs**2"] = np.ascontiguousarray(np.diagonal(st["obs*obs.T"], axis1=1, axis2=2))
     return st
+
+
+def _embedded_fit_gmm(models, features, transcripts, n_iter, tol, exit_states, word_penalty, names):
+    """:func:`embedded_fit` over ``GMMHMM`` word models."""
+    from .gmm_hmm import gmm_m_step
+    from .hmmlearn_hmm import ConvergenceMonitor
+
+    def network():
+        # (packing validates every model and notes the feature width on the object: done on shallow copies, so that a
+        # word that is never trained keeps its bytes)
+        return ConnectedNetwork.from_models([copy.copy(m) for m in models], exit_states, word_penalty, names, "gmmhmm")
+
+    net = network()
+    _transcripts(transcripts, len(features), net)  # (refused before a device is asked for)
+    feats, offs_dev, offs = _features(features)
+    monitor = ConvergenceMonitor(tol, n_iter)
+    for _ in range(n_iter):
+        net = network()
+        res = _run_embed(emit_gmm(feats, net), feats, offs_dev, offs, transcripts, net, True, False, mixtures=True)
+        for w, m in enumerate(models):
+            st = res.split(w)
+            if st["nobs"] == 0:
+                continue
+            m.startprob_, m.transmat_, m.weights_, m.means_, m.covars_ = gmm_m_step(
+                st, m.startprob_, m.transmat_, m.weights_, m.means_, m.covars_, m.params, m.startprob_prior,
+                m.transmat_prior, m.weights_prior, m.means_prior, m.means_weight, m.covars_prior, m.covars_weight,
+                m.min_covar)
+        monitor.report(float(res.loglik[np.isfinite(res.loglik)].sum()))
+        if monitor.converged:
+            break
+    return list(monitor.history)
 
 
 def embedded_fit(models, features, transcripts, n_iter=10, tol=1e-2, exit_states="last", word_penalty=0.0,
@@ -718,9 +821,19 @@ def embedded_fit(models, features, transcripts, n_iter=10, tol=1e-2, exit_states
     ``second_moments=False`` serves "diag" / "spherical" vocabularies (``sapr_connected_embed``).  With
     ``second_moments=True`` any ``GaussianHMM`` vocabulary trains, "full" and "tied" members included: the E-step is
     ``sapr_connected_embed_full``, a "tied" model ends with one ``(D, D)`` matrix, and a "diag" / "spherical" member
-    reads the diagonal of its second-moment matrices."""
+    reads the diagonal of its second-moment matrices.
+
+    A list of ``GMMHMM`` objects (that share ``n_mix`` and the feature width) trains through
+    ``sapr_connected_embed_gmm``: per iteration the network over the vocabulary's ``GmmPack``, ``emit_gmm``, the E-step
+    with mixture responsibilities, then ``gmm_hmm.gmm_m_step`` per model with the model's own hyper-parameters.  A
+    list that mixes ``GMMHMM`` and ``GaussianHMM`` objects is a ``ValueError``."""
     from .hmmlearn_hmm import ConvergenceMonitor, m_step_typed
     models = list(models)
+    if vocabulary_family(models, names, None) == "gmm":
+        if second_moments:
+            raise ValueError("second_moments=True serves GaussianHMM vocabularies; GMMHMM word models train on "
+                             "mixture responsibilities")
+        return _embedded_fit_gmm(models, features, transcripts, n_iter, tol, exit_states, word_penalty, names)
     family = vocabulary_family(models, names, "hmmlearn")
     if family != "diag" and not second_moments:
         raise ValueError("embedded_fit serves 'diag' and 'spherical' GaussianHMM vocabularies by default: a 'full' or "

@@ -28,6 +28,9 @@
 //   levels with fixed boundaries (chunks of 256 slots, n ascending; then the chunks, ascending).
 // embed_full_accum_kernel<DP>, embed_full_fold_kernel (sapr_connected_embed_full): the second moments sum gamma x x^T
 //   per word model on the float64 matrix cores, behind the same recursions; described where they stand.
+// embed_gmm_accum_kernel<MP, DP> (sapr_connected_embed_gmm): the mixture statistics sum r [x, x^2, 1] per word model
+//   with r = the chain's gamma shared out among a state's components, the product again on the float64 matrix cores;
+//   described where it stands.
 //
 // No atomics anywhere; an utterance's outputs are a function of its own frames, its own transcript and the network, and
 // the fold adds in slot order: two calls return the same bytes.  Every index is clamped into its row and offsets that
@@ -702,17 +705,17 @@ inline size_t em_full_p(int S, int D) { return static_cast<size_t>(S) * D + stat
 struct EmFullWorkspace {
   size_t base_bytes;  // what sapr_connected_embed takes at D = 0 (alpha / gamma first)
   double *head;       // [W][2 + S + S * S + S]
-  double *part;       // [groups][W][S * D + S * D * D]
+  double *part;       // [groups][W][P]: P = S * D + S * D * D (second moments) or S * M * (2 D + 1) (mixtures)
   size_t bytes;
 };
 
 inline EmFullWorkspace em_full_carve(void *base, int64_t total_frames, int64_t n_utts, int64_t total_words,
-                                     int32_t max_words, int W, int S, int D) {
+                                     int32_t max_words, int W, int S, size_t P) {
   EmFullWorkspace w;
   uint8_t *p = static_cast<uint8_t *>(base);
   w.base_bytes = em_carve(nullptr, total_frames, total_words, max_words, S, 0).bytes;
   const size_t h = em_align16(static_cast<size_t>(W) * em_head_width(S) * sizeof(double));
-  const size_t f = em_align16(static_cast<size_t>(em_full_groups(n_utts)) * W * em_full_p(S, D) * sizeof(double));
+  const size_t f = em_align16(static_cast<size_t>(em_full_groups(n_utts)) * W * P * sizeof(double));
   w.head = reinterpret_cast<double *>(p + w.base_bytes);
   w.part = reinterpret_cast<double *>(p + w.base_bytes + h);
   w.bytes = w.base_bytes + h + f;
@@ -859,6 +862,183 @@ __global__ __launch_bounds__(kEmBlock) void embed_full_fold_kernel(const double 
   stats[static_cast<int64_t>(w) * width + e] = sum;
 }
 
+// ---- mixture statistics over the chain posteriors (sapr_connected_embed_gmm) ---------------------------------------
+// embed_gmm_accum_kernel<MP, DP>: with g_t(w, s) = sum_{k: w_k = w, k ascending} gamma_t(k, s) and lc the component
+//   log-terms of word w's block of the GmmPack (mix_log_terms, gmm_ops.h),
+//     r_t(w, s, m) = g_t(w, s) exp(lc[m] - max lc) / sum_m exp(lc[m] - max lc)       (gmm_accum_kernel's rule)
+//     post_mix[w][s][m] = sum r     obs[w][s][m] = sum r x_t     obs2[w][s][m] = sum r RN32(x_t x_t)
+//   The grid, the utterance groups, the utterances left out and the collapse of the slots are those of
+//   embed_full_accum_kernel.  A pass serves SG = min(64 / MP, 18) states, i.e. at most 64 (state, component) rows.
+//   Per chunk of 64 frames, phase A (lane = frame, the pass's states dealt round to the wavefronts) recomputes lc from
+//   the staged float32 frame and writes r into LDS as r[row][frame]; a state whose 64 weights are all 0.0 writes
+//   zeros without evaluating lc.  Phase B is the product r^T [x | RN32(x x) | 1] on the float64 matrix cores, four
+//   frames per v_mfma_f64_16x16x4_f64: wavefront v owns rows 16 v .. 16 v + 15 of the pass and all NT column tiles;
+//   the B operand is formed from the staged float32 frame as it is read.  A chunk, and a 4-frame step of a row tile,
+//   whose weights are all exactly 0.0 is skipped.  One partial row {post_mix[S][M], obs[S][M][D], obs2[S][M][D]} per
+//   (group, w), every element of it written; embed_full_fold_kernel adds the groups behind the head.
+constexpr int kEmGmmFS = kEmFullChunk + 2;  // LDS stride of r[row][frame] (doubles): the 16 rows x 2 frames of a
+                                            // half-wavefront's A operand on 32 distinct bank pairs
+constexpr int kEmGmmGF = kEmFullChunk + 1;  // LDS stride of g[state][frame] (doubles), odd
+
+template <int MP>
+constexpr int kEmGmmStates = 64 / MP > kMaxS ? kMaxS : 64 / MP;  // states of one pass
+
+inline size_t em_gmm_p(int S, int M, int D) { return static_cast<size_t>(S) * M * (2 * D + 1); }
+
+template <int MP, int DP>
+__global__ __launch_bounds__(kEmBlock) void embed_gmm_accum_kernel(
+    const double *__restrict__ gamma, const float *__restrict__ feats, int32_t D, const double *__restrict__ pack,
+    int64_t pack_stride, int32_t M, const int64_t *__restrict__ offsets, int64_t n_utts, int64_t total_frames,
+    const int32_t *__restrict__ words, const int64_t *__restrict__ word_offsets, int64_t total_words,
+    int32_t max_words, int32_t W, int32_t S, int32_t SP, int64_t group_utts, const double *__restrict__ loglik,
+    double *__restrict__ part) {
+  constexpr int SG = kEmGmmStates<MP>;
+  constexpr int RW = SG * MP;                  // rows of r in a pass
+  constexpr int RT = (RW + 15) / 16;           // 16-row tiles of a pass: one wavefront each
+  constexpr int NT = (2 * DP + 1 + 15) / 16;   // 16-wide column tiles: x[0..D), RN32(x x)[0..D), the constant 1
+  constexpr int FS = kEmGmmFS, GF = kEmGmmGF;
+  constexpr int XF = DP | 1;                   // LDS row stride of the staged frames (floats), odd
+  static_assert(RT <= kEmWaves && RW <= 16 * RT, "a row tile per wavefront");
+  __shared__ double s_r[16 * RT * FS];
+  __shared__ double s_g[SG * GF];
+  __shared__ float s_x[kEmFullChunk * XF];
+
+  const int tid = threadIdx.x, lane = tid & 63, n = lane & 15, k = lane >> 4;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int64_t grp = blockIdx.x;
+  const int w = blockIdx.y;
+  const int64_t u_lo = grp * group_utts;
+  const int64_t u_hi = u_lo + group_utts < n_utts ? u_lo + group_utts : n_utts;
+  const int MPW = max_words * SP;
+  const double *__restrict__ mdl = pack + static_cast<int64_t>(w) * pack_stride;  // (uniform)
+  const double *__restrict__ cc = mdl + off_cc(SP);
+  const double *__restrict__ prm = mdl + off_prm(SP, MP);
+  double *__restrict__ out = part + (grp * W + w) * static_cast<int64_t>(S * M * (2 * D + 1));
+
+  // column 16 t + n of B: feature ci[t] as it is (kind 0), its float32 square (1), the constant 1 (2), nothing (3)
+  int ci[NT], kind[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int c = 16 * t + n;
+    kind[t] = c < D ? 0 : (c < 2 * D ? 1 : (c == 2 * D ? 2 : 3));
+    ci[t] = c < D ? c : (c < 2 * D ? c - D : 0);
+  }
+  // (the rows of the last tile behind RW are read by phase B and never written by phase A)
+  for (int i = tid; i < 16 * RT * FS; i += kEmBlock) s_r[i] = 0.0;
+
+  for (int g = 0; g * SG < S; ++g) {  // (uniform trip counts: every thread reaches the barriers)
+    f64x4_em acc[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[t] = f64x4_em{0.0, 0.0, 0.0, 0.0};
+    for (int64_t u = u_lo; u < u_hi; ++u) {
+      const EmUtt ut = em_utt(offsets, total_frames, word_offsets, total_words, max_words, u);
+      // (as in embed_full_accum_kernel: the gamma rows of an utterance without a finite likelihood were never written
+      // and may hold NaN; a frame that is read belongs to an utterance whose every logb, hence every feature, is finite)
+      if (!ut.path || !finite_f64(loglik[u])) continue;  // (uniform)
+      const int wd = lane < ut.K ? words[ut.wbeg + lane] : -1;
+      const uint64_t slots = __ballot(wd == w);  // the slots of word w (the same in every wavefront)
+      if (slots == 0) continue;
+      const double *__restrict__ gu = gamma + ut.beg * MPW;
+      const float *__restrict__ xu = feats + ut.beg * D;
+      for (int64_t c0 = 0; c0 < ut.T; c0 += kEmFullChunk) {
+        {  // g_t(w, s) of the pass's states, the slots collapsed k ascending; 0.0 selected behind the utterance's end
+          bool nz = false;
+          for (int item = tid; item < kEmFullChunk * SG; item += kEmBlock) {
+            const int f = item / SG, sj = item - f * SG;
+            const int64_t t = c0 + f;
+            const int st = g * SG + sj;
+            const bool live = t < ut.T && st < S;
+            const double *__restrict__ src = gu + (live ? t : 0) * MPW + (live ? st : 0);  // (dead: a valid address)
+            double gw = 0.0;
+            for (uint64_t m = slots; m; m &= m - 1) gw += src[__builtin_ctzll(m) * SP];
+            gw = live ? gw : 0.0;
+            s_g[sj * GF + f] = gw;
+            nz = nz || gw != 0.0;
+          }
+          if (!__syncthreads_or(nz)) continue;  // (uniform) nothing of word w in these frames
+        }
+        // the chunk's frames into LDS, float32 as they are; zeros in the padded dimensions (against their zero mean
+        // and zero coefficient they add +0.0) and in the rows past the utterance's last frame
+        for (int item = tid; item < kEmFullChunk * DP; item += kEmBlock) {
+          const int f = item / DP, d = item - f * DP;
+          const int64_t t = c0 + f;
+          s_x[f * XF + d] = (t < ut.T && d < D) ? xu[t * D + d] : 0.0f;
+        }
+        __syncthreads();
+        // ---- phase A: r of the pass's states for the chunk's 64 frames, lane = frame -----------------------------
+        {
+          const float *__restrict__ xrow = s_x + lane * XF;
+          for (int j = wv; j < SG; j += kEmWaves) {
+            const int s = g * SG + j;
+            const double gm = s_g[j * GF + lane];
+            double r[MP];
+#pragma unroll
+            for (int m = 0; m < MP; ++m) r[m] = 0.0;
+            if (s < S && __ballot(gm != 0.0) != 0) {  // (wavefront-uniform)
+              double lc[MP];
+              mix_log_terms<MP, DP, 16 / MP>([&](int d) { return static_cast<double>(xrow[d]); },
+                                             prm + static_cast<int64_t>(s) * DP * MP * 2, cc + s * MP, lc);
+              double mx = lc[0];
+#pragma unroll
+              for (int m = 1; m < MP; ++m) mx = lc[m] > mx ? lc[m] : mx;
+              double den = 0.0;
+#pragma unroll
+              for (int m = 0; m < MP; ++m) {
+                r[m] = exp_unit(lc[m] - mx);
+                den += r[m];
+              }
+              const double scale = gm / den;
+              const bool off = mx == neg_inf() || gm == 0.0;  // every component switched off, or no weight
+#pragma unroll
+              for (int m = 0; m < MP; ++m) r[m] = off ? 0.0 : r[m] * scale;
+            }
+#pragma unroll
+            for (int m = 0; m < MP; ++m) s_r[(j * MP + m) * FS + lane] = r[m];
+          }
+        }
+        __syncthreads();
+        // ---- phase B: acc[row][col] += r[f][row] * B[f][col] on the matrix cores, four frames per instruction ----
+        if (wv < RT) {  // (uniform)
+          for (int step = 0; step < kEmFullChunk / 4; ++step) {
+            // A and B of the float64 MFMA: lane & 15 = row (column), lane >> 4 = the K index, here the frame
+            const int f = 4 * step + k;
+            const double ra = s_r[(16 * wv + n) * FS + f];
+            if (__ballot(ra != 0.0) == 0) continue;  // (wavefront-uniform) 16 rows x 4 frames that add exact zeros
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+              const float xf = s_x[f * XF + ci[t]];
+              const float v = kind[t] == 1 ? xf * xf : xf;  // X**2 in float32, as numpy squares the array
+              const double xb = kind[t] < 2 ? static_cast<double>(v) : (kind[t] == 2 ? 1.0 : 0.0);
+              acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ra, xb, acc[t], 0, 0, 0);
+            }
+          }
+        }
+        __syncthreads();
+      }
+    }
+    if (wv < RT) {
+      // C of the float64 MFMA: column = lane & 15, row = (lane >> 4) + 4 * register
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = 16 * wv + k + 4 * r, c = 16 * t + n;
+          const int s = g * SG + row / MP, m = row % MP;
+          if (row < RW && s < S && m < M && c <= 2 * D) {
+            const int sm = s * M + m;
+            const double v = acc[t][r];
+            if (c == 2 * D)
+              out[sm] = v;
+            else if (c < D)
+              out[S * M + sm * D + c] = v;
+            else
+              out[S * M + S * M * D + sm * D + (c - D)] = v;
+          }
+        }
+    }
+  }
+}
+
 }  // namespace
 }  // namespace sapr
 
@@ -958,7 +1138,7 @@ extern "C" int sapr_connected_embed_full_workspace_bytes(int64_t total_frames, i
                (long long)total_frames, (long long)n_utts, (long long)total_words, max_words, W, S, D);
   if (int rc = em_check_shape(W, S, max_words)) return rc;
   if (int rc = em_check_dims(D)) return rc;
-  *bytes = em_full_carve(nullptr, total_frames, n_utts, total_words, max_words, W, S, D).bytes;
+  *bytes = em_full_carve(nullptr, total_frames, n_utts, total_words, max_words, W, S, em_full_p(S, D)).bytes;
   return 0;
 }
 
@@ -981,7 +1161,8 @@ extern "C" int sapr_connected_embed_full(const double *logb, const float *feats,
                need);
   SAPR_REQUIRE(!stats || D >= 1, "the second moments need D >= 1 (got D=%d)", D);
   SAPR_REQUIRE(!stats || n_utts == 0 || total_frames == 0 || feats, "NULL pointer argument");
-  const EmFullWorkspace ws = em_full_carve(workspace, total_frames, n_utts, total_words, max_words, W, S, D);
+  const EmFullWorkspace ws =
+      em_full_carve(workspace, total_frames, n_utts, total_words, max_words, W, S, em_full_p(S, D));
   // the recursions, loglik, post and the head of the row: sapr_connected_embed itself on the front of the workspace,
   // without features (the head does not depend on them); gamma stays behind in the workspace
   if (int rc = sapr_connected_embed(logb, nullptr, 0, offsets, n_utts, total_frames, words, word_offsets, total_words,
@@ -1008,6 +1189,94 @@ extern "C" int sapr_connected_embed_full(const double *logb, const float *feats,
   const unsigned tiles = static_cast<unsigned>((hw + P + kEmBlock - 1) / kEmBlock);
   SAPR_LAUNCH(embed_full_fold_kernel, dim3(tiles, static_cast<unsigned>(W)), dim3(kEmBlock), 0, st, ws.head, ws.part,
               groups, W, hw, P, stats);
+  SAPR_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int sapr_connected_embed_gmm_stats_width(int32_t S, int32_t M, int32_t D, int32_t *width) {
+  SAPR_REQUIRE(width && S > 0 && M > 0 && D > 0, "bad sizes (S=%d M=%d D=%d)", S, M, D);
+  if (int rc = em_check_shape(1, S, 1)) return rc;
+  if (int rc = em_check_dims(D)) return rc;
+  if (int rc = check_shape(S, M, D)) return rc;
+  *width = static_cast<int32_t>(em_head_width(S) + em_gmm_p(S, M, D));
+  return 0;
+}
+
+extern "C" int sapr_connected_embed_gmm_workspace_bytes(int64_t total_frames, int64_t n_utts, int64_t total_words,
+                                                        int32_t max_words, int32_t W, int32_t S, int32_t M, int32_t D,
+                                                        size_t *bytes) {
+  SAPR_REQUIRE(bytes && total_frames >= 0 && n_utts >= 0 && total_words >= 0 && max_words > 0 && W > 0 && S > 0 &&
+                   M > 0 && D >= 0,
+               "bad sizes (total_frames=%lld n_utts=%lld total_words=%lld max_words=%d W=%d S=%d M=%d D=%d)",
+               (long long)total_frames, (long long)n_utts, (long long)total_words, max_words, W, S, M, D);
+  if (int rc = em_check_shape(W, S, max_words)) return rc;
+  if (int rc = em_check_dims(D)) return rc;
+  if (int rc = check_shape(S, M, D)) return rc;
+  *bytes = em_full_carve(nullptr, total_frames, n_utts, total_words, max_words, W, S, em_gmm_p(S, M, D)).bytes;
+  return 0;
+}
+
+extern "C" int sapr_connected_embed_gmm(const double *logb, const float *feats, int32_t D, const double *pack,
+                                        int32_t M, const int64_t *offsets, int64_t n_utts, int64_t total_frames,
+                                        const int32_t *words, const int64_t *word_offsets, int64_t total_words,
+                                        int32_t max_words, const double *log_start, const double *log_trans,
+                                        const double *log_exit, double word_penalty, int32_t W, int32_t S,
+                                        void *workspace, size_t workspace_bytes, double *loglik, double *stats,
+                                        double *post, void *stream) {
+  SAPR_REQUIRE(n_utts >= 0 && total_frames >= 0 && total_words >= 0 && max_words > 0 && W > 0 && S > 0 && M > 0 &&
+                   D >= 0,
+               "bad sizes (n_utts=%lld total_frames=%lld total_words=%lld max_words=%d W=%d S=%d M=%d D=%d)",
+               (long long)n_utts, (long long)total_frames, (long long)total_words, max_words, W, S, M, D);
+  if (int rc = em_check_shape(W, S, max_words)) return rc;
+  if (int rc = em_check_dims(D)) return rc;
+  if (int rc = check_shape(S, M, D)) return rc;
+  size_t need = 0;
+  if (int rc =
+          sapr_connected_embed_gmm_workspace_bytes(total_frames, n_utts, total_words, max_words, W, S, M, D, &need))
+    return rc;
+  SAPR_REQUIRE(workspace_bytes >= need && (need == 0 || workspace), "workspace too small: %zu < %zu", workspace_bytes,
+               need);
+  SAPR_REQUIRE(!stats || D >= 1, "the mixture statistics need D >= 1 (got D=%d)", D);
+  SAPR_REQUIRE(!stats || n_utts == 0 || pack, "NULL pointer argument (pack)");
+  SAPR_REQUIRE(!stats || n_utts == 0 || total_frames == 0 || feats, "NULL pointer argument");
+  const size_t P = em_gmm_p(S, M, D);
+  const EmFullWorkspace ws = em_full_carve(workspace, total_frames, n_utts, total_words, max_words, W, S, P);
+  // as sapr_connected_embed_full: the recursions, loglik, post and the head of the row are sapr_connected_embed itself
+  // on the front of the workspace, without features; gamma stays behind in the workspace
+  if (int rc = sapr_connected_embed(logb, nullptr, 0, offsets, n_utts, total_frames, words, word_offsets, total_words,
+                                    max_words, log_start, log_trans, log_exit, word_penalty, W, S, workspace,
+                                    ws.base_bytes, loglik, stats ? ws.head : nullptr, post, stream))
+    return rc;
+  if (n_utts == 0 || !stats) return 0;
+  hipStream_t st = as_stream(stream);
+  const int32_t SP = sp_of(S);
+  const int64_t groups = em_full_groups(n_utts), per = em_full_group_utts(n_utts);
+  const int64_t stride = static_cast<int64_t>(model_doubles(SP, mp_of(M), dp_of(D)));
+  const double *gamma = static_cast<const double *>(workspace);
+  const dim3 grid(static_cast<unsigned>(groups), static_cast<unsigned>(W));
+#define SAPR_EM_GMM_ACCUM(MP, DP)                                                                                     \
+  SAPR_LAUNCH((embed_gmm_accum_kernel<MP, DP>), grid, dim3(kEmBlock), 0, st, gamma, feats, D, pack, stride, M,        \
+              offsets, n_utts, total_frames, words, word_offsets, total_words, max_words, W, S, SP, per, loglik,      \
+              ws.part)
+#define SAPR_EM_GMM_ACCUM_DP(MP)                                                                                      \
+  switch (dp_of(D)) {                                                                                                 \
+    case 13: SAPR_EM_GMM_ACCUM(MP, 13); break;                                                                        \
+    case 26: SAPR_EM_GMM_ACCUM(MP, 26); break;                                                                        \
+    default: SAPR_EM_GMM_ACCUM(MP, 39); break;                                                                        \
+  }
+  switch (mp_of(M)) {
+    case 1: SAPR_EM_GMM_ACCUM_DP(1); break;
+    case 2: SAPR_EM_GMM_ACCUM_DP(2); break;
+    case 4: SAPR_EM_GMM_ACCUM_DP(4); break;
+    default: SAPR_EM_GMM_ACCUM_DP(8); break;
+  }
+#undef SAPR_EM_GMM_ACCUM_DP
+#undef SAPR_EM_GMM_ACCUM
+  SAPR_HIP_TRY(hipGetLastError());
+  const int32_t hw = static_cast<int32_t>(em_head_width(S));
+  const unsigned tiles = static_cast<unsigned>((hw + P + kEmBlock - 1) / kEmBlock);
+  SAPR_LAUNCH(embed_full_fold_kernel, dim3(tiles, static_cast<unsigned>(W)), dim3(kEmBlock), 0, st, ws.head, ws.part,
+              groups, W, hw, static_cast<int32_t>(P), stats);
   SAPR_HIP_TRY(hipGetLastError());
   return 0;
 }

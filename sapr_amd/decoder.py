@@ -198,13 +198,14 @@ class Decoder:
 
         Served for ``implementation="hmmlearn"``: "diag" / "spherical" vocabularies through ``sapr_connected_embed``,
         a vocabulary that holds a "full" or "tied" model through ``sapr_connected_embed_full`` (second-moment
-        matrices; ``embedded_fit(..., second_moments=True)``).  Another implementation is refused with a
-        ``ValueError`` that says why.  A word that is not in the vocabulary is refused with a ``ValueError`` that
-        names it."""
-        if self.implementation != "hmmlearn":
-            raise ValueError(f"embedded training needs implementation='hmmlearn' (GaussianHMM word models): "
-                             f"the embedded E-step accumulates single-Gaussian statistics, not those of "
-                             f"implementation={self.implementation!r}")
+        matrices; ``embedded_fit(..., second_moments=True)``).  Served for ``implementation="gmmhmm"`` through
+        ``sapr_connected_embed_gmm`` (mixture responsibilities over the chain posteriors, then
+        ``gmm_hmm.gmm_m_step`` per word).  Another implementation is refused with a ``ValueError`` that says why.  A
+        word that is not in the vocabulary is refused with a ``ValueError`` that names it."""
+        if self.implementation not in ("hmmlearn", "gmmhmm"):
+            raise ValueError(f"embedded training needs implementation='hmmlearn' (GaussianHMM word models) or "
+                             f"'gmmhmm' (GMMHMM word models): the embedded E-step accumulates Gaussian and "
+                             f"Gaussian-mixture statistics, not those of implementation={self.implementation!r}")
         from .connected import embedded_fit
         if len(feature_list) == 0:
             raise ValueError("empty utterance list")
