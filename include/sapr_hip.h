@@ -493,6 +493,47 @@ int sapr_connected_viterbi(const double *logb, const int64_t *offsets, int64_t n
                            void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Connected-word recognition under a word-pair language model (csrc/connected_bigram.hip): the word loop in which the
+ * step from word v to word w costs lm[v][w] (the same word may follow itself), the first word lm_start[w] and the last
+ * word lm_end[v].  The definition is the CPU restatement tests/_bigram_ref.py; with b_t(w,s) = logb[t][w * SP + s]:
+ *     delta_0(w,j)  = (lm_start[w] + log_start[w][j]) + b_0(w,j)
+ *     X_{t-1}(v)    = max_s (delta_{t-1}(v,s) + log_exit[v][s])        s ascending, the first maximum
+ *     N_{t-1}(w)    = max_v (X_{t-1}(v) + lm[v][w])                    v ascending, the first maximum
+ *     within        = max_i (delta_{t-1}(w,i) + log_trans[w][i][j])    i ascending, the first maximum
+ *     entry         = N_{t-1}(w) + log_start[w][j]
+ *     delta_t(w,j)  = max(within, entry) + b_t(w,j)                    entry only where strictly greater
+ *     score         = max_v (X_{T-1}(v) + lm_end[v])                   v ascending, the first maximum
+ * The additions are made in the order written: float64 adds and compares only, bit for bit numpy's.  -inf in lm,
+ * lm_start or lm_end forbids a pair, a first word or a last word — a finite-state word-pair grammar is a table of 0.0
+ * and -inf.  There is no separate word_penalty: the caller folds it into lm (sapr_amd/connected.py
+ * WordBigram.scaled).  Two identities follow: with lm == p, lm_start == 0 and lm_end == 0 the score is
+ * sapr_connected_viterbi's with word_penalty = p bit for bit (every output with p = 0.0); with lm = -inf except
+ * lm[w_k][w_{k+1}] = p along a transcript of distinct words, lm_start = -inf except 0.0 at w_0 and lm_end = -inf except
+ * 0.0 at w_{K-1}, every output is sapr_connected_align's with word_penalty = p.
+ *   logb, offsets, log_start, log_trans, log_exit, W, S: as for sapr_connected_viterbi (same layout, same limits)
+ *   lm         [W][W] float64, lm_start [W], lm_end [W]
+ *   workspace  sapr_connected_bigram_workspace_bytes:
+ *                  a16(total_frames * R) + 2 * a16(total_frames * W) + a16(4 * n_utts)   bytes, a16 rounding up to 16:
+ *              back-pointers, one byte per (frame, flat state) — the predecessor state, or 255 for an entry; one byte
+ *              per (frame, word), the state that attained X_t(v); one byte per (frame, word), the predecessor word
+ *              that attained N_t(w); one int32 per utterance, the final word
+ *   score, n_words, path_word, path_state, path_entry: as for sapr_connected_viterbi (each but score may be NULL)
+ * No atomics: outputs are bit-identical from run to run, and an utterance's outputs are a function of its own frames
+ * and the network alone.  Non-finite values propagate; every index of the walk is clamped into its row.
+ *
+ * Bad sizes, NULL required pointers (lm, lm_start and lm_end among them) and a workspace that is too small return
+ * SAPR_ERR_ARG, S > 18 or W * SP > 256 SAPR_ERR_UNSUPPORTED (from the size function too), all before any launch;
+ * n_utts == 0 returns 0 after these checks. */
+int sapr_connected_bigram_workspace_bytes(int64_t total_frames, int64_t n_utts, int32_t W, int32_t S, size_t *bytes);
+int sapr_connected_bigram(const double *logb, const int64_t *offsets, int64_t n_utts, int64_t total_frames,
+                          const double *log_start, const double *log_trans, const double *log_exit,
+                          const double *lm /* [W][W] */, const double *lm_start /* [W] */,
+                          const double *lm_end /* [W] */, int32_t W, int32_t S, void *workspace,
+                          size_t workspace_bytes, double *score, int32_t *n_words /* may be NULL */,
+                          int32_t *path_word /* may be NULL */, int32_t *path_state /* may be NULL */,
+                          uint8_t *path_entry /* may be NULL */, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Forced alignment (csrc/connected_align.hip): Viterbi over the left-to-right chain of the K words an utterance is
  * known to hold — where does each word begin and end, and which state explains each frame.  Word slot k is entered
  * only from the exit of slot k - 1 and the score is read only at the exit of the last slot.  The definition is the CPU

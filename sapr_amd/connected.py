@@ -9,6 +9,11 @@ family: ``sapr_connected_emit_diag`` for diagonal-Gaussian word models ("diag", 
 are read as they are).  Stage 2, ``sapr_connected_viterbi``, runs the recursion over any ``logb`` it is given.  The CPU
 restatement ``tests/_connected_ref.py`` is the definition; the recursion reproduces it bit for bit.
 
+A network that carries a :class:`WordBigram` — word-pair log scores ``lm[v, w]``, ``lm_start``, ``lm_end``, with
+``-inf`` for what a grammar forbids — is decoded by ``sapr_connected_bigram`` (``csrc/connected_bigram.hip``) instead:
+the same recursion with a per-word entry score ``N(w) = max_v (X(v) + lm[v, w])``.  The definition is
+``tests/_bigram_ref.py``.  Alignment and embedded training do not read the bigram.
+
 Forced alignment is the inverse question — the words of a recording are known, where does each begin and end:
 ``sapr_connected_align`` (``csrc/connected_align.hip``) runs the Viterbi recursion over the left-to-right chain of an
 utterance's own transcript, on the same ``logb`` (:func:`align_viterbi`, :func:`connected_align`; the definition is
@@ -121,16 +126,109 @@ def vocabulary_family(models, names=None, implementation=None) -> str:
     return "full" if full else "diag"
 
 
+class WordBigram:
+    """A word-pair language model over a vocabulary of W words, in log scores (float64): ``lm[v, w]`` is added when
+    word ``w`` follows word ``v`` (the same word may follow itself), ``lm_start[w]`` when an utterance begins with
+    ``w``, ``lm_end[v]`` when it ends with ``v``.  ``-inf`` forbids a pair, a first or a last word, so a finite-state
+    word-pair grammar is a table of 0.0 and ``-inf`` (:meth:`from_grammar`).  A network that carries one
+    (``ConnectedNetwork(bigram=...)``) is decoded by ``sapr_connected_bigram``; the definition is
+    ``tests/_bigram_ref.py``."""
+
+    def __init__(self, lm, lm_start, lm_end):
+        self.lm = np.ascontiguousarray(lm, dtype=np.float64)
+        self.lm_start = np.ascontiguousarray(lm_start, dtype=np.float64)
+        self.lm_end = np.ascontiguousarray(lm_end, dtype=np.float64)
+        if self.lm.ndim != 2 or self.lm.shape[0] != self.lm.shape[1] or self.lm.shape[0] == 0:
+            raise ValueError(f"lm must be [W, W] with W >= 1, got {self.lm.shape}")
+        self.W = int(self.lm.shape[0])
+        if self.lm_start.shape != (self.W,) or self.lm_end.shape != (self.W,):
+            raise ValueError(f"lm_start and lm_end must be [W={self.W}], got {self.lm_start.shape} and "
+                             f"{self.lm_end.shape}")
+
+    @staticmethod
+    def from_transcripts(transcripts, W, add_k=1.0) -> "WordBigram":
+        """Add-k smoothed log-probabilities from word strings (sequences of vocabulary indices 0..W-1; an empty string
+        counts nothing).  Row ``v`` is normalised over the W successor words plus the end of the string:
+        ``lm[v, w] = log((n(v, w) + k) / (n(v, .) + n(v, end) + k (W + 1)))`` and ``lm_end[v]`` the same with
+        ``n(v, end)``; ``lm_start[w] = log((n(start, w) + k) / (n(start, .) + k W))``.  With ``add_k=0`` an unseen
+        pair is ``-inf`` (and a word that never occurs has a row of ``-inf``)."""
+        W = int(W)
+        if W < 1:
+            raise ValueError("W must be >= 1")
+        k = float(add_k)
+        if not k >= 0.0:
+            raise ValueError(f"add_k must be >= 0, got {add_k!r}")
+        pair = np.zeros((W, W + 1))
+        first = np.zeros(W)
+        for u, words in enumerate(transcripts):
+            words = np.asarray(words, dtype=np.int64).reshape(-1)
+            if words.size == 0:
+                continue
+            if words.min() < 0 or words.max() >= W:
+                raise ValueError(f"transcript {u} names a word outside the vocabulary 0..{W - 1}")
+            first[words[0]] += 1.0
+            for a, b in zip(words[:-1], words[1:]):
+                pair[a, b] += 1.0
+            pair[words[-1], W] += 1.0
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rows = np.log((pair + k) / (pair.sum(axis=1, keepdims=True) + k * (W + 1)))
+            start = np.log((first + k) / (first.sum() + k * W))
+        rows = np.where(np.isnan(rows), -np.inf, rows)   # (0 / 0: a word that never occurs, without smoothing)
+        start = np.where(np.isnan(start), -np.inf, start)
+        return WordBigram(rows[:, :W], start, rows[:, W])
+
+    @staticmethod
+    def from_grammar(W, pairs, starts=None, ends=None) -> "WordBigram":
+        """A word-pair grammar: 0.0 for every ``(v, w)`` in ``pairs`` and ``-inf`` elsewhere; ``starts`` / ``ends``:
+        the words an utterance may begin / end with (``None``: any)."""
+        W = int(W)
+        if W < 1:
+            raise ValueError("W must be >= 1")
+
+        def index(w, what):
+            if not 0 <= int(w) < W:
+                raise ValueError(f"{what} names word {w!r} outside the vocabulary 0..{W - 1}")
+            return int(w)
+
+        lm = np.full((W, W), -np.inf)
+        for v, w in pairs:
+            lm[index(v, "pairs"), index(w, "pairs")] = 0.0
+        lm_start = np.zeros(W) if starts is None else np.full(W, -np.inf)
+        lm_end = np.zeros(W) if ends is None else np.full(W, -np.inf)
+        for w in ([] if starts is None else starts):
+            lm_start[index(w, "starts")] = 0.0
+        for w in ([] if ends is None else ends):
+            lm_end[index(w, "ends")] = 0.0
+        return WordBigram(lm, lm_start, lm_end)
+
+    def scaled(self, scale, word_penalty=0.0) -> "WordBigram":
+        """``scale * lm + word_penalty`` with ``lm_start`` and ``lm_end`` scaled but not penalised: the usual
+        language-model weight and word insertion penalty (one penalty per word boundary, as the word loop's).
+        ``scale`` must be >= 0; ``0 * -inf`` stays ``-inf`` (a forbidden pair stays forbidden)."""
+        scale = float(scale)
+        if not scale >= 0.0:
+            raise ValueError(f"scale must be >= 0, got {scale!r}")
+
+        def times(a):
+            with np.errstate(invalid="ignore"):
+                out = scale * a
+            return np.where(np.isnan(out) & ~np.isnan(a), -np.inf, out)
+
+        return WordBigram(times(self.lm) + np.float64(word_penalty), times(self.lm_start), times(self.lm_end))
+
+
 class ConnectedNetwork:
     """The word loop: W word models padded to S = the largest model's states.  ``log_start[W, S]``,
     ``log_trans[W, S, S]``, ``log_exit[W, S]`` (``-inf``: a word may not end in this state; a padded state has ``-inf``
     everywhere) and the scalar ``word_penalty`` added once per word boundary.  Built from models
     (:meth:`from_models`) it also carries its emission ``family``: "diag" with the diagonal-Gaussian parameters
     ``means``, ``vars``, ``gconst``; "gmm" or "full" with the ``tile_family.VocabPack`` it was built from (``pack``: a
-    ``gmm_hmm.GmmPack`` or a ``full_cov.FullPack``, whose device copy the emission reads in place)."""
+    ``gmm_hmm.GmmPack`` or a ``full_cov.FullPack``, whose device copy the emission reads in place).  ``bigram``: a
+    :class:`WordBigram` over the W words; the decoding entry points then run ``sapr_connected_bigram``.  Such a
+    network takes its penalty through ``WordBigram.scaled``: its own ``word_penalty`` must be 0.0."""
 
     def __init__(self, log_start, log_trans, log_exit, word_penalty=0.0, n_states=None, means=None, vars_=None,
-                 gconst=None, family="diag", pack=None):
+                 gconst=None, family="diag", pack=None, bigram=None):
         self.log_start = np.ascontiguousarray(log_start, dtype=np.float64)
         self.log_trans = np.ascontiguousarray(log_trans, dtype=np.float64)
         self.log_exit = np.ascontiguousarray(log_exit, dtype=np.float64)
@@ -153,11 +251,20 @@ class ConnectedNetwork:
         self.family, self.pack = family, pack
         self.D = int(pack.D) if pack is not None else (0 if self.means is None else int(self.means.shape[2]))
         self.SP, self.DP, self.R = layout(self.W, self.S, max(self.D, 1))
-        self._dev = None
+        if bigram is not None:
+            if not isinstance(bigram, WordBigram):
+                raise ValueError(f"bigram must be a WordBigram, got a {type(bigram).__name__}")
+            if bigram.W != self.W:
+                raise ValueError(f"the bigram is over {bigram.W} words, the network over {self.W}")
+            if self.word_penalty != 0.0:
+                raise ValueError(f"a network with a bigram takes its penalty through WordBigram.scaled(scale, "
+                                 f"word_penalty): its own word_penalty must be 0.0, got {self.word_penalty!r}")
+        self.bigram = bigram
+        self._dev = self._dev_lm = None
 
     @staticmethod
     def from_models(models, exit_states="last", word_penalty=0.0, names=None, implementation=None,
-                    pack=None) -> "ConnectedNetwork":
+                    pack=None, bigram=None) -> "ConnectedNetwork":
         """``models``: the fitted word models of one family (:func:`vocabulary_family` decides and validates; ``names``
         and ``implementation`` are what its messages speak of):
 
@@ -227,12 +334,16 @@ class ConnectedNetwork:
             for w, k in enumerate(n_states):
                 log_exit[w, k:] = -np.inf
         return ConnectedNetwork(log_start, log_trans, log_exit, word_penalty, n_states, means, vars_, gconst, family,
-                                pack)
+                                pack, bigram)
 
     def device(self, dev):
         """The device copies ``(log_start, log_trans, log_exit, ops | None)``; made once per device.  ``ops`` is the
-        operand block of the family's emission: :func:`emit_operands` for "diag", the pack's own device copy else."""
+        operand block of the family's emission: :func:`emit_operands` for "diag", the pack's own device copy else.
+        A network with a bigram uploads ``(lm, lm_start, lm_end)`` beside them (``_dev_lm``)."""
         torch = _torch()
+        if self.bigram is not None and (self._dev_lm is None or self._dev_lm[0].device != dev):
+            self._dev_lm = tuple(torch.from_numpy(a).to(dev)
+                                 for a in (self.bigram.lm, self.bigram.lm_start, self.bigram.lm_end))
         if self._dev is None or self._dev[0].device != dev:
             ops = None
             if self.pack is not None:
@@ -313,8 +424,42 @@ def emit_full(feats, network: ConnectedNetwork):
 _EMIT = {"diag": emit_diag, "gmm": emit_gmm, "full": emit_full}
 
 
+def bigram_workspace_bytes(total_frames, n_utts, W, S) -> int:
+    n = C.c_size_t(0)
+    _lib.check(_lib.load().sapr_connected_bigram_workspace_bytes(total_frames, n_utts, W, S, C.byref(n)),
+               "sapr_connected_bigram_workspace_bytes")
+    return int(n.value)
+
+
+def _run_bigram(logb, offs_dev, n_utts, total, network, want_paths=True):
+    """One ``sapr_connected_bigram`` -> device tensors (score, n_words, path_word, path_state, path_entry);
+    ``want_paths=False``: the scores alone (the other four are ``None`` and no back-trace is launched)."""
+    torch = _torch()
+    dev = logb.device
+    ls, lt, lx, _ = network.device(dev)
+    lm, lm_start, lm_end = network._dev_lm
+    ws_bytes = bigram_workspace_bytes(total, n_utts, network.W, network.S)
+    workspace = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    score = torch.empty(n_utts, dtype=torch.float64, device=dev)
+    n_words = path_word = path_state = path_entry = None
+    if want_paths:
+        n_words = torch.empty(n_utts, dtype=torch.int32, device=dev)
+        path_word = torch.empty(total, dtype=torch.int32, device=dev)
+        path_state = torch.empty(total, dtype=torch.int32, device=dev)
+        path_entry = torch.empty(total, dtype=torch.uint8, device=dev)
+    _lib.check(_lib.load().sapr_connected_bigram(
+        _lib.ptr(logb), _lib.ptr(offs_dev), n_utts, total, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx), _lib.ptr(lm),
+        _lib.ptr(lm_start), _lib.ptr(lm_end), network.W, network.S, _lib.ptr(workspace), ws_bytes, _lib.ptr(score),
+        _lib.ptr(n_words), _lib.ptr(path_word), _lib.ptr(path_state), _lib.ptr(path_entry), _lib.current_stream()),
+        "sapr_connected_bigram")
+    return score, n_words, path_word, path_state, path_entry
+
+
 def _run_viterbi(logb, offs_dev, n_utts, total, network):
-    """One ``sapr_connected_viterbi`` -> device tensors (score, n_words, path_word, path_state, path_entry)."""
+    """One ``sapr_connected_viterbi`` — ``sapr_connected_bigram`` where the network carries a bigram — -> device
+    tensors (score, n_words, path_word, path_state, path_entry)."""
+    if network.bigram is not None:
+        return _run_bigram(logb, offs_dev, n_utts, total, network)
     torch = _torch()
     dev = logb.device
     ls, lt, lx, _ = network.device(dev)
@@ -360,7 +505,7 @@ def _flat_logb(logb, total, network, dev):
 def connected_viterbi(logb, lengths, network: ConnectedNetwork) -> ConnectedResult:
     """The recursion over a given ``logb``: float64 ``[total_frames, W, S]`` (the network's own S: padded here with
     ``-inf``), ``[total_frames, W, SP]`` or ``[total_frames, W * SP]``, a host array or a device tensor; host
-    ``lengths``.  Any emission family may supply ``logb``."""
+    ``lengths``.  Any emission family may supply ``logb``.  A network with a bigram runs ``sapr_connected_bigram``."""
     torch = _torch()
     dev = _lib.require_gpu()
     lengths, offs = _offsets(lengths)

@@ -107,7 +107,7 @@ class Decoder:
 
     # ---- connected words ------------------------------------------------------------------------
     def decode_connected(self, feature_list: List[np.ndarray], word_penalty: float = 0.0,
-                         exit_states="last") -> List[Dict]:
+                         exit_states="last", bigram=None) -> List[Dict]:
         """Recordings that hold several words in a row: one-pass Viterbi over the word loop (``sapr_amd.connected``:
         the emission stage of the vocabulary's family, then ``sapr_connected_viterbi``).  ``feature_list``: (D, T)
         arrays as in ``decode_batch``.  Per utterance ``{"words": [...], "log_likelihood": float, "segments": [(word,
@@ -115,6 +115,12 @@ class Decoder:
         utterance no word string can explain (or one without frames) has no words, ``-inf`` and states of -1.
         ``word_penalty`` is added once per word boundary; ``exit_states``: "last", "any" or an array [W, S]
         (``ConnectedNetwork.from_models``).
+
+        ``bigram``: a word-pair language model or grammar — a ``sapr_amd.WordBigram`` over the vocabulary in load order,
+        or a list of transcripts of word names, which ``WordBigram.from_transcripts`` turns into add-one smoothed
+        log-probabilities (a word that is not in the vocabulary is refused with a ``ValueError`` that names it, as
+        ``align`` does).  The search then runs ``sapr_connected_bigram`` over ``bigram.scaled(1.0, word_penalty)``: the
+        step from word v to word w costs ``lm[v, w] + word_penalty``, and ``-inf`` forbids it.
 
         Served for ``implementation="hmmlearn"`` — "diag" / "spherical" vocabularies through
         ``sapr_connected_emit_diag``, a vocabulary with a "full" or "tied" model through ``sapr_connected_emit_full``
@@ -128,7 +134,10 @@ class Decoder:
         if len(feature_list) == 0:
             raise ValueError("empty utterance list")
         words = list(self.models)
-        net = self._connected_network(exit_states, word_penalty)
+        if bigram is None:
+            net = self._connected_network(exit_states, word_penalty)
+        else:
+            net = self._connected_network(exit_states, 0.0, self._word_bigram(bigram).scaled(1.0, word_penalty))
         res = connected_decode([np.asarray(f).T for f in feature_list], net)
         out = []
         for u in range(len(feature_list)):
@@ -139,7 +148,28 @@ class Decoder:
                         "state_sequence": res.path_state[lo:hi].astype(np.int64)})
         return out
 
-    def _connected_network(self, exit_states, word_penalty):
+    def _word_bigram(self, bigram):
+        """``decode_connected``'s ``bigram`` as a ``WordBigram`` over the vocabulary in load order."""
+        from .connected import WordBigram
+        words = list(self.models)
+        if isinstance(bigram, WordBigram):
+            if bigram.W != len(words):
+                raise ValueError(f"the bigram is over {bigram.W} words, the vocabulary has {len(words)} "
+                                 f"({', '.join(words)})")
+            return bigram
+        index = {w: i for i, w in enumerate(words)}
+        rows = []
+        for u, names in enumerate(bigram):
+            if isinstance(names, str):
+                raise ValueError(f"transcript {u} of the bigram is a string; a transcript is a list of word names")
+            for name in names:
+                if name not in index:
+                    raise ValueError(f"transcript {u} of the bigram names {name!r}, which is not in the vocabulary "
+                                     f"({', '.join(words)})")
+            rows.append([index[name] for name in names])
+        return WordBigram.from_transcripts(rows, len(words))
+
+    def _connected_network(self, exit_states, word_penalty, bigram=None):
         """The vocabulary as a ``ConnectedNetwork`` of its emission family, over the decoder's own pack."""
         from .connected import ConnectedNetwork, vocabulary_family
         words = list(self.models)
@@ -147,7 +177,7 @@ class Decoder:
         family = vocabulary_family(self._model_list(), words, self.implementation)
         return ConnectedNetwork.from_models(self._model_list(), exit_states=exit_states, word_penalty=word_penalty,
                                             names=words, implementation=self.implementation,
-                                            pack=None if family == "diag" else self._vocab_pack())
+                                            pack=None if family == "diag" else self._vocab_pack(), bigram=bigram)
 
     def align(self, feature_list: List[np.ndarray], transcripts, word_penalty: float = 0.0,
               exit_states="last") -> List[Dict]:
