@@ -534,6 +534,59 @@ int sapr_connected_bigram(const double *logb, const int64_t *offsets, int64_t n_
                           uint8_t *path_entry /* may be NULL */, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Connected-word confidence (csrc/connected_loop_fb.hip): forward-backward over the word loop under the word-pair
+ * language model of sapr_connected_bigram — the sum over every word string the grammar allows where that function
+ * takes the maximum.  The definition is the CPU restatement tests/_loop_fb_ref.py; with b_t(w,s) = logb[t][w * SP + s]
+ * and lse the log-sum-exp:
+ *     alpha_0(w,j)  = (lm_start[w] + log_start[w][j]) + b_0(w,j)
+ *     X_t(v)        = lse_s (alpha_t(v,s) + log_exit[v][s])
+ *     N_t(w)        = lse_v (X_t(v) + lm[v][w])
+ *     alpha_t(w,j)  = lse( lse_i (alpha_{t-1}(w,i) + log_trans[w][i][j]),  N_{t-1}(w) + log_start[w][j] ) + b_t(w,j)
+ *     loglik        = lse_v (X_{T-1}(v) + lm_end[v])
+ *
+ *     beta_{T-1}(v,s) = log_exit[v][s] + lm_end[v]
+ *     E_t(w)        = lse_j (log_start[w][j] + b_t(w,j) + beta_t(w,j))
+ *     F_t(v)        = lse_w (lm[v][w] + E_t(w))
+ *     beta_t(v,i)   = lse( lse_j (log_trans[v][i][j] + b_{t+1}(v,j) + beta_{t+1}(v,j)),  log_exit[v][i] + F_{t+1}(v) )
+ *
+ *     post_t(w,s)    = exp(alpha_t(w,s) + beta_t(w,s) - loglik)
+ *     word_post_t(w) = sum_s post_t(w,s)                       s ascending
+ *     entry_post_0(w) = word_post_0(w)
+ *     entry_post_t(w) = exp(N_{t-1}(w) + E_t(w) - loglik)      t >= 1: "a word w begins at frame t"
+ * A step inside a word and a step that leaves the word and enters the same word again (lm[w][w]) are different paths;
+ * both count.  loglik - (the score of sapr_connected_bigram on the same logb) is >= 0 and its negative is the log
+ * posterior of the decoded path.  Two identities follow: the chain language model of a transcript of distinct words
+ * (see sapr_connected_bigram) gives sapr_connected_embed's loglik and gamma; every pair forbidden, lm_start = lm_end
+ * = 0 and log_exit = 0 give the log-sum over the words of the isolated-word forward likelihoods and their softmax.
+ *   logb, offsets, log_start, log_trans, log_exit, lm, lm_start, lm_end, W, S: as for sapr_connected_bigram (same
+ *              layout, same limits)
+ *   workspace  sapr_connected_posteriors_workspace_bytes:
+ *                  a16(8 * total_frames * R) + a16(8 * total_frames * W)   bytes, a16 rounding up to 16:
+ *              alpha_t and N_t in float64, 8 (R + W) bytes per frame
+ *   loglik     [n_utts]: -inf for an utterance without frames or without a path; NaN where a NaN was met anywhere in
+ *              the utterance's frames or in the tables
+ *   word_post  [total_frames][W], entry_post [total_frames][W], post [total_frames][R], each may be NULL; with all
+ *              three NULL only the forward pass is launched.  An utterance whose loglik is not finite gets exact zeros
+ *              in its rows (the rule of sapr_connected_embed); a padded state gets 0.0 in post; frames that belong to
+ *              no utterance are not written.
+ * No atomics and a fixed order in every sum: outputs are bit-identical from run to run, and an utterance's outputs are
+ * a function of its own frames and the network alone.
+ *
+ * Bad sizes, NULL required pointers (lm, lm_start and lm_end among them) and a workspace that is too small return
+ * SAPR_ERR_ARG, S > 18 or W * SP > 256 SAPR_ERR_UNSUPPORTED (from the size function too), all before any launch;
+ * n_utts == 0 returns 0 after these checks. */
+int sapr_connected_posteriors_workspace_bytes(int64_t total_frames, int64_t n_utts, int32_t W, int32_t S,
+                                              size_t *bytes);
+int sapr_connected_posteriors(const double *logb, const int64_t *offsets, int64_t n_utts, int64_t total_frames,
+                              const double *log_start, const double *log_trans, const double *log_exit,
+                              const double *lm /* [W][W] */, const double *lm_start /* [W] */,
+                              const double *lm_end /* [W] */, int32_t W, int32_t S, void *workspace,
+                              size_t workspace_bytes, double *loglik /* [n_utts] */,
+                              double *word_post /* [total_frames][W] or NULL */,
+                              double *entry_post /* [total_frames][W] or NULL */,
+                              double *post /* [total_frames][R] or NULL */, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Forced alignment (csrc/connected_align.hip): Viterbi over the left-to-right chain of the K words an utterance is
  * known to hold — where does each word begin and end, and which state explains each frame.  Word slot k is entered
  * only from the exit of slot k - 1 and the score is read only at the exit of the last slot.  The definition is the CPU

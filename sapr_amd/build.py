@@ -23,7 +23,8 @@ SOURCES = ["viterbi_exact_39_18_t1s1.hip", "viterbi_exact_39_18_t1s0.hip", "vite
            "viterbi_bound.hip", "mfcc.hip", "viterbi_exact_13_10.hip", "custom_estep.hip", "custom_emission.hip",
            "custom_update.hip", "custom_decode.hip", "viterbi.hip", "common.hip",
            "resample.hip", "kmeans.hip", "gmm_hmm.hip", "gmm_vocab.hip", "full_vocab.hip",
-           "connected.hip", "connected_align.hip", "connected_embed.hip", "connected_bigram.hip"]
+           "connected.hip", "connected_align.hip", "connected_embed.hip", "connected_bigram.hip",
+           "connected_loop_fb.hip"]
 # -ffp-contract=off: the trellis kernels must perform the individually rounded IEEE
 # operations numpy performs (bit-identical Viterbi scores); kernels that want FMAs
 # call fma()/__builtin_fmaf explicitly.

@@ -14,6 +14,12 @@ A network that carries a :class:`WordBigram` — word-pair log scores ``lm[v, w]
 the same recursion with a per-word entry score ``N(w) = max_v (X(v) + lm[v, w])``.  The definition is
 ``tests/_bigram_ref.py``.  Alignment and embedded training do not read the bigram.
 
+How much to believe a decoded string: ``sapr_connected_posteriors`` (``csrc/connected_loop_fb.hip``) runs
+forward-backward over the same loop under the same language model — the sum over every word string where the search
+takes the best one — and returns the total log-likelihood, the per-frame word and word-boundary posteriors and, from
+these, a confidence per decoded segment (:func:`connected_posteriors`, ``connected_decode(..., posteriors=True)``;
+the definition is ``tests/_loop_fb_ref.py``).
+
 Forced alignment is the inverse question — the words of a recording are known, where does each begin and end:
 ``sapr_connected_align`` (``csrc/connected_align.hip``) runs the Viterbi recursion over the left-to-right chain of an
 utterance's own transcript, on the same ``logb`` (:func:`align_viterbi`, :func:`connected_align`; the definition is
@@ -260,7 +266,7 @@ class ConnectedNetwork:
                 raise ValueError(f"a network with a bigram takes its penalty through WordBigram.scaled(scale, "
                                  f"word_penalty): its own word_penalty must be 0.0, got {self.word_penalty!r}")
         self.bigram = bigram
-        self._dev = self._dev_lm = None
+        self._dev = self._dev_lm = self._dev_loop_lm = None
 
     @staticmethod
     def from_models(models, exit_states="last", word_penalty=0.0, names=None, implementation=None,
@@ -354,6 +360,47 @@ class ConnectedNetwork:
                 + (ops,)
         return self._dev
 
+    def loop_lm(self):
+        """The language model the word loop runs under, on the host: the bigram's ``(lm, lm_start, lm_end)``, or
+        ``lm == word_penalty``, ``lm_start == lm_end == 0`` for a network without one."""
+        if self.bigram is not None:
+            return self.bigram.lm, self.bigram.lm_start, self.bigram.lm_end
+        return np.full((self.W, self.W), np.float64(self.word_penalty)), np.zeros(self.W), np.zeros(self.W)
+
+    def device_lm(self, dev):
+        """The device copies of :meth:`loop_lm`, made once per device beside the tables: one kernel serves a network
+        with a bigram and one without (``sapr_connected_posteriors``)."""
+        torch = _torch()
+        if self.bigram is not None:
+            self.device(dev)
+            return self._dev_lm
+        if self._dev_loop_lm is None or self._dev_loop_lm[0].device != dev:
+            self._dev_loop_lm = tuple(torch.from_numpy(a).to(dev) for a in self.loop_lm())
+        return self._dev_loop_lm
+
+
+@dataclass
+class ConnectedPosteriors:
+    """Forward-backward over the word loop (``sapr_connected_posteriors``; the definition is
+    ``tests/_loop_fb_ref.py``): the sum over every word string the network's language model allows."""
+    loglik: np.ndarray      # [N] f64: log P(utterance) over all word strings; -inf without a path, NaN if one was met
+    word_post: np.ndarray   # [total_frames, W] f64: the posterior of being in word w at frame t
+    entry_post: np.ndarray  # [total_frames, W] f64: the posterior that a word w begins at frame t
+    post: np.ndarray        # [total_frames, W * SP] f64: the posterior of flat state w * SP + s, or None
+    offsets: np.ndarray     # [N + 1] i64
+
+    def segment_confidence(self, result, u):
+        """One float per segment ``(w, a, b)`` of ``result.segments(u)``: the mean of ``word_post[a:b, w]`` over the
+        segment's frames — how much of the probability mass agrees that these frames belong to word ``w``."""
+        lo = int(self.offsets[u])
+        return [float(self.word_post[lo + a:lo + b, w].mean()) for w, a, b in result.segments(u)]
+
+    def path_log_posterior(self, result):
+        """``result.score - loglik`` per utterance: the log posterior of the decoded path among all paths (NaN where
+        both are -inf)."""
+        with np.errstate(invalid="ignore"):
+            return np.asarray(result.score, dtype=np.float64) - self.loglik
+
 
 @dataclass
 class ConnectedResult:
@@ -363,6 +410,7 @@ class ConnectedResult:
     path_state: np.ndarray  # [total_frames] i32 (-1 where the score is not finite)
     path_entry: np.ndarray  # [total_frames] u8: 1 where a word begins
     offsets: np.ndarray     # [N + 1] i64
+    posteriors: ConnectedPosteriors = None  # connected_decode(..., posteriors=True): over the same logb
 
     def segments(self, u):
         """``[(word_index, start, end_exclusive), ...]`` of utterance ``u``, frames counted from its own start."""
@@ -536,12 +584,56 @@ def _features(batch_or_feature_list):
     return torch.from_numpy(packed).to(dev), torch.from_numpy(offs).to(dev), offs
 
 
-def connected_decode(batch_or_feature_list, network: ConnectedNetwork) -> ConnectedResult:
+def posteriors_workspace_bytes(total_frames, n_utts, W, S) -> int:
+    n = C.c_size_t(0)
+    _lib.check(_lib.load().sapr_connected_posteriors_workspace_bytes(total_frames, n_utts, W, S, C.byref(n)),
+               "sapr_connected_posteriors_workspace_bytes")
+    return int(n.value)
+
+
+def _run_posteriors(logb, offs_dev, offs, network, want_post=False) -> ConnectedPosteriors:
+    """One ``sapr_connected_posteriors`` over device ``logb[total_frames, R]``, under the network's bigram or, without
+    one, under ``lm == word_penalty``."""
+    torch = _torch()
+    dev = logb.device
+    n_utts, total = int(offs.size - 1), int(offs[-1])
+    ls, lt, lx, _ = network.device(dev)
+    lm, lm_start, lm_end = network.device_lm(dev)
+    ws_bytes = posteriors_workspace_bytes(total, n_utts, network.W, network.S)
+    workspace = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    loglik = torch.empty(n_utts, dtype=torch.float64, device=dev)
+    word_post = torch.empty((total, network.W), dtype=torch.float64, device=dev)
+    entry_post = torch.empty((total, network.W), dtype=torch.float64, device=dev)
+    post = torch.empty((total, network.R), dtype=torch.float64, device=dev) if want_post else None
+    _lib.check(_lib.load().sapr_connected_posteriors(
+        _lib.ptr(logb), _lib.ptr(offs_dev), n_utts, total, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx), _lib.ptr(lm),
+        _lib.ptr(lm_start), _lib.ptr(lm_end), network.W, network.S, _lib.ptr(workspace), ws_bytes, _lib.ptr(loglik),
+        _lib.ptr(word_post), _lib.ptr(entry_post), _lib.ptr(post), _lib.current_stream()), "sapr_connected_posteriors")
+    host = [None if a is None else a.cpu().numpy() for a in (loglik, word_post, entry_post, post)]
+    return ConnectedPosteriors(*host, offsets=offs)
+
+
+def connected_posteriors(logb, lengths, network: ConnectedNetwork, want_post=False) -> ConnectedPosteriors:
+    """Forward-backward over the word loop on a given ``logb`` (the shapes :func:`connected_viterbi` takes): the total
+    log-likelihood over every word string the network's language model allows, and per frame the posterior of each
+    word and of each word boundary; ``want_post``: the state posteriors ``post[total_frames, W * SP]`` too."""
+    torch = _torch()
+    dev = _lib.require_gpu()
+    lengths, offs = _offsets(lengths)
+    logb = _flat_logb(logb, int(offs[-1]), network, dev)
+    return _run_posteriors(logb, torch.from_numpy(offs).to(dev), offs, network, want_post)
+
+
+def connected_decode(batch_or_feature_list, network: ConnectedNetwork, posteriors=False) -> ConnectedResult:
     """Emission (by the network's family) and recursion: a ``trellis.FeatureBatch`` or a list of frame-major
-    ``(T, D)`` feature arrays -> :class:`ConnectedResult`."""
+    ``(T, D)`` feature arrays -> :class:`ConnectedResult`.  ``posteriors``: forward-backward over the same ``logb``
+    as well (one emission, both recursions); the result then carries its :class:`ConnectedPosteriors`."""
     feats, offs_dev, offs = _features(batch_or_feature_list)
     logb = _EMIT[network.family](feats, network)
-    return _result(_run_viterbi(logb, offs_dev, int(offs.size - 1), int(offs[-1]), network), offs)
+    res = _result(_run_viterbi(logb, offs_dev, int(offs.size - 1), int(offs[-1]), network), offs)
+    if posteriors:
+        res.posteriors = _run_posteriors(logb, offs_dev, offs, network)
+    return res
 
 
 # ---- forced alignment ---------------------------------------------------------------------------

@@ -107,7 +107,7 @@ class Decoder:
 
     # ---- connected words ------------------------------------------------------------------------
     def decode_connected(self, feature_list: List[np.ndarray], word_penalty: float = 0.0,
-                         exit_states="last", bigram=None) -> List[Dict]:
+                         exit_states="last", bigram=None, confidence=False) -> List[Dict]:
         """Recordings that hold several words in a row: one-pass Viterbi over the word loop (``sapr_amd.connected``:
         the emission stage of the vocabulary's family, then ``sapr_connected_viterbi``).  ``feature_list``: (D, T)
         arrays as in ``decode_batch``.  Per utterance ``{"words": [...], "log_likelihood": float, "segments": [(word,
@@ -121,6 +121,12 @@ class Decoder:
         log-probabilities (a word that is not in the vocabulary is refused with a ``ValueError`` that names it, as
         ``align`` does).  The search then runs ``sapr_connected_bigram`` over ``bigram.scaled(1.0, word_penalty)``: the
         step from word v to word w costs ``lm[v, w] + word_penalty``, and ``-inf`` forbids it.
+
+        ``confidence=True``: forward-backward over the same word loop under the same language model, on the same
+        emission (``sapr_connected_posteriors``).  Each dict gains ``"confidence"`` — one float per segment, the mean
+        posterior of the segment's word over its frames —, ``"total_log_likelihood"`` — the log-likelihood of the
+        recording over every word string the language model allows — and ``"log_posterior"`` =
+        ``log_likelihood - total_log_likelihood``, the log posterior of the decoded path among all paths.
 
         Served for ``implementation="hmmlearn"`` — "diag" / "spherical" vocabularies through
         ``sapr_connected_emit_diag``, a vocabulary with a "full" or "tied" model through ``sapr_connected_emit_full``
@@ -138,7 +144,7 @@ class Decoder:
             net = self._connected_network(exit_states, word_penalty)
         else:
             net = self._connected_network(exit_states, 0.0, self._word_bigram(bigram).scaled(1.0, word_penalty))
-        res = connected_decode([np.asarray(f).T for f in feature_list], net)
+        res = connected_decode([np.asarray(f).T for f in feature_list], net, posteriors=bool(confidence))
         out = []
         for u in range(len(feature_list)):
             segs = res.segments(u)
@@ -146,6 +152,12 @@ class Decoder:
             out.append({"words": [words[w] for w, _, _ in segs], "log_likelihood": float(res.score[u]),
                         "segments": [(words[w], a, b) for w, a, b in segs],
                         "state_sequence": res.path_state[lo:hi].astype(np.int64)})
+        if confidence:
+            log_post = res.posteriors.path_log_posterior(res)
+            for u, row in enumerate(out):
+                row["confidence"] = res.posteriors.segment_confidence(res, u)
+                row["total_log_likelihood"] = float(res.posteriors.loglik[u])
+                row["log_posterior"] = float(log_post[u])
         return out
 
     def _word_bigram(self, bigram):
