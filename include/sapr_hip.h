@@ -534,6 +534,67 @@ int sapr_connected_bigram(const double *logb, const int64_t *offsets, int64_t n_
                           uint8_t *path_entry /* may be NULL */, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Connected-word recognition with a known or bounded number of words (csrc/connected_levels.hip): level building over
+ * the word loop of sapr_connected_bigram.  A path carries, next to (word, state), its level l = 0 .. L - 1 — level l
+ * holds the paths that are in their (l + 1)-th word — and one pass returns the best string of exactly k words for
+ * every k = 1 .. L.  The definition is the CPU restatement tests/_levels_ref.py; with b_t(w,s) = logb[t][w * SP + s]:
+ *     delta_0(0,w,j) = (lm_start[w] + log_start[w][j]) + b_0(w,j)          delta_0(l>0,.,.) = -inf
+ *     X_t(l,v)       = max_s (delta_t(l,v,s) + log_exit[v][s])             s ascending, the first maximum
+ *     N_t(l,w)       = max_v (X_t(l-1,v) + lm[v][w])   for l >= 1          v ascending, the first maximum;  N_t(0,w) = -inf
+ *     within         = max_i (delta_{t-1}(l,w,i) + log_trans[w][i][j])     i ascending, the first maximum
+ *     entry          = N_{t-1}(l,w) + log_start[w][j]
+ *     delta_t(l,w,j) = max(within, entry) + b_t(w,j)                       entry only where strictly greater
+ *     level_score[k-1] = max_v (X_{T-1}(k-1,v) + lm_end[v])   k = 1..L     v ascending, the first maximum
+ * float64 adds and compares only, in the order written, b_t last: bit for bit numpy's.  An utterance without frames
+ * scores -inf on every level.  Three identities follow from the monotone rounding of add and max: where
+ * sapr_connected_bigram on the same logb and tables decodes n <= L words, level_score[n-1] is its score bit for bit and
+ * no level scores higher; with L = 1, level_score[0] is sapr_connected_bigram's score with every pair forbidden; with
+ * the chain language model of a transcript of K distinct words (see sapr_connected_bigram), level_score[K-1] and its
+ * path are sapr_connected_align's outputs and every other level is -inf.
+ *
+ * The work is split in two so that one recursion serves any number of back-traces over the workspace it left.
+ * sapr_connected_levels runs the recursion and writes level_score.  sapr_connected_levels_backtrace selects a count per
+ * utterance and walks back: from k = lo it takes a later k <= hi only where level_score[k-1] is strictly greater (on a
+ * tie the fewest words win), starts in level k - 1 from the word that attained level_score[k-1] in the state that
+ * attained its X, and where entry won at frame t steps to level l - 1, to the word that attained N_{t-1}(l,.) in the
+ * state that attained that word's X_{t-1}(l-1,.).
+ *   logb, offsets, log_start, log_trans, log_exit, lm, lm_start, lm_end, W, S: as for sapr_connected_bigram (same
+ *              layout, same limits)
+ *   L          the largest number of words, 1 .. 8
+ *   workspace  sapr_connected_levels_workspace_bytes:
+ *                  a16(total_frames * L * R) + 2 * a16(total_frames * L * W) + a16(4 * n_utts * L)   bytes, a16 rounding
+ *              up to 16: per (frame, level) one back-pointer byte per flat state — the predecessor state, or 255 for an
+ *              entry —, one byte per word for the state that attained X_t(l,v) and one for the predecessor word that
+ *              attained N_t(l,w); one int32 per (utterance, level), the final word.  The back-trace takes the workspace
+ *              the recursion wrote, with the same sizes.
+ *   level_score [n_utts][L]: written by the recursion, read by the back-trace
+ *   count_lo, count_hi  [n_utts] int32, each may be NULL (1 and L): the range of counts per utterance.  lo > hi selects
+ *              nothing (score -inf, no path); otherwise both are clamped into 1 .. L.
+ *   score      [n_utts]: the selected level's score.  n_words, path_word, path_state, path_entry: as for
+ *              sapr_connected_viterbi (each may be NULL); where the selected score is not finite the path rows are -1,
+ *              the entry flags 0 and n_words 0, otherwise n_words is the selected k.
+ * No atomics: outputs are bit-identical from run to run, and an utterance's outputs are a function of its own frames
+ * and the tables alone.  Non-finite values propagate; every index of the walk is clamped into its row.
+ *
+ * Bad sizes, NULL required pointers (lm, lm_start and lm_end among them) and a workspace that is too small return
+ * SAPR_ERR_ARG, S > 18, W * SP > 256 or L outside 1 .. 8 SAPR_ERR_UNSUPPORTED (from the size function too), all before
+ * any launch; n_utts == 0 returns 0 after these checks. */
+int sapr_connected_levels_workspace_bytes(int64_t total_frames, int64_t n_utts, int32_t W, int32_t S, int32_t L,
+                                          size_t *bytes);
+int sapr_connected_levels(const double *logb, const int64_t *offsets, int64_t n_utts, int64_t total_frames,
+                          const double *log_start, const double *log_trans, const double *log_exit,
+                          const double *lm /* [W][W] */, const double *lm_start /* [W] */,
+                          const double *lm_end /* [W] */, int32_t W, int32_t S, int32_t L, void *workspace,
+                          size_t workspace_bytes, double *level_score /* [n_utts][L] */, void *stream);
+int sapr_connected_levels_backtrace(const int64_t *offsets, int64_t n_utts, int64_t total_frames, int32_t W, int32_t S,
+                                    int32_t L, void *workspace, size_t workspace_bytes,
+                                    const double *level_score /* [n_utts][L] */,
+                                    const int32_t *count_lo /* may be NULL */, const int32_t *count_hi /* may be NULL */,
+                                    double *score, int32_t *n_words /* may be NULL */,
+                                    int32_t *path_word /* may be NULL */, int32_t *path_state /* may be NULL */,
+                                    uint8_t *path_entry /* may be NULL */, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Connected-word confidence (csrc/connected_loop_fb.hip): forward-backward over the word loop under the word-pair
  * language model of sapr_connected_bigram — the sum over every word string the grammar allows where that function
  * takes the maximum.  The definition is the CPU restatement tests/_loop_fb_ref.py; with b_t(w,s) = logb[t][w * SP + s]

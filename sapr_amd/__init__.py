@@ -11,7 +11,8 @@ behaviour) over hand-written HIP kernels in ``libsapr_hip.so``:
 * ``sapr_amd.full_cov``      the full-covariance kernels behind ``GaussianHMM(covariance_type="full" | "tied")`` and the
                              recogniser's scoring over a vocabulary of such models
 * ``sapr_amd.connected``     connected-word recognition: one-pass Viterbi over the word loop (under a word bigram or a
-                             word-pair grammar where one is given: ``WordBigram``), word and segment confidences
+                             word-pair grammar where one is given: ``WordBigram``; with a known or bounded number of
+                             words by level building: ``connected_levels``), word and segment confidences
                              from forward-backward over the same loop (``connected_posteriors``), forced alignment of
                              a recording to its known word string, and embedded Baum-Welch training from such
                              recordings (no counterpart in the reference, whose decoder labels a recording as one word)
@@ -29,7 +30,8 @@ def __getattr__(name):
     ``sapr_amd.EmbeddedStats`` / ``sapr_amd.embedded_forward_backward`` / ``sapr_amd.embedded_estep`` /
     ``sapr_amd.embedded_fit`` / ``sapr_amd.embed_full_stats_width`` / ``sapr_amd.embed_full_workspace_bytes`` /
     ``sapr_amd.embed_gmm_stats_width`` / ``sapr_amd.embed_gmm_workspace_bytes`` / ``sapr_amd.ConnectedPosteriors`` /
-    ``sapr_amd.connected_posteriors`` / ``sapr_amd.posteriors_workspace_bytes``
+    ``sapr_amd.connected_posteriors`` / ``sapr_amd.posteriors_workspace_bytes`` / ``sapr_amd.LevelResult`` /
+    ``sapr_amd.connected_levels`` / ``sapr_amd.levels_workspace_bytes``
     (resolved on first use: importing the package stays light)."""
     if name in ("GMMHMM", "fit_gmm_models", "vocab_scores"):
         from . import gmm_hmm
@@ -38,7 +40,7 @@ def __getattr__(name):
                 "AlignResult", "align_viterbi", "connected_align", "EmbeddedStats", "embedded_forward_backward", "embedded_estep",
                 "embedded_fit", "embed_full_stats_width", "embed_full_workspace_bytes", "embed_gmm_stats_width",
                 "embed_gmm_workspace_bytes", "ConnectedPosteriors", "connected_posteriors",
-                "posteriors_workspace_bytes"):
+                "posteriors_workspace_bytes", "LevelResult", "connected_levels", "levels_workspace_bytes"):
         from . import connected
         return getattr(connected, name)
     if name == "full_vocab_scores":

@@ -96,6 +96,14 @@ SIGNATURES = {
     "sapr_connected_bigram": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sapr_connected_levels_workspace_bytes": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int32,
+                                                      C.POINTER(c_size_t)]),
+    "sapr_connected_levels": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_size_t, c_void_p,
+                                      c_void_p]),
+    "sapr_connected_levels_backtrace": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p,
+                                                c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                c_void_p, c_void_p, c_void_p]),
     "sapr_connected_posteriors_workspace_bytes": (c_int, [c_int64, c_int64, c_int32, c_int32, C.POINTER(c_size_t)]),
     "sapr_connected_posteriors": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p, c_void_p,

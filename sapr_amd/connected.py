@@ -14,6 +14,12 @@ A network that carries a :class:`WordBigram` — word-pair log scores ``lm[v, w]
 the same recursion with a per-word entry score ``N(w) = max_v (X(v) + lm[v, w])``.  The definition is
 ``tests/_bigram_ref.py``.  Alignment and embedded training do not read the bigram.
 
+Where the number of words is known or bounded (a PIN, a phone number), ``sapr_connected_levels``
+(``csrc/connected_levels.hip``) runs level building over the same loop under the same language model: one pass returns
+the best string of exactly k words for every k up to a bound of at most 8, and ``sapr_connected_levels_backtrace``
+walks back from a known count, a range of counts or each count in turn (:func:`connected_levels`,
+:class:`LevelResult`, ``connected_decode(..., n_words=, max_words=)``; the definition is ``tests/_levels_ref.py``).
+
 How much to believe a decoded string: ``sapr_connected_posteriors`` (``csrc/connected_loop_fb.hip``) runs
 forward-backward over the same loop under the same language model — the sum over every word string where the search
 takes the best one — and returns the total log-likelihood, the per-frame word and word-boundary posteriors and, from
@@ -411,6 +417,8 @@ class ConnectedResult:
     path_entry: np.ndarray  # [total_frames] u8: 1 where a word begins
     offsets: np.ndarray     # [N + 1] i64
     posteriors: ConnectedPosteriors = None  # connected_decode(..., posteriors=True): over the same logb
+    level_score: np.ndarray = None  # [N, L] f64: connected_decode(..., n_words= / max_words=): the best score per count
+    levels: "LevelResult" = None    # ... and the recursion it was selected from (further back-traces, N-best strings)
 
     def segments(self, u):
         """``[(word_index, start, end_exclusive), ...]`` of utterance ``u``, frames counted from its own start."""
@@ -624,13 +632,160 @@ def connected_posteriors(logb, lengths, network: ConnectedNetwork, want_post=Fal
     return _run_posteriors(logb, torch.from_numpy(offs).to(dev), offs, network, want_post)
 
 
-def connected_decode(batch_or_feature_list, network: ConnectedNetwork, posteriors=False) -> ConnectedResult:
+MAX_LEVELS = 8
+
+
+def levels_workspace_bytes(total_frames, n_utts, W, S, max_words) -> int:
+    n = C.c_size_t(0)
+    _lib.check(_lib.load().sapr_connected_levels_workspace_bytes(total_frames, n_utts, W, S, max_words, C.byref(n)),
+               "sapr_connected_levels_workspace_bytes")
+    return int(n.value)
+
+
+def _check_counts(n_words, max_words, n_utts):
+    """``connected_decode``'s ``n_words`` / ``max_words`` -> ``(n_words, L)``: ``n_words`` is ``None``, an int or an
+    int32 array of one count per utterance, every count inside 1 .. L; L inside 1 .. MAX_LEVELS.  ``n_words`` alone
+    implies ``max_words`` = its largest count."""
+    if n_words is not None:
+        arr = np.asarray(n_words)
+        if arr.dtype.kind not in "iu" or arr.ndim > 1:
+            raise ValueError(f"n_words must be an int or one int per utterance, got {n_words!r}")
+        if arr.ndim == 1 and arr.size != n_utts:
+            raise ValueError(f"{arr.size} word counts for {n_utts} utterances")
+        n_words = int(arr) if arr.ndim == 0 else arr.astype(np.int32)
+        if max_words is None:
+            max_words = int(arr.max()) if arr.size else 1
+    L = int(max_words)
+    if not 1 <= L <= MAX_LEVELS:
+        raise ValueError(f"max_words must be inside 1..{MAX_LEVELS} (the levels one wavefront holds), got {L}")
+    if n_words is not None and (np.min(n_words) < 1 or np.max(n_words) > L):
+        got = f"{int(np.min(n_words))}..{int(np.max(n_words))}" if np.ndim(n_words) else f"{n_words}"
+        raise ValueError(f"n_words must be inside 1..max_words = 1..{L} (max_words is at most {MAX_LEVELS}), got {got}")
+    return n_words, L
+
+
+class LevelResult:
+    """One level-building recursion (``sapr_connected_levels``; the definition is ``tests/_levels_ref.py``):
+    ``level_score[N, L]``, the best score of a string of exactly k words for k = 1 .. L, and the live device workspace
+    any number of back-traces are taken from (:meth:`select`, :meth:`strings`)."""
+
+    def __init__(self, level_score, offsets, network, max_words, level_dev, offs_dev, workspace, ws_bytes):
+        self.level_score = level_score  # [N, L] f64; -inf where no string of k words explains the utterance
+        self.offsets = offsets          # [N + 1] i64
+        self.max_words = int(max_words)
+        self._network, self._level_dev, self._offs_dev = network, level_dev, offs_dev
+        self._workspace, self._ws_bytes = workspace, ws_bytes
+        self._by_count = {}
+
+    def select(self, n_words=None) -> ConnectedResult:
+        """One ``sapr_connected_levels_backtrace``.  ``n_words``: ``None`` — the best count in 1 .. L; an int — exactly
+        that many words; an array of one int per utterance; a tuple ``(lo, hi)`` of ints or per-utterance arrays — the
+        best count inside the range.  Among counts that tie exactly the fewest words win; ``lo > hi`` selects nothing.
+        A count outside 1 .. L is a ``ValueError`` for an int or an array, and is clamped in a range."""
+        torch = _torch()
+        n_utts, total = int(self.offsets.size - 1), int(self.offsets[-1])
+        dev = self._level_dev.device
+        if isinstance(n_words, tuple):
+            if len(n_words) != 2:
+                raise ValueError("a range of counts is a tuple (lo, hi)")
+            lo, hi = n_words
+        else:
+            if n_words is not None:
+                n_words, _ = _check_counts(n_words, self.max_words, n_utts)
+            lo = hi = n_words
+
+        def per_utt(a):
+            if a is None:
+                return None
+            a = np.asarray(a)
+            if a.dtype.kind not in "iu" or a.ndim > 1 or (a.ndim == 1 and a.size != n_utts):
+                raise ValueError(f"a count is an int or one int per utterance ({n_utts}), got {a!r}")
+            return torch.from_numpy(np.array(np.broadcast_to(a, (n_utts,)), dtype=np.int32)).to(dev)
+
+        lo_dev, hi_dev = per_utt(lo), per_utt(hi)
+        net = self._network
+        score = torch.empty(n_utts, dtype=torch.float64, device=dev)
+        count = torch.empty(n_utts, dtype=torch.int32, device=dev)
+        path_word = torch.empty(total, dtype=torch.int32, device=dev)
+        path_state = torch.empty(total, dtype=torch.int32, device=dev)
+        path_entry = torch.empty(total, dtype=torch.uint8, device=dev)
+        _lib.check(_lib.load().sapr_connected_levels_backtrace(
+            _lib.ptr(self._offs_dev), n_utts, total, net.W, net.S, self.max_words, _lib.ptr(self._workspace),
+            self._ws_bytes, _lib.ptr(self._level_dev), _lib.ptr(lo_dev), _lib.ptr(hi_dev), _lib.ptr(score),
+            _lib.ptr(count), _lib.ptr(path_word), _lib.ptr(path_state), _lib.ptr(path_entry), _lib.current_stream()),
+            "sapr_connected_levels_backtrace")
+        res = _result((score, count, path_word, path_state, path_entry), self.offsets)
+        res.level_score, res.levels = self.level_score, self
+        return res
+
+    def strings(self, u):
+        """The up to L strings of utterance ``u``, one per count with a finite score, best first (among equal scores
+        the fewer words first): ``[(k, score, words, segments), ...]`` — a length-indexed N-best list.  The back-trace
+        of a count is run once for the whole batch and kept."""
+        out = []
+        for k in range(1, self.max_words + 1):
+            if not np.isfinite(self.level_score[u, k - 1]):
+                continue
+            if k not in self._by_count:
+                self._by_count[k] = self.select(k)
+            res = self._by_count[k]
+            out.append((k, float(res.score[u]), res.words(u), res.segments(u)))
+        out.sort(key=lambda row: -row[1])   # (stable: the fewer words first among equals)
+        return out
+
+
+def _run_levels(logb, offs_dev, offs, network, max_words) -> LevelResult:
+    """One ``sapr_connected_levels`` over device ``logb[total_frames, R]``, under the network's bigram or, without
+    one, under ``lm == word_penalty``."""
+    torch = _torch()
+    dev = logb.device
+    n_utts, total = int(offs.size - 1), int(offs[-1])
+    L = int(max_words)
+    ls, lt, lx, _ = network.device(dev)
+    lm, lm_start, lm_end = network.device_lm(dev)
+    ws_bytes = levels_workspace_bytes(total, n_utts, network.W, network.S, L)
+    workspace = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    level = torch.empty((n_utts, L), dtype=torch.float64, device=dev)
+    _lib.check(_lib.load().sapr_connected_levels(
+        _lib.ptr(logb), _lib.ptr(offs_dev), n_utts, total, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx), _lib.ptr(lm),
+        _lib.ptr(lm_start), _lib.ptr(lm_end), network.W, network.S, L, _lib.ptr(workspace), ws_bytes, _lib.ptr(level),
+        _lib.current_stream()), "sapr_connected_levels")
+    return LevelResult(level.cpu().numpy(), offs, network, L, level, offs_dev, workspace, ws_bytes)
+
+
+def connected_levels(logb, lengths, network: ConnectedNetwork, max_words) -> LevelResult:
+    """Level building over a given ``logb`` (the shapes :func:`connected_viterbi` takes): the best string of exactly
+    k words for every k = 1 .. ``max_words`` (at most 8) in one pass, under the network's bigram or, without one,
+    under its ``word_penalty``.  The result selects a known count, a range of counts or all the strings."""
+    torch = _torch()
+    L = _check_counts(None, max_words, 0)[1]
+    dev = _lib.require_gpu()
+    lengths, offs = _offsets(lengths)
+    logb = _flat_logb(logb, int(offs[-1]), network, dev)
+    return _run_levels(logb, torch.from_numpy(offs).to(dev), offs, network, L)
+
+
+def connected_decode(batch_or_feature_list, network: ConnectedNetwork, posteriors=False, n_words=None,
+                     max_words=None) -> ConnectedResult:
     """Emission (by the network's family) and recursion: a ``trellis.FeatureBatch`` or a list of frame-major
     ``(T, D)`` feature arrays -> :class:`ConnectedResult`.  ``posteriors``: forward-backward over the same ``logb``
-    as well (one emission, both recursions); the result then carries its :class:`ConnectedPosteriors`."""
-    feats, offs_dev, offs = _features(batch_or_feature_list)
-    logb = _EMIT[network.family](feats, network)
-    res = _result(_run_viterbi(logb, offs_dev, int(offs.size - 1), int(offs[-1]), network), offs)
+    as well (one emission, both recursions); the result then carries its :class:`ConnectedPosteriors`.
+
+    ``n_words`` (an int or one per utterance): the number of words is known; ``max_words``: it is at most this.  Either
+    runs level building (``sapr_connected_levels``) instead of the free loop and the result carries ``level_score`` and
+    its :class:`LevelResult`; ``n_words`` alone implies ``max_words`` = its largest count.  ``max_words`` above 8 or an
+    ``n_words`` outside 1 .. ``max_words`` is a ``ValueError``."""
+    if n_words is None and max_words is None:
+        feats, offs_dev, offs = _features(batch_or_feature_list)
+        logb = _EMIT[network.family](feats, network)
+        res = _result(_run_viterbi(logb, offs_dev, int(offs.size - 1), int(offs[-1]), network), offs)
+    else:
+        b = batch_or_feature_list
+        n_utts = len(b.lengths) if hasattr(b, "offsets") and hasattr(b, "order") else len(b)
+        n_words, L = _check_counts(n_words, max_words, n_utts)  # (refused before a device is asked for)
+        feats, offs_dev, offs = _features(b)
+        logb = _EMIT[network.family](feats, network)
+        res = _run_levels(logb, offs_dev, offs, network, L).select(n_words)
     if posteriors:
         res.posteriors = _run_posteriors(logb, offs_dev, offs, network)
     return res

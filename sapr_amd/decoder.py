@@ -107,7 +107,8 @@ class Decoder:
 
     # ---- connected words ------------------------------------------------------------------------
     def decode_connected(self, feature_list: List[np.ndarray], word_penalty: float = 0.0,
-                         exit_states="last", bigram=None, confidence=False) -> List[Dict]:
+                         exit_states="last", bigram=None, confidence=False, n_words=None, max_words=None,
+                         nbest=False) -> List[Dict]:
         """Recordings that hold several words in a row: one-pass Viterbi over the word loop (``sapr_amd.connected``:
         the emission stage of the vocabulary's family, then ``sapr_connected_viterbi``).  ``feature_list``: (D, T)
         arrays as in ``decode_batch``.  Per utterance ``{"words": [...], "log_likelihood": float, "segments": [(word,
@@ -128,6 +129,14 @@ class Decoder:
         recording over every word string the language model allows — and ``"log_posterior"`` =
         ``log_likelihood - total_log_likelihood``, the log posterior of the decoded path among all paths.
 
+        ``n_words`` (an int, or one per recording): the number of words is known; ``max_words``: it is at most this (up
+        to 8).  The search then runs level building (``sapr_connected_levels``): one pass that returns the best string
+        of exactly k words for every k up to the bound, under the same language model.  Each dict gains
+        ``"level_log_likelihoods"``, one float per count 1 .. ``max_words`` (``-inf`` where no string of that many
+        words explains the recording).  ``nbest=True`` (with ``max_words=8`` unless a bound is given): each dict gains
+        ``"strings"``, a list of ``{"words", "log_likelihood", "segments"}``, one per count with a finite score, best
+        first; its first entry is the result itself unless ``n_words`` asked for another count.
+
         Served for ``implementation="hmmlearn"`` — "diag" / "spherical" vocabularies through
         ``sapr_connected_emit_diag``, a vocabulary with a "full" or "tied" model through ``sapr_connected_emit_full``
         over the decoder's ``FullPack`` — and for ``implementation="gmmhmm"`` through ``sapr_connected_emit_gmm`` over
@@ -144,7 +153,10 @@ class Decoder:
             net = self._connected_network(exit_states, word_penalty)
         else:
             net = self._connected_network(exit_states, 0.0, self._word_bigram(bigram).scaled(1.0, word_penalty))
-        res = connected_decode([np.asarray(f).T for f in feature_list], net, posteriors=bool(confidence))
+        if nbest and n_words is None and max_words is None:
+            from .connected import MAX_LEVELS as max_words
+        res = connected_decode([np.asarray(f).T for f in feature_list], net, posteriors=bool(confidence),
+                               n_words=n_words, max_words=max_words)
         out = []
         for u in range(len(feature_list)):
             segs = res.segments(u)
@@ -152,6 +164,13 @@ class Decoder:
             out.append({"words": [words[w] for w, _, _ in segs], "log_likelihood": float(res.score[u]),
                         "segments": [(words[w], a, b) for w, a, b in segs],
                         "state_sequence": res.path_state[lo:hi].astype(np.int64)})
+        if res.level_score is not None:
+            for u, row in enumerate(out):
+                row["level_log_likelihoods"] = [float(v) for v in res.level_score[u]]
+                if nbest:
+                    row["strings"] = [{"words": [words[w] for w in ws], "log_likelihood": sc,
+                                       "segments": [(words[w], a, b) for w, a, b in segs]}
+                                      for _, sc, ws, segs in res.levels.strings(u)]
         if confidence:
             log_post = res.posteriors.path_log_posterior(res)
             for u, row in enumerate(out):
