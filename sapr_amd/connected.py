@@ -58,11 +58,15 @@ def layout(W, S, D=1):
     return int(sp.value), int(dp.value), int(r.value)
 
 
-def workspace_bytes(total_frames, n_utts, W, S) -> int:
+def _workspace_bytes(entry, *sizes) -> int:
+    """``entry(*sizes, &bytes)`` of the library: the workspace one call at these sizes takes."""
     n = C.c_size_t(0)
-    _lib.check(_lib.load().sapr_connected_workspace_bytes(total_frames, n_utts, W, S, C.byref(n)),
-               "sapr_connected_workspace_bytes")
+    _lib.check(getattr(_lib.load(), entry)(*sizes, C.byref(n)), entry)
     return int(n.value)
+
+
+def workspace_bytes(total_frames, n_utts, W, S) -> int:
+    return _workspace_bytes("sapr_connected_workspace_bytes", total_frames, n_utts, W, S)
 
 
 def emit_operands(means, vars_, gconst, n_states=None) -> np.ndarray:
@@ -481,10 +485,19 @@ _EMIT = {"diag": emit_diag, "gmm": emit_gmm, "full": emit_full}
 
 
 def bigram_workspace_bytes(total_frames, n_utts, W, S) -> int:
-    n = C.c_size_t(0)
-    _lib.check(_lib.load().sapr_connected_bigram_workspace_bytes(total_frames, n_utts, W, S, C.byref(n)),
-               "sapr_connected_bigram_workspace_bytes")
-    return int(n.value)
+    return _workspace_bytes("sapr_connected_bigram_workspace_bytes", total_frames, n_utts, W, S)
+
+
+def _path_tensors(n_utts, total, dev, want_paths=True):
+    """Uninitialised device tensors (score, n_words, path_word, path_state, path_entry) for a back-trace to fill;
+    ``want_paths=False``: the score alone, the other four ``None``."""
+    torch = _torch()
+    score = torch.empty(n_utts, dtype=torch.float64, device=dev)
+    if not want_paths:
+        return score, None, None, None, None
+    return (score, torch.empty(n_utts, dtype=torch.int32, device=dev),
+            torch.empty(total, dtype=torch.int32, device=dev), torch.empty(total, dtype=torch.int32, device=dev),
+            torch.empty(total, dtype=torch.uint8, device=dev))
 
 
 def _run_bigram(logb, offs_dev, n_utts, total, network, want_paths=True):
@@ -496,13 +509,7 @@ def _run_bigram(logb, offs_dev, n_utts, total, network, want_paths=True):
     lm, lm_start, lm_end = network._dev_lm
     ws_bytes = bigram_workspace_bytes(total, n_utts, network.W, network.S)
     workspace = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    score = torch.empty(n_utts, dtype=torch.float64, device=dev)
-    n_words = path_word = path_state = path_entry = None
-    if want_paths:
-        n_words = torch.empty(n_utts, dtype=torch.int32, device=dev)
-        path_word = torch.empty(total, dtype=torch.int32, device=dev)
-        path_state = torch.empty(total, dtype=torch.int32, device=dev)
-        path_entry = torch.empty(total, dtype=torch.uint8, device=dev)
+    score, n_words, path_word, path_state, path_entry = _path_tensors(n_utts, total, dev, want_paths)
     _lib.check(_lib.load().sapr_connected_bigram(
         _lib.ptr(logb), _lib.ptr(offs_dev), n_utts, total, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx), _lib.ptr(lm),
         _lib.ptr(lm_start), _lib.ptr(lm_end), network.W, network.S, _lib.ptr(workspace), ws_bytes, _lib.ptr(score),
@@ -521,11 +528,7 @@ def _run_viterbi(logb, offs_dev, n_utts, total, network):
     ls, lt, lx, _ = network.device(dev)
     ws_bytes = workspace_bytes(total, n_utts, network.W, network.S)
     workspace = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    score = torch.empty(n_utts, dtype=torch.float64, device=dev)
-    n_words = torch.empty(n_utts, dtype=torch.int32, device=dev)
-    path_word = torch.empty(total, dtype=torch.int32, device=dev)
-    path_state = torch.empty(total, dtype=torch.int32, device=dev)
-    path_entry = torch.empty(total, dtype=torch.uint8, device=dev)
+    score, n_words, path_word, path_state, path_entry = _path_tensors(n_utts, total, dev)
     _lib.check(_lib.load().sapr_connected_viterbi(
         _lib.ptr(logb), _lib.ptr(offs_dev), n_utts, total, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx),
         network.word_penalty, network.W, network.S, _lib.ptr(workspace), ws_bytes, _lib.ptr(score), _lib.ptr(n_words),
@@ -593,10 +596,7 @@ def _features(batch_or_feature_list):
 
 
 def posteriors_workspace_bytes(total_frames, n_utts, W, S) -> int:
-    n = C.c_size_t(0)
-    _lib.check(_lib.load().sapr_connected_posteriors_workspace_bytes(total_frames, n_utts, W, S, C.byref(n)),
-               "sapr_connected_posteriors_workspace_bytes")
-    return int(n.value)
+    return _workspace_bytes("sapr_connected_posteriors_workspace_bytes", total_frames, n_utts, W, S)
 
 
 def _run_posteriors(logb, offs_dev, offs, network, want_post=False) -> ConnectedPosteriors:
@@ -636,10 +636,7 @@ MAX_LEVELS = 8
 
 
 def levels_workspace_bytes(total_frames, n_utts, W, S, max_words) -> int:
-    n = C.c_size_t(0)
-    _lib.check(_lib.load().sapr_connected_levels_workspace_bytes(total_frames, n_utts, W, S, max_words, C.byref(n)),
-               "sapr_connected_levels_workspace_bytes")
-    return int(n.value)
+    return _workspace_bytes("sapr_connected_levels_workspace_bytes", total_frames, n_utts, W, S, max_words)
 
 
 def _check_counts(n_words, max_words, n_utts):
@@ -704,11 +701,7 @@ class LevelResult:
 
         lo_dev, hi_dev = per_utt(lo), per_utt(hi)
         net = self._network
-        score = torch.empty(n_utts, dtype=torch.float64, device=dev)
-        count = torch.empty(n_utts, dtype=torch.int32, device=dev)
-        path_word = torch.empty(total, dtype=torch.int32, device=dev)
-        path_state = torch.empty(total, dtype=torch.int32, device=dev)
-        path_entry = torch.empty(total, dtype=torch.uint8, device=dev)
+        score, count, path_word, path_state, path_entry = _path_tensors(n_utts, total, dev)
         _lib.check(_lib.load().sapr_connected_levels_backtrace(
             _lib.ptr(self._offs_dev), n_utts, total, net.W, net.S, self.max_words, _lib.ptr(self._workspace),
             self._ws_bytes, _lib.ptr(self._level_dev), _lib.ptr(lo_dev), _lib.ptr(hi_dev), _lib.ptr(score),
@@ -793,10 +786,7 @@ def connected_decode(batch_or_feature_list, network: ConnectedNetwork, posterior
 
 # ---- forced alignment ---------------------------------------------------------------------------
 def align_workspace_bytes(total_frames, n_utts, max_words, S) -> int:
-    n = C.c_size_t(0)
-    _lib.check(_lib.load().sapr_connected_align_workspace_bytes(total_frames, n_utts, max_words, S, C.byref(n)),
-               "sapr_connected_align_workspace_bytes")
-    return int(n.value)
+    return _workspace_bytes("sapr_connected_align_workspace_bytes", total_frames, n_utts, max_words, S)
 
 
 @dataclass
@@ -912,10 +902,7 @@ def embed_stats_width(S, D) -> int:
 
 
 def embed_workspace_bytes(total_frames, n_utts, total_words, max_words, S, D) -> int:
-    n = C.c_size_t(0)
-    _lib.check(_lib.load().sapr_connected_embed_workspace_bytes(total_frames, n_utts, total_words, max_words, S, D,
-                                                                C.byref(n)), "sapr_connected_embed_workspace_bytes")
-    return int(n.value)
+    return _workspace_bytes("sapr_connected_embed_workspace_bytes", total_frames, n_utts, total_words, max_words, S, D)
 
 
 def embed_full_stats_width(S, D) -> int:
@@ -926,11 +913,8 @@ def embed_full_stats_width(S, D) -> int:
 
 
 def embed_full_workspace_bytes(total_frames, n_utts, total_words, max_words, W, S, D) -> int:
-    n = C.c_size_t(0)
-    _lib.check(_lib.load().sapr_connected_embed_full_workspace_bytes(total_frames, n_utts, total_words, max_words, W,
-                                                                     S, D, C.byref(n)),
-               "sapr_connected_embed_full_workspace_bytes")
-    return int(n.value)
+    return _workspace_bytes("sapr_connected_embed_full_workspace_bytes", total_frames, n_utts, total_words, max_words,
+                            W, S, D)
 
 
 def embed_gmm_stats_width(S, M, D) -> int:
@@ -941,11 +925,8 @@ def embed_gmm_stats_width(S, M, D) -> int:
 
 
 def embed_gmm_workspace_bytes(total_frames, n_utts, total_words, max_words, W, S, M, D) -> int:
-    n = C.c_size_t(0)
-    _lib.check(_lib.load().sapr_connected_embed_gmm_workspace_bytes(total_frames, n_utts, total_words, max_words, W,
-                                                                    S, M, D, C.byref(n)),
-               "sapr_connected_embed_gmm_workspace_bytes")
-    return int(n.value)
+    return _workspace_bytes("sapr_connected_embed_gmm_workspace_bytes", total_frames, n_utts, total_words, max_words,
+                            W, S, M, D)
 
 
 @dataclass

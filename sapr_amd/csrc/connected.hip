@@ -22,16 +22,11 @@
 // holds, and costs no arithmetic.
 //
 // Stage 2, sapr_connected_viterbi: the recursion over a given logb; it knows nothing about the emission family.
-//     One wavefront serves one utterance (four utterances per workgroup, which share the transition table in LDS).
-//     The R <= 256 flat states lie along the lanes, RL in {1, 2, 4} per lane: flat state r = k * 64 + lane sits in
-//     register k of its lane, so row t of logb is RL coalesced 512-byte reads and the next frame's row is in flight
-//     under the current frame.  The predecessor at distance d = j - i of state r is flat state r - d: lane
-//     (lane - d) & 63 (ds_bpermute), register k, or k -/+ 1 where lane - d leaves 0..63 (d runs over
-//     -(SP - 1) .. SP - 1: a dense model also steps back).  Distances at which no transition of the
-//     vocabulary is finite are skipped wavefront-uniformly (the mask is taken from the table by the kernel itself:
-//     a bidiagonal vocabulary costs two candidates per state, a dense one 2 S - 1).  E_{t-1} = max_r (delta + log_exit)
-//     is one wave-wide butterfly over (value, flat index), the lowest index among equals.
-//     Back-pointers: one byte per (frame, flat state) — the predecessor state, or kEntry where the word entry won —
+//     connected_viterbi_kernel<RL>: the lane layout of connected_lanes.h over the flat states, four utterances per
+//     workgroup, the transition table by source (SP is a run-time value here).  The coupling is this unit's own: any
+//     word may follow any word, so E_{t-1} = max_r (delta + log_exit) is one wave-wide butterfly over (value, flat
+//     index), the lowest index among equals, and needs no LDS row.
+//     Back-pointers: one byte per (frame, flat state) — the predecessor state, or kXEntry where the word entry won —
 //     and the flat arg-max of E per frame (int32), both in the workspace.  A second kernel, one lane per utterance,
 //     walks back and writes path_word, path_state, path_entry, n_words.
 //
@@ -46,34 +41,29 @@ namespace {
 #include "lse_ops.h"
 #include "gmm_ops.h"
 #include "fullcov_emit.h"
-
-constexpr int kCnMaxS = kMaxS, kCnMaxD = kMaxD, kCnMaxR = 256;
-constexpr int kCnBlock = 256;         // 4 wavefronts per workgroup
-constexpr int kCnWaves = kCnBlock / kWave;
-constexpr int kEntry = 255;           // back-pointer byte: the word was entered at this frame
+#include "connected_lanes.h"
 
 constexpr int cn_sp_of(int S) { return sp_of(S); }  // (the padding rules of every family: gmm_ops.h)
 constexpr int cn_dp_of(int D) { return dp_of(D); }
 
+// the emission stages' check: x_check_shape and the feature dimension
 inline int cn_check_shape(int32_t W, int32_t S, int32_t D) {
-  if (S > kCnMaxS || D > kCnMaxD || static_cast<int64_t>(W) * cn_sp_of(S) > kCnMaxR)
+  if (S > kMaxS || D > kMaxD || static_cast<int64_t>(W) * cn_sp_of(S) > kXMaxR)
     return fail(SAPR_ERR_UNSUPPORTED,
                 "the connected-word kernels serve S in 1..%d, D in 1..%d and W * SP <= %d; got W=%d S=%d D=%d",
-                kCnMaxS, kCnMaxD, kCnMaxR, W, S, D);
+                kMaxS, kMaxD, kXMaxR, W, S, D);
   return 0;
 }
-
-inline size_t cn_align16(size_t x) { return (x + 15) / 16 * 16; }
 
 // ---------------------------------------------------------------------------------------
 // stage 1: diagonal-Gaussian emissions
 // ---------------------------------------------------------------------------------------
 template <int DP>
-__global__ __launch_bounds__(kCnBlock) void connected_emit_kernel(const float *__restrict__ feats,
-                                                                   int64_t total_frames, int32_t D, int32_t R,
-                                                                   const double *__restrict__ ops,
-                                                                   double *__restrict__ logb) {
-  const int64_t t = static_cast<int64_t>(blockIdx.x) * kCnBlock + threadIdx.x;
+__global__ __launch_bounds__(kXBlock) void connected_emit_kernel(const float *__restrict__ feats,
+                                                                 int64_t total_frames, int32_t D, int32_t R,
+                                                                 const double *__restrict__ ops,
+                                                                 double *__restrict__ logb) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * kXBlock + threadIdx.x;
   const bool live = t < total_frames;
   double x[DP];
   const float *__restrict__ xp = feats + (live ? t : 0) * D;
@@ -98,11 +88,11 @@ __global__ __launch_bounds__(kCnBlock) void connected_emit_kernel(const float *_
 // stage 1: mixture and full-covariance emissions, grid (frame blocks, W)
 // ---------------------------------------------------------------------------------------
 template <int MP, int DP>
-__global__ __launch_bounds__(kCnBlock) void connected_emit_gmm_kernel(const float *__restrict__ feats,
-                                                                       int64_t total_frames, int32_t D, int32_t SP,
-                                                                       int32_t R, const double *__restrict__ pack,
-                                                                       double *__restrict__ logb) {
-  const int64_t t = static_cast<int64_t>(blockIdx.x) * kCnBlock + threadIdx.x;
+__global__ __launch_bounds__(kXBlock) void connected_emit_gmm_kernel(const float *__restrict__ feats,
+                                                                     int64_t total_frames, int32_t D, int32_t SP,
+                                                                     int32_t R, const double *__restrict__ pack,
+                                                                     double *__restrict__ logb) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * kXBlock + threadIdx.x;
   if (t >= total_frames) return;
   const int w = blockIdx.y;
   double x[DP];
@@ -133,11 +123,11 @@ __global__ __launch_bounds__(kCnBlock) void connected_emit_gmm_kernel(const floa
 }
 
 template <int DP>
-__global__ __launch_bounds__(kCnBlock) void connected_emit_full_kernel(const float *__restrict__ feats,
-                                                                        int64_t total_frames, int32_t D, int32_t SP,
-                                                                        int32_t R, const double *__restrict__ pack,
-                                                                        double *__restrict__ logb) {
-  const int64_t t = static_cast<int64_t>(blockIdx.x) * kCnBlock + threadIdx.x;
+__global__ __launch_bounds__(kXBlock) void connected_emit_full_kernel(const float *__restrict__ feats,
+                                                                      int64_t total_frames, int32_t D, int32_t SP,
+                                                                      int32_t R, const double *__restrict__ pack,
+                                                                      double *__restrict__ logb) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * kXBlock + threadIdx.x;
   if (t >= total_frames) return;
   const int w = blockIdx.y;
   double x[DP];
@@ -181,59 +171,36 @@ __device__ __forceinline__ ValIdx wave_argmax_first(ValIdx a) {
 }
 
 template <int RL>
-__global__ __launch_bounds__(kCnBlock) void connected_viterbi_kernel(
+__global__ __launch_bounds__(kXBlock) void connected_viterbi_kernel(
     const double *__restrict__ logb, const int64_t *__restrict__ offsets, int64_t n_utts, int64_t total_frames,
     const double *__restrict__ log_start, const double *__restrict__ log_trans, const double *__restrict__ log_exit,
     double word_penalty, int32_t W, int32_t S, int32_t SP, uint8_t *__restrict__ bp, int32_t *__restrict__ exit_idx,
     double *__restrict__ score) {
   constexpr int RP = kWave * RL;  // flat states the lanes hold (R <= RP)
-  extern __shared__ double tab[];  // [SP][RP]: tab[i][r] = log_trans[w][i][s], the transition INTO flat state r from i
+  extern __shared__ double tab[];  // [SP][RP] by source
   const int R = W * SP;
-  for (int n = threadIdx.x; n < SP * RP; n += kCnBlock) {
-    const int i = n / RP, r = n - i * RP;
-    const int w = r / SP, s = r - w * SP;
-    double v = neg_inf();
-    if (r < R && s < S && i < S) v = log_trans[(static_cast<int64_t>(w) * S + i) * S + s];
-    tab[n] = v;
-  }
+  x_load_by_source(tab, log_trans, W, S, SP, RP, kXBlock);
   __syncthreads();
 
   const int lane = threadIdx.x & (kWave - 1);
-  const int64_t u = static_cast<int64_t>(blockIdx.x) * kCnWaves + (threadIdx.x / kWave);
+  const int64_t u = static_cast<int64_t>(blockIdx.x) * kXWaves + (threadIdx.x / kWave);
   if (u >= n_utts) return;  // (after the only barrier; a whole wavefront leaves)
-  int64_t beg = offsets[u], end = offsets[u + 1];
-  if (beg < 0 || end < beg || end > total_frames) end = beg = 0;  // offsets that leave the batch: served as empty
-  const int64_t T = end - beg;
+  const XFrames fr = x_frames(offsets, total_frames, u);
+  const int64_t beg = fr.beg, T = fr.T;
 
   double ls[RL], lx[RL], delta[RL], bn[RL];
   int sk[RL];
   bool ok[RL];
 #pragma unroll
   for (int k = 0; k < RL; ++k) {
-    const int r = k * kWave + lane;
-    const int w = r / SP, s = r - w * SP;
-    ok[k] = r < R;
-    sk[k] = s;
-    const bool real = ok[k] && s < S;
-    ls[k] = real ? log_start[w * S + s] : neg_inf();
-    lx[k] = real ? log_exit[w * S + s] : neg_inf();
+    const XState x = x_flat_state(k * kWave + lane, R, SP, S, log_start, log_exit);
+    ok[k] = x.ok;
+    sk[k] = x.s;
+    ls[k] = x.ls;
+    lx[k] = x.lx;
     delta[k] = neg_inf();
   }
-  // the distances d = j - i in -(SP - 1) .. SP - 1 at which some transition of the vocabulary is finite
-  // (wavefront-uniform; bit d + SP - 1)
-  uint64_t dmask = 0;
-  for (int d = 1 - SP; d < SP; ++d) {
-    bool any = false;
-#pragma unroll
-    for (int k = 0; k < RL; ++k) {
-      const int i = sk[k] - d;
-      const bool in = i >= 0 && i < SP;
-      any |= in && !(tab[(in ? i : 0) * RP + k * kWave + lane] == neg_inf());
-    }
-    if (__ballot(any)) dmask |= 1ull << (d + SP - 1);
-  }
-  dmask = (static_cast<uint64_t>(__builtin_amdgcn_readfirstlane(static_cast<unsigned>(dmask >> 32))) << 32) |
-          __builtin_amdgcn_readfirstlane(static_cast<unsigned>(dmask));
+  const uint64_t dmask = x_mask_by_source<RL>(tab, sk, lane, SP);
 
   const double *__restrict__ brow = logb + beg * R;
 #pragma unroll
@@ -255,7 +222,7 @@ __global__ __launch_bounds__(kCnBlock) void connected_viterbi_kernel(
 #pragma unroll
       for (int k = 0; k < RL; ++k) {
         v[k] = ls[k];
-        back[k] = kEntry;
+        back[k] = kXEntry;
       }
     } else {
       double best[RL];
@@ -266,18 +233,8 @@ __global__ __launch_bounds__(kCnBlock) void connected_viterbi_kernel(
       }
       // predecessors i ascending = distances descending; the first maximum stays (strict compare)
       for (int d = SP - 1; d > -SP; --d) {
-        if (!((dmask >> (d + SP - 1)) & 1ull)) continue;  // (uniform)
-        // flat state r - d: lane (lane - d) & 63 of register k, of k - 1 where lane < d, of k + 1 where lane - d >= 64
-        const int off = lane - d;
-        const int src = off & (kWave - 1);
-        double rot[RL];
-#pragma unroll
-        for (int k = 0; k < RL; ++k) rot[k] = __shfl(delta[k], src, kWave);
-#pragma unroll
-        for (int k = 0; k < RL; ++k) {
-          const double below = k > 0 ? rot[k > 0 ? k - 1 : 0] : neg_inf();
-          const double above = k + 1 < RL ? rot[k + 1 < RL ? k + 1 : k] : neg_inf();
-          const double prev = off < 0 ? below : (off >= kWave ? above : rot[k]);
+        if (!x_live(dmask, d, SP)) continue;  // (uniform)
+        x_rotate<RL>(delta, lane, d, [=, &best, &back](int k, double prev) {
           const int i = sk[k] - d;
           const bool in = i >= 0 && i < SP;  // (outside the word: no such predecessor)
           const double lt = tab[(in ? i : 0) * RP + k * kWave + lane];
@@ -285,7 +242,7 @@ __global__ __launch_bounds__(kCnBlock) void connected_viterbi_kernel(
           const bool take = c > best[k];
           best[k] = take ? c : best[k];
           back[k] = take ? i : back[k];
-        }
+        });
       }
       const double ep = E.v + word_penalty;
 #pragma unroll
@@ -293,7 +250,7 @@ __global__ __launch_bounds__(kCnBlock) void connected_viterbi_kernel(
         const double entry = ep + ls[k];
         const bool take = entry > best[k];
         v[k] = take ? entry : best[k];
-        back[k] = take ? kEntry : back[k];
+        back[k] = take ? kXEntry : back[k];
       }
     }
     uint8_t *__restrict__ bprow = bp + (beg + t) * R;
@@ -316,26 +273,17 @@ __global__ __launch_bounds__(kCnBlock) void connected_viterbi_kernel(
 }
 
 // one lane per utterance walks back from the best exit of the last frame
-__global__ __launch_bounds__(kCnBlock) void connected_backtrace_kernel(
+__global__ __launch_bounds__(kXBlock) void connected_backtrace_kernel(
     const int64_t *__restrict__ offsets, int64_t n_utts, int64_t total_frames, int32_t SP, int32_t R,
     const uint8_t *__restrict__ bp, const int32_t *__restrict__ exit_idx, const double *__restrict__ score,
     int32_t *__restrict__ n_words, int32_t *__restrict__ path_word, int32_t *__restrict__ path_state,
     uint8_t *__restrict__ path_entry) {
-  const int64_t u = static_cast<int64_t>(blockIdx.x) * kCnBlock + threadIdx.x;
+  const int64_t u = static_cast<int64_t>(blockIdx.x) * kXBlock + threadIdx.x;
   if (u >= n_utts) return;
-  const int64_t beg = offsets[u], end = offsets[u + 1];
-  if (beg < 0 || end < beg || end > total_frames) {
-    if (n_words) n_words[u] = 0;
-    return;
-  }
-  const int64_t T = end - beg;
-  const double sc = score[u];
-  if (!(sc - sc == 0.0) || T == 0) {  // a non-finite score has no path
-    for (int64_t t = 0; t < T; ++t) {
-      if (path_word) path_word[beg + t] = -1;
-      if (path_state) path_state[beg + t] = -1;
-      if (path_entry) path_entry[beg + t] = 0;
-    }
+  const XFrames fr = x_frames(offsets, total_frames, u);
+  const int64_t beg = fr.beg, T = fr.T;
+  if (!finite_f64(score[u]) || T == 0) {
+    x_no_path(beg, T, path_word, path_state, path_entry);
     if (n_words) n_words[u] = 0;
     return;
   }
@@ -346,7 +294,7 @@ __global__ __launch_bounds__(kCnBlock) void connected_backtrace_kernel(
     if (path_word) path_word[beg + t] = w;
     if (path_state) path_state[beg + t] = r - w * SP;
     const int b = bp[(beg + t) * R + r];
-    const bool entry = t == 0 || b == kEntry;
+    const bool entry = t == 0 || b == kXEntry;
     if (path_entry) path_entry[beg + t] = entry ? 1 : 0;
     if (entry) {
       ++nw;
@@ -356,20 +304,6 @@ __global__ __launch_bounds__(kCnBlock) void connected_backtrace_kernel(
     }
   }
   if (n_words) n_words[u] = nw;
-}
-
-template <int RL>
-int launch_connected(const double *logb, const int64_t *offsets, int64_t n_utts, int64_t total_frames,
-                     const double *log_start, const double *log_trans, const double *log_exit, double word_penalty,
-                     int32_t W, int32_t S, int32_t SP, uint8_t *bp, int32_t *exit_idx, double *score,
-                     hipStream_t stream) {
-  const size_t lds = static_cast<size_t>(SP) * kWave * RL * sizeof(double);
-  const int64_t blocks = (n_utts + kCnWaves - 1) / kCnWaves;
-  SAPR_LAUNCH((connected_viterbi_kernel<RL>), dim3(static_cast<unsigned>(blocks)), dim3(kCnBlock), lds, stream, logb,
-              offsets, n_utts, total_frames, log_start, log_trans, log_exit, word_penalty, W, S, SP, bp, exit_idx,
-              score);
-  SAPR_HIP_TRY(hipGetLastError());
-  return 0;
 }
 
 }  // namespace
@@ -393,7 +327,7 @@ extern "C" int sapr_connected_workspace_bytes(int64_t total_frames, int64_t n_ut
   if (int rc = cn_check_shape(W, S, 1)) return rc;
   const size_t R = static_cast<size_t>(W) * cn_sp_of(S);
   // back-pointers [total_frames][R] bytes (padded to 16), then the exit index of every frame (int32)
-  *bytes = cn_align16(static_cast<size_t>(total_frames) * R) + static_cast<size_t>(total_frames) * sizeof(int32_t);
+  *bytes = x_align16(static_cast<size_t>(total_frames) * R) + static_cast<size_t>(total_frames) * sizeof(int32_t);
   return 0;
 }
 
@@ -402,12 +336,12 @@ extern "C" int sapr_connected_emit_diag(const float *feats, int64_t total_frames
   SAPR_REQUIRE(total_frames >= 0 && W > 0 && S > 0 && D > 0, "bad sizes (total_frames=%lld W=%d S=%d D=%d)",
                (long long)total_frames, W, S, D);
   if (int rc = cn_check_shape(W, S, D)) return rc;
-  const int64_t blocks = (total_frames + kCnBlock - 1) / kCnBlock;
+  const int64_t blocks = (total_frames + kXBlock - 1) / kXBlock;
   SAPR_REQUIRE(blocks <= 0x7fffffffLL, "grid too large (%lld blocks)", (long long)blocks);
   if (total_frames == 0) return 0;
   SAPR_REQUIRE(feats && ops && logb, "NULL pointer argument");
   const int32_t R = W * cn_sp_of(S);
-  const dim3 grid(static_cast<unsigned>(blocks)), block(kCnBlock);
+  const dim3 grid(static_cast<unsigned>(blocks)), block(kXBlock);
   hipStream_t st = as_stream(stream);
   switch (cn_dp_of(D)) {
     case 13: SAPR_LAUNCH((connected_emit_kernel<13>), grid, block, 0, st, feats, total_frames, D, R, ops, logb); break;
@@ -425,7 +359,7 @@ namespace {
 int cn_emit_checks(const void *feats, int64_t total_frames, int32_t D, const void *pack, int32_t W, int32_t S,
                    const void *logb, int64_t *blocks) {
   if (int rc = cn_check_shape(W, S, D)) return rc;
-  *blocks = (total_frames + kCnBlock - 1) / kCnBlock;
+  *blocks = (total_frames + kXBlock - 1) / kXBlock;
   SAPR_REQUIRE(*blocks <= 0x7fffffffLL, "grid too large (%lld blocks)", (long long)*blocks);
   if (total_frames == 0) return 0;
   SAPR_REQUIRE(feats && pack && logb, "NULL pointer argument");
@@ -435,7 +369,7 @@ int cn_emit_checks(const void *feats, int64_t total_frames, int32_t D, const voi
 template <int MP>
 int launch_emit_gmm(dim3 grid, hipStream_t st, const float *feats, int64_t total_frames, int32_t D, int32_t SP,
                     int32_t R, const double *pack, double *logb) {
-  const dim3 block(kCnBlock);
+  const dim3 block(kXBlock);
   switch (cn_dp_of(D)) {
     case 13:
       SAPR_LAUNCH((connected_emit_gmm_kernel<MP, 13>), grid, block, 0, st, feats, total_frames, D, SP, R, pack, logb);
@@ -481,7 +415,7 @@ extern "C" int sapr_connected_emit_full(const float *feats, int64_t total_frames
   if (int rc = cn_emit_checks(feats, total_frames, D, pack, W, S, logb, &blocks)) return rc;
   if (total_frames == 0) return 0;
   const int32_t SP = cn_sp_of(S), R = W * SP;
-  const dim3 grid(static_cast<unsigned>(blocks), static_cast<unsigned>(W)), block(kCnBlock);
+  const dim3 grid(static_cast<unsigned>(blocks), static_cast<unsigned>(W)), block(kXBlock);
   hipStream_t st = as_stream(stream);
   switch (cn_dp_of(D)) {
     case 13:
@@ -510,7 +444,7 @@ extern "C" int sapr_connected_viterbi(const double *logb, const int64_t *offsets
   if (int rc = sapr_connected_workspace_bytes(total_frames, n_utts, W, S, &need)) return rc;
   SAPR_REQUIRE(workspace_bytes >= need && (need == 0 || workspace), "workspace too small: %zu < %zu", workspace_bytes,
                need);
-  const int64_t blocks = (n_utts + kCnWaves - 1) / kCnWaves;
+  const int64_t blocks = (n_utts + kXWaves - 1) / kXWaves;
   SAPR_REQUIRE(blocks <= 0x7fffffffLL, "grid too large (%lld blocks)", (long long)blocks);
   if (n_utts == 0) return 0;
   SAPR_REQUIRE(offsets && log_start && log_trans && log_exit && score && (total_frames == 0 || logb),
@@ -519,24 +453,17 @@ extern "C" int sapr_connected_viterbi(const double *logb, const int64_t *offsets
   const int32_t R = W * SP;
   uint8_t *bp = static_cast<uint8_t *>(workspace);
   int32_t *exit_idx =
-      reinterpret_cast<int32_t *>(bp + cn_align16(static_cast<size_t>(total_frames) * static_cast<size_t>(R)));
+      reinterpret_cast<int32_t *>(bp + x_align16(static_cast<size_t>(total_frames) * static_cast<size_t>(R)));
   hipStream_t st = as_stream(stream);
-  int rc;
-  if (R <= kWave)
-    rc = launch_connected<1>(logb, offsets, n_utts, total_frames, log_start, log_trans, log_exit, word_penalty, W, S,
-                             SP, bp, exit_idx, score, st);
-  else if (R <= 2 * kWave)
-    rc = launch_connected<2>(logb, offsets, n_utts, total_frames, log_start, log_trans, log_exit, word_penalty, W, S,
-                             SP, bp, exit_idx, score, st);
-  else
-    rc = launch_connected<4>(logb, offsets, n_utts, total_frames, log_start, log_trans, log_exit, word_penalty, W, S,
-                             SP, bp, exit_idx, score, st);
-  if (rc) return rc;
-  if (n_words || path_word || path_state || path_entry) {
-    SAPR_LAUNCH(connected_backtrace_kernel, dim3(static_cast<unsigned>((n_utts + kCnBlock - 1) / kCnBlock)),
-                dim3(kCnBlock), 0, st, offsets, n_utts, total_frames, SP, R, bp, exit_idx, score, n_words, path_word,
-                path_state, path_entry);
-    SAPR_HIP_TRY(hipGetLastError());
-  }
+  if (int rc = x_dispatch(SP, R, [&](auto rl, auto) {  // (the kernel takes SP as a run-time value)
+        constexpr int RL = decltype(rl)::value;
+        const size_t lds = static_cast<size_t>(SP) * kWave * RL * sizeof(double);
+        return x_launch(connected_viterbi_kernel<RL>, blocks, kXBlock, lds, st, logb, offsets, n_utts, total_frames,
+                        log_start, log_trans, log_exit, word_penalty, W, S, SP, bp, exit_idx, score);
+      }))
+    return rc;
+  if (n_words || path_word || path_state || path_entry)
+    return x_launch(connected_backtrace_kernel, (n_utts + kXBlock - 1) / kXBlock, kXBlock, 0, st, offsets, n_utts,
+                    total_frames, SP, R, bp, exit_idx, score, n_words, path_word, path_state, path_entry);
   return 0;
 }

@@ -3,20 +3,17 @@
 // CPU restatement, which is the definition: tests/_align_ref.py.  The input logb[total_frames][R = W * SP] is what the
 // three emission stages of connected.hip write; this unit knows nothing about the emission family.
 //
-// connected_align_kernel<RL, SP>: one wavefront serves one utterance, four utterances per workgroup.  The P = K * SP
-// chain positions lie along the lanes, RL in {1, 2, 4} per lane: position p = k * 64 + lane sits in register k of its
-// lane and belongs to word slot p / SP, state p % SP — the layout of connected_viterbi_kernel, so the within-word
-// predecessor at distance d = j - i is again position p - d (ds_bpermute rotations, only at the distances at which some
-// transition of the VOCABULARY is finite: the mask is workgroup-uniform).  What differs from the word loop:
-//   * the network differs per utterance, so the workgroup shares the vocabulary's table [W][SP][SP] in LDS
-//     (<= 256 * 18 doubles = 36 KB) and every lane indexes it through its own word.  The table is stored by diagonals,
-//     tab[w][(j - i) mod SP][j]: at one distance the SP lanes of a slot read SP consecutive doubles;
+// connected_align_kernel<RL, SP>: the lane layout of connected_lanes.h over the P = K * SP chain positions, four
+// utterances per workgroup (written out in the kernel: it keeps the text it was timed with, and takes the constants,
+// the X step and the host side from the header).  What differs from the word loop:
+//   * the network differs per utterance, so the workgroup shares the vocabulary's table by word in LDS
+//     (<= 256 * 18 doubles = 36 KB) and every lane indexes it through its own word;
 //   * the emission row is a gather: the lane reads logb[t][w_k * SP + s] (consecutive doubles within a slot; the next
 //     frame's values are in flight under the current frame's chain);
 //   * the coupling is a segmented exit maximum through a per-wavefront LDS row: every lane writes delta + log_exit,
 //     lane q < K takes the first maximum over the SP values of slot q (s ascending) and writes X(q) behind it, and the
-//     lanes of slot q + 1 read it back.  A wavefront's LDS operations complete in order, so no barrier is needed.
-// Back-pointers: one byte per (frame, position) — the predecessor state, or kEntry where the entry won — in rows of
+//     lanes of slot q + 1 read it back.
+// Back-pointers: one byte per (frame, position) — the predecessor state, or kXEntry where the entry won — in rows of
 // max_words * SP, and one byte per (frame, slot) — the state that attained X — in rows of max_words, both in the
 // workspace.  connected_align_backtrace_kernel, one lane per utterance, walks back and writes the path rows and
 // word_start.
@@ -31,34 +28,16 @@ namespace {
 
 #include "lse_ops.h"
 #include "gmm_ops.h"
+#include "connected_lanes.h"
 
-constexpr int kAlMaxP = 256;          // chain positions (and flat states of the vocabulary) one wavefront holds
-constexpr int kAlBlock = 256;         // 4 wavefronts per workgroup
-constexpr int kAlWaves = kAlBlock / kWave;
-constexpr int kAlEntry = 255;         // back-pointer byte: the word was entered at this frame (connected.hip kEntry)
 constexpr int kAlXRow = kWave + 2;    // X row of one wavefront: [0] = -inf (nothing enters slot 0), [q + 1] = X(q)
 
 inline int al_check_shape(int32_t W, int32_t S, int32_t max_words) {
-  if (S > kMaxS || static_cast<int64_t>(W) * sp_of(S) > kAlMaxP || static_cast<int64_t>(max_words) * sp_of(S) > kAlMaxP)
-    return fail(SAPR_ERR_UNSUPPORTED,
-                "the alignment kernels serve S in 1..%d, W * SP <= %d and max_words * SP <= %d; got W=%d S=%d "
-                "max_words=%d (SP=%d)",
-                kMaxS, kAlMaxP, kAlMaxP, W, S, max_words, sp_of(S));
-  return 0;
-}
-
-inline size_t al_align16(size_t x) { return (x + 15) / 16 * 16; }
-
-// between the lanes of ONE wavefront: what the lanes wrote to LDS before is what they read after.  The hardware
-// completes a wavefront's LDS operations in order; the fences keep the compiler from moving or caching across it.
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  return x_check_chain_shape("alignment", W, S, max_words);
 }
 
 template <int RL, int SP>
-__global__ __launch_bounds__(kAlBlock) void connected_align_kernel(
+__global__ __launch_bounds__(kXBlock) void connected_align_kernel(
     const double *__restrict__ logb, const int64_t *__restrict__ offsets, int64_t n_utts, int64_t total_frames,
     const int32_t *__restrict__ words, const int64_t *__restrict__ word_offsets, int64_t total_words, int32_t max_words,
     const double *__restrict__ log_start, const double *__restrict__ log_trans, const double *__restrict__ log_exit,
@@ -69,7 +48,7 @@ __global__ __launch_bounds__(kAlBlock) void connected_align_kernel(
   extern __shared__ double smem[];
   double *tab = smem;
   const int n_tab = W * SP * SP;
-  for (int n = threadIdx.x; n < n_tab; n += kAlBlock) {
+  for (int n = threadIdx.x; n < n_tab; n += kXBlock) {
     const int w = n / (SP * SP), rem = n - w * (SP * SP);
     const int dd = rem / SP, j = rem - dd * SP;
     const int i = j >= dd ? j - dd : j - dd + SP;
@@ -81,7 +60,7 @@ __global__ __launch_bounds__(kAlBlock) void connected_align_kernel(
   const int wave = threadIdx.x / kWave;
   double *cbuf = smem + n_tab + wave * (PP + kAlXRow);
   double *xbuf = cbuf + PP;
-  const int64_t u = static_cast<int64_t>(blockIdx.x) * kAlWaves + wave;
+  const int64_t u = static_cast<int64_t>(blockIdx.x) * kXWaves + wave;
   if (u >= n_utts) return;  // (after the only barrier; a whole wavefront leaves)
   int64_t beg = offsets[u], end = offsets[u + 1];
   if (beg < 0 || end < beg || end > total_frames) end = beg = 0;  // offsets that leave the batch: served as empty
@@ -162,7 +141,7 @@ __global__ __launch_bounds__(kAlBlock) void connected_align_kernel(
 #pragma unroll
       for (int k = 0; k < RL; ++k) {
         v[k] = ls[k];
-        back[k] = kAlEntry;
+        back[k] = kXEntry;
       }
     } else {
       double xe[RL];  // X_{t-1} of the slot before the lane's own (-inf in front of slot 0)
@@ -204,7 +183,7 @@ __global__ __launch_bounds__(kAlBlock) void connected_align_kernel(
         const double entry = (xe[k] + word_penalty) + ls[k];
         const bool take = entry > best[k];
         v[k] = take ? entry : best[k];
-        back[k] = take ? kAlEntry : back[k];
+        back[k] = take ? kXEntry : back[k];
       }
     }
     uint8_t *__restrict__ bprow = bp + (beg + t) * MP;
@@ -218,17 +197,8 @@ __global__ __launch_bounds__(kAlBlock) void connected_align_kernel(
     }
     wave_lds_sync();
     if (lane < K) {  // the first maximum over the slot's states, s ascending
-      double c[SP];
-#pragma unroll
-      for (int s = 0; s < SP; ++s) c[s] = cbuf[lane * SP + s];
-      xv = c[0];
-      int xs = 0;
-#pragma unroll
-      for (int s = 1; s < SP; ++s) {
-        const bool take = c[s] > xv;
-        xv = take ? c[s] : xv;
-        xs = take ? s : xs;
-      }
+      int xs;
+      xv = x_first_max<SP>(cbuf + lane * SP, &xs);
       xbuf[lane + 1] = xv;
       xarg[(beg + t) * max_words + lane] = static_cast<uint8_t>(xs);
     }
@@ -238,40 +208,33 @@ __global__ __launch_bounds__(kAlBlock) void connected_align_kernel(
 }
 
 // one lane per utterance walks back from the last slot's best exit at the last frame
-__global__ __launch_bounds__(kAlBlock) void connected_align_backtrace_kernel(
+__global__ __launch_bounds__(kXBlock) void connected_align_backtrace_kernel(
     const int64_t *__restrict__ offsets, int64_t n_utts, int64_t total_frames, const int32_t *__restrict__ words,
     const int64_t *__restrict__ word_offsets, int64_t total_words, int32_t max_words, int32_t SP,
     const uint8_t *__restrict__ bp, const uint8_t *__restrict__ xarg, const double *__restrict__ score,
     int32_t *__restrict__ path_word, int32_t *__restrict__ path_state, uint8_t *__restrict__ path_entry,
     int32_t *__restrict__ word_start) {
-  const int64_t u = static_cast<int64_t>(blockIdx.x) * kAlBlock + threadIdx.x;
+  const int64_t u = static_cast<int64_t>(blockIdx.x) * kXBlock + threadIdx.x;
   if (u >= n_utts) return;
-  int64_t beg = offsets[u], end = offsets[u + 1];
-  if (beg < 0 || end < beg || end > total_frames) end = beg = 0;
-  int64_t wbeg = word_offsets[u], wend = word_offsets[u + 1];
-  if (wbeg < 0 || wend < wbeg || wend > total_words) wend = wbeg = 0;
-  const int64_t T = end - beg, K = wend - wbeg;
-  if (word_start)
-    for (int64_t k = 0; k < K; ++k) word_start[wbeg + k] = -1;
-  const double sc = score[u];
+  const XUtt ut = x_utt(offsets, total_frames, word_offsets, total_words, max_words, u);
+  const int64_t beg = ut.beg, T = ut.T, wbeg = ut.wbeg;
+  if (word_start)  // (every word of the transcript, laid out or not)
+    for (int64_t k = 0; k < ut.n_words; ++k) word_start[wbeg + k] = -1;
   // (a finite score was written only for 0 < K <= max_words, T > 0 and words inside the vocabulary)
-  if (!(sc - sc == 0.0) || T == 0 || K == 0 || K > max_words) {
-    for (int64_t t = 0; t < T; ++t) {
-      if (path_word) path_word[beg + t] = -1;
-      if (path_state) path_state[beg + t] = -1;
-      if (path_entry) path_entry[beg + t] = 0;
-    }
+  if (!finite_f64(score[u]) || !ut.path) {
+    x_no_path(beg, T, path_word, path_state, path_entry);
     return;
   }
+  const int K = ut.K;
   const int64_t MP = static_cast<int64_t>(max_words) * SP;
-  int q = static_cast<int>(K) - 1;
+  int q = K - 1;
   int s = xarg[(beg + T - 1) * max_words + q];
   s = s < SP ? s : 0;
   for (int64_t t = T - 1; t >= 0; --t) {
     if (path_word) path_word[beg + t] = words[wbeg + q];
     if (path_state) path_state[beg + t] = s;
     const int b = bp[(beg + t) * MP + q * SP + s];
-    const bool entry = t == 0 || b == kAlEntry;
+    const bool entry = t == 0 || b == kXEntry;
     if (path_entry) path_entry[beg + t] = entry ? 1 : 0;
     if (entry) {
       if (word_start) word_start[wbeg + q] = static_cast<int32_t>(t);
@@ -284,28 +247,6 @@ __global__ __launch_bounds__(kAlBlock) void connected_align_backtrace_kernel(
       s = b < SP ? b : 0;
     }
   }
-}
-
-template <int RL, int SP>
-int launch_align(const double *logb, const int64_t *offsets, int64_t n_utts, int64_t total_frames,
-                 const int32_t *words, const int64_t *word_offsets, int64_t total_words, int32_t max_words,
-                 const double *log_start, const double *log_trans, const double *log_exit, double word_penalty,
-                 int32_t W, int32_t S, uint8_t *bp, uint8_t *xarg, double *score, hipStream_t stream) {
-  const size_t lds =
-      (static_cast<size_t>(W) * SP * SP + static_cast<size_t>(kAlWaves) * (kWave * RL + kAlXRow)) * sizeof(double);
-  const int64_t blocks = (n_utts + kAlWaves - 1) / kAlWaves;
-  SAPR_LAUNCH((connected_align_kernel<RL, SP>), dim3(static_cast<unsigned>(blocks)), dim3(kAlBlock), lds, stream, logb,
-              offsets, n_utts, total_frames, words, word_offsets, total_words, max_words, log_start, log_trans,
-              log_exit, word_penalty, W, S, bp, xarg, score);
-  SAPR_HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-template <int SP, typename... Args>
-int launch_align_rl(int positions, Args... args) {
-  if (positions <= kWave) return launch_align<1, SP>(args...);
-  if (positions <= 2 * kWave) return launch_align<2, SP>(args...);
-  return launch_align<4, SP>(args...);
 }
 
 }  // namespace
@@ -321,8 +262,8 @@ extern "C" int sapr_connected_align_workspace_bytes(int64_t total_frames, int64_
   if (int rc = al_check_shape(1, S, max_words)) return rc;
   const size_t MP = static_cast<size_t>(max_words) * sp_of(S);
   // back-pointers [total_frames][max_words * SP] bytes, then the exit state of every (frame, slot), each padded to 16
-  *bytes = al_align16(static_cast<size_t>(total_frames) * MP) +
-           al_align16(static_cast<size_t>(total_frames) * static_cast<size_t>(max_words));
+  *bytes = x_align16(static_cast<size_t>(total_frames) * MP) +
+           x_align16(static_cast<size_t>(total_frames) * static_cast<size_t>(max_words));
   return 0;
 }
 
@@ -340,7 +281,7 @@ extern "C" int sapr_connected_align(const double *logb, const int64_t *offsets, 
   if (int rc = sapr_connected_align_workspace_bytes(total_frames, n_utts, max_words, S, &need)) return rc;
   SAPR_REQUIRE(workspace_bytes >= need && (need == 0 || workspace), "workspace too small: %zu < %zu", workspace_bytes,
                need);
-  const int64_t blocks = (n_utts + kAlWaves - 1) / kAlWaves;
+  const int64_t blocks = (n_utts + kXWaves - 1) / kXWaves;
   SAPR_REQUIRE(blocks <= 0x7fffffffLL, "grid too large (%lld blocks)", (long long)blocks);
   if (n_utts == 0) return 0;
   SAPR_REQUIRE(offsets && word_offsets && log_start && log_trans && log_exit && score && (total_frames == 0 || logb) &&
@@ -348,25 +289,20 @@ extern "C" int sapr_connected_align(const double *logb, const int64_t *offsets, 
                "NULL pointer argument");
   const int32_t SP = sp_of(S);
   uint8_t *bp = static_cast<uint8_t *>(workspace);
-  uint8_t *xarg = bp + al_align16(static_cast<size_t>(total_frames) * static_cast<size_t>(max_words) * SP);
+  uint8_t *xarg = bp + x_align16(static_cast<size_t>(total_frames) * static_cast<size_t>(max_words) * SP);
   hipStream_t st = as_stream(stream);
-  const int positions = max_words * SP;
-  int rc;
-  if (SP == 4)
-    rc = launch_align_rl<4>(positions, logb, offsets, n_utts, total_frames, words, word_offsets, total_words, max_words,
-                            log_start, log_trans, log_exit, word_penalty, W, S, bp, xarg, score, st);
-  else if (SP == 10)
-    rc = launch_align_rl<10>(positions, logb, offsets, n_utts, total_frames, words, word_offsets, total_words,
-                             max_words, log_start, log_trans, log_exit, word_penalty, W, S, bp, xarg, score, st);
-  else
-    rc = launch_align_rl<18>(positions, logb, offsets, n_utts, total_frames, words, word_offsets, total_words,
-                             max_words, log_start, log_trans, log_exit, word_penalty, W, S, bp, xarg, score, st);
-  if (rc) return rc;
-  if (path_word || path_state || path_entry || word_start) {
-    SAPR_LAUNCH(connected_align_backtrace_kernel, dim3(static_cast<unsigned>((n_utts + kAlBlock - 1) / kAlBlock)),
-                dim3(kAlBlock), 0, st, offsets, n_utts, total_frames, words, word_offsets, total_words, max_words, SP,
-                bp, xarg, score, path_word, path_state, path_entry, word_start);
-    SAPR_HIP_TRY(hipGetLastError());
-  }
+  if (int rc = x_dispatch(SP, max_words * SP, [&](auto rl, auto sp) {
+        constexpr int RL = decltype(rl)::value, SPc = decltype(sp)::value;
+        const size_t lds =
+            (static_cast<size_t>(W) * SPc * SPc + static_cast<size_t>(kXWaves) * (kWave * RL + kAlXRow)) * sizeof(double);
+        return x_launch(connected_align_kernel<RL, SPc>, blocks, kXBlock, lds, st, logb, offsets, n_utts, total_frames,
+                        words, word_offsets, total_words, max_words, log_start, log_trans, log_exit, word_penalty, W, S,
+                        bp, xarg, score);
+      }))
+    return rc;
+  if (path_word || path_state || path_entry || word_start)
+    return x_launch(connected_align_backtrace_kernel, (n_utts + kXBlock - 1) / kXBlock, kXBlock, 0, st, offsets, n_utts,
+                    total_frames, words, word_offsets, total_words, max_words, SP, bp, xarg, score, path_word,
+                    path_state, path_entry, word_start);
   return 0;
 }

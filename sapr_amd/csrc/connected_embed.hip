@@ -3,13 +3,13 @@
 // definition: tests/_embedded_ref.py.  The input logb[total_frames][R = W * SP] is what the three emission stages of
 // connected.hip write; the recursion knows nothing about the emission family.
 //
-// The layout is that of connected_align.hip: one wavefront serves one utterance, chain position p = k * 64 + lane sits
-// in register k of its lane (RL in {1, 2, 4}) and belongs to word slot p / SP, state p % SP; the vocabulary's table lies
-// in LDS by diagonals, tab[w][(j - i) mod SP][j]; rotations run only at the distances d = j - i at which some
-// transition of the vocabulary is finite; the coupling between the slots goes through a per-wavefront LDS row.
+// The recursions use the lane layout of connected_lanes.h over the chain positions, with the vocabulary's table by word
+// in LDS and the coupling between the slots through a per-wavefront LDS row.  The two kernels lay out the positions and
+// rotate in code of their own (they keep the text they were timed with); the table loader, its mask, the utterance
+// span, the segmented log-sum-exp, the constants and the host side are the header's.
 //
 // embed_forward_kernel<RL, SP>  (four wavefronts per workgroup): the alignment recursion with the two-term log-sum-exp
-//   of lse_ops.h in place of the strict maximum and a segmented log-sum-exp (slot_lse: the lanes of slot q evaluate
+//   of lse_ops.h in place of the strict maximum and a segmented log-sum-exp (x_segment_lse: the lanes of slot q evaluate
 //   its SP exponentials, lane q takes the maximum before and the sum after) in place of the segmented maximum.  Per
 //   frame it writes alpha[t][max_words * SP] and X[t][max_words] into the workspace; at the end loglik[u].  A NaN met
 //   anywhere (lse2 would drop it) makes the likelihood NaN.
@@ -42,22 +42,15 @@ namespace {
 
 #include "lse_ops.h"
 #include "gmm_ops.h"
+#include "connected_lanes.h"
 
-constexpr int kEmMaxP = 256;          // chain positions (and flat states of the vocabulary) one wavefront holds
-constexpr int kEmBlock = 256;         // forward: 4 wavefronts per workgroup
-constexpr int kEmWaves = kEmBlock / kWave;
 constexpr int kEmXRow = kWave + 2;    // coupling row of one wavefront: [0] = -inf (nothing enters slot 0), [q + 1]
 constexpr int kEmRows = kEmXRow + kWave;  // ... and the row of the slots' maxima behind it
 constexpr int kEmMaxD = 39;
 constexpr int kEmFoldChunk = 256;     // slots one block of the first fold level adds up (fixed: it fixes the order)
 
 inline int em_check_shape(int32_t W, int32_t S, int32_t max_words) {
-  if (S > kMaxS || static_cast<int64_t>(W) * sp_of(S) > kEmMaxP || static_cast<int64_t>(max_words) * sp_of(S) > kEmMaxP)
-    return fail(SAPR_ERR_UNSUPPORTED,
-                "the embedded Baum-Welch kernels serve S in 1..%d, W * SP <= %d and max_words * SP <= %d; got W=%d "
-                "S=%d max_words=%d (SP=%d)",
-                kMaxS, kEmMaxP, kEmMaxP, W, S, max_words, sp_of(S));
-  return 0;
+  return x_check_chain_shape("embedded Baum-Welch", W, S, max_words);
 }
 
 inline int em_check_dims(int32_t D) {
@@ -65,8 +58,6 @@ inline int em_check_dims(int32_t D) {
     return fail(SAPR_ERR_UNSUPPORTED, "the embedded Baum-Welch kernels serve D in 0..%d; got D=%d", kEmMaxD, D);
   return 0;
 }
-
-inline size_t em_align16(size_t x) { return (x + 15) / 16 * 16; }
 
 // doubles of one slot's partial row: {start[SP], trans[SP][SP], post[SP], obs[SP][D], obs2[SP][D]}
 inline size_t em_part_width(int SP, int D) { return static_cast<size_t>(SP) * (2 + SP + 2 * D); }
@@ -86,11 +77,11 @@ inline EmWorkspace em_carve(void *base, int64_t total_frames, int64_t total_word
   const int SP = sp_of(S);
   EmWorkspace w;
   uint8_t *p = static_cast<uint8_t *>(base);
-  const size_t a = em_align16(static_cast<size_t>(total_frames) * max_words * SP * sizeof(double));
-  const size_t x = em_align16(static_cast<size_t>(total_frames) * max_words * sizeof(double));
-  const size_t s = em_align16(static_cast<size_t>(total_words) * em_part_width(SP, D) * sizeof(double));
-  const size_t o = em_align16(static_cast<size_t>(total_words));
-  const size_t f = em_align16(static_cast<size_t>(em_chunks(total_words)) * (kEmMaxP / SP) *
+  const size_t a = x_align16(static_cast<size_t>(total_frames) * max_words * SP * sizeof(double));
+  const size_t x = x_align16(static_cast<size_t>(total_frames) * max_words * sizeof(double));
+  const size_t s = x_align16(static_cast<size_t>(total_words) * em_part_width(SP, D) * sizeof(double));
+  const size_t o = x_align16(static_cast<size_t>(total_words));
+  const size_t f = x_align16(static_cast<size_t>(em_chunks(total_words)) * (kXMaxR / SP) *
                               (2 + S + S * S + S + 2 * S * D) * sizeof(double));
   w.alpha = reinterpret_cast<double *>(p);
   w.X = reinterpret_cast<double *>(p + a);
@@ -101,118 +92,8 @@ inline EmWorkspace em_carve(void *base, int64_t total_frames, int64_t total_word
   return w;
 }
 
-// between the lanes of ONE wavefront: what the lanes wrote to LDS before is what they read after (connected_align.hip)
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ bool finite_f64(double v) { return v - v == 0.0; }
-
-// The segmented log-sum-exp: val[k] is the term of the lane's position in register k (in[k]: inside the chain); lane
-// q < K returns the log-sum-exp over the SP terms of slot q — the operations of lse_all<SP> over them in its order (the
-// first maximum by strict compares, the exponentials added s ascending, log(sum) + max; an infinite maximum is the
-// result), but with the SP exponentials of a slot evaluated by the SP lanes that hold its positions instead of by lane
-// q alone: lse_all on K lanes costs the whole wavefront SP exponentials per frame, this costs RL.  Three hand-overs
-// through the wavefront's own LDS rows; the caller synchronises before it writes cbuf again.
 template <int RL, int SP>
-__device__ __forceinline__ double slot_lse(double *cbuf, double *mbuf, const double (&val)[RL], const bool (&in)[RL],
-                                           const int (&qk)[RL], int lane, int K) {
-#pragma unroll
-  for (int k = 0; k < RL; ++k)
-    if (in[k]) cbuf[k * kWave + lane] = val[k];
-  wave_lds_sync();
-  double m = neg_inf();
-  if (lane < K) {
-    m = cbuf[lane * SP];
-#pragma unroll
-    for (int s = 1; s < SP; ++s) {
-      const double v = cbuf[lane * SP + s];
-      m = v > m ? v : m;
-    }
-    mbuf[lane] = m;
-  }
-  wave_lds_sync();
-#pragma unroll
-  for (int k = 0; k < RL; ++k)
-    if (in[k]) cbuf[k * kWave + lane] = exp_unit(val[k] - mbuf[qk[k]]);  // (an infinite maximum: selected away below)
-  wave_lds_sync();
-  double r = m;
-  if (lane < K) {
-    double acc = 0.0;
-#pragma unroll
-    for (int s = 0; s < SP; ++s) acc += cbuf[lane * SP + s];
-    r = isinf(m) ? m : log(acc) + m;
-  }
-  return r;
-}
-
-// the part every kernel of this unit starts with: the utterance's frames, transcript and whether the chain can be laid
-// out at all (the likelihood decides the rest)
-struct EmUtt {
-  int64_t beg, T, wbeg;
-  int K;
-  bool path;
-};
-
-__device__ __forceinline__ EmUtt em_utt(const int64_t *__restrict__ offsets, int64_t total_frames,
-                                        const int64_t *__restrict__ word_offsets, int64_t total_words,
-                                        int32_t max_words, int64_t u) {
-  EmUtt r;
-  int64_t beg = offsets[u], end = offsets[u + 1];
-  if (beg < 0 || end < beg || end > total_frames) end = beg = 0;  // offsets that leave the batch: served as empty
-  int64_t wbeg = word_offsets[u], wend = word_offsets[u + 1];
-  if (wbeg < 0 || wend < wbeg || wend > total_words) wend = wbeg = 0;
-  const int64_t K64 = wend - wbeg;
-  r.beg = beg;
-  r.T = end - beg;
-  r.wbeg = wbeg;
-  r.path = r.T > 0 && K64 > 0 && K64 <= max_words;  // (max_words <= 64: a slot per lane in the coupling step)
-  r.K = r.path ? static_cast<int>(K64) : 0;
-  return r;
-}
-
-// tab[w][dd][j] = log_trans[w][i][j] with i = (j - dd) mod SP (all threads of the workgroup; followed by a barrier)
-template <int SP>
-__device__ __forceinline__ void em_load_table(double *tab, const double *__restrict__ log_trans, int W, int S) {
-  const int n_tab = W * SP * SP;
-  for (int n = threadIdx.x; n < n_tab; n += blockDim.x) {
-    const int w = n / (SP * SP), rem = n - w * (SP * SP);
-    const int dd = rem / SP, j = rem - dd * SP;
-    const int i = j >= dd ? j - dd : j - dd + SP;
-    tab[n] = (i < S && j < S) ? log_trans[(static_cast<int64_t>(w) * S + i) * S + j] : neg_inf();
-  }
-  __syncthreads();
-}
-
-// the distances d = j - i in -(SP - 1) .. SP - 1 at which some transition of the vocabulary is finite (bit d + SP - 1),
-// wavefront-uniform; *nan: the table holds a NaN
-template <int SP>
-__device__ __forceinline__ uint64_t em_distance_mask(const double *tab, int n_tab, int lane, bool *nan) {
-  uint64_t dmask = 0;
-  unsigned bad = 0;
-  for (int n = lane; n < n_tab; n += kWave) {
-    const int rem = n % (SP * SP);
-    const int dd = rem / SP, j = rem - dd * SP;
-    const int d = j >= dd ? dd : dd - SP;
-    const double v = tab[n];
-    if (!(v == neg_inf())) dmask |= 1ull << (d + SP - 1);
-    if (v != v) bad = 1;
-  }
-  unsigned lo = static_cast<unsigned>(dmask), hi = static_cast<unsigned>(dmask >> 32);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lo |= __shfl_xor(lo, o, kWave);
-    hi |= __shfl_xor(hi, o, kWave);
-    bad |= __shfl_xor(bad, o, kWave);
-  }
-  *nan = __builtin_amdgcn_readfirstlane(bad) != 0;
-  return (static_cast<uint64_t>(__builtin_amdgcn_readfirstlane(hi)) << 32) | __builtin_amdgcn_readfirstlane(lo);
-}
-
-template <int RL, int SP>
-__global__ __launch_bounds__(kEmBlock) void embed_forward_kernel(
+__global__ __launch_bounds__(kXBlock) void embed_forward_kernel(
     const double *__restrict__ logb, const int64_t *__restrict__ offsets, int64_t n_utts, int64_t total_frames,
     const int32_t *__restrict__ words, const int64_t *__restrict__ word_offsets, int64_t total_words, int32_t max_words,
     const double *__restrict__ log_start, const double *__restrict__ log_trans, const double *__restrict__ log_exit,
@@ -222,16 +103,16 @@ __global__ __launch_bounds__(kEmBlock) void embed_forward_kernel(
   extern __shared__ double smem[];
   double *tab = smem;
   const int n_tab = W * SP * SP;
-  em_load_table<SP>(tab, log_trans, W, S);
+  x_load_by_word<SP>(tab, log_trans, W, S);
 
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = threadIdx.x / kWave;
   double *cbuf = smem + n_tab + wave * (PP + kEmRows);
   double *xbuf = cbuf + PP;
   double *mbuf = xbuf + kEmXRow;
-  const int64_t u = static_cast<int64_t>(blockIdx.x) * kEmWaves + wave;
+  const int64_t u = static_cast<int64_t>(blockIdx.x) * kXWaves + wave;
   if (u >= n_utts) return;  // (after the only barrier; a whole wavefront leaves)
-  const EmUtt ut = em_utt(offsets, total_frames, word_offsets, total_words, max_words, u);
+  const XUtt ut = x_utt(offsets, total_frames, word_offsets, total_words, max_words, u);
   bool path = ut.path;
   const int K = ut.K;
   {  // a word outside the vocabulary: no path, and nothing of it is used as an index
@@ -248,7 +129,7 @@ __global__ __launch_bounds__(kEmBlock) void embed_forward_kernel(
   const int MP = max_words * SP;
 
   bool tab_nan;
-  const uint64_t dmask = em_distance_mask<SP>(tab, n_tab, lane, &tab_nan);
+  const uint64_t dmask = x_mask_by_word<SP>(tab, n_tab, lane, &tab_nan);
 
   double ls[RL], lx[RL], alpha[RL], bn[RL];
   int sk[RL], qk[RL], col[RL], tb[RL];
@@ -330,7 +211,7 @@ __global__ __launch_bounds__(kEmBlock) void embed_forward_kernel(
       if (ok[k]) arow[k * kWave + lane] = alpha[k];
       ex[k] = alpha[k] + lx[k];
     }
-    xv = slot_lse<RL, SP>(cbuf, mbuf, ex, ok, qk, lane, K);  // the log-sum-exp over the slot's states
+    xv = x_segment_lse<RL, SP>(cbuf, mbuf, ex, ok, qk, lane, K);  // the log-sum-exp over the slot's states
     if (lane < K) {
       xbuf[lane + 1] = xv;
       x_ws[(beg + t) * max_words + lane] = xv;
@@ -342,7 +223,7 @@ __global__ __launch_bounds__(kEmBlock) void embed_forward_kernel(
 }
 
 template <int RL, int SP>
-__global__ __launch_bounds__(kEmBlock) void embed_backward_kernel(
+__global__ __launch_bounds__(kXBlock) void embed_backward_kernel(
     const double *__restrict__ logb, const int64_t *__restrict__ offsets, int64_t n_utts, int64_t total_frames,
     const int32_t *__restrict__ words, const int64_t *__restrict__ word_offsets, int64_t total_words, int32_t max_words,
     const double *__restrict__ log_start, const double *__restrict__ log_trans, const double *__restrict__ log_exit,
@@ -354,7 +235,7 @@ __global__ __launch_bounds__(kEmBlock) void embed_backward_kernel(
   extern __shared__ double smem[];
   double *tab = smem;
   const int n_tab = W * SP * SP;
-  em_load_table<SP>(tab, log_trans, W, S);
+  x_load_by_word<SP>(tab, log_trans, W, S);
 
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = threadIdx.x / kWave;
@@ -365,7 +246,7 @@ __global__ __launch_bounds__(kEmBlock) void embed_backward_kernel(
   double *acc = mbuf + kWave;
   const int64_t u = static_cast<int64_t>(blockIdx.x) * waves + wave;
   if (u >= n_utts) return;  // (after the only barrier; a whole wavefront leaves)
-  const EmUtt ut = em_utt(offsets, total_frames, word_offsets, total_words, max_words, u);
+  const XUtt ut = x_utt(offsets, total_frames, word_offsets, total_words, max_words, u);
   const int64_t beg = ut.beg, T = ut.T;
   const int MP = max_words * SP;
   const double ll = loglik[u];
@@ -386,7 +267,7 @@ __global__ __launch_bounds__(kEmBlock) void embed_backward_kernel(
   const int R = W * SP;
 
   bool tab_nan;  // (a NaN in the table made the likelihood NaN: not reached)
-  const uint64_t dmask = em_distance_mask<SP>(tab, n_tab, lane, &tab_nan);
+  const uint64_t dmask = x_mask_by_word<SP>(tab, n_tab, lane, &tab_nan);
   (void)tab_nan;
 
   double ls[RL], lx[RL], beta[RL], acur[RL], bcur[RL], gsum[RL], sacc[RL];
@@ -454,7 +335,7 @@ __global__ __launch_bounds__(kEmBlock) void embed_backward_kernel(
       sacc[k] += exp_unit(((xe[k] + word_penalty) + en[k]) - ll);
     }
     {
-      const double e = slot_lse<RL, SP>(cbuf, mbuf, en, ok, qk, lane, K);
+      const double e = x_segment_lse<RL, SP>(cbuf, mbuf, en, ok, qk, lane, K);
       if (lane >= 1 && lane < K) ebuf[lane] = word_penalty + e;
     }
     wave_lds_sync();
@@ -511,25 +392,25 @@ __global__ __launch_bounds__(kEmBlock) void embed_backward_kernel(
 }
 
 // sum_t gamma_t(p) [x_t, x_t^2]: one workgroup per utterance, thread (p, d) with d fastest
-__global__ __launch_bounds__(kEmBlock) void embed_obs_kernel(
+__global__ __launch_bounds__(kXBlock) void embed_obs_kernel(
     const double *__restrict__ gamma, const float *__restrict__ feats, int32_t D, const int64_t *__restrict__ offsets,
     int64_t n_utts, int64_t total_frames, const int64_t *__restrict__ word_offsets, int64_t total_words,
     int32_t max_words, int32_t SP, int32_t part_width, const double *__restrict__ loglik, double *__restrict__ part) {
   const int64_t u = blockIdx.x;
   if (u >= n_utts) return;
-  const EmUtt ut = em_utt(offsets, total_frames, word_offsets, total_words, max_words, u);
+  const XUtt ut = x_utt(offsets, total_frames, word_offsets, total_words, max_words, u);
   if (!ut.path || !finite_f64(loglik[u])) return;
   const int MP = max_words * SP;
   const int n = ut.K * SP * D;
   const double *__restrict__ g = gamma + ut.beg * MP;
   const float *__restrict__ x = feats + ut.beg * D;
   constexpr int NP = 4;  // (position, feature) pairs a thread carries at once: independent chains, each t ascending
-  for (int base = threadIdx.x; base < n; base += kEmBlock * NP) {
+  for (int base = threadIdx.x; base < n; base += kXBlock * NP) {
     int p[NP], d[NP];
     double a1[NP], a2[NP];
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
-      const int idx = base + j * kEmBlock < n ? base + j * kEmBlock : n - 1;  // (behind the end: computed, not stored)
+      const int idx = base + j * kXBlock < n ? base + j * kXBlock : n - 1;  // (behind the end: computed, not stored)
       p[j] = idx / D;
       d[j] = idx - p[j] * D;
       a1[j] = a2[j] = 0.0;
@@ -545,7 +426,7 @@ __global__ __launch_bounds__(kEmBlock) void embed_obs_kernel(
     }
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
-      if (base + j * kEmBlock >= n) continue;
+      if (base + j * kXBlock >= n) continue;
       const int q = p[j] / SP, s = p[j] - q * SP;
       double *__restrict__ row = part + (ut.wbeg + q) * static_cast<int64_t>(part_width) + SP * (2 + SP);
       row[s * D + d[j]] = a1[j];
@@ -557,13 +438,13 @@ __global__ __launch_bounds__(kEmBlock) void embed_obs_kernel(
 // stats[w][e]: {nobs, 0.0, start[S], trans[S][S], post[S], obs[S][D], obs2[S][D]} over the counted slots of word w, in
 // two levels with fixed boundaries: fold[c][w][e] = the sum over the slots n of chunk c (kEmFoldChunk of them), n
 // ascending; then stats[w][e] = the sum over the chunks, c ascending
-__global__ __launch_bounds__(kEmBlock) void embed_fold_chunk_kernel(const double *__restrict__ part,
+__global__ __launch_bounds__(kXBlock) void embed_fold_chunk_kernel(const double *__restrict__ part,
                                                                     const uint8_t *__restrict__ slot_ok,
                                                                     const int32_t *__restrict__ words,
                                                                     int64_t total_words, int32_t W, int32_t S,
                                                                     int32_t SP, int32_t D, int32_t part_width,
                                                                     int32_t width, double *__restrict__ fold) {
-  const int e = blockIdx.x * kEmBlock + threadIdx.x;
+  const int e = blockIdx.x * kXBlock + threadIdx.x;
   const int w = blockIdx.y;
   const int64_t c = blockIdx.z;
   if (e >= width) return;
@@ -593,9 +474,9 @@ __global__ __launch_bounds__(kEmBlock) void embed_fold_chunk_kernel(const double
   fold[(c * W + w) * width + e] = sum;
 }
 
-__global__ __launch_bounds__(kEmBlock) void embed_fold_kernel(const double *__restrict__ fold, int64_t chunks,
+__global__ __launch_bounds__(kXBlock) void embed_fold_kernel(const double *__restrict__ fold, int64_t chunks,
                                                               int32_t W, int32_t width, double *__restrict__ stats) {
-  const int e = blockIdx.x * kEmBlock + threadIdx.x;
+  const int e = blockIdx.x * kXBlock + threadIdx.x;
   const int w = blockIdx.y;
   if (e >= width) return;
   double sum = 0.0;
@@ -616,57 +497,28 @@ struct EmArgs {
   int32_t W, S;
 };
 
+// the forward kernel, then (backward) the backward kernel with as many wavefronts per workgroup as the LDS holds next
+// to the vocabulary's table: its transition accumulators take SP * 64 * RL doubles per wavefront (36 KB at SP = 18,
+// RL = 4)
 template <int RL, int SP>
-int launch_forward(const EmArgs &a, const EmWorkspace &ws, double *loglik, hipStream_t stream) {
-  const size_t lds =
-      (static_cast<size_t>(a.W) * SP * SP + static_cast<size_t>(kEmWaves) * (kWave * RL + kEmRows)) * sizeof(double);
-  const int64_t blocks = (a.n_utts + kEmWaves - 1) / kEmWaves;
-  SAPR_LAUNCH((embed_forward_kernel<RL, SP>), dim3(static_cast<unsigned>(blocks)), dim3(kEmBlock), lds, stream, a.logb,
-              a.offsets, a.n_utts, a.total_frames, a.words, a.word_offsets, a.total_words, a.max_words, a.log_start,
-              a.log_trans, a.log_exit, a.word_penalty, a.W, a.S, ws.alpha, ws.X, loglik);
-  SAPR_HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-template <int RL, int SP>
-int launch_backward(const EmArgs &a, const EmWorkspace &ws, int32_t part_width, const double *loglik, double *post,
-                    hipStream_t stream) {
-  // as many wavefronts per workgroup as the LDS holds next to the vocabulary's table: the transition accumulators take
-  // SP * 64 * RL doubles per wavefront (36 KB at SP = 18, RL = 4)
-  constexpr int lds_max = 160 * 1024;  // a gfx950 workgroup's LDS
-  const size_t tab = static_cast<size_t>(a.W) * SP * SP * sizeof(double);
-  const size_t per_wave = static_cast<size_t>(kWave * RL + kEmRows + SP * kWave * RL) * sizeof(double);
-  int waves = kEmWaves;
-  while (waves > 1 && tab + waves * per_wave > static_cast<size_t>(lds_max)) --waves;
-  const size_t lds = tab + waves * per_wave;
-  if (lds > static_cast<size_t>(lds_max))
-    return fail(SAPR_ERR_UNSUPPORTED, "the backward kernel needs %zu bytes of LDS, the device offers %d", lds, lds_max);
-  const auto kern = embed_backward_kernel<RL, SP>;
-  if (lds > 64 * 1024)  // per launch, not once: the attribute belongs to the current device's copy of the kernel
-    SAPR_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     static_cast<int>(lds)));
-  const int64_t blocks = (a.n_utts + waves - 1) / waves;
-  SAPR_LAUNCH(kern, dim3(static_cast<unsigned>(blocks)), dim3(waves * kWave), lds, stream, a.logb, a.offsets, a.n_utts,
-              a.total_frames, a.words, a.word_offsets, a.total_words, a.max_words, a.log_start, a.log_trans,
-              a.log_exit, a.word_penalty, a.W, a.S, part_width, ws.alpha, ws.X, loglik, ws.part, ws.slot_ok, post);
-  SAPR_HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-template <int SP>
 int launch_recursions(const EmArgs &a, const EmWorkspace &ws, int32_t part_width, double *loglik, double *post,
                       bool backward, hipStream_t stream) {
-  const int positions = a.max_words * SP;
-  if (positions <= kWave) {
-    if (int rc = launch_forward<1, SP>(a, ws, loglik, stream)) return rc;
-    return backward ? launch_backward<1, SP>(a, ws, part_width, loglik, post, stream) : 0;
-  }
-  if (positions <= 2 * kWave) {
-    if (int rc = launch_forward<2, SP>(a, ws, loglik, stream)) return rc;
-    return backward ? launch_backward<2, SP>(a, ws, part_width, loglik, post, stream) : 0;
-  }
-  if (int rc = launch_forward<4, SP>(a, ws, loglik, stream)) return rc;
-  return backward ? launch_backward<4, SP>(a, ws, part_width, loglik, post, stream) : 0;
+  const size_t tab = static_cast<size_t>(a.W) * SP * SP * sizeof(double);
+  if (int rc = x_launch(embed_forward_kernel<RL, SP>, (a.n_utts + kXWaves - 1) / kXWaves, kXBlock,
+                        tab + static_cast<size_t>(kXWaves) * (kWave * RL + kEmRows) * sizeof(double), stream, a.logb,
+                        a.offsets, a.n_utts, a.total_frames, a.words, a.word_offsets, a.total_words, a.max_words,
+                        a.log_start, a.log_trans, a.log_exit, a.word_penalty, a.W, a.S, ws.alpha, ws.X, loglik))
+    return rc;
+  if (!backward) return 0;
+  size_t lds = 0;
+  const int waves = x_waves(tab, static_cast<size_t>(kWave * RL + kEmRows + SP * kWave * RL) * sizeof(double), &lds);
+  if (lds > static_cast<size_t>(kXLdsMax))
+    return fail(SAPR_ERR_UNSUPPORTED, "the backward kernel needs %zu bytes of LDS, the device offers %d", lds,
+                kXLdsMax);
+  return x_launch(embed_backward_kernel<RL, SP>, (a.n_utts + waves - 1) / waves, waves * kWave, lds, stream, a.logb,
+                  a.offsets, a.n_utts, a.total_frames, a.words, a.word_offsets, a.total_words, a.max_words, a.log_start,
+                  a.log_trans, a.log_exit, a.word_penalty, a.W, a.S, part_width, ws.alpha, ws.X, loglik, ws.part,
+                  ws.slot_ok, post);
 }
 
 // ---- second moments over the chain posteriors (sapr_connected_embed_full) ----------------------------------------
@@ -714,8 +566,8 @@ inline EmFullWorkspace em_full_carve(void *base, int64_t total_frames, int64_t n
   EmFullWorkspace w;
   uint8_t *p = static_cast<uint8_t *>(base);
   w.base_bytes = em_carve(nullptr, total_frames, total_words, max_words, S, 0).bytes;
-  const size_t h = em_align16(static_cast<size_t>(W) * em_head_width(S) * sizeof(double));
-  const size_t f = em_align16(static_cast<size_t>(em_full_groups(n_utts)) * W * P * sizeof(double));
+  const size_t h = x_align16(static_cast<size_t>(W) * em_head_width(S) * sizeof(double));
+  const size_t f = x_align16(static_cast<size_t>(em_full_groups(n_utts)) * W * P * sizeof(double));
   w.head = reinterpret_cast<double *>(p + w.base_bytes);
   w.part = reinterpret_cast<double *>(p + w.base_bytes + h);
   w.bytes = w.base_bytes + h + f;
@@ -723,7 +575,7 @@ inline EmFullWorkspace em_full_carve(void *base, int64_t total_frames, int64_t n
 }
 
 template <int DP>
-__global__ __launch_bounds__(kEmBlock) void embed_full_accum_kernel(
+__global__ __launch_bounds__(kXBlock) void embed_full_accum_kernel(
     const double *__restrict__ gamma, const float *__restrict__ feats, int32_t D, const int64_t *__restrict__ offsets,
     int64_t n_utts, int64_t total_frames, const int32_t *__restrict__ words, const int64_t *__restrict__ word_offsets,
     int64_t total_words, int32_t max_words, int32_t W, int32_t S, int32_t SP, int64_t group_utts,
@@ -733,9 +585,9 @@ __global__ __launch_bounds__(kEmBlock) void embed_full_accum_kernel(
   constexpr int XS = NT == 2 ? 48 : 16 * NT;   // LDS row stride (doubles): four consecutive rows on distinct banks
   constexpr int GS = kEmFullGS;
   constexpr int T1 = DP / 16, N1 = DP % 16;    // where the constant 1 sits
-  constexpr int NI = kEmFullChunk * XS / kEmBlock;  // staged features per thread and chunk
-  static_assert(NI * kEmBlock == kEmFullChunk * XS, "the staging loop covers the chunk exactly");
-  static_assert(kEmFullChunk * 4 == kEmBlock, "one staged weight per thread: 64 frames x the pass's four states");
+  constexpr int NI = kEmFullChunk * XS / kXBlock;  // staged features per thread and chunk
+  static_assert(NI * kXBlock == kEmFullChunk * XS, "the staging loop covers the chunk exactly");
+  static_assert(kEmFullChunk * 4 == kXBlock, "one staged weight per thread: 64 frames x the pass's four states");
   __shared__ double s_x[kEmFullChunk * XS];
   __shared__ double s_g[kEmFullChunk * GS];
 
@@ -758,7 +610,7 @@ __global__ __launch_bounds__(kEmBlock) void embed_full_accum_kernel(
 #pragma unroll
     for (int tau = 0; tau < NTU; ++tau) acc[tau] = f64x4_em{0.0, 0.0, 0.0, 0.0};
     for (int64_t u = u_lo; u < u_hi; ++u) {
-      const EmUtt ut = em_utt(offsets, total_frames, word_offsets, total_words, max_words, u);
+      const XUtt ut = x_utt(offsets, total_frames, word_offsets, total_words, max_words, u);
       // (a finite likelihood was written only for 0 < K <= max_words, T > 0 and words inside the vocabulary; the
       // gamma rows of every other utterance hold whatever the workspace held: left out, not multiplied by zero)
       if (!ut.path || !finite_f64(loglik[u])) continue;  // (uniform)
@@ -784,13 +636,13 @@ __global__ __launch_bounds__(kEmBlock) void embed_full_accum_kernel(
         float xv[NI];
 #pragma unroll
         for (int q = 0; q < NI; ++q) {
-          const int item = tid + q * kEmBlock, f = item / XS, col = item - f * XS;
+          const int item = tid + q * kXBlock, f = item / XS, col = item - f * XS;
           const int64_t t = c0 + f;
           xv[q] = xu[(t < ut.T && col < D) ? t * D + col : 0];
         }
 #pragma unroll
         for (int q = 0; q < NI; ++q) {
-          const int item = tid + q * kEmBlock, f = item / XS, col = item - f * XS;
+          const int item = tid + q * kXBlock, f = item / XS, col = item - f * XS;
           const bool live = c0 + f < ut.T;
           s_x[item] = live ? (col < D ? static_cast<double>(xv[q]) : (col == DP ? 1.0 : 0.0)) : 0.0;
         }
@@ -844,11 +696,11 @@ __global__ __launch_bounds__(kEmBlock) void embed_full_accum_kernel(
 
 // stats[w][e]: the head as sapr_connected_embed folded it, then {obs[S][D], oo[S][D][D]} = the sum over the groups'
 // partial rows, group ascending; one thread per element
-__global__ __launch_bounds__(kEmBlock) void embed_full_fold_kernel(const double *__restrict__ head,
+__global__ __launch_bounds__(kXBlock) void embed_full_fold_kernel(const double *__restrict__ head,
                                                                    const double *__restrict__ part, int64_t groups,
                                                                    int32_t W, int32_t head_width, int32_t P,
                                                                    double *__restrict__ stats) {
-  const int e = blockIdx.x * kEmBlock + threadIdx.x;
+  const int e = blockIdx.x * kXBlock + threadIdx.x;
   const int w = blockIdx.y;
   const int width = head_width + P;
   if (e >= width) return;
@@ -886,7 +738,7 @@ constexpr int kEmGmmStates = 64 / MP > kMaxS ? kMaxS : 64 / MP;  // states of on
 inline size_t em_gmm_p(int S, int M, int D) { return static_cast<size_t>(S) * M * (2 * D + 1); }
 
 template <int MP, int DP>
-__global__ __launch_bounds__(kEmBlock) void embed_gmm_accum_kernel(
+__global__ __launch_bounds__(kXBlock) void embed_gmm_accum_kernel(
     const double *__restrict__ gamma, const float *__restrict__ feats, int32_t D, const double *__restrict__ pack,
     int64_t pack_stride, int32_t M, const int64_t *__restrict__ offsets, int64_t n_utts, int64_t total_frames,
     const int32_t *__restrict__ words, const int64_t *__restrict__ word_offsets, int64_t total_words,
@@ -898,7 +750,7 @@ __global__ __launch_bounds__(kEmBlock) void embed_gmm_accum_kernel(
   constexpr int NT = (2 * DP + 1 + 15) / 16;   // 16-wide column tiles: x[0..D), RN32(x x)[0..D), the constant 1
   constexpr int FS = kEmGmmFS, GF = kEmGmmGF;
   constexpr int XF = DP | 1;                   // LDS row stride of the staged frames (floats), odd
-  static_assert(RT <= kEmWaves && RW <= 16 * RT, "a row tile per wavefront");
+  static_assert(RT <= kXWaves && RW <= 16 * RT, "a row tile per wavefront");
   __shared__ double s_r[16 * RT * FS];
   __shared__ double s_g[SG * GF];
   __shared__ float s_x[kEmFullChunk * XF];
@@ -924,14 +776,14 @@ __global__ __launch_bounds__(kEmBlock) void embed_gmm_accum_kernel(
     ci[t] = c < D ? c : (c < 2 * D ? c - D : 0);
   }
   // (the rows of the last tile behind RW are read by phase B and never written by phase A)
-  for (int i = tid; i < 16 * RT * FS; i += kEmBlock) s_r[i] = 0.0;
+  for (int i = tid; i < 16 * RT * FS; i += kXBlock) s_r[i] = 0.0;
 
   for (int g = 0; g * SG < S; ++g) {  // (uniform trip counts: every thread reaches the barriers)
     f64x4_em acc[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) acc[t] = f64x4_em{0.0, 0.0, 0.0, 0.0};
     for (int64_t u = u_lo; u < u_hi; ++u) {
-      const EmUtt ut = em_utt(offsets, total_frames, word_offsets, total_words, max_words, u);
+      const XUtt ut = x_utt(offsets, total_frames, word_offsets, total_words, max_words, u);
       // (as in embed_full_accum_kernel: the gamma rows of an utterance without a finite likelihood were never written
       // and may hold NaN; a frame that is read belongs to an utterance whose every logb, hence every feature, is finite)
       if (!ut.path || !finite_f64(loglik[u])) continue;  // (uniform)
@@ -943,7 +795,7 @@ __global__ __launch_bounds__(kEmBlock) void embed_gmm_accum_kernel(
       for (int64_t c0 = 0; c0 < ut.T; c0 += kEmFullChunk) {
         {  // g_t(w, s) of the pass's states, the slots collapsed k ascending; 0.0 selected behind the utterance's end
           bool nz = false;
-          for (int item = tid; item < kEmFullChunk * SG; item += kEmBlock) {
+          for (int item = tid; item < kEmFullChunk * SG; item += kXBlock) {
             const int f = item / SG, sj = item - f * SG;
             const int64_t t = c0 + f;
             const int st = g * SG + sj;
@@ -959,7 +811,7 @@ __global__ __launch_bounds__(kEmBlock) void embed_gmm_accum_kernel(
         }
         // the chunk's frames into LDS, float32 as they are; zeros in the padded dimensions (against their zero mean
         // and zero coefficient they add +0.0) and in the rows past the utterance's last frame
-        for (int item = tid; item < kEmFullChunk * DP; item += kEmBlock) {
+        for (int item = tid; item < kEmFullChunk * DP; item += kXBlock) {
           const int f = item / DP, d = item - f * DP;
           const int64_t t = c0 + f;
           s_x[f * XF + d] = (t < ut.T && d < D) ? xu[t * D + d] : 0.0f;
@@ -968,7 +820,7 @@ __global__ __launch_bounds__(kEmBlock) void embed_gmm_accum_kernel(
         // ---- phase A: r of the pass's states for the chunk's 64 frames, lane = frame -----------------------------
         {
           const float *__restrict__ xrow = s_x + lane * XF;
-          for (int j = wv; j < SG; j += kEmWaves) {
+          for (int j = wv; j < SG; j += kXWaves) {
             const int s = g * SG + j;
             const double gm = s_g[j * GF + lane];
             double r[MP];
@@ -1094,28 +946,24 @@ extern "C" int sapr_connected_embed(const double *logb, const float *feats, int3
                  log_start, log_trans, log_exit, word_penalty, W, S};
   const bool backward = stats || post;
   if (backward && total_words > 0) SAPR_HIP_TRY(hipMemsetAsync(ws.slot_ok, 0, static_cast<size_t>(total_words), st));
-  int rc;
-  if (SP == 4)
-    rc = launch_recursions<4>(a, ws, part_width, loglik, post, backward, st);
-  else if (SP == 10)
-    rc = launch_recursions<10>(a, ws, part_width, loglik, post, backward, st);
-  else
-    rc = launch_recursions<18>(a, ws, part_width, loglik, post, backward, st);
+  const int rc = x_dispatch(SP, max_words * SP, [&](auto rl, auto sp) {
+    return launch_recursions<decltype(rl)::value, decltype(sp)::value>(a, ws, part_width, loglik, post, backward, st);
+  });
   if (rc || !stats) return rc;
   if (D > 0 && total_frames > 0) {
-    SAPR_LAUNCH(embed_obs_kernel, dim3(static_cast<unsigned>(n_utts)), dim3(kEmBlock), 0, st, ws.alpha, feats, D,
+    SAPR_LAUNCH(embed_obs_kernel, dim3(static_cast<unsigned>(n_utts)), dim3(kXBlock), 0, st, ws.alpha, feats, D,
                 offsets, n_utts, total_frames, word_offsets, total_words, max_words, SP, part_width, loglik, ws.part);
     SAPR_HIP_TRY(hipGetLastError());
   }
   const int32_t width = 2 + S + S * S + S + 2 * S * D;
   const int64_t chunks = em_chunks(total_words);
-  const unsigned tiles = static_cast<unsigned>((width + kEmBlock - 1) / kEmBlock);
+  const unsigned tiles = static_cast<unsigned>((width + kXBlock - 1) / kXBlock);
   if (chunks > 0) {
     SAPR_LAUNCH(embed_fold_chunk_kernel, dim3(tiles, static_cast<unsigned>(W), static_cast<unsigned>(chunks)),
-                dim3(kEmBlock), 0, st, ws.part, ws.slot_ok, words, total_words, W, S, SP, D, part_width, width, ws.fold);
+                dim3(kXBlock), 0, st, ws.part, ws.slot_ok, words, total_words, W, S, SP, D, part_width, width, ws.fold);
     SAPR_HIP_TRY(hipGetLastError());
   }
-  SAPR_LAUNCH(embed_fold_kernel, dim3(tiles, static_cast<unsigned>(W)), dim3(kEmBlock), 0, st, ws.fold, chunks, W,
+  SAPR_LAUNCH(embed_fold_kernel, dim3(tiles, static_cast<unsigned>(W)), dim3(kXBlock), 0, st, ws.fold, chunks, W,
               width, stats);
   SAPR_HIP_TRY(hipGetLastError());
   return 0;
@@ -1176,7 +1024,7 @@ extern "C" int sapr_connected_embed_full(const double *logb, const float *feats,
   const double *gamma = static_cast<const double *>(workspace);
   const dim3 grid(static_cast<unsigned>(groups), static_cast<unsigned>(W));
 #define SAPR_EM_FULL_ACCUM(DP)                                                                                        \
-  SAPR_LAUNCH(embed_full_accum_kernel<DP>, grid, dim3(kEmBlock), 0, st, gamma, feats, D, offsets, n_utts,            \
+  SAPR_LAUNCH(embed_full_accum_kernel<DP>, grid, dim3(kXBlock), 0, st, gamma, feats, D, offsets, n_utts,            \
               total_frames, words, word_offsets, total_words, max_words, W, S, SP, per, loglik, ws.part)
   switch (dp_of(D)) {
     case 13: SAPR_EM_FULL_ACCUM(13); break;
@@ -1186,8 +1034,8 @@ extern "C" int sapr_connected_embed_full(const double *logb, const float *feats,
 #undef SAPR_EM_FULL_ACCUM
   SAPR_HIP_TRY(hipGetLastError());
   const int32_t hw = static_cast<int32_t>(em_head_width(S)), P = static_cast<int32_t>(em_full_p(S, D));
-  const unsigned tiles = static_cast<unsigned>((hw + P + kEmBlock - 1) / kEmBlock);
-  SAPR_LAUNCH(embed_full_fold_kernel, dim3(tiles, static_cast<unsigned>(W)), dim3(kEmBlock), 0, st, ws.head, ws.part,
+  const unsigned tiles = static_cast<unsigned>((hw + P + kXBlock - 1) / kXBlock);
+  SAPR_LAUNCH(embed_full_fold_kernel, dim3(tiles, static_cast<unsigned>(W)), dim3(kXBlock), 0, st, ws.head, ws.part,
               groups, W, hw, P, stats);
   SAPR_HIP_TRY(hipGetLastError());
   return 0;
@@ -1255,7 +1103,7 @@ extern "C" int sapr_connected_embed_gmm(const double *logb, const float *feats, 
   const double *gamma = static_cast<const double *>(workspace);
   const dim3 grid(static_cast<unsigned>(groups), static_cast<unsigned>(W));
 #define SAPR_EM_GMM_ACCUM(MP, DP)                                                                                     \
-  SAPR_LAUNCH((embed_gmm_accum_kernel<MP, DP>), grid, dim3(kEmBlock), 0, st, gamma, feats, D, pack, stride, M,        \
+  SAPR_LAUNCH((embed_gmm_accum_kernel<MP, DP>), grid, dim3(kXBlock), 0, st, gamma, feats, D, pack, stride, M,        \
               offsets, n_utts, total_frames, words, word_offsets, total_words, max_words, W, S, SP, per, loglik,      \
               ws.part)
 #define SAPR_EM_GMM_ACCUM_DP(MP)                                                                                      \
@@ -1274,8 +1122,8 @@ extern "C" int sapr_connected_embed_gmm(const double *logb, const float *feats, 
 #undef SAPR_EM_GMM_ACCUM
   SAPR_HIP_TRY(hipGetLastError());
   const int32_t hw = static_cast<int32_t>(em_head_width(S));
-  const unsigned tiles = static_cast<unsigned>((hw + P + kEmBlock - 1) / kEmBlock);
-  SAPR_LAUNCH(embed_full_fold_kernel, dim3(tiles, static_cast<unsigned>(W)), dim3(kEmBlock), 0, st, ws.head, ws.part,
+  const unsigned tiles = static_cast<unsigned>((hw + P + kXBlock - 1) / kXBlock);
+  SAPR_LAUNCH(embed_full_fold_kernel, dim3(tiles, static_cast<unsigned>(W)), dim3(kXBlock), 0, st, ws.head, ws.part,
               groups, W, hw, static_cast<int32_t>(P), stats);
   SAPR_HIP_TRY(hipGetLastError());
   return 0;

@@ -4,21 +4,22 @@
 // restatement, which is the definition: tests/_levels_ref.py.  The input logb[total_frames][R = W * SP] is what the
 // three emission stages of connected.hip write; the language model is sapr_connected_bigram's.
 //
-// connected_levels_kernel<RL, SP, LT>: the mapping of connected_bigram_kernel — one wavefront serves one utterance, the
-// R flat states lie along the lanes, RL in {1, 2, 4} per lane, tab[i][r] and the transposed lm are shared in LDS — with
-// delta of all L <= LT levels in registers, LT * RL doubles per lane.  Row t of logb is read once and serves every
-// level; inside the distance loop one tab read and one lane-address computation serve L candidates, and the L
-// dependent chains of a frame (one per level: they do not read each other) fill each other's latency.  Level l needs
-// its own old delta and N_{t-1}(l,.) alone, so the update is in place.  The three hand-overs through per-wavefront LDS
-// rows are made for all levels together, three wave_lds_sync per frame:
+// connected_levels_kernel<RL, SP, LT>: the lane layout of connected_lanes.h over the flat states, the transition table
+// by source and the transposed lm in LDS as in the bigram decoder (written out in the kernel: it keeps the text it was
+// timed with, and takes the constants, the X step and the host side from the header) — with delta of all L <= LT levels in registers,
+// LT * RL doubles per lane.  Row t of logb is read once and serves every level; inside the distance loop one tab read
+// and one lane-address computation serve L candidates, and the L dependent chains of a frame (one per level: they do
+// not read each other) fill each other's latency.  Level l needs its own old delta and N_{t-1}(l,.) alone, so the
+// update is in place.  The three hand-overs through per-wavefront LDS rows are made for all levels together, three
+// wave_lds_sync per frame:
 //   1. every lane writes delta(l) + log_exit to cbuf[l][r];
 //   2. the L * W (level, word) pairs are spread over the lanes in ceil(L W / 64) passes: pair p = l * W + v takes the
 //      first maximum over the SP values of word v on level l and writes X(l,v) to xbuf[l][v], the state to the workspace;
 //   3. pair p = l * W + w, l >= 1, takes the first maximum over v ascending of xbuf[l - 1][v] + lm[v][w] and writes
 //      N(l,w) to nbuf[l][w], the predecessor word to the workspace; nbuf[0][.] stays -inf.  The state lanes read the N
 //      of their own word from nbuf when the next frame compares it.
-// Workspace: per (frame, level) what connected_bigram_kernel keeps per frame — one back-pointer byte per flat state
-// (kLvEntry where the entry won), one byte per word for the state that attained X, one for the word that attained N —
+// Workspace: per (frame, level) what the bigram decoder keeps per frame — one back-pointer byte per flat state
+// (kXEntry where the entry won), one byte per word for the state that attained X, one for the word that attained N —
 // and one int32 per (utterance, level), the word that attained level_score.  connected_levels_backtrace_kernel, one
 // lane per utterance, selects the count and walks back; it may be launched any number of times over one workspace.
 //
@@ -32,40 +33,23 @@ namespace {
 
 #include "lse_ops.h"
 #include "gmm_ops.h"
+#include "connected_lanes.h"
 
-constexpr int kLvMaxR = 256;          // flat states one wavefront holds
 constexpr int kLvMaxL = 8;            // levels one wavefront holds
-constexpr int kLvBlock = 256;         // at most 4 wavefronts per workgroup
-constexpr int kLvMaxWaves = kLvBlock / kWave;
-constexpr int kLvEntry = 255;         // back-pointer byte: the word was entered at this frame (connected.hip kEntry)
-constexpr int kLvLdsMax = 160 * 1024; // LDS of one gfx950 compute unit
 
 inline int lv_check_shape(int32_t W, int32_t S, int32_t L) {
-  if (S > kMaxS || static_cast<int64_t>(W) * sp_of(S) > kLvMaxR)
-    return fail(SAPR_ERR_UNSUPPORTED, "the connected-word kernels serve S in 1..%d and W * SP <= %d; got W=%d S=%d",
-                kMaxS, kLvMaxR, W, S);
+  if (int rc = x_check_shape(W, S)) return rc;
   if (L < 1 || L > kLvMaxL)
     return fail(SAPR_ERR_UNSUPPORTED, "the level-building kernels serve L in 1..%d words; got L=%d", kLvMaxL, L);
   return 0;
 }
 
-inline size_t lv_align16(size_t x) { return (x + 15) / 16 * 16; }
-
-constexpr int lv_lm_stride(int W) { return W | 1; }  // doubles per row of the transposed lm in LDS
-
 // LDS in doubles.  Shared by the workgroup: tab[SP][64 RL], lmt[W][W | 1], lm_end[W]; per wavefront: cbuf[L][64 RL],
 // xbuf[L][W], nbuf[L][W]
 constexpr size_t lv_shared_doubles(int W, int SP, int RL) {
-  return static_cast<size_t>(SP) * kWave * RL + static_cast<size_t>(W) * lv_lm_stride(W) + W;
+  return static_cast<size_t>(SP) * kWave * RL + static_cast<size_t>(W) * x_lm_stride(W) + W;
 }
 constexpr size_t lv_wave_doubles(int W, int RL, int L) { return static_cast<size_t>(L) * (kWave * RL + 2 * W); }
-
-// between the lanes of ONE wavefront: what the lanes wrote to LDS before is what they read after (connected_align.hip)
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // the workspace of sapr_connected_levels_workspace_bytes, cut up
 struct LvWorkspace {
@@ -79,9 +63,9 @@ inline LvWorkspace lv_cut(void *workspace, int64_t total_frames, int32_t W, int3
   const size_t rows = static_cast<size_t>(total_frames) * static_cast<size_t>(L);
   LvWorkspace ws;
   ws.bp = static_cast<uint8_t *>(workspace);
-  ws.xarg = ws.bp + lv_align16(rows * static_cast<size_t>(W) * static_cast<size_t>(SP));
-  ws.warg = ws.xarg + lv_align16(rows * static_cast<size_t>(W));
-  ws.fin = reinterpret_cast<int32_t *>(ws.warg + lv_align16(rows * static_cast<size_t>(W)));
+  ws.xarg = ws.bp + x_align16(rows * static_cast<size_t>(W) * static_cast<size_t>(SP));
+  ws.warg = ws.xarg + x_align16(rows * static_cast<size_t>(W));
+  ws.fin = reinterpret_cast<int32_t *>(ws.warg + x_align16(rows * static_cast<size_t>(W)));
   return ws;
 }
 
@@ -89,7 +73,7 @@ inline LvWorkspace lv_cut(void *workspace, int64_t total_frames, int32_t W, int3
 constexpr int lv_group(int RL, int LT) { return LT < 4 ? LT : (RL == 4 && LT == 8 ? 2 : 4); }
 
 template <int RL, int SP, int LT>
-__global__ __launch_bounds__(kLvBlock) void connected_levels_kernel(
+__global__ __launch_bounds__(kXBlock) void connected_levels_kernel(
     const double *__restrict__ logb, const int64_t *__restrict__ offsets, int64_t n_utts, int64_t total_frames,
     const double *__restrict__ log_start, const double *__restrict__ log_trans, const double *__restrict__ log_exit,
     const double *__restrict__ lm, const double *__restrict__ lm_start, const double *__restrict__ lm_end, int32_t W,
@@ -100,7 +84,7 @@ __global__ __launch_bounds__(kLvBlock) void connected_levels_kernel(
   extern __shared__ double smem[];
   double *tab = smem;             // [SP][RP]: tab[i][r] = log_trans[w][i][s], the transition INTO flat state r from i
   const int R = W * SP;
-  const int LS = lv_lm_stride(W);
+  const int LS = x_lm_stride(W);
   const int LW = L * W;           // (level, word) pairs
   double *lmt = tab + SP * RP;    // [W][LS]: lmt[w][v] = lm[v][w]
   double *lme = lmt + W * LS;     // [W]
@@ -193,7 +177,7 @@ __global__ __launch_bounds__(kLvBlock) void connected_levels_kernel(
 #pragma unroll
           for (int k = 0; k < RL; ++k) {
             v[j][k] = g + j == 0 ? ls0[k] : neg_inf();
-            back[j][k] = kLvEntry;
+            back[j][k] = kXEntry;
           }
         }
       } else {
@@ -252,7 +236,7 @@ __global__ __launch_bounds__(kLvBlock) void connected_levels_kernel(
               const double entry = nbuf[(g + j) * W + wk[k]] + ls[k];
               const bool take = entry > v[j][k];
               v[j][k] = take ? entry : v[j][k];
-              back[j][k] = take ? kLvEntry : back[j][k];
+              back[j][k] = take ? kXEntry : back[j][k];
             }
           }
         }
@@ -278,16 +262,8 @@ __global__ __launch_bounds__(kLvBlock) void connected_levels_kernel(
 #pragma unroll 1
     for (int p = lane; p < LW; p += kWave) {  // X(l,v): the first maximum over the word's states, s ascending
       const int l = (p * winv) >> 16, w = p - l * W;
-      const double *__restrict__ c = cbuf + l * RP + w * SP;
-      double xv = c[0];
-      int xs = 0;
-#pragma unroll
-      for (int s = 1; s < SP; ++s) {
-        const double cs = c[s];
-        const bool take = cs > xv;
-        xv = take ? cs : xv;
-        xs = take ? s : xs;
-      }
+      int xs;
+      const double xv = x_first_max<SP>(cbuf + l * RP + w * SP, &xs);
       xbuf[p] = xv;
       xrow[p] = static_cast<uint8_t>(xs);
     }
@@ -333,21 +309,16 @@ __global__ __launch_bounds__(kLvBlock) void connected_levels_kernel(
 
 // one lane per utterance selects the count k in lo .. hi — from lo, a later k only where its score is strictly
 // greater — and walks back from level k - 1: the last word's best exit at the last frame, down one level at every entry
-__global__ __launch_bounds__(kLvBlock) void connected_levels_backtrace_kernel(
+__global__ __launch_bounds__(kXBlock) void connected_levels_backtrace_kernel(
     const int64_t *__restrict__ offsets, int64_t n_utts, int64_t total_frames, int32_t W, int32_t SP, int32_t L,
     const uint8_t *__restrict__ bp, const uint8_t *__restrict__ xarg, const uint8_t *__restrict__ warg,
     const int32_t *__restrict__ fin, const double *__restrict__ level_score, const int32_t *__restrict__ count_lo,
     const int32_t *__restrict__ count_hi, double *__restrict__ score, int32_t *__restrict__ n_words,
     int32_t *__restrict__ path_word, int32_t *__restrict__ path_state, uint8_t *__restrict__ path_entry) {
-  const int64_t u = static_cast<int64_t>(blockIdx.x) * kLvBlock + threadIdx.x;
+  const int64_t u = static_cast<int64_t>(blockIdx.x) * kXBlock + threadIdx.x;
   if (u >= n_utts) return;
-  const int64_t beg = offsets[u], end = offsets[u + 1];
-  if (beg < 0 || end < beg || end > total_frames) {
-    score[u] = neg_inf();
-    if (n_words) n_words[u] = 0;
-    return;
-  }
-  const int64_t T = end - beg;
+  const XFrames fr = x_frames(offsets, total_frames, u);
+  const int64_t beg = fr.beg, T = fr.T;
   int lo = count_lo ? count_lo[u] : 1, hi = count_hi ? count_hi[u] : L;
   const bool none = lo > hi;  // an empty range selects nothing
   lo = lo < 1 ? 1 : (lo > L ? L : lo);
@@ -364,12 +335,8 @@ __global__ __launch_bounds__(kLvBlock) void connected_levels_backtrace_kernel(
     }
   }
   score[u] = sc;
-  if (!(sc - sc == 0.0)) {  // a non-finite score has no path
-    for (int64_t t = 0; t < T; ++t) {
-      if (path_word) path_word[beg + t] = -1;
-      if (path_state) path_state[beg + t] = -1;
-      if (path_entry) path_entry[beg + t] = 0;
-    }
+  if (!finite_f64(sc)) {
+    x_no_path(beg, T, path_word, path_state, path_entry);
     if (n_words) n_words[u] = 0;
     return;
   }
@@ -383,7 +350,7 @@ __global__ __launch_bounds__(kLvBlock) void connected_levels_backtrace_kernel(
     if (path_word) path_word[beg + t] = w;
     if (path_state) path_state[beg + t] = s;
     const int b = bp[((beg + t) * L + l) * R + w * SP + s];
-    const bool entry = t == 0 || b == kLvEntry;
+    const bool entry = t == 0 || b == kXEntry;
     if (path_entry) path_entry[beg + t] = entry ? 1 : 0;
     if (entry) {
       if (t > 0) {
@@ -410,33 +377,17 @@ struct LvArgs {
   double *level_score;
 };
 
-// as many wavefronts per workgroup as the LDS holds next to tab and lm, at most four (connected_loop_fb.hip lf_waves)
-inline int lv_waves(int W, int SP, int RL, int L, size_t *lds) {
-  const size_t shared = lv_shared_doubles(W, SP, RL) * sizeof(double);
-  const size_t per_wave = lv_wave_doubles(W, RL, L) * sizeof(double);
-  int waves = kLvMaxWaves;
-  while (waves > 1 && shared + waves * per_wave > static_cast<size_t>(kLvLdsMax)) --waves;
-  *lds = shared + waves * per_wave;
-  return waves;
-}
-
 template <int RL, int SP, int LT>
 int launch_levels(const LvArgs &a, hipStream_t stream) {
   size_t lds = 0;
-  const int waves = lv_waves(a.W, SP, RL, a.L, &lds);
-  if (lds > static_cast<size_t>(kLvLdsMax))
+  const int waves = x_waves(lv_shared_doubles(a.W, SP, RL) * sizeof(double),
+                            lv_wave_doubles(a.W, RL, a.L) * sizeof(double), &lds);
+  if (lds > static_cast<size_t>(kXLdsMax))
     return fail(SAPR_ERR_UNSUPPORTED, "the level-building kernel needs %zu bytes of LDS, the device offers %d", lds,
-                kLvLdsMax);
-  const int64_t blocks = (a.n_utts + waves - 1) / waves;
-  const auto kern = connected_levels_kernel<RL, SP, LT>;
-  if (lds > 64 * 1024)  // per launch, not once: the attribute belongs to the current device's copy of the kernel
-    SAPR_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     static_cast<int>(lds)));
-  SAPR_LAUNCH(kern, dim3(static_cast<unsigned>(blocks)), dim3(waves * kWave), lds, stream, a.logb, a.offsets, a.n_utts,
-              a.total_frames, a.log_start, a.log_trans, a.log_exit, a.lm, a.lm_start, a.lm_end, a.W, a.S, a.L, a.ws.bp,
-              a.ws.xarg, a.ws.warg, a.ws.fin, a.level_score);
-  SAPR_HIP_TRY(hipGetLastError());
-  return 0;
+                kXLdsMax);
+  return x_launch(connected_levels_kernel<RL, SP, LT>, (a.n_utts + waves - 1) / waves, waves * kWave, lds, stream,
+                  a.logb, a.offsets, a.n_utts, a.total_frames, a.log_start, a.log_trans, a.log_exit, a.lm, a.lm_start,
+                  a.lm_end, a.W, a.S, a.L, a.ws.bp, a.ws.xarg, a.ws.warg, a.ws.fin, a.level_score);
 }
 
 template <int RL, int SP>
@@ -445,13 +396,6 @@ int launch_levels_lt(const LvArgs &a, hipStream_t stream) {
   if (a.L <= 2) return launch_levels<RL, SP, 2>(a, stream);
   if (a.L <= 4) return launch_levels<RL, SP, 4>(a, stream);
   return launch_levels<RL, SP, 8>(a, stream);
-}
-
-template <int SP>
-int launch_levels_rl(int R, const LvArgs &a, hipStream_t stream) {
-  if (R <= kWave) return launch_levels_lt<1, SP>(a, stream);
-  if (R <= 2 * kWave) return launch_levels_lt<2, SP>(a, stream);
-  return launch_levels_lt<4, SP>(a, stream);
 }
 
 }  // namespace
@@ -468,8 +412,8 @@ extern "C" int sapr_connected_levels_workspace_bytes(int64_t total_frames, int64
   const size_t rows = static_cast<size_t>(total_frames) * static_cast<size_t>(L);
   // per (frame, level): back-pointers [R] bytes, the exit state and the predecessor word of every word; per
   // (utterance, level) the final word (int32); each array padded to 16
-  *bytes = lv_align16(rows * R) + 2 * lv_align16(rows * static_cast<size_t>(W)) +
-           lv_align16(static_cast<size_t>(n_utts) * static_cast<size_t>(L) * sizeof(int32_t));
+  *bytes = x_align16(rows * R) + 2 * x_align16(rows * static_cast<size_t>(W)) +
+           x_align16(static_cast<size_t>(n_utts) * static_cast<size_t>(L) * sizeof(int32_t));
   return 0;
 }
 
@@ -496,9 +440,9 @@ extern "C" int sapr_connected_levels(const double *logb, const int64_t *offsets,
                  lm,       lm_start, lm_end, W,           S,         L,         lv_cut(workspace, total_frames, W, SP, L),
                  level_score};
   hipStream_t st = as_stream(stream);
-  if (SP == 4) return launch_levels_rl<4>(R, a, st);
-  if (SP == 10) return launch_levels_rl<10>(R, a, st);
-  return launch_levels_rl<18>(R, a, st);
+  return x_dispatch(SP, R, [&](auto rl, auto sp) {
+    return launch_levels_lt<decltype(rl)::value, decltype(sp)::value>(a, st);
+  });
 }
 
 extern "C" int sapr_connected_levels_backtrace(const int64_t *offsets, int64_t n_utts, int64_t total_frames, int32_t W,
@@ -514,15 +458,13 @@ extern "C" int sapr_connected_levels_backtrace(const int64_t *offsets, int64_t n
   if (int rc = sapr_connected_levels_workspace_bytes(total_frames, n_utts, W, S, L, &need)) return rc;
   SAPR_REQUIRE(workspace_bytes >= need && (need == 0 || workspace), "workspace too small: %zu < %zu", workspace_bytes,
                need);
-  const int64_t blocks = (n_utts + kLvBlock - 1) / kLvBlock;
+  const int64_t blocks = (n_utts + kXBlock - 1) / kXBlock;
   SAPR_REQUIRE(blocks <= 0x7fffffffLL, "grid too large (%lld blocks)", (long long)blocks);
   if (n_utts == 0) return 0;
   SAPR_REQUIRE(offsets && level_score && score, "NULL pointer argument");
   const int32_t SP = sp_of(S);
   const LvWorkspace ws = lv_cut(workspace, total_frames, W, SP, L);
-  SAPR_LAUNCH(connected_levels_backtrace_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kLvBlock), 0,
-              as_stream(stream), offsets, n_utts, total_frames, W, SP, L, ws.bp, ws.xarg, ws.warg, ws.fin, level_score,
-              count_lo, count_hi, score, n_words, path_word, path_state, path_entry);
-  SAPR_HIP_TRY(hipGetLastError());
-  return 0;
+  return x_launch(connected_levels_backtrace_kernel, blocks, kXBlock, 0, as_stream(stream), offsets, n_utts,
+                  total_frames, W, SP, L, ws.bp, ws.xarg, ws.warg, ws.fin, level_score, count_lo, count_hi, score,
+                  n_words, path_word, path_state, path_entry);
 }

@@ -4,16 +4,14 @@
 // include/sapr_hip.h.  The input logb[total_frames][R = W * SP] is what the three emission stages of connected.hip
 // write; this unit knows nothing about the emission family.
 //
-// The mapping is connected_bigram_kernel's: one wavefront serves one utterance, the R flat states lie along the lanes,
-// RL in {1, 2, 4} per lane (flat state r = k * 64 + lane sits in register k), the within-word neighbour at distance
-// d = j - i comes by ds_bpermute only at the distances at which some transition of the vocabulary is finite, and the
-// coupling between the words goes through per-wavefront LDS rows between wave_lds_sync's: the frame loop has no
-// workgroup barrier.  The transition table lies in LDS by diagonals, tab[(j - i) mod SP][r of j]; the forward kernel
-// reads diagonal d at its own flat state, the backward kernel the same diagonal at flat state r + d (transposed).
-// The arithmetic is connected_embed.hip's: lse2 over the live distances, then the entry (exit) term; the per-word
-// log-sum-exp over a word's states as slot_lse does it (word_lse below).
+// The lane layout of connected_lanes.h over the flat states, written out in the two kernels (they keep the text they
+// were timed with; the constants, the per-word log-sum-exp and the host side are the header's).  The transition table
+// lies in LDS by diagonal, tab[(j - i) mod SP][r of j]: the forward kernel reads diagonal d at its own flat state, the
+// backward kernel the same diagonal at flat state r + d (transposed).
+// The arithmetic is the sum-product one: lse2 over the live distances, then the entry (exit) term; the per-word
+// log-sum-exp over a word's states is x_segment_lse.
 //
-// New here is the W x W log-sum-exp against lm (pair_lse): N_t(w) = lse_v (X_t(v) + lm[v][w]) forward,
+// This unit's own is the W x W log-sum-exp against lm (pair_lse): N_t(w) = lse_v (X_t(v) + lm[v][w]) forward,
 // F_t(v) = lse_w (lm[v][w] + E_t(w)) backward.  lm lies in LDS in rows of W | 1 doubles — transposed in the forward
 // kernel, row-major in the backward kernel — so that lane q walks its own row while the other operand is a broadcast:
 //   1. lane q < W takes the maximum of its W terms (adds and compares, pipelined LDS reads);
@@ -38,75 +36,15 @@ namespace {
 
 #include "lse_ops.h"
 #include "gmm_ops.h"
-
-constexpr int kLfMaxR = 256;              // flat states one wavefront holds
-constexpr int kLfMaxWaves = 4;            // wavefronts per workgroup, where the LDS holds them
-constexpr int kLfBlock = kLfMaxWaves * kWave;
-constexpr int kLfLdsMax = 160 * 1024;     // a gfx950 workgroup's LDS
-
-inline int lf_check_shape(int32_t W, int32_t S) {
-  if (S > kMaxS || static_cast<int64_t>(W) * sp_of(S) > kLfMaxR)
-    return fail(SAPR_ERR_UNSUPPORTED, "the connected-word kernels serve S in 1..%d and W * SP <= %d; got W=%d S=%d",
-                kMaxS, kLfMaxR, W, S);
-  return 0;
-}
-
-inline size_t lf_align16(size_t x) { return (x + 15) / 16 * 16; }
-
-constexpr int lf_lm_stride(int W) { return W | 1; }  // doubles per row of lm, and of the exponentials, in LDS
+#include "connected_lanes.h"
 
 // LDS in doubles: tab[SP][64 RL], lm[W][W | 1], lm_end[W] for the workgroup; cbuf[64 RL], xbuf[64], mbuf[64], nbuf[64]
 // and the exponentials ebuf[W][W | 1] for every wavefront
 constexpr size_t lf_shared_doubles(int W, int SP, int RL) {
-  return static_cast<size_t>(SP) * kWave * RL + static_cast<size_t>(W) * lf_lm_stride(W) + W;
+  return static_cast<size_t>(SP) * kWave * RL + static_cast<size_t>(W) * x_lm_stride(W) + W;
 }
 constexpr size_t lf_wave_doubles(int W, int RL) {
-  return static_cast<size_t>(kWave) * RL + 3 * kWave + static_cast<size_t>(W) * lf_lm_stride(W);
-}
-
-// between the lanes of ONE wavefront: what the lanes wrote to LDS before is what they read after (connected_align.hip)
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ bool finite_f64(double v) { return v - v == 0.0; }
-
-// The log-sum-exp over a word's states (connected_embed.hip slot_lse): val[k] is the term of the lane's flat state in
-// register k; lane q < W returns the log-sum-exp over the SP terms of word q — the first maximum, one exponential per
-// state lane, the exponentials added s ascending, log(sum) + max; an infinite maximum is the result.  The caller
-// synchronises before it writes cbuf again.
-template <int RL, int SP>
-__device__ __forceinline__ double word_lse(double *cbuf, double *mbuf, const double (&val)[RL], const bool (&ok)[RL],
-                                           const int (&wk)[RL], int lane, int W) {
-#pragma unroll
-  for (int k = 0; k < RL; ++k)
-    if (ok[k]) cbuf[k * kWave + lane] = val[k];
-  wave_lds_sync();
-  double m = neg_inf();
-  if (lane < W) {
-    m = cbuf[lane * SP];
-#pragma unroll
-    for (int s = 1; s < SP; ++s) {
-      const double v = cbuf[lane * SP + s];
-      m = v > m ? v : m;
-    }
-    mbuf[lane] = m;
-  }
-  wave_lds_sync();
-#pragma unroll
-  for (int k = 0; k < RL; ++k)
-    if (ok[k]) cbuf[k * kWave + lane] = exp_unit(val[k] - mbuf[wk[k]]);  // (an infinite maximum: selected away below)
-  wave_lds_sync();
-  double r = m;
-  if (lane < W) {
-    double acc = 0.0;
-#pragma unroll
-    for (int s = 0; s < SP; ++s) acc += cbuf[lane * SP + s];
-    r = isinf(m) ? m : log(acc) + m;
-  }
-  return r;
+  return static_cast<size_t>(kWave) * RL + 3 * kWave + static_cast<size_t>(W) * x_lm_stride(W);
 }
 
 // The W x W log-sum-exp: lane q < W returns lse_p (mat[q][p] + xbuf[p]), p ascending (the three steps above).  xbuf is
@@ -158,7 +96,7 @@ __device__ __forceinline__ void lf_load_tables(double *tab, double *lmx, double 
                                                const double *__restrict__ lm_end, int W, int S, int RP,
                                                bool transposed) {
   const int R = W * SP;
-  const int LS = lf_lm_stride(W);
+  const int LS = x_lm_stride(W);
   for (int n = threadIdx.x; n < SP * RP; n += blockDim.x) {
     const int dd = n / RP, r = n - dd * RP;
     const int w = r / SP, s = r - w * SP;
@@ -202,7 +140,7 @@ __device__ __forceinline__ uint64_t lf_distance_mask(const double *tab, const in
 }
 
 template <int RL, int SP>
-__global__ __launch_bounds__(kLfBlock) void loop_forward_kernel(
+__global__ __launch_bounds__(kXBlock) void loop_forward_kernel(
     const double *__restrict__ logb, const int64_t *__restrict__ offsets, int64_t n_utts, int64_t total_frames,
     const double *__restrict__ log_start, const double *__restrict__ log_trans, const double *__restrict__ log_exit,
     const double *__restrict__ lm, const double *__restrict__ lm_start, const double *__restrict__ lm_end, int32_t W,
@@ -210,7 +148,7 @@ __global__ __launch_bounds__(kLfBlock) void loop_forward_kernel(
   constexpr int RP = kWave * RL;  // flat states the lanes hold (R <= RP)
   extern __shared__ double smem[];
   const int R = W * SP;
-  const int LS = lf_lm_stride(W);
+  const int LS = x_lm_stride(W);
   double *tab = smem;             // [SP][RP] by diagonals
   double *lmt = tab + SP * RP;    // [W][LS]: lmt[w][v] = lm[v][w]
   double *lme = lmt + W * LS;     // [W]
@@ -325,7 +263,7 @@ __global__ __launch_bounds__(kLfBlock) void loop_forward_kernel(
       if (ok[k]) arow[k * kWave + lane] = alpha[k];
       ex[k] = alpha[k] + lx[k];
     }
-    const double xv = word_lse<RL, SP>(cbuf, mbuf, ex, ok, wk, lane, W);  // X_t(v) on lane v
+    const double xv = x_segment_lse<RL, SP>(cbuf, mbuf, ex, ok, wk, lane, W);  // X_t(v) on lane v
     if (lane < W) xbuf[lane] = xv;
     bad = bad || xv != xv;
     wave_lds_sync();
@@ -359,7 +297,7 @@ __global__ __launch_bounds__(kLfBlock) void loop_forward_kernel(
 }
 
 template <int RL, int SP>
-__global__ __launch_bounds__(kLfBlock) void loop_backward_kernel(
+__global__ __launch_bounds__(kXBlock) void loop_backward_kernel(
     const double *__restrict__ logb, const int64_t *__restrict__ offsets, int64_t n_utts, int64_t total_frames,
     const double *__restrict__ log_start, const double *__restrict__ log_trans, const double *__restrict__ log_exit,
     const double *__restrict__ lm, const double *__restrict__ lm_end, int32_t W, int32_t S,
@@ -368,7 +306,7 @@ __global__ __launch_bounds__(kLfBlock) void loop_backward_kernel(
   constexpr int RP = kWave * RL;
   extern __shared__ double smem[];
   const int R = W * SP;
-  const int LS = lf_lm_stride(W);
+  const int LS = x_lm_stride(W);
   double *tab = smem;             // [SP][RP] by diagonals
   double *lmr = tab + SP * RP;    // [W][LS]: lmr[v][w] = lm[v][w]
   double *lme = lmr + W * LS;     // [W]
@@ -463,7 +401,7 @@ __global__ __launch_bounds__(kLfBlock) void loop_backward_kernel(
     double en[RL];
 #pragma unroll
     for (int k = 0; k < RL; ++k) en[k] = ls[k] + c[k];
-    const double ev = word_lse<RL, SP>(cbuf, mbuf, en, ok, wk, lane, W);  // E_t(w) on lane w
+    const double ev = x_segment_lse<RL, SP>(cbuf, mbuf, en, ok, wk, lane, W);  // E_t(w) on lane w
     if (lane < W) {
       xbuf[lane] = ev;
       if (entry_post) entry_post[(beg + t) * W + lane] = exp_unit((nprev + ev) - ll);
@@ -524,50 +462,24 @@ struct LfArgs {
   bool backward;
 };
 
-// as many wavefronts per workgroup as the LDS holds next to tab and lm, at most four (connected_embed.hip
-// launch_backward): the exponentials take W * (W | 1) doubles per wavefront, 33 KB at W = 64
-inline int lf_waves(int W, int SP, int RL, size_t *lds) {
-  const size_t shared = lf_shared_doubles(W, SP, RL) * sizeof(double);
-  const size_t per_wave = lf_wave_doubles(W, RL) * sizeof(double);
-  int waves = kLfMaxWaves;
-  while (waves > 1 && shared + waves * per_wave > static_cast<size_t>(kLfLdsMax)) --waves;
-  *lds = shared + waves * per_wave;
-  return waves;
-}
-
+// the exponentials take W * (W | 1) doubles per wavefront, 33 KB at W = 64: three wavefronts per workgroup there
 template <int RL, int SP>
 int launch_loop(const LfArgs &a, hipStream_t stream) {
   size_t lds = 0;
-  const int waves = lf_waves(a.W, SP, RL, &lds);
-  if (lds > static_cast<size_t>(kLfLdsMax))
+  const int waves =
+      x_waves(lf_shared_doubles(a.W, SP, RL) * sizeof(double), lf_wave_doubles(a.W, RL) * sizeof(double), &lds);
+  if (lds > static_cast<size_t>(kXLdsMax))
     return fail(SAPR_ERR_UNSUPPORTED, "the word-loop kernels need %zu bytes of LDS, the device offers %d", lds,
-                kLfLdsMax);
+                kXLdsMax);
   const int64_t blocks = (a.n_utts + waves - 1) / waves;
-  const auto fwd = loop_forward_kernel<RL, SP>;
-  const auto bwd = loop_backward_kernel<RL, SP>;
-  if (lds > 64 * 1024)  // per launch, not once: the attribute belongs to the current device's copy of the kernel
-    SAPR_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(fwd), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     static_cast<int>(lds)));
-  SAPR_LAUNCH(fwd, dim3(static_cast<unsigned>(blocks)), dim3(waves * kWave), lds, stream, a.logb, a.offsets, a.n_utts,
-              a.total_frames, a.log_start, a.log_trans, a.log_exit, a.lm, a.lm_start, a.lm_end, a.W, a.S, a.alpha, a.N,
-              a.loglik);
-  SAPR_HIP_TRY(hipGetLastError());
+  if (int rc = x_launch(loop_forward_kernel<RL, SP>, blocks, waves * kWave, lds, stream, a.logb, a.offsets, a.n_utts,
+                        a.total_frames, a.log_start, a.log_trans, a.log_exit, a.lm, a.lm_start, a.lm_end, a.W, a.S,
+                        a.alpha, a.N, a.loglik))
+    return rc;
   if (!a.backward) return 0;
-  if (lds > 64 * 1024)
-    SAPR_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bwd), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     static_cast<int>(lds)));
-  SAPR_LAUNCH(bwd, dim3(static_cast<unsigned>(blocks)), dim3(waves * kWave), lds, stream, a.logb, a.offsets, a.n_utts,
-              a.total_frames, a.log_start, a.log_trans, a.log_exit, a.lm, a.lm_end, a.W, a.S, a.alpha, a.N, a.loglik,
-              a.word_post, a.entry_post, a.post);
-  SAPR_HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-template <int SP>
-int launch_loop_rl(int R, const LfArgs &a, hipStream_t stream) {
-  if (R <= kWave) return launch_loop<1, SP>(a, stream);
-  if (R <= 2 * kWave) return launch_loop<2, SP>(a, stream);
-  return launch_loop<4, SP>(a, stream);
+  return x_launch(loop_backward_kernel<RL, SP>, blocks, waves * kWave, lds, stream, a.logb, a.offsets, a.n_utts,
+                  a.total_frames, a.log_start, a.log_trans, a.log_exit, a.lm, a.lm_end, a.W, a.S, a.alpha, a.N,
+                  a.loglik, a.word_post, a.entry_post, a.post);
 }
 
 }  // namespace
@@ -579,11 +491,11 @@ extern "C" int sapr_connected_posteriors_workspace_bytes(int64_t total_frames, i
                                                          size_t *bytes) {
   SAPR_REQUIRE(bytes && total_frames >= 0 && n_utts >= 0 && W > 0 && S > 0,
                "bad sizes (total_frames=%lld n_utts=%lld W=%d S=%d)", (long long)total_frames, (long long)n_utts, W, S);
-  if (int rc = lf_check_shape(W, S)) return rc;
+  if (int rc = x_check_shape(W, S)) return rc;
   const size_t R = static_cast<size_t>(W) * sp_of(S);
   // alpha [total_frames][R] and N [total_frames][W], float64, each padded to 16
-  *bytes = lf_align16(static_cast<size_t>(total_frames) * R * sizeof(double)) +
-           lf_align16(static_cast<size_t>(total_frames) * static_cast<size_t>(W) * sizeof(double));
+  *bytes = x_align16(static_cast<size_t>(total_frames) * R * sizeof(double)) +
+           x_align16(static_cast<size_t>(total_frames) * static_cast<size_t>(W) * sizeof(double));
   return 0;
 }
 
@@ -595,7 +507,7 @@ extern "C" int sapr_connected_posteriors(const double *logb, const int64_t *offs
                                          double *post, void *stream) {
   SAPR_REQUIRE(n_utts >= 0 && total_frames >= 0 && W > 0 && S > 0,
                "bad sizes (n_utts=%lld total_frames=%lld W=%d S=%d)", (long long)n_utts, (long long)total_frames, W, S);
-  if (int rc = lf_check_shape(W, S)) return rc;
+  if (int rc = x_check_shape(W, S)) return rc;
   SAPR_REQUIRE(lm && lm_start && lm_end, "NULL language model (lm, lm_start, lm_end)");
   size_t need = 0;
   if (int rc = sapr_connected_posteriors_workspace_bytes(total_frames, n_utts, W, S, &need)) return rc;
@@ -622,14 +534,14 @@ extern "C" int sapr_connected_posteriors(const double *logb, const int64_t *offs
   a.S = S;
   a.alpha = static_cast<double *>(workspace);
   a.N = reinterpret_cast<double *>(static_cast<uint8_t *>(workspace) +
-                                   lf_align16(static_cast<size_t>(total_frames) * R * sizeof(double)));
+                                   x_align16(static_cast<size_t>(total_frames) * R * sizeof(double)));
   a.loglik = loglik;
   a.word_post = word_post;
   a.entry_post = entry_post;
   a.post = post;
   a.backward = word_post || entry_post || post;
   hipStream_t st = as_stream(stream);
-  if (SP == 4) return launch_loop_rl<4>(R, a, st);
-  if (SP == 10) return launch_loop_rl<10>(R, a, st);
-  return launch_loop_rl<18>(R, a, st);
+  return x_dispatch(SP, R, [&](auto rl, auto sp) {
+    return launch_loop<decltype(rl)::value, decltype(sp)::value>(a, st);
+  });
 }

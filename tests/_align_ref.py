@@ -130,7 +130,10 @@ def brute(logb, words, ls, lt, lx, pen):
 
 
 # ---- the recursion test's generator (tests/test_align_gpu.py; tests/test_align_cpu.py checks its condition) --------
-RECURSION_SHAPES = [(3, 4, 64), (11, 10, 5), (11, 18, 5), (14, 18, 14), (5, 7, 25), (2, 1, 64)]   # (W, S, max_words)
+# (W, S, max_words); RL follows max_words * SP.  The second row: (RL, SP) = (1, 4), (2, 4), (2, 10), (1, 18) — with the
+# first row's (4, 4), (1, 10), (2, 18), (4, 18), (4, 10), all nine
+RECURSION_SHAPES = [(3, 4, 64), (11, 10, 5), (11, 18, 5), (14, 18, 14), (5, 7, 25), (2, 1, 64),
+                    (3, 4, 10), (3, 4, 20), (4, 10, 9), (3, 12, 3)]
 RECURSION_LENGTHS = [3, 64, 1, 300, 0, 65, 2, 63, 40, 129]
 TOPOLOGIES = ("bidiag", "skip", "dense")
 EXITS = ("last", "any")

@@ -14,7 +14,8 @@ from tests import _connected_ref as ref
 pytestmark = pytest.mark.gpu
 
 NEG = -np.inf
-SHAPES = [(3, 4), (11, 10), (11, 18), (14, 18), (64, 4), (5, 7), (2, 1)]
+SHAPES = [(3, 4), (11, 10), (11, 18), (14, 18), (64, 4), (5, 7), (2, 1),
+          (3, 12), (17, 3), (4, 11)]   # RL = 1, 2, 2 at SP = 18, 4, 18: shapes the lists of the sibling decoders share
 LENGTHS = [3, 64, 1, 300, 0, 65, 2, 63]   # mixed within one batch, an empty utterance in the middle
 
 

@@ -19,7 +19,8 @@ NEG = -np.inf
 FIELDS = ("score", "n_words", "path_word", "path_state", "path_entry")
 # (tests/test_bigram_gpu.py) RL = 1; RL = 2 (word 6 straddles lanes 63 / 64); RL = 4, R = 252 twice; R = 250; R = 256
 # and the largest lm; padded
-SHAPES = [(3, 4), (11, 10), (11, 18), (14, 18), (25, 10), (64, 4), (5, 7), (2, 1)]
+SHAPES = [(3, 4), (11, 10), (11, 18), (14, 18), (25, 10), (64, 4), (5, 7), (2, 1),
+          (3, 12), (17, 3), (4, 11)]                # (RL, SP) = (1, 18), (2, 4), (2, 18): with the rest, all nine
 LENGTHS = [3, 40, 1, 65, 0, 17, 2, 64, 33]          # 9 utterances: not a multiple of the 4 a workgroup serves
 MORE_LEVELS = {(11, 10): (1, 2, 3, 5), (11, 18): (1, 2, 3, 5)}  # every LT instantiation, and an L below its LT
 

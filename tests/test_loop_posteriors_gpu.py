@@ -20,7 +20,8 @@ NEG = -np.inf
 RTOL_LL = 1e-11
 TOL = 1e-9
 # RL = 1; RL = 2 (word 6 straddles lanes 63 / 64); RL = 4, R = 252 twice; R = 250; R = 256 and the largest lm; padded
-SHAPES = [(3, 4), (11, 10), (11, 18), (14, 18), (25, 10), (64, 4), (5, 7), (2, 1)]
+SHAPES = [(3, 4), (11, 10), (11, 18), (14, 18), (25, 10), (64, 4), (5, 7), (2, 1),
+          (3, 12), (17, 3), (4, 11)]                # (RL, SP) = (1, 18), (2, 4), (2, 18): with the rest, all nine
 LENGTHS = [3, 40, 1, 65, 0, 17, 2, 64, 33]          # 9 utterances: not a multiple of the 4 (3) a workgroup serves
 LONG = [LENGTHS.index(T) for T in (33, 40, 64, 65)]
 FIELDS = ("loglik", "word_post", "entry_post", "post")
