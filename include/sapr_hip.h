@@ -803,6 +803,77 @@ int sapr_connected_embed_gmm(const double *logb, const float *feats /* [total_fr
                              double *loglik /* [n_utts] */, double *stats /* [W][width] or NULL */,
                              double *post /* [total_frames][max_words*SP] or NULL */, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Optional transcript slots in the two chain units: `optional` [total_words] uint8, laid out like words,
+ * marks slots the path may walk through or step over — `sil? w1 sil? w2 ... wK sil?` is silence nobody wrote down.  No
+ * two neighbouring slots are optional and at least one slot is mandatory, so a slot has at most two predecessor slots;
+ * far(k) holds for k >= 2 with opt_{k-1} = 1: slot k may be entered from slot k - 2.  The definition is the CPU
+ * restatement tests/_optional_ref.py.  Alignment, in the notation of sapr_connected_align:
+ *     delta_0(0,j) = log_start[w_0][j] + b_0(0,j)
+ *     delta_0(1,j) = log_start[w_1][j] + b_0(1,j)   where opt_0 = 1 and K > 1;   every other slot -inf
+ *     enter(k)     = X_{t-1}(k-1);  where far(k) and X_{t-1}(k-2) is STRICTLY greater: X_{t-1}(k-2), a "skip entry"
+ *     entry        = (enter(k) + word_penalty) + log_start[w_k][j]        (k = 0: -inf)
+ *     delta_t(k,j) = max(within, entry) + b_t(k,j)                        entry only where strictly greater
+ *     score        = X_{T-1}(K-1);  where opt_{K-1} = 1, K >= 2 and X_{T-1}(K-2) is STRICTLY greater: X_{T-1}(K-2), and
+ *                    the path ends in slot K-2
+ * The nearer slot wins every tie; word_penalty is paid for every slot entered, optional or not, and never for a slot
+ * stepped over; the back-trace steps two slots back over a skip entry and word_start[k] = -1 for a slot the path
+ * stepped over.  Forward-backward is the same chain with lse in place of max, in the notation of sapr_connected_embed:
+ *     alpha_0                  the two start slots above
+ *     alpha_t(k,j) entry term  (lse(X_{t-1}(k-1), X_{t-1}(k-2) where far(k)) + word_penalty) + log_start[w_k][j]
+ *     loglik                   lse(X_{T-1}(K-1), X_{T-1}(K-2) where opt_{K-1} = 1 and K >= 2)
+ *     beta_{T-1}(k,s)          log_exit for k = K-1, and for k = K-2 where opt_{K-1} = 1;   else -inf
+ *     beta_t(k,i) exit term    log_exit[w_k][i] + lse(E_{t+1}(k+1), E_{t+1}(k+2) where far(k+2))
+ *     start[k]                 sum_t exp((lse(X_{t-1}(k-1), X_{t-1}(k-2) where far(k)) + word_penalty) + log_start
+ *                              + b_t + beta_t - loglik), plus gamma_0 of the start slots
+ * gamma, trans, post, the observation sums, the second moments and the mixture responsibilities are per slot exactly
+ * as without flags; nobs counts the slots of utterances with a path, whether or not mass went through them.
+ *   optional      [total_words] uint8 (0 / 1), between word_offsets and total_words in the argument list; NULL means
+ *                 all zero, and the call then IS the entry point without _opt: the same launches, the same bytes
+ *   workspace     sapr_connected_align_opt_workspace_bytes: what sapr_connected_align takes, then one byte per
+ *                 utterance (the slot its path ends in), rounded up to 16; with optional == NULL the size of
+ *                 sapr_connected_align_workspace_bytes is enough.  The three embed entry points keep their size
+ *                 functions: their workspaces do not grow
+ * Every other argument, output, check and error code is that of the entry point without _opt.  An utterance whose
+ * flags break the two rules, or hold a byte other than 0 / 1, has no path (-inf, rows of -1, exact zeros in the
+ * statistics) and nothing else in the batch changes.  max_words counts optional slots too. */
+int sapr_connected_align_opt_workspace_bytes(int64_t total_frames, int64_t n_utts, int32_t max_words, int32_t S,
+                                             size_t *bytes);
+int sapr_connected_align_opt(const double *logb, const int64_t *offsets, int64_t n_utts, int64_t total_frames,
+                             const int32_t *words /* [total_words] */, const int64_t *word_offsets /* [n_utts + 1] */,
+                             const uint8_t *optional /* [total_words] or NULL */, int64_t total_words,
+                             int32_t max_words, const double *log_start, const double *log_trans,
+                             const double *log_exit, double word_penalty, int32_t W, int32_t S, void *workspace,
+                             size_t workspace_bytes, double *score, int32_t *path_word /* may be NULL */,
+                             int32_t *path_state /* may be NULL */, uint8_t *path_entry /* may be NULL */,
+                             int32_t *word_start /* [total_words], may be NULL */, void *stream);
+int sapr_connected_embed_opt(const double *logb, const float *feats /* [total_frames][D]; NULL iff D == 0 */,
+                             int32_t D, const int64_t *offsets, int64_t n_utts, int64_t total_frames,
+                             const int32_t *words, const int64_t *word_offsets,
+                             const uint8_t *optional /* [total_words] or NULL */, int64_t total_words,
+                             int32_t max_words, const double *log_start, const double *log_trans,
+                             const double *log_exit, double word_penalty, int32_t W, int32_t S, void *workspace,
+                             size_t workspace_bytes, double *loglik /* [n_utts] */,
+                             double *stats /* [W][width] or NULL */,
+                             double *post /* [total_frames][max_words*SP] or NULL */, void *stream);
+int sapr_connected_embed_full_opt(const double *logb, const float *feats /* [total_frames][D] */, int32_t D,
+                                  const int64_t *offsets, int64_t n_utts, int64_t total_frames, const int32_t *words,
+                                  const int64_t *word_offsets, const uint8_t *optional /* [total_words] or NULL */,
+                                  int64_t total_words, int32_t max_words, const double *log_start,
+                                  const double *log_trans, const double *log_exit, double word_penalty, int32_t W,
+                                  int32_t S, void *workspace, size_t workspace_bytes, double *loglik /* [n_utts] */,
+                                  double *stats /* [W][width] or NULL */,
+                                  double *post /* [total_frames][max_words*SP] or NULL */, void *stream);
+int sapr_connected_embed_gmm_opt(const double *logb, const float *feats /* [total_frames][D] */, int32_t D,
+                                 const double *pack /* [W][sapr_gmm_pack_layout(S, M, D)] */, int32_t M,
+                                 const int64_t *offsets, int64_t n_utts, int64_t total_frames, const int32_t *words,
+                                 const int64_t *word_offsets, const uint8_t *optional /* [total_words] or NULL */,
+                                 int64_t total_words, int32_t max_words, const double *log_start,
+                                 const double *log_trans, const double *log_exit, double word_penalty, int32_t W,
+                                 int32_t S, void *workspace, size_t workspace_bytes, double *loglik /* [n_utts] */,
+                                 double *stats /* [W][width] or NULL */,
+                                 double *post /* [total_frames][max_words*SP] or NULL */, void *stream);
+
 /* Flat start of HMMLearnModel (hmmlearn_hmm.py:83-94: np.mean / np.var over axis 0 of the concatenated float32
  * features): numpy adds row after row in float32, so each column is one sequential float32 chain — reproduced
  * bit for bit.  center == NULL: out[d] = sum_r x[r][d]; else out[d] = sum_r RN32(RN32(x[r][d] - center[d])^2).

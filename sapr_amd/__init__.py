@@ -31,7 +31,8 @@ def __getattr__(name):
     ``sapr_amd.embedded_fit`` / ``sapr_amd.embed_full_stats_width`` / ``sapr_amd.embed_full_workspace_bytes`` /
     ``sapr_amd.embed_gmm_stats_width`` / ``sapr_amd.embed_gmm_workspace_bytes`` / ``sapr_amd.ConnectedPosteriors`` /
     ``sapr_amd.connected_posteriors`` / ``sapr_amd.posteriors_workspace_bytes`` / ``sapr_amd.LevelResult`` /
-    ``sapr_amd.connected_levels`` / ``sapr_amd.levels_workspace_bytes``
+    ``sapr_amd.connected_levels`` / ``sapr_amd.levels_workspace_bytes`` / ``sapr_amd.with_optional`` /
+    ``sapr_amd.align_opt_workspace_bytes``
     (resolved on first use: importing the package stays light)."""
     if name in ("GMMHMM", "fit_gmm_models", "vocab_scores"):
         from . import gmm_hmm
@@ -40,7 +41,8 @@ def __getattr__(name):
                 "AlignResult", "align_viterbi", "connected_align", "EmbeddedStats", "embedded_forward_backward", "embedded_estep",
                 "embedded_fit", "embed_full_stats_width", "embed_full_workspace_bytes", "embed_gmm_stats_width",
                 "embed_gmm_workspace_bytes", "ConnectedPosteriors", "connected_posteriors",
-                "posteriors_workspace_bytes", "LevelResult", "connected_levels", "levels_workspace_bytes"):
+                "posteriors_workspace_bytes", "LevelResult", "connected_levels", "levels_workspace_bytes",
+                "with_optional", "align_opt_workspace_bytes"):
         from . import connected
         return getattr(connected, name)
     if name == "full_vocab_scores":

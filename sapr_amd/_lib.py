@@ -131,6 +131,22 @@ SIGNATURES = {
                                          c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_double,
                                          c_int32, c_int32, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
                                          c_void_p]),
+    # optional transcript slots: the entry point without _opt with `optional` between word_offsets and total_words
+    "sapr_connected_align_opt_workspace_bytes": (c_int, [c_int64, c_int64, c_int32, c_int32, C.POINTER(c_size_t)]),
+    "sapr_connected_align_opt": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                         c_int32, c_void_p, c_void_p, c_void_p, c_double, c_int32, c_int32, c_void_p,
+                                         c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sapr_connected_embed_opt": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
+                                         c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_double, c_int32,
+                                         c_int32, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sapr_connected_embed_full_opt": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_void_p,
+                                              c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p,
+                                              c_double, c_int32, c_int32, c_void_p, c_size_t, c_void_p, c_void_p,
+                                              c_void_p, c_void_p]),
+    "sapr_connected_embed_gmm_opt": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64,
+                                             c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
+                                             c_void_p, c_void_p, c_double, c_int32, c_int32, c_void_p, c_size_t,
+                                             c_void_p, c_void_p, c_void_p, c_void_p]),
     "sapr_colsum_f32":(c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     "sapr_custom_estep": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32] + [c_void_p] * 5
                           + [c_int64] + [c_void_p] * 6 + [c_void_p]),

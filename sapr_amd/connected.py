@@ -799,16 +799,25 @@ class AlignResult:
     word_offsets: np.ndarray  # [N + 1] i64: transcript k of utterance u is entry word_offsets[u] + k
     offsets: np.ndarray       # [N + 1] i64
     words: np.ndarray         # [total_words] i32: the transcripts, one after the other
+    optional: np.ndarray = None  # [total_words] u8: 1 where the slot could be stepped over; None: no flags were given
 
     def segments(self, u):
-        """``[(word_index, start, end_exclusive), ...]`` of utterance ``u``: one entry per transcript word, frames
-        counted from the utterance's own start; ``[]`` where there is no path."""
+        """``[(word_index, start, end_exclusive), ...]`` of utterance ``u``: one entry per transcript slot the path
+        took (every slot, unless optional slots were given: a slot the path stepped over has ``word_start`` -1 and no
+        entry), frames counted from the utterance's own start; a slot ends where the next taken slot begins.  ``[]``
+        where there is no path."""
         lo, hi = int(self.word_offsets[u]), int(self.word_offsets[u + 1])
-        if hi == lo or int(self.word_start[lo]) < 0:
+        if self.optional is None:
+            if hi == lo or int(self.word_start[lo]) < 0:
+                return []
+            starts = [int(a) for a in self.word_start[lo:hi]]
+            ends = starts[1:] + [int(self.offsets[u + 1] - self.offsets[u])]
+            return [(int(w), a, b) for w, a, b in zip(self.words[lo:hi], starts, ends)]
+        taken = [(int(w), int(a)) for w, a in zip(self.words[lo:hi], self.word_start[lo:hi]) if int(a) >= 0]
+        if not taken or not np.isfinite(self.score[u]):
             return []
-        starts = [int(a) for a in self.word_start[lo:hi]]
-        ends = starts[1:] + [int(self.offsets[u + 1] - self.offsets[u])]
-        return [(int(w), a, b) for w, a, b in zip(self.words[lo:hi], starts, ends)]
+        ends = [a for _, a in taken[1:]] + [int(self.offsets[u + 1] - self.offsets[u])]
+        return [(w, a, b) for (w, a), b in zip(taken, ends)]
 
     def word_examples(self, features):
         """Cut the utterances at the word boundaries: ``features`` are the frame-major ``(T, D)`` arrays that were
@@ -827,8 +836,53 @@ class AlignResult:
         return out
 
 
-def _transcripts(transcripts, n_utts, network):
-    """Validated transcripts -> ``(words[total_words] i32, word_offsets[N + 1] i64, max_words)``."""
+def with_optional(transcripts, word):
+    """``(transcripts', optional')`` with vocabulary index ``word`` as an optional slot in front of, between and behind
+    the words of every transcript: ``word? w1 word? w2 ... wK word?`` — silence nobody wrote down, a filler the speaker
+    may have said.  Where a transcript already names ``word`` no second one is put beside it."""
+    word = int(word)
+    out_t, out_o = [], []
+    for t in transcripts:
+        t = [int(w) for w in t]
+        nt, no = [], []
+        for k, w in enumerate(t):
+            if w != word and (k == 0 or t[k - 1] != word):
+                nt.append(word)
+                no.append(1)
+            nt.append(w)
+            no.append(0)
+        if t and t[-1] != word:
+            nt.append(word)
+            no.append(1)
+        out_t.append(nt)
+        out_o.append(no)
+    return out_t, out_o
+
+
+def _optional(optional, transcripts):
+    """Validated flags -> ``optional[total_words] u8`` (``None`` stays ``None``: the kernels without flags)."""
+    if optional is None:
+        return None
+    optional = [np.asarray(o).reshape(-1) for o in optional]
+    if len(optional) != len(transcripts):
+        raise ValueError(f"{len(optional)} optional-flag sequences for {len(transcripts)} transcripts")
+    for u, (o, t) in enumerate(zip(optional, transcripts)):
+        if o.size != t.size:
+            raise ValueError(f"utterance {u} has {o.size} optional flags for {t.size} transcript slots")
+        if not np.isin(o, (0, 1)).all():
+            raise ValueError(f"the optional flags of utterance {u} must be 0 or 1")
+        o = o.astype(bool)
+        if (o[1:] & o[:-1]).any():
+            raise ValueError(f"utterance {u} has two neighbouring optional slots: at most one slot in a row may be "
+                             f"stepped over")
+        if o.all():
+            raise ValueError(f"every slot of utterance {u} is optional: at least one slot must be mandatory")
+    return (np.concatenate(optional).astype(np.uint8) if optional else np.zeros(0, np.uint8))
+
+
+def _transcripts(transcripts, n_utts, network, optional=None):
+    """Validated transcripts -> ``(words[total_words] i32, word_offsets[N + 1] i64, max_words)``, and with
+    ``optional`` given a fourth entry, the validated flags ``[total_words] u8``."""
     transcripts = [np.asarray(t, dtype=np.int64).reshape(-1) for t in transcripts]
     if len(transcripts) != n_utts:
         raise ValueError(f"{len(transcripts)} transcripts for {n_utts} utterances")
@@ -843,11 +897,49 @@ def _transcripts(transcripts, n_utts, network):
                              f"exceeds the limit of {MAX_FLAT} chain positions ({limit} words at SP = {network.SP})")
     _, word_offs = _offsets([t.size for t in transcripts])
     words = np.concatenate(transcripts).astype(np.int32) if transcripts else np.zeros(0, np.int32)
-    return words, word_offs, max((t.size for t in transcripts), default=1)
+    max_words = max((t.size for t in transcripts), default=1)
+    if optional is None:
+        return words, word_offs, max_words
+    return words, word_offs, max_words, _optional(optional, transcripts)
 
 
-def _run_align(logb, offs_dev, offs, transcripts, network) -> AlignResult:
-    """One ``sapr_connected_align`` over device ``logb[total_frames, R]``."""
+def align_opt_workspace_bytes(total_frames, n_utts, max_words, S) -> int:
+    return _workspace_bytes("sapr_connected_align_opt_workspace_bytes", total_frames, n_utts, max_words, S)
+
+
+def _run_align_opt(logb, offs_dev, offs, transcripts, network, optional) -> AlignResult:
+    """One ``sapr_connected_align_opt`` over device ``logb[total_frames, R]``."""
+    torch = _torch()
+    dev = logb.device
+    n_utts, total = int(offs.size - 1), int(offs[-1])
+    words, word_offs, max_words, flags = _transcripts(transcripts, n_utts, network, optional)
+    total_words = int(word_offs[-1])
+    ls, lt, lx, _ = network.device(dev)
+    words_dev = torch.from_numpy(words).to(dev)
+    word_offs_dev = torch.from_numpy(word_offs).to(dev)
+    flags_dev = torch.from_numpy(flags).to(dev)
+    ws_bytes = align_opt_workspace_bytes(total, n_utts, max_words, network.S)
+    workspace = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    score = torch.empty(n_utts, dtype=torch.float64, device=dev)
+    path_word = torch.empty(total, dtype=torch.int32, device=dev)
+    path_state = torch.empty(total, dtype=torch.int32, device=dev)
+    path_entry = torch.empty(total, dtype=torch.uint8, device=dev)
+    word_start = torch.empty(total_words, dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().sapr_connected_align_opt(
+        _lib.ptr(logb), _lib.ptr(offs_dev), n_utts, total, _lib.ptr(words_dev), _lib.ptr(word_offs_dev),
+        _lib.ptr(flags_dev), total_words, max_words, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx), network.word_penalty,
+        network.W, network.S, _lib.ptr(workspace), ws_bytes, _lib.ptr(score), _lib.ptr(path_word),
+        _lib.ptr(path_state), _lib.ptr(path_entry), _lib.ptr(word_start), _lib.current_stream()),
+        "sapr_connected_align_opt")
+    host = [a.copy() for a in _lib.to_host(score, path_word, path_state, path_entry, word_start)]
+    return AlignResult(*host, word_offsets=word_offs, offsets=offs, words=words, optional=flags)
+
+
+def _run_align(logb, offs_dev, offs, transcripts, network, optional=None) -> AlignResult:
+    """One ``sapr_connected_align`` over device ``logb[total_frames, R]`` (``optional``: one
+    ``sapr_connected_align_opt``)."""
+    if optional is not None:
+        return _run_align_opt(logb, offs_dev, offs, transcripts, network, optional)
     torch = _torch()
     dev = logb.device
     n_utts, total = int(offs.size - 1), int(offs[-1])
@@ -872,26 +964,30 @@ def _run_align(logb, offs_dev, offs, transcripts, network) -> AlignResult:
     return AlignResult(*host, word_offsets=word_offs, offsets=offs, words=words)
 
 
-def align_viterbi(logb, lengths, transcripts, network: ConnectedNetwork) -> AlignResult:
+def align_viterbi(logb, lengths, transcripts, network: ConnectedNetwork, optional=None) -> AlignResult:
     """Forced alignment over a given ``logb`` (the shapes :func:`connected_viterbi` takes): ``transcripts`` is one
-    sequence of vocabulary indices per utterance, the words the utterance is known to hold, in order."""
+    sequence of vocabulary indices per utterance, the words the utterance is known to hold, in order.  ``optional``:
+    one 0/1 sequence per utterance, as long as its transcript — a slot marked 1 may be walked through or stepped over
+    (no two neighbours, not every slot; :func:`with_optional` builds ``sil? w1 sil? ... wK sil?``).  The definition is
+    ``tests/_optional_ref.py``; a stepped-over slot has ``word_start`` -1 and no entry in ``segments``."""
     torch = _torch()
     lengths, offs = _offsets(lengths)
-    _transcripts(transcripts, int(lengths.size), network)  # (refused before a device is asked for)
+    _transcripts(transcripts, int(lengths.size), network, optional)  # (refused before a device is asked for)
     dev = _lib.require_gpu()
     logb = _flat_logb(logb, int(offs[-1]), network, dev)
-    return _run_align(logb, torch.from_numpy(offs).to(dev), offs, transcripts, network)
+    return _run_align(logb, torch.from_numpy(offs).to(dev), offs, transcripts, network, optional)
 
 
-def connected_align(batch_or_feature_list, transcripts, network: ConnectedNetwork) -> AlignResult:
+def connected_align(batch_or_feature_list, transcripts, network: ConnectedNetwork, optional=None) -> AlignResult:
     """Emission (by the network's family) and the alignment recursion: a ``trellis.FeatureBatch`` or a list of
-    frame-major ``(T, D)`` feature arrays, with one transcript of vocabulary indices per utterance."""
+    frame-major ``(T, D)`` feature arrays, with one transcript of vocabulary indices per utterance (and ``optional``
+    as :func:`align_viterbi` takes it)."""
     b = batch_or_feature_list
     n_utts = len(b.lengths) if hasattr(b, "offsets") and hasattr(b, "order") else len(b)
-    _transcripts(transcripts, n_utts, network)  # (refused before a device is asked for)
+    _transcripts(transcripts, n_utts, network, optional)  # (refused before a device is asked for)
     feats, offs_dev, offs = _features(b)
     logb = _EMIT[network.family](feats, network)
-    return _run_align(logb, offs_dev, offs, transcripts, network)
+    return _run_align(logb, offs_dev, offs, transcripts, network, optional)
 
 
 # ---- embedded Baum-Welch --------------------------------------------------------------------------
@@ -969,8 +1065,17 @@ class EmbeddedStats:
         return self.post[lo:hi].reshape(hi - lo, -1, self.SP)[:, :K]
 
 
+def _flag_args(transcripts, n_utts, network, optional, dev):
+    """``(words, word_offsets, max_words, entry-point suffix, the extra pointer argument as a list, its tensor)``."""
+    if optional is None:
+        return (*_transcripts(transcripts, n_utts, network), "", [], None)
+    words, word_offs, max_words, flags = _transcripts(transcripts, n_utts, network, optional)
+    flags_dev = _torch().from_numpy(flags).to(dev)
+    return words, word_offs, max_words, "_opt", [_lib.ptr(flags_dev)], flags_dev
+
+
 def _run_embed(logb, feats, offs_dev, offs, transcripts, network, want_stats, want_post,
-               second_moments=False, mixtures=False) -> EmbeddedStats:
+               second_moments=False, mixtures=False, optional=None) -> EmbeddedStats:
     """One ``sapr_connected_embed`` over device ``logb[total_frames, R]`` (and device ``feats`` or ``None``);
     ``second_moments``: one ``sapr_connected_embed_full`` instead, whose rows carry ``obs*obs.T``; ``mixtures``: one
     ``sapr_connected_embed_gmm``, whose rows carry the statistics per mixture component."""
@@ -978,14 +1083,14 @@ def _run_embed(logb, feats, offs_dev, offs, transcripts, network, want_stats, wa
     if mixtures and want_stats:
         if feats is None or int(feats.shape[1]) == 0:
             raise ValueError("the mixture statistics need the frames: feats [total_frames, D] with D >= 1")
-        return _run_embed_gmm(logb, feats, offs_dev, offs, transcripts, network, want_post)
+        return _run_embed_gmm(logb, feats, offs_dev, offs, transcripts, network, want_post, optional)
     if second_moments and want_stats:
         if feats is None or int(feats.shape[1]) == 0:
             raise ValueError("the second moments need the frames: feats [total_frames, D] with D >= 1")
-        return _run_embed_full(logb, feats, offs_dev, offs, transcripts, network, want_post)
+        return _run_embed_full(logb, feats, offs_dev, offs, transcripts, network, want_post, optional)
     dev = logb.device
     n_utts, total = int(offs.size - 1), int(offs[-1])
-    words, word_offs, max_words = _transcripts(transcripts, n_utts, network)
+    words, word_offs, max_words, sfx, flag, _keep = _flag_args(transcripts, n_utts, network, optional, dev)
     total_words = int(word_offs[-1])
     D = 0 if feats is None else int(feats.shape[1])
     ls, lt, lx, _ = network.device(dev)
@@ -997,22 +1102,22 @@ def _run_embed(logb, feats, offs_dev, offs, transcripts, network, want_stats, wa
     stats = torch.empty((network.W, embed_stats_width(network.S, D)), dtype=torch.float64, device=dev) \
         if want_stats else None
     post = torch.zeros((total, max_words * network.SP), dtype=torch.float64, device=dev) if want_post else None
-    _lib.check(_lib.load().sapr_connected_embed(
+    _lib.check(getattr(_lib.load(), "sapr_connected_embed" + sfx)(
         _lib.ptr(logb), _lib.ptr(feats), D, _lib.ptr(offs_dev), n_utts, total, _lib.ptr(words_dev),
-        _lib.ptr(word_offs_dev), total_words, max_words, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx),
+        _lib.ptr(word_offs_dev), *flag, total_words, max_words, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx),
         network.word_penalty, network.W, network.S, _lib.ptr(workspace), ws_bytes, _lib.ptr(loglik), _lib.ptr(stats),
-        _lib.ptr(post), _lib.current_stream()), "sapr_connected_embed")
+        _lib.ptr(post), _lib.current_stream()), "sapr_connected_embed" + sfx)
     host = [None if a is None else a.cpu().numpy() for a in (loglik, stats, post)]
     return EmbeddedStats(*host, offsets=offs, word_offsets=word_offs, words=words, S=network.S, SP=network.SP, D=D,
                          n_states=tuple(network.n_states))
 
 
-def _run_embed_full(logb, feats, offs_dev, offs, transcripts, network, want_post) -> EmbeddedStats:
+def _run_embed_full(logb, feats, offs_dev, offs, transcripts, network, want_post, optional=None) -> EmbeddedStats:
     """One ``sapr_connected_embed_full`` over device ``logb[total_frames, R]`` and device ``feats``."""
     torch = _torch()
     dev = logb.device
     n_utts, total = int(offs.size - 1), int(offs[-1])
-    words, word_offs, max_words = _transcripts(transcripts, n_utts, network)
+    words, word_offs, max_words, sfx, flag, _keep = _flag_args(transcripts, n_utts, network, optional, dev)
     total_words = int(word_offs[-1])
     D = int(feats.shape[1])
     ls, lt, lx, _ = network.device(dev)
@@ -1023,23 +1128,23 @@ def _run_embed_full(logb, feats, offs_dev, offs, transcripts, network, want_post
     loglik = torch.empty(n_utts, dtype=torch.float64, device=dev)
     stats = torch.empty((network.W, embed_full_stats_width(network.S, D)), dtype=torch.float64, device=dev)
     post = torch.zeros((total, max_words * network.SP), dtype=torch.float64, device=dev) if want_post else None
-    _lib.check(_lib.load().sapr_connected_embed_full(
+    _lib.check(getattr(_lib.load(), "sapr_connected_embed_full" + sfx)(
         _lib.ptr(logb), _lib.ptr(feats), D, _lib.ptr(offs_dev), n_utts, total, _lib.ptr(words_dev),
-        _lib.ptr(word_offs_dev), total_words, max_words, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx),
+        _lib.ptr(word_offs_dev), *flag, total_words, max_words, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx),
         network.word_penalty, network.W, network.S, _lib.ptr(workspace), ws_bytes, _lib.ptr(loglik), _lib.ptr(stats),
-        _lib.ptr(post), _lib.current_stream()), "sapr_connected_embed_full")
+        _lib.ptr(post), _lib.current_stream()), "sapr_connected_embed_full" + sfx)
     host = [None if a is None else a.cpu().numpy() for a in (loglik, stats, post)]
     return EmbeddedStats(*host, offsets=offs, word_offsets=word_offs, words=words, S=network.S, SP=network.SP, D=D,
                          n_states=tuple(network.n_states), layout="full")
 
 
-def _run_embed_gmm(logb, feats, offs_dev, offs, transcripts, network, want_post) -> EmbeddedStats:
+def _run_embed_gmm(logb, feats, offs_dev, offs, transcripts, network, want_post, optional=None) -> EmbeddedStats:
     """One ``sapr_connected_embed_gmm`` over device ``logb[total_frames, R]``, device ``feats`` and the network's
     ``GmmPack`` as the emission read it."""
     torch = _torch()
     dev = logb.device
     n_utts, total = int(offs.size - 1), int(offs[-1])
-    words, word_offs, max_words = _transcripts(transcripts, n_utts, network)
+    words, word_offs, max_words, sfx, flag, _keep = _flag_args(transcripts, n_utts, network, optional, dev)
     total_words = int(word_offs[-1])
     D, M = int(feats.shape[1]), int(network.pack.M)
     if D != network.D:
@@ -1052,11 +1157,11 @@ def _run_embed_gmm(logb, feats, offs_dev, offs, transcripts, network, want_post)
     loglik = torch.empty(n_utts, dtype=torch.float64, device=dev)
     stats = torch.empty((network.W, embed_gmm_stats_width(network.S, M, D)), dtype=torch.float64, device=dev)
     post = torch.zeros((total, max_words * network.SP), dtype=torch.float64, device=dev) if want_post else None
-    _lib.check(_lib.load().sapr_connected_embed_gmm(
+    _lib.check(getattr(_lib.load(), "sapr_connected_embed_gmm" + sfx)(
         _lib.ptr(logb), _lib.ptr(feats), D, _lib.ptr(pack), M, _lib.ptr(offs_dev), n_utts, total, _lib.ptr(words_dev),
-        _lib.ptr(word_offs_dev), total_words, max_words, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx),
+        _lib.ptr(word_offs_dev), *flag, total_words, max_words, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx),
         network.word_penalty, network.W, network.S, _lib.ptr(workspace), ws_bytes, _lib.ptr(loglik), _lib.ptr(stats),
-        _lib.ptr(post), _lib.current_stream()), "sapr_connected_embed_gmm")
+        _lib.ptr(post), _lib.current_stream()), "sapr_connected_embed_gmm" + sfx)
     host = [None if a is None else a.cpu().numpy() for a in (loglik, stats, post)]
     return EmbeddedStats(*host, offsets=offs, word_offsets=word_offs, words=words, S=network.S, SP=network.SP, D=D,
                          n_states=tuple(network.n_states), layout="gmm", M=M)
@@ -1086,7 +1191,7 @@ def _refuse_stats(network, second_moments=False, mixtures=False):
 
 
 def embedded_forward_backward(logb, lengths, transcripts, network: ConnectedNetwork, feats=None,
-                              want_post=False, second_moments=False, mixtures=False) -> EmbeddedStats:
+                              want_post=False, second_moments=False, mixtures=False, optional=None) -> EmbeddedStats:
     """Forward-backward over every utterance's transcript chain on a given ``logb`` (the shapes
     :func:`connected_viterbi` takes) — the counterpart of :func:`align_viterbi`.  ``feats``: the float32 frames
     ``[total_frames, D]`` (host array or device tensor) for the ``obs`` blocks of the statistics; without them the
@@ -1094,10 +1199,11 @@ def embedded_forward_backward(logb, lengths, transcripts, network: ConnectedNetw
     ``second_moments=True`` (needs ``feats``): the rows carry ``obs*obs.T`` in place of ``obs**2``
     (``sapr_connected_embed_full``; definition ``tests/_embedded_full_ref.py``).  ``mixtures=True`` (needs ``feats``
     and a "gmm" network, whose ``GmmPack`` supplies the components): the rows carry ``post_mix`` and the per-component
-    ``obs`` / ``obs**2`` (``sapr_connected_embed_gmm``; definition ``tests/_embedded_gmm_ref.py``)."""
+    ``obs`` / ``obs**2`` (``sapr_connected_embed_gmm``; definition ``tests/_embedded_gmm_ref.py``).  ``optional``: the
+    flags :func:`align_viterbi` takes — the ``_opt`` entry points; definition ``tests/_optional_ref.py``."""
     torch = _torch()
     lengths, offs = _offsets(lengths)
-    _transcripts(transcripts, int(lengths.size), network)  # (refused before a device is asked for)
+    _transcripts(transcripts, int(lengths.size), network, optional)  # (refused before a device is asked for)
     if mixtures:
         _refuse_stats(network, second_moments, mixtures)
         if network.pack is None or not hasattr(network.pack, "M"):
@@ -1117,11 +1223,11 @@ def embedded_forward_backward(logb, lengths, transcripts, network: ConnectedNetw
         if int(feats.shape[1]) == 0:
             feats = None
     return _run_embed(logb, feats, torch.from_numpy(offs).to(dev), offs, transcripts, network, True, want_post,
-                      second_moments, mixtures)
+                      second_moments, mixtures, optional)
 
 
 def embedded_estep(batch_or_feature_list, transcripts, network: ConnectedNetwork, want_post=False,
-                   want_stats=True, second_moments=False, mixtures=False) -> EmbeddedStats:
+                   want_stats=True, second_moments=False, mixtures=False, optional=None) -> EmbeddedStats:
     """Emission (by the network's family) and forward-backward over the transcript chains — the counterpart of
     :func:`connected_align`.  ``loglik`` and ``post`` are served for all three families; the statistics for "diag"
     by default (for "gmm" and "full" asking for them without their switch raises ``NotImplementedError``).  With
@@ -1129,16 +1235,16 @@ def embedded_estep(batch_or_feature_list, transcripts, network: ConnectedNetwork
     (``sapr_connected_embed_full``), what the M-step of a "full" or "tied" model reads.  With ``mixtures=True`` the
     statistics of a "gmm" network carry ``post_mix`` and the per-component ``obs`` / ``obs**2``
     (``sapr_connected_embed_gmm``), what ``gmm_hmm.gmm_m_step`` reads; on another family, or together with
-    ``second_moments=True``, the switch is a ``ValueError``."""
+    ``second_moments=True``, the switch is a ``ValueError``.  ``optional``: the flags :func:`align_viterbi` takes."""
     b = batch_or_feature_list
     n_utts = len(b.lengths) if hasattr(b, "offsets") and hasattr(b, "order") else len(b)
-    _transcripts(transcripts, n_utts, network)  # (refused before a device is asked for)
+    _transcripts(transcripts, n_utts, network, optional)  # (refused before a device is asked for)
     if want_stats or mixtures:
         _refuse_stats(network, second_moments, mixtures)
     feats, offs_dev, offs = _features(b)
     logb = _EMIT[network.family](feats, network)
     return _run_embed(logb, feats if want_stats else None, offs_dev, offs, transcripts, network, want_stats, want_post,
-                      second_moments, mixtures)
+                      second_moments, mixtures, optional)
 
 
 def _diag_of_moments(st, covariance_type):
@@ -1151,7 +1257,7 @@ def _diag_of_moments(st, covariance_type):
     return st
 
 
-def _embedded_fit_gmm(models, features, transcripts, n_iter, tol, exit_states, word_penalty, names):
+def _embedded_fit_gmm(models, features, transcripts, n_iter, tol, exit_states, word_penalty, names, optional=None):
     """:func:`embedded_fit` over ``GMMHMM`` word models."""
     from .gmm_hmm import gmm_m_step
     from .hmmlearn_hmm import ConvergenceMonitor
@@ -1162,12 +1268,13 @@ def _embedded_fit_gmm(models, features, transcripts, n_iter, tol, exit_states, w
         return ConnectedNetwork.from_models([copy.copy(m) for m in models], exit_states, word_penalty, names, "gmmhmm")
 
     net = network()
-    _transcripts(transcripts, len(features), net)  # (refused before a device is asked for)
+    _transcripts(transcripts, len(features), net, optional)  # (refused before a device is asked for)
     feats, offs_dev, offs = _features(features)
     monitor = ConvergenceMonitor(tol, n_iter)
     for _ in range(n_iter):
         net = network()
-        res = _run_embed(emit_gmm(feats, net), feats, offs_dev, offs, transcripts, net, True, False, mixtures=True)
+        res = _run_embed(emit_gmm(feats, net), feats, offs_dev, offs, transcripts, net, True, False, mixtures=True,
+                         optional=optional)
         for w, m in enumerate(models):
             st = res.split(w)
             if st["nobs"] == 0:
@@ -1183,7 +1290,7 @@ def _embedded_fit_gmm(models, features, transcripts, n_iter, tol, exit_states, w
 
 
 def embedded_fit(models, features, transcripts, n_iter=10, tol=1e-2, exit_states="last", word_penalty=0.0,
-                 names=None, second_moments=False):
+                 names=None, second_moments=False, optional=None):
     """Embedded Baum-Welch: train the word models of a ``GaussianHMM`` vocabulary in place from recordings of several
     words (``features``: frame-major ``(T, D)`` arrays) and their transcripts (vocabulary indices), without cutting
     the recordings.  Each iteration: ``ConnectedNetwork.from_models``, the emission, the E-step, then
@@ -1199,14 +1306,19 @@ def embedded_fit(models, features, transcripts, n_iter=10, tol=1e-2, exit_states
     A list of ``GMMHMM`` objects (that share ``n_mix`` and the feature width) trains through
     ``sapr_connected_embed_gmm``: per iteration the network over the vocabulary's ``GmmPack``, ``emit_gmm``, the E-step
     with mixture responsibilities, then ``gmm_hmm.gmm_m_step`` per model with the model's own hyper-parameters.  A
-    list that mixes ``GMMHMM`` and ``GaussianHMM`` objects is a ``ValueError``."""
+    list that mixes ``GMMHMM`` and ``GaussianHMM`` objects is a ``ValueError``.
+
+    ``optional``: the flags :func:`align_viterbi` takes, e.g. ``embedded_fit(models, features,
+    *with_optional(transcripts, sil))`` — a skippable silence model between the words, trained with them; every
+    family goes through its ``_opt`` entry point."""
     from .hmmlearn_hmm import ConvergenceMonitor, m_step_typed
     models = list(models)
     if vocabulary_family(models, names, None) == "gmm":
         if second_moments:
             raise ValueError("second_moments=True serves GaussianHMM vocabularies; GMMHMM word models train on "
                              "mixture responsibilities")
-        return _embedded_fit_gmm(models, features, transcripts, n_iter, tol, exit_states, word_penalty, names)
+        return _embedded_fit_gmm(models, features, transcripts, n_iter, tol, exit_states, word_penalty, names,
+                                 optional)
     family = vocabulary_family(models, names, "hmmlearn")
     if family != "diag" and not second_moments:
         raise ValueError("embedded_fit serves 'diag' and 'spherical' GaussianHMM vocabularies by default: a 'full' or "
@@ -1218,13 +1330,13 @@ def embedded_fit(models, features, transcripts, n_iter=10, tol=1e-2, exit_states
                                             exit_states, word_penalty, names, "hmmlearn")
 
     net = network()
-    _transcripts(transcripts, len(features), net)  # (refused before a device is asked for)
+    _transcripts(transcripts, len(features), net, optional)  # (refused before a device is asked for)
     feats, offs_dev, offs = _features(features)
     monitor = ConvergenceMonitor(tol, n_iter)
     for _ in range(n_iter):
         net = network()
         res = _run_embed(_EMIT[net.family](feats, net), feats, offs_dev, offs, transcripts, net, True, False,
-                         second_moments)
+                         second_moments, optional=optional)
         for w, m in enumerate(models):
             st = res.split(w)
             if second_moments:

@@ -92,13 +92,25 @@ inline EmWorkspace em_carve(void *base, int64_t total_frames, int64_t total_word
   return w;
 }
 
-template <int RL, int SP>
+// OPT (both recursion kernels): optional[] marks transcript slots that may be stepped over.  bit q of
+// `om` = slot q is optional; far = the slot may be entered from slot q - 2; the coupling rows get a second leading
+// -inf so that no index is conditional.  Flags that are not 0 / 1, two optional neighbours or no mandatory slot: no
+// path.  The OPT = false instantiations are the kernels as they were.
+__device__ __forceinline__ bool em_flags(const uint8_t *__restrict__ optional, int64_t wbeg, int K, int lane,
+                                         uint64_t *om) {
+  const int o = lane < K ? optional[wbeg + lane] : 0;
+  *om = __ballot(o == 1);
+  const uint64_t all = K >= kWave ? ~0ull : (1ull << K) - 1;
+  return !(__ballot(o > 1) || (*om & (*om >> 1)) || *om == all);
+}
+
+template <int RL, int SP, bool OPT>
 __global__ __launch_bounds__(kXBlock) void embed_forward_kernel(
     const double *__restrict__ logb, const int64_t *__restrict__ offsets, int64_t n_utts, int64_t total_frames,
     const int32_t *__restrict__ words, const int64_t *__restrict__ word_offsets, int64_t total_words, int32_t max_words,
     const double *__restrict__ log_start, const double *__restrict__ log_trans, const double *__restrict__ log_exit,
     double word_penalty, int32_t W, int32_t S, double *__restrict__ alpha_ws, double *__restrict__ x_ws,
-    double *__restrict__ loglik) {
+    double *__restrict__ loglik, const uint8_t *__restrict__ optional) {
   constexpr int PP = kWave * RL;
   extern __shared__ double smem[];
   double *tab = smem;
@@ -119,6 +131,9 @@ __global__ __launch_bounds__(kXBlock) void embed_forward_kernel(
     const int w = lane < K ? words[ut.wbeg + lane] : 0;
     if (__ballot(w < 0 || w >= W)) path = false;
   }
+  [[maybe_unused]] uint64_t om = 0;
+  if constexpr (OPT)
+    if (!em_flags(optional, ut.wbeg, K, lane, &om)) path = false;
   if (!path) {
     if (lane == 0) loglik[u] = neg_inf();
     return;
@@ -134,6 +149,7 @@ __global__ __launch_bounds__(kXBlock) void embed_forward_kernel(
   double ls[RL], lx[RL], alpha[RL], bn[RL];
   int sk[RL], qk[RL], col[RL], tb[RL];
   bool ok[RL], real[RL];
+  [[maybe_unused]] bool far[RL], first[RL];
   bool bad = tab_nan || word_penalty != word_penalty;
 #pragma unroll
   for (int k = 0; k < RL; ++k) {
@@ -143,6 +159,10 @@ __global__ __launch_bounds__(kXBlock) void embed_forward_kernel(
     const int w = ok[k] ? words[ut.wbeg + q] : 0;  // (checked above: 0 .. W - 1)
     sk[k] = s;
     qk[k] = ok[k] ? q : 0;
+    if constexpr (OPT) {
+      far[k] = ok[k] && q >= 2 && ((om >> (q - 1)) & 1ull);
+      first[k] = qk[k] == 0 || (qk[k] == 1 && (om & 1ull));  // the start slots (qk = 1 only where K > 1)
+    }
     col[k] = w * SP + s;
     tb[k] = w * (SP * SP) + s;
     real[k] = ok[k] && s < S;
@@ -156,6 +176,8 @@ __global__ __launch_bounds__(kXBlock) void embed_forward_kernel(
 #pragma unroll
   for (int k = 0; k < RL; ++k) bn[k] = ok[k] ? brow[col[k]] : neg_inf();
   if (lane == 0) xbuf[0] = neg_inf();
+  if constexpr (OPT)  // [q + 2] = X(q): slot q reads [q + 1] (near) and [q] (far)
+    if (lane == 0) xbuf[1] = neg_inf();
 
   double xv = neg_inf();  // lane q: X(q) of the frame just finished
   for (int64_t t = 0; t < T; ++t) {
@@ -169,13 +191,21 @@ __global__ __launch_bounds__(kXBlock) void embed_forward_kernel(
     }
     double v[RL];
     if (t == 0) {
+      if constexpr (OPT) {
 #pragma unroll
-      for (int k = 0; k < RL; ++k) v[k] = qk[k] == 0 ? ls[k] : neg_inf();
+        for (int k = 0; k < RL; ++k) v[k] = first[k] ? ls[k] : neg_inf();
+      } else {
+#pragma unroll
+        for (int k = 0; k < RL; ++k) v[k] = qk[k] == 0 ? ls[k] : neg_inf();
+      }
     } else {
       double xe[RL];  // X_{t-1} of the slot before the lane's own (-inf in front of slot 0)
 #pragma unroll
       for (int k = 0; k < RL; ++k) {
-        xe[k] = xbuf[qk[k]];
+        if constexpr (OPT)  // ... joined with that of the slot two before it where the one between is optional
+          xe[k] = lse2(xbuf[qk[k] + 1], far[k] ? xbuf[qk[k]] : neg_inf());
+        else
+          xe[k] = xbuf[qk[k]];
         v[k] = neg_inf();
       }
 #pragma unroll 1
@@ -213,23 +243,31 @@ __global__ __launch_bounds__(kXBlock) void embed_forward_kernel(
     }
     xv = x_segment_lse<RL, SP>(cbuf, mbuf, ex, ok, qk, lane, K);  // the log-sum-exp over the slot's states
     if (lane < K) {
-      xbuf[lane + 1] = xv;
+      xbuf[lane + (OPT ? 2 : 1)] = xv;
       x_ws[(beg + t) * max_words + lane] = xv;
     }
     wave_lds_sync();
   }
   const bool any_bad = __ballot(bad) != 0;
-  if (lane == K - 1) loglik[u] = any_bad ? __builtin_nan("") : xv;
+  if constexpr (OPT) {  // an optional last slot: the chain may also end in the slot before it
+    const double before = __shfl(xv, (lane - 1) & (kWave - 1), kWave);
+    if (lane == K - 1) {
+      const bool two = K >= 2 && ((om >> (K - 1)) & 1ull);
+      loglik[u] = any_bad ? __builtin_nan("") : lse2(xv, two ? before : neg_inf());
+    }
+  } else {
+    if (lane == K - 1) loglik[u] = any_bad ? __builtin_nan("") : xv;
+  }
 }
 
-template <int RL, int SP>
+template <int RL, int SP, bool OPT>
 __global__ __launch_bounds__(kXBlock) void embed_backward_kernel(
     const double *__restrict__ logb, const int64_t *__restrict__ offsets, int64_t n_utts, int64_t total_frames,
     const int32_t *__restrict__ words, const int64_t *__restrict__ word_offsets, int64_t total_words, int32_t max_words,
     const double *__restrict__ log_start, const double *__restrict__ log_trans, const double *__restrict__ log_exit,
     double word_penalty, int32_t W, int32_t S, int32_t part_width, double *__restrict__ alpha_ws,
     const double *__restrict__ x_ws, const double *__restrict__ loglik, double *__restrict__ part,
-    uint8_t *__restrict__ slot_ok, double *__restrict__ post) {
+    uint8_t *__restrict__ slot_ok, double *__restrict__ post, const uint8_t *__restrict__ optional) {
   constexpr int PP = kWave * RL;
   constexpr int kPerWave = PP + kEmRows + SP * PP;  // cbuf, ebuf, mbuf, the transition accumulators [SP][PP]
   extern __shared__ double smem[];
@@ -257,6 +295,9 @@ __global__ __launch_bounds__(kXBlock) void embed_backward_kernel(
     const int w = lane < K ? words[ut.wbeg + lane] : 0;
     if (__ballot(w < 0 || w >= W)) path = false;
   }
+  [[maybe_unused]] uint64_t om = 0;
+  if constexpr (OPT)
+    if (!em_flags(optional, ut.wbeg, K, lane, &om)) path = false;  // (their likelihood is -inf: not reached)
   if (!path) {  // zero posterior rows; the slots stay uncounted
     if (post)
       for (int64_t t = 0; t < T; ++t)
@@ -273,6 +314,7 @@ __global__ __launch_bounds__(kXBlock) void embed_backward_kernel(
   double ls[RL], lx[RL], beta[RL], acur[RL], bcur[RL], gsum[RL], sacc[RL];
   int sk[RL], qk[RL], col[RL], tb[RL];
   bool ok[RL], real[RL];
+  [[maybe_unused]] bool far[RL], first[RL], over[RL];  // OPT: over = slot q + 2 may be entered from this one
 #pragma unroll
   for (int k = 0; k < RL; ++k) {
     const int p = k * kWave + lane;
@@ -286,7 +328,15 @@ __global__ __launch_bounds__(kXBlock) void embed_backward_kernel(
     real[k] = ok[k] && s < S;  // (a padded state carries nothing, whatever its column of logb holds)
     ls[k] = real[k] ? log_start[w * S + s] : neg_inf();
     lx[k] = real[k] ? log_exit[w * S + s] : neg_inf();
-    beta[k] = (ok[k] && q == K - 1) ? lx[k] : neg_inf();
+    if constexpr (OPT) {
+      far[k] = ok[k] && q >= 2 && ((om >> (q - 1)) & 1ull);
+      first[k] = ok[k] && (q == 0 || (q == 1 && (om & 1ull)));
+      over[k] = ok[k] && q + 2 < K && ((om >> (q + 1)) & 1ull);
+      const bool last = q == K - 1 || (q == K - 2 && ((om >> (K - 1)) & 1ull));  // the slots the chain may end in
+      beta[k] = (ok[k] && last) ? lx[k] : neg_inf();
+    } else {
+      beta[k] = (ok[k] && q == K - 1) ? lx[k] : neg_inf();
+    }
     gsum[k] = 0.0;
     sacc[k] = 0.0;
 #pragma unroll 1
@@ -317,7 +367,12 @@ __global__ __launch_bounds__(kXBlock) void embed_backward_kernel(
     }
     if (t == 0) {
 #pragma unroll
-      for (int k = 0; k < RL; ++k) sacc[k] += (ok[k] && qk[k] == 0) ? g[k] : 0.0;
+      for (int k = 0; k < RL; ++k) {
+        if constexpr (OPT)
+          sacc[k] += first[k] ? g[k] : 0.0;
+        else
+          sacc[k] += (ok[k] && qk[k] == 0) ? g[k] : 0.0;
+      }
       break;
     }
     double ap[RL], bn[RL], xe[RL];
@@ -326,6 +381,7 @@ __global__ __launch_bounds__(kXBlock) void embed_backward_kernel(
       ap[k] = ok[k] ? abase[(t - 1) * MP + k * kWave + lane] : neg_inf();
       bn[k] = real[k] ? brow[(t - 1) * R + col[k]] : neg_inf();
       xe[k] = (ok[k] && qk[k] > 0) ? xbase[(t - 1) * max_words + qk[k] - 1] : neg_inf();
+      if constexpr (OPT) xe[k] = lse2(xe[k], far[k] ? xbase[(t - 1) * max_words + qk[k] - 2] : neg_inf());
     }
     // the entry share of slot q >= 1 at frame t, and E_t(q) through the coupling row
     double en[RL];
@@ -341,7 +397,12 @@ __global__ __launch_bounds__(kXBlock) void embed_backward_kernel(
     wave_lds_sync();
     double nb[RL];
 #pragma unroll
-    for (int k = 0; k < RL; ++k) nb[k] = lx[k] + ebuf[qk[k] + 1];  // (ebuf[K] stays -inf: nothing follows the last slot)
+    for (int k = 0; k < RL; ++k) {
+      if constexpr (OPT)  // (ebuf[K], ebuf[K + 1] stay -inf)
+        nb[k] = lx[k] + lse2(ebuf[qk[k] + 1], over[k] ? ebuf[qk[k] + 2] : neg_inf());
+      else
+        nb[k] = lx[k] + ebuf[qk[k] + 1];  // (ebuf[K] stays -inf: nothing follows the last slot)
+    }
 #pragma unroll 1
     for (int d = SP - 1; d > -SP; --d) {
       if (!((dmask >> (d + SP - 1)) & 1ull)) continue;  // (uniform)
@@ -495,19 +556,21 @@ struct EmArgs {
   const double *log_start, *log_trans, *log_exit;
   double word_penalty;
   int32_t W, S;
+  const uint8_t *optional;  // [total_words] or NULL: the OPT = false kernels
 };
 
 // the forward kernel, then (backward) the backward kernel with as many wavefronts per workgroup as the LDS holds next
 // to the vocabulary's table: its transition accumulators take SP * 64 * RL doubles per wavefront (36 KB at SP = 18,
 // RL = 4)
-template <int RL, int SP>
+template <int RL, int SP, bool OPT>
 int launch_recursions(const EmArgs &a, const EmWorkspace &ws, int32_t part_width, double *loglik, double *post,
                       bool backward, hipStream_t stream) {
   const size_t tab = static_cast<size_t>(a.W) * SP * SP * sizeof(double);
-  if (int rc = x_launch(embed_forward_kernel<RL, SP>, (a.n_utts + kXWaves - 1) / kXWaves, kXBlock,
+  if (int rc = x_launch(embed_forward_kernel<RL, SP, OPT>, (a.n_utts + kXWaves - 1) / kXWaves, kXBlock,
                         tab + static_cast<size_t>(kXWaves) * (kWave * RL + kEmRows) * sizeof(double), stream, a.logb,
                         a.offsets, a.n_utts, a.total_frames, a.words, a.word_offsets, a.total_words, a.max_words,
-                        a.log_start, a.log_trans, a.log_exit, a.word_penalty, a.W, a.S, ws.alpha, ws.X, loglik))
+                        a.log_start, a.log_trans, a.log_exit, a.word_penalty, a.W, a.S, ws.alpha, ws.X, loglik,
+                        a.optional))
     return rc;
   if (!backward) return 0;
   size_t lds = 0;
@@ -515,10 +578,10 @@ int launch_recursions(const EmArgs &a, const EmWorkspace &ws, int32_t part_width
   if (lds > static_cast<size_t>(kXLdsMax))
     return fail(SAPR_ERR_UNSUPPORTED, "the backward kernel needs %zu bytes of LDS, the device offers %d", lds,
                 kXLdsMax);
-  return x_launch(embed_backward_kernel<RL, SP>, (a.n_utts + waves - 1) / waves, waves * kWave, lds, stream, a.logb,
+  return x_launch(embed_backward_kernel<RL, SP, OPT>, (a.n_utts + waves - 1) / waves, waves * kWave, lds, stream, a.logb,
                   a.offsets, a.n_utts, a.total_frames, a.words, a.word_offsets, a.total_words, a.max_words, a.log_start,
                   a.log_trans, a.log_exit, a.word_penalty, a.W, a.S, part_width, ws.alpha, ws.X, loglik, ws.part,
-                  ws.slot_ok, post);
+                  ws.slot_ok, post, a.optional);
 }
 
 // ---- second moments over the chain posteriors (sapr_connected_embed_full) ----------------------------------------
@@ -915,12 +978,13 @@ extern "C" int sapr_connected_embed_workspace_bytes(int64_t total_frames, int64_
   return 0;
 }
 
-extern "C" int sapr_connected_embed(const double *logb, const float *feats, int32_t D, const int64_t *offsets,
-                                    int64_t n_utts, int64_t total_frames, const int32_t *words,
-                                    const int64_t *word_offsets, int64_t total_words, int32_t max_words,
-                                    const double *log_start, const double *log_trans, const double *log_exit,
-                                    double word_penalty, int32_t W, int32_t S, void *workspace, size_t workspace_bytes,
-                                    double *loglik, double *stats, double *post, void *stream) {
+extern "C" int sapr_connected_embed_opt(const double *logb, const float *feats, int32_t D, const int64_t *offsets,
+                                        int64_t n_utts, int64_t total_frames, const int32_t *words,
+                                        const int64_t *word_offsets, const uint8_t *optional, int64_t total_words,
+                                        int32_t max_words, const double *log_start, const double *log_trans,
+                                        const double *log_exit, double word_penalty, int32_t W, int32_t S,
+                                        void *workspace, size_t workspace_bytes, double *loglik, double *stats,
+                                        double *post, void *stream) {
   SAPR_REQUIRE(n_utts >= 0 && total_frames >= 0 && total_words >= 0 && max_words > 0 && W > 0 && S > 0 && D >= 0,
                "bad sizes (n_utts=%lld total_frames=%lld total_words=%lld max_words=%d W=%d S=%d D=%d)",
                (long long)n_utts, (long long)total_frames, (long long)total_words, max_words, W, S, D);
@@ -943,11 +1007,13 @@ extern "C" int sapr_connected_embed(const double *logb, const float *feats, int3
   const int32_t part_width = static_cast<int32_t>(em_part_width(SP, D));
   hipStream_t st = as_stream(stream);
   const EmArgs a{logb, offsets, n_utts, total_frames, words, word_offsets, total_words, max_words,
-                 log_start, log_trans, log_exit, word_penalty, W, S};
+                 log_start, log_trans, log_exit, word_penalty, W, S, optional};
   const bool backward = stats || post;
   if (backward && total_words > 0) SAPR_HIP_TRY(hipMemsetAsync(ws.slot_ok, 0, static_cast<size_t>(total_words), st));
   const int rc = x_dispatch(SP, max_words * SP, [&](auto rl, auto sp) {
-    return launch_recursions<decltype(rl)::value, decltype(sp)::value>(a, ws, part_width, loglik, post, backward, st);
+    constexpr int RL = decltype(rl)::value, SPc = decltype(sp)::value;
+    return optional ? launch_recursions<RL, SPc, true>(a, ws, part_width, loglik, post, backward, st)
+                    : launch_recursions<RL, SPc, false>(a, ws, part_width, loglik, post, backward, st);
   });
   if (rc || !stats) return rc;
   if (D > 0 && total_frames > 0) {
@@ -967,6 +1033,17 @@ extern "C" int sapr_connected_embed(const double *logb, const float *feats, int3
               width, stats);
   SAPR_HIP_TRY(hipGetLastError());
   return 0;
+}
+
+extern "C" int sapr_connected_embed(const double *logb, const float *feats, int32_t D, const int64_t *offsets,
+                                    int64_t n_utts, int64_t total_frames, const int32_t *words,
+                                    const int64_t *word_offsets, int64_t total_words, int32_t max_words,
+                                    const double *log_start, const double *log_trans, const double *log_exit,
+                                    double word_penalty, int32_t W, int32_t S, void *workspace, size_t workspace_bytes,
+                                    double *loglik, double *stats, double *post, void *stream) {
+  return sapr_connected_embed_opt(logb, feats, D, offsets, n_utts, total_frames, words, word_offsets, nullptr,
+                                  total_words, max_words, log_start, log_trans, log_exit, word_penalty, W, S, workspace,
+                                  workspace_bytes, loglik, stats, post, stream);
 }
 
 extern "C" int sapr_connected_embed_full_stats_width(int32_t S, int32_t D, int32_t *width) {
@@ -990,13 +1067,14 @@ extern "C" int sapr_connected_embed_full_workspace_bytes(int64_t total_frames, i
   return 0;
 }
 
-extern "C" int sapr_connected_embed_full(const double *logb, const float *feats, int32_t D, const int64_t *offsets,
-                                         int64_t n_utts, int64_t total_frames, const int32_t *words,
-                                         const int64_t *word_offsets, int64_t total_words, int32_t max_words,
-                                         const double *log_start, const double *log_trans, const double *log_exit,
-                                         double word_penalty, int32_t W, int32_t S, void *workspace,
-                                         size_t workspace_bytes, double *loglik, double *stats, double *post,
-                                         void *stream) {
+extern "C" int sapr_connected_embed_full_opt(const double *logb, const float *feats, int32_t D,
+                                             const int64_t *offsets, int64_t n_utts, int64_t total_frames,
+                                             const int32_t *words, const int64_t *word_offsets,
+                                             const uint8_t *optional, int64_t total_words, int32_t max_words,
+                                             const double *log_start, const double *log_trans, const double *log_exit,
+                                             double word_penalty, int32_t W, int32_t S, void *workspace,
+                                             size_t workspace_bytes, double *loglik, double *stats, double *post,
+                                             void *stream) {
   SAPR_REQUIRE(n_utts >= 0 && total_frames >= 0 && total_words >= 0 && max_words > 0 && W > 0 && S > 0 && D >= 0,
                "bad sizes (n_utts=%lld total_frames=%lld total_words=%lld max_words=%d W=%d S=%d D=%d)",
                (long long)n_utts, (long long)total_frames, (long long)total_words, max_words, W, S, D);
@@ -1013,9 +1091,9 @@ extern "C" int sapr_connected_embed_full(const double *logb, const float *feats,
       em_full_carve(workspace, total_frames, n_utts, total_words, max_words, W, S, em_full_p(S, D));
   // the recursions, loglik, post and the head of the row: sapr_connected_embed itself on the front of the workspace,
   // without features (the head does not depend on them); gamma stays behind in the workspace
-  if (int rc = sapr_connected_embed(logb, nullptr, 0, offsets, n_utts, total_frames, words, word_offsets, total_words,
-                                    max_words, log_start, log_trans, log_exit, word_penalty, W, S, workspace,
-                                    ws.base_bytes, loglik, stats ? ws.head : nullptr, post, stream))
+  if (int rc = sapr_connected_embed_opt(logb, nullptr, 0, offsets, n_utts, total_frames, words, word_offsets, optional,
+                                        total_words, max_words, log_start, log_trans, log_exit, word_penalty, W, S,
+                                        workspace, ws.base_bytes, loglik, stats ? ws.head : nullptr, post, stream))
     return rc;
   if (n_utts == 0 || !stats) return 0;
   hipStream_t st = as_stream(stream);
@@ -1041,6 +1119,18 @@ extern "C" int sapr_connected_embed_full(const double *logb, const float *feats,
   return 0;
 }
 
+extern "C" int sapr_connected_embed_full(const double *logb, const float *feats, int32_t D, const int64_t *offsets,
+                                         int64_t n_utts, int64_t total_frames, const int32_t *words,
+                                         const int64_t *word_offsets, int64_t total_words, int32_t max_words,
+                                         const double *log_start, const double *log_trans, const double *log_exit,
+                                         double word_penalty, int32_t W, int32_t S, void *workspace,
+                                         size_t workspace_bytes, double *loglik, double *stats, double *post,
+                                         void *stream) {
+  return sapr_connected_embed_full_opt(logb, feats, D, offsets, n_utts, total_frames, words, word_offsets, nullptr,
+                                       total_words, max_words, log_start, log_trans, log_exit, word_penalty, W, S,
+                                       workspace, workspace_bytes, loglik, stats, post, stream);
+}
+
 extern "C" int sapr_connected_embed_gmm_stats_width(int32_t S, int32_t M, int32_t D, int32_t *width) {
   SAPR_REQUIRE(width && S > 0 && M > 0 && D > 0, "bad sizes (S=%d M=%d D=%d)", S, M, D);
   if (int rc = em_check_shape(1, S, 1)) return rc;
@@ -1064,13 +1154,14 @@ extern "C" int sapr_connected_embed_gmm_workspace_bytes(int64_t total_frames, in
   return 0;
 }
 
-extern "C" int sapr_connected_embed_gmm(const double *logb, const float *feats, int32_t D, const double *pack,
-                                        int32_t M, const int64_t *offsets, int64_t n_utts, int64_t total_frames,
-                                        const int32_t *words, const int64_t *word_offsets, int64_t total_words,
-                                        int32_t max_words, const double *log_start, const double *log_trans,
-                                        const double *log_exit, double word_penalty, int32_t W, int32_t S,
-                                        void *workspace, size_t workspace_bytes, double *loglik, double *stats,
-                                        double *post, void *stream) {
+extern "C" int sapr_connected_embed_gmm_opt(const double *logb, const float *feats, int32_t D, const double *pack,
+                                            int32_t M, const int64_t *offsets, int64_t n_utts, int64_t total_frames,
+                                            const int32_t *words, const int64_t *word_offsets,
+                                            const uint8_t *optional, int64_t total_words, int32_t max_words,
+                                            const double *log_start, const double *log_trans, const double *log_exit,
+                                            double word_penalty, int32_t W, int32_t S, void *workspace,
+                                            size_t workspace_bytes, double *loglik, double *stats, double *post,
+                                            void *stream) {
   SAPR_REQUIRE(n_utts >= 0 && total_frames >= 0 && total_words >= 0 && max_words > 0 && W > 0 && S > 0 && M > 0 &&
                    D >= 0,
                "bad sizes (n_utts=%lld total_frames=%lld total_words=%lld max_words=%d W=%d S=%d M=%d D=%d)",
@@ -1091,9 +1182,9 @@ extern "C" int sapr_connected_embed_gmm(const double *logb, const float *feats, 
   const EmFullWorkspace ws = em_full_carve(workspace, total_frames, n_utts, total_words, max_words, W, S, P);
   // as sapr_connected_embed_full: the recursions, loglik, post and the head of the row are sapr_connected_embed itself
   // on the front of the workspace, without features; gamma stays behind in the workspace
-  if (int rc = sapr_connected_embed(logb, nullptr, 0, offsets, n_utts, total_frames, words, word_offsets, total_words,
-                                    max_words, log_start, log_trans, log_exit, word_penalty, W, S, workspace,
-                                    ws.base_bytes, loglik, stats ? ws.head : nullptr, post, stream))
+  if (int rc = sapr_connected_embed_opt(logb, nullptr, 0, offsets, n_utts, total_frames, words, word_offsets, optional,
+                                        total_words, max_words, log_start, log_trans, log_exit, word_penalty, W, S,
+                                        workspace, ws.base_bytes, loglik, stats ? ws.head : nullptr, post, stream))
     return rc;
   if (n_utts == 0 || !stats) return 0;
   hipStream_t st = as_stream(stream);
@@ -1127,4 +1218,16 @@ extern "C" int sapr_connected_embed_gmm(const double *logb, const float *feats, 
               groups, W, hw, static_cast<int32_t>(P), stats);
   SAPR_HIP_TRY(hipGetLastError());
   return 0;
+}
+
+extern "C" int sapr_connected_embed_gmm(const double *logb, const float *feats, int32_t D, const double *pack,
+                                        int32_t M, const int64_t *offsets, int64_t n_utts, int64_t total_frames,
+                                        const int32_t *words, const int64_t *word_offsets, int64_t total_words,
+                                        int32_t max_words, const double *log_start, const double *log_trans,
+                                        const double *log_exit, double word_penalty, int32_t W, int32_t S,
+                                        void *workspace, size_t workspace_bytes, double *loglik, double *stats,
+                                        double *post, void *stream) {
+  return sapr_connected_embed_gmm_opt(logb, feats, D, pack, M, offsets, n_utts, total_frames, words, word_offsets,
+                                      nullptr, total_words, max_words, log_start, log_trans, log_exit, word_penalty, W,
+                                      S, workspace, workspace_bytes, loglik, stats, post, stream);
 }

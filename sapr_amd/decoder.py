@@ -210,8 +210,16 @@ class Decoder:
                                             names=words, implementation=self.implementation,
                                             pack=None if family == "diag" else self._vocab_pack(), bigram=bigram)
 
+    def _silence_index(self, optional_silence):
+        """The vocabulary index of the word that may stand, unwritten, around the words of a transcript."""
+        words = list(self.models)
+        if optional_silence not in words:
+            raise ValueError(f"optional_silence names {optional_silence!r}, which is not in the vocabulary "
+                             f"({', '.join(words)})")
+        return words.index(optional_silence)
+
     def align(self, feature_list: List[np.ndarray], transcripts, word_penalty: float = 0.0,
-              exit_states="last") -> List[Dict]:
+              exit_states="last", optional_silence=None) -> List[Dict]:
         """Forced alignment: the words of every recording are known (``transcripts``: one list of word names per
         utterance, in spoken order; a word may follow itself), where does each begin and end.  Viterbi over the chain
         of the transcript's word models (``sapr_amd.connected.connected_align``: the emission stage of the vocabulary's
@@ -219,6 +227,12 @@ class Decoder:
         utterance ``{"words": [...], "log_likelihood": float, "segments": [(word, start, end_exclusive), ...],
         "state_sequence": ndarray}`` with one segment per transcript word; an utterance its transcript cannot explain
         (too few frames, no path) has no words, no segments, ``-inf`` and states of -1.
+
+        ``optional_silence``: the name of a vocabulary word that may have been spoken, unwritten, before, between and
+        after the transcript's words (``sil? w1 sil? ... wK sil?``, ``connected.with_optional``; the path walks through
+        each of these slots or steps over it, and ``word_penalty`` is paid for the ones it walks through).  ``words``
+        is then still the caller's transcript, and ``segments`` gets one more entry under that word's name for every
+        pause the path took.
 
         Served for the implementations and families ``decode_connected`` serves.  A word that is not in the
         vocabulary is refused with a ``ValueError`` that names it."""
@@ -237,25 +251,32 @@ class Decoder:
                     raise ValueError(f"the transcript of utterance {u} names {name!r}, which is not in the vocabulary "
                                      f"({', '.join(words)})")
             rows.append([index[name] for name in names])
+        flags = None
+        if optional_silence is not None:
+            from .connected import with_optional
+            said = rows
+            rows, flags = with_optional(rows, self._silence_index(optional_silence))
         net = self._connected_network(exit_states, word_penalty)
-        res = connected_align([np.asarray(f).T for f in feature_list], rows, net)
+        res = connected_align([np.asarray(f).T for f in feature_list], rows, net, flags)
         out = []
         for u in range(len(feature_list)):
             segs = res.segments(u)
             lo, hi = int(res.offsets[u]), int(res.offsets[u + 1])
-            out.append({"words": [words[w] for w, _, _ in segs], "log_likelihood": float(res.score[u]),
+            spoken = [words[w] for w, _, _ in segs] if flags is None else [words[w] for w in said[u]] if segs else []
+            out.append({"words": spoken, "log_likelihood": float(res.score[u]),
                         "segments": [(words[w], a, b) for w, a, b in segs],
                         "state_sequence": res.path_state[lo:hi].astype(np.int64)})
         return out
 
     def train_embedded(self, feature_list: List[np.ndarray], transcripts, n_iter: int = 10, tol: float = 1e-2,
-                       word_penalty: float = 0.0, exit_states="last") -> List[float]:
+                       word_penalty: float = 0.0, exit_states="last", optional_silence=None) -> List[float]:
         """Embedded Baum-Welch over recordings of several words: the loaded word models are re-estimated IN PLACE from
         ``feature_list`` ((D, T) arrays as in ``align``) and ``transcripts`` (one list of word names per utterance, in
         spoken order), without cutting the recordings at word boundaries (``sapr_amd.connected.embedded_fit``:
         forward-backward over the chain of each transcript's word models, ``sapr_connected_embed``).  Returns the
         history of the summed log-likelihood, one entry per iteration.  A word that is in no transcript keeps its
-        parameters.
+        parameters.  ``optional_silence``: as in ``align`` — the named word's model is a skippable slot around every
+        transcript word and is trained with them on the pauses the recordings hold.
 
         Served for ``implementation="hmmlearn"``: "diag" / "spherical" vocabularies through ``sapr_connected_embed``,
         a vocabulary that holds a "full" or "tied" model through ``sapr_connected_embed_full`` (second-moment
@@ -279,9 +300,13 @@ class Decoder:
                     raise ValueError(f"the transcript of utterance {u} names {name!r}, which is not in the vocabulary "
                                      f"({', '.join(words)})")
             rows.append([index[name] for name in names])
+        flags = None
+        if optional_silence is not None:
+            from .connected import with_optional
+            rows, flags = with_optional(rows, self._silence_index(optional_silence))
         history = embedded_fit(self._model_list(), [np.asarray(f).T for f in feature_list], rows, n_iter=n_iter,
                                tol=tol, exit_states=exit_states, word_penalty=word_penalty, names=words,
-                               second_moments=self._is_full())
+                               second_moments=self._is_full(), optional=flags)
         self._pack = self._vocab = None  # (packed from the old parameters)
         return history
 
