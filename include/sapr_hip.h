@@ -648,6 +648,35 @@ int sapr_connected_posteriors(const double *logb, const int64_t *offsets, int64_
                               double *post /* [total_frames][R] or NULL */, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Denominator statistics of discriminative (MMI) training (csrc/connected_loop_stats.hip): the state posteriors
+ * post[total_frames][R = W * SP] of sapr_connected_posteriors reduced to per-word sufficient statistics.  The
+ * definition is the CPU restatement tests/_mmi_ref.py (den_stats); with r = w * SP + s, s < S, x_t the float32 frame
+ * and the sums over the frames t of the utterances u with utt_keep[u] != 0 (all of them where utt_keep is NULL):
+ *     post[w][s] = sum post_t(r)      obs[w][s] = sum post_t(r) x_t      obs2[w][s] = sum post_t(r) RN32(x_t x_t)
+ * in float64 (x_t x_t is the float32 square, widened: sapr_connected_embed's rule).  This is the product
+ * post^T [x | x^2 | 1], R rows by 2 D + 1 columns, on the float64 matrix cores.
+ *   stats      [W][sapr_connected_embed_stats_width(S, D)], the row of sapr_connected_embed:
+ *              {nobs, 0.0, start[S], trans[S][S], post[S], obs[S][D], obs2[S][D]}.  nobs = the number of kept
+ *              utterances with at least one frame, the same in every row; the reserved slot, start and trans are exact
+ *              zeros (transitions are not trained discriminatively); padded states have no place in a row
+ *   offsets    [n_utts + 1]; a range that leaves the batch is served as empty.  A frame outside every kept utterance's
+ *              range is never read, neither its row of post nor its features
+ *   workspace  sapr_connected_loop_stats_workspace_bytes:  a16(8 * parts * R * (2 D + 1))  bytes with
+ *              span = max(256, ceil(ceil(total_frames / 1024) / 128) * 128) frames, parts = ceil(total_frames / span):
+ *              one partial row per span of frames, added span ascending
+ * No atomics and a fixed order in every sum: the bytes are the same from run to run.
+ *
+ * Bad sizes (D < 1 among them), NULL required pointers and a workspace that is too small return SAPR_ERR_ARG, S > 18,
+ * W * SP > 256 or D > 39 SAPR_ERR_UNSUPPORTED (from the size function too), all before any launch; n_utts == 0 writes
+ * a zero stats and returns 0 after these checks. */
+int sapr_connected_loop_stats_workspace_bytes(int64_t total_frames, int64_t n_utts, int32_t W, int32_t S, int32_t D,
+                                              size_t *bytes);
+int sapr_connected_loop_stats(const double *post /* [total_frames][W*SP] */, const float *feats /* [total_frames][D] */,
+                              int32_t D, const int64_t *offsets, int64_t n_utts, int64_t total_frames,
+                              const uint8_t *utt_keep /* [n_utts] or NULL = all */, int32_t W, int32_t S,
+                              void *workspace, size_t workspace_bytes, double *stats /* [W][width] */, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Forced alignment (csrc/connected_align.hip): Viterbi over the left-to-right chain of the K words an utterance is
  * known to hold — where does each word begin and end, and which state explains each frame.  Word slot k is entered
  * only from the exit of slot k - 1 and the score is read only at the exit of the last slot.  The definition is the CPU

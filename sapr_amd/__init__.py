@@ -14,8 +14,9 @@ behaviour) over hand-written HIP kernels in ``libsapr_hip.so``:
                              word-pair grammar where one is given: ``WordBigram``; with a known or bounded number of
                              words by level building: ``connected_levels``), word and segment confidences
                              from forward-backward over the same loop (``connected_posteriors``), forced alignment of
-                             a recording to its known word string, and embedded Baum-Welch training from such
-                             recordings (no counterpart in the reference, whose decoder labels a recording as one word)
+                             a recording to its known word string, embedded Baum-Welch training from such
+                             recordings, and discriminative (MMI) training of the word models against the word loop
+                             (``mmi_fit``) (no counterpart in the reference, whose decoder labels a recording as one word)
 
 ``sapr_amd/compat`` holds same-named top-level shims so the reference's ``train.py`` /
 ``eval.py`` / tests import the drop-in unmodified.
@@ -32,7 +33,8 @@ def __getattr__(name):
     ``sapr_amd.embed_gmm_stats_width`` / ``sapr_amd.embed_gmm_workspace_bytes`` / ``sapr_amd.ConnectedPosteriors`` /
     ``sapr_amd.connected_posteriors`` / ``sapr_amd.posteriors_workspace_bytes`` / ``sapr_amd.LevelResult`` /
     ``sapr_amd.connected_levels`` / ``sapr_amd.levels_workspace_bytes`` / ``sapr_amd.with_optional`` /
-    ``sapr_amd.align_opt_workspace_bytes``
+    ``sapr_amd.align_opt_workspace_bytes`` / ``sapr_amd.loop_stats`` / ``sapr_amd.loop_stats_workspace_bytes`` /
+    ``sapr_amd.MmiStats`` / ``sapr_amd.mmi_estep`` / ``sapr_amd.mmi_update`` / ``sapr_amd.mmi_fit``
     (resolved on first use: importing the package stays light)."""
     if name in ("GMMHMM", "fit_gmm_models", "vocab_scores"):
         from . import gmm_hmm
@@ -42,7 +44,8 @@ def __getattr__(name):
                 "embedded_fit", "embed_full_stats_width", "embed_full_workspace_bytes", "embed_gmm_stats_width",
                 "embed_gmm_workspace_bytes", "ConnectedPosteriors", "connected_posteriors",
                 "posteriors_workspace_bytes", "LevelResult", "connected_levels", "levels_workspace_bytes",
-                "with_optional", "align_opt_workspace_bytes"):
+                "with_optional", "align_opt_workspace_bytes", "loop_stats", "loop_stats_workspace_bytes", "MmiStats",
+                "mmi_estep", "mmi_update", "mmi_fit"):
         from . import connected
         return getattr(connected, name)
     if name == "full_vocab_scores":

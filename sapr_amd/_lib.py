@@ -108,6 +108,10 @@ SIGNATURES = {
     "sapr_connected_posteriors": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p]),
+    "sapr_connected_loop_stats_workspace_bytes": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int32,
+                                                          C.POINTER(c_size_t)]),
+    "sapr_connected_loop_stats": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_void_p, c_int32,
+                                          c_int32, c_void_p, c_size_t, c_void_p, c_void_p]),
     "sapr_connected_align_workspace_bytes": (c_int, [c_int64, c_int64, c_int32, c_int32, C.POINTER(c_size_t)]),
     "sapr_connected_align": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int32,
                                      c_void_p, c_void_p, c_void_p, c_double, c_int32, c_int32, c_void_p, c_size_t,

@@ -30,6 +30,12 @@ Forced alignment is the inverse question — the words of a recording are known,
 ``sapr_connected_align`` (``csrc/connected_align.hip``) runs the Viterbi recursion over the left-to-right chain of an
 utterance's own transcript, on the same ``logb`` (:func:`align_viterbi`, :func:`connected_align`; the definition is
 ``tests/_align_ref.py``).
+
+Discriminative training: maximum mutual information over the word loop with the extended Baum-Welch update
+(:func:`mmi_estep`, :func:`mmi_update`, :func:`mmi_fit`).  The numerator is the embedded E-step over the transcript's
+chain, the denominator forward-backward over the word loop on the same ``logb``; ``sapr_connected_loop_stats``
+(``csrc/connected_loop_stats.hip``, :func:`loop_stats`) reduces the loop's state posteriors to per-word statistics rows
+on the device (the definition is ``tests/_mmi_ref.py``).
 """
 from __future__ import annotations
 
@@ -599,9 +605,10 @@ def posteriors_workspace_bytes(total_frames, n_utts, W, S) -> int:
     return _workspace_bytes("sapr_connected_posteriors_workspace_bytes", total_frames, n_utts, W, S)
 
 
-def _run_posteriors(logb, offs_dev, offs, network, want_post=False) -> ConnectedPosteriors:
+def _posteriors_device(logb, offs_dev, offs, network, want_words=True, want_post=False):
     """One ``sapr_connected_posteriors`` over device ``logb[total_frames, R]``, under the network's bigram or, without
-    one, under ``lm == word_penalty``."""
+    one, under ``lm == word_penalty`` -> device tensors ``(loglik, word_post, entry_post, post)``; what was not asked
+    for is ``None`` (and not computed)."""
     torch = _torch()
     dev = logb.device
     n_utts, total = int(offs.size - 1), int(offs[-1])
@@ -610,14 +617,20 @@ def _run_posteriors(logb, offs_dev, offs, network, want_post=False) -> Connected
     ws_bytes = posteriors_workspace_bytes(total, n_utts, network.W, network.S)
     workspace = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
     loglik = torch.empty(n_utts, dtype=torch.float64, device=dev)
-    word_post = torch.empty((total, network.W), dtype=torch.float64, device=dev)
-    entry_post = torch.empty((total, network.W), dtype=torch.float64, device=dev)
+    word_post = torch.empty((total, network.W), dtype=torch.float64, device=dev) if want_words else None
+    entry_post = torch.empty((total, network.W), dtype=torch.float64, device=dev) if want_words else None
     post = torch.empty((total, network.R), dtype=torch.float64, device=dev) if want_post else None
     _lib.check(_lib.load().sapr_connected_posteriors(
         _lib.ptr(logb), _lib.ptr(offs_dev), n_utts, total, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx), _lib.ptr(lm),
         _lib.ptr(lm_start), _lib.ptr(lm_end), network.W, network.S, _lib.ptr(workspace), ws_bytes, _lib.ptr(loglik),
         _lib.ptr(word_post), _lib.ptr(entry_post), _lib.ptr(post), _lib.current_stream()), "sapr_connected_posteriors")
-    host = [None if a is None else a.cpu().numpy() for a in (loglik, word_post, entry_post, post)]
+    return loglik, word_post, entry_post, post
+
+
+def _run_posteriors(logb, offs_dev, offs, network, want_post=False) -> ConnectedPosteriors:
+    """:func:`_posteriors_device` with everything copied to the host."""
+    host = [None if a is None else a.cpu().numpy()
+            for a in _posteriors_device(logb, offs_dev, offs, network, True, want_post)]
     return ConnectedPosteriors(*host, offsets=offs)
 
 
@@ -1351,3 +1364,261 @@ def embedded_fit(models, features, transcripts, n_iter=10, tol=1e-2, exit_states
         if monitor.converged:
             break
     return list(monitor.history)
+
+
+# ---- discriminative (MMI) training ------------------------------------------------------------------
+def loop_stats_workspace_bytes(total_frames, n_utts, W, S, D) -> int:
+    return _workspace_bytes("sapr_connected_loop_stats_workspace_bytes", total_frames, n_utts, W, S, D)
+
+
+def _run_loop_stats(post, feats, offs_dev, n_utts, total, network, keep_dev=None):
+    """One ``sapr_connected_loop_stats`` over device ``post[total_frames, R]`` and device ``feats`` -> the device rows
+    ``[W, sapr_connected_embed_stats_width(S, D)]``; ``keep_dev``: a device uint8 per utterance, or ``None`` (all)."""
+    torch = _torch()
+    dev = post.device
+    D = int(feats.shape[1])
+    ws_bytes = loop_stats_workspace_bytes(total, n_utts, network.W, network.S, D)
+    workspace = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    stats = torch.empty((network.W, embed_stats_width(network.S, D)), dtype=torch.float64, device=dev)
+    _lib.check(_lib.load().sapr_connected_loop_stats(
+        _lib.ptr(post), _lib.ptr(feats), D, _lib.ptr(offs_dev), n_utts, total, _lib.ptr(keep_dev), network.W,
+        network.S, _lib.ptr(workspace), ws_bytes, _lib.ptr(stats), _lib.current_stream()), "sapr_connected_loop_stats")
+    return stats
+
+
+def _keep_flags(keep, n_utts):
+    if keep is None:
+        return None
+    keep = np.asarray(keep).reshape(-1)
+    if keep.size != n_utts:
+        raise ValueError(f"{keep.size} keep flags for {n_utts} utterances")
+    return np.ascontiguousarray(keep != 0, dtype=np.uint8)
+
+
+def loop_stats(post, feats, lengths, network: ConnectedNetwork, keep=None) -> np.ndarray:
+    """The word loop's state posteriors reduced to per-word statistics (``sapr_connected_loop_stats``; the definition
+    is ``tests/_mmi_ref.py``): ``post`` is float64 ``[total_frames, W * SP]``, ``[total_frames, W, SP]`` or
+    ``[total_frames, W, S]`` (what :func:`connected_posteriors` returns with ``want_post=True``), ``feats`` the float32
+    frames ``[total_frames, D]``, either a host array or a device tensor; ``keep``: one flag per utterance, the
+    utterances that count (``None``: all).  Returns the rows ``[W, width]`` of ``sapr_connected_embed``'s layout with
+    ``post``, ``obs`` and ``obs**2`` filled, ``nobs`` = the kept utterances with a frame and zeros elsewhere:
+    ``trellis.split_stats(rows[w], S, D, n_states[w], D)`` reads them, as ``EmbeddedStats.split`` does."""
+    torch = _torch()
+    lengths, offs = _offsets(lengths)
+    n_utts, total = int(lengths.size), int(offs[-1])
+    keep = _keep_flags(keep, n_utts)
+    dev = _lib.require_gpu()
+    if not torch.is_tensor(post):
+        post = torch.from_numpy(np.ascontiguousarray(post, dtype=np.float64))
+    post = post.to(dev)
+    W, S, SP, R = network.W, network.S, network.SP, network.R
+    if post.dtype != torch.float64 or int(post.shape[0]) != total:
+        raise ValueError("post must be float64 with sum(lengths) rows")
+    if tuple(post.shape[1:]) == (W, S) and S != SP:
+        wide = torch.zeros((total, W, SP), dtype=torch.float64, device=dev)
+        wide[:, :, :S] = post
+        post = wide
+    if tuple(post.shape[1:]) not in ((W, SP), (R,)):
+        raise ValueError(f"post must be [total_frames, {W}, {S}], [total_frames, {W}, {SP}] or [total_frames, {R}]; "
+                         f"got {tuple(post.shape)}")
+    post = post.reshape(total, R).contiguous()
+    if not torch.is_tensor(feats):
+        feats = torch.from_numpy(np.ascontiguousarray(feats, dtype=np.float32))
+    feats = feats.to(dev).contiguous()
+    if feats.dtype != torch.float32 or feats.dim() != 2 or int(feats.shape[0]) != total or int(feats.shape[1]) < 1:
+        raise ValueError("feats must be float32 [sum(lengths), D] with D >= 1")
+    keep_dev = None if keep is None else torch.from_numpy(keep).to(dev)
+    return _run_loop_stats(post, feats, torch.from_numpy(offs).to(dev), n_utts, total, network, keep_dev).cpu().numpy()
+
+
+@dataclass
+class MmiStats:
+    """One E-step of MMI training (:func:`mmi_estep`; the definition is ``tests/_mmi_ref.py``)."""
+    num: EmbeddedStats        # the numerator: sapr_connected_embed over the kept utterances' transcript chains
+    den_stats: np.ndarray     # [W, width] f64: the denominator rows of sapr_connected_loop_stats, num.stats' layout
+    num_loglik: np.ndarray    # [N] f64: the transcript chain's log-likelihood plus the transcript's lmscore
+    den_loglik: np.ndarray    # [N] f64: the word loop's log-likelihood, over every word string the grammar allows
+    lmscore: np.ndarray       # [N] f64: the language-model score of the transcript
+    keep: np.ndarray          # [N] bool: both likelihoods finite — the utterances that count
+    objective: float          # F = the sum over the kept utterances of num_loglik - den_loglik (<= 0 up to rounding)
+
+    def split(self, w):
+        """``(numerator dict, denominator dict)`` of word model ``w``: hmmlearn's statistics dicts, cut to the model's
+        own states; the denominator's ``start`` and ``trans`` are zeros."""
+        from .trellis import split_stats
+        n = self.num
+        return n.split(w), split_stats(self.den_stats[w], n.S, n.D, n.n_states[w] if n.n_states else None, n.D)
+
+
+def _lm_scores(transcripts, network):
+    """``lmscore[u] = lm_start[w_0] + sum_k lm[w_{k-1}, w_k] + lm_end[w_{K-1}]`` under :meth:`loop_lm`, float64 on the
+    host, added in transcript order.  A transcript the language model forbids is a ``ValueError`` that names it."""
+    lm, lm_start, lm_end = network.loop_lm()
+    out = np.zeros(len(transcripts))
+    for u, t in enumerate(transcripts):
+        t = [int(w) for w in t]
+        sc = np.float64(lm_start[t[0]])
+        for a, b in zip(t[:-1], t[1:]):
+            sc = sc + lm[a, b]
+        sc = sc + lm_end[t[-1]]
+        if not np.isfinite(sc):
+            raise ValueError(f"the grammar forbids the transcript of utterance {u} ({t}): its language-model score is "
+                             f"{float(sc)!r}")
+        out[u] = sc
+    return out
+
+
+def _refuse_mmi_family(family):
+    if family != "diag":
+        raise NotImplementedError(
+            f"MMI training is served for 'diag' and 'spherical' GaussianHMM word models; the {family!r} family needs a "
+            f"denominator kernel of its own ({'mixture responsibilities' if family == 'gmm' else 'second moments'} "
+            f"over the word loop's posteriors)")
+
+
+def _check_mmi_transcripts(transcripts, n_utts, network, names=None):
+    """The transcripts validated on the host (an unknown word is named), and their language-model scores."""
+    rows = [np.asarray(t, dtype=np.int64).reshape(-1) for t in transcripts]
+    for u, t in enumerate(rows):
+        for w in t:
+            if not 0 <= int(w) < network.W:
+                raise ValueError(f"the transcript of utterance {u} names word {int(w)}, which is outside the "
+                                 f"vocabulary 0..{network.W - 1}"
+                                 + (f" ({', '.join(map(str, names))})" if names is not None else ""))
+    _transcripts(rows, n_utts, network)
+    return _lm_scores(rows, network)
+
+
+def mmi_estep(batch_or_feature_list, transcripts, network: ConnectedNetwork, acoustic_scale=1.0) -> MmiStats:
+    """One E-step of maximum-mutual-information training on a "diag" network.  With ``logb' = acoustic_scale * logb``
+    (at 1.0 ``logb`` as it is): the numerator is ``sapr_connected_embed`` over each transcript's chain with
+    ``word_penalty = 0.0`` plus the transcript's language-model score under ``network.loop_lm()``; the denominator is
+    ``sapr_connected_posteriors`` over the word loop on the same ``logb'``, whose state posteriors
+    ``sapr_connected_loop_stats`` reduces to per-word rows on the device (they never reach the host).  An utterance
+    counts (``keep``) where both likelihoods are finite.  Where an utterance was dropped the numerator statistics come
+    from a second run of the E-step over the kept utterances alone.  A transcript the grammar forbids is refused with a
+    ``ValueError`` that names the utterance, before a device is asked for; optional transcript slots are not
+    offered (the transcript's language-model score would depend on the path)."""
+    import dataclasses
+    torch = _torch()
+    b = batch_or_feature_list
+    n_utts = len(b.lengths) if hasattr(b, "offsets") and hasattr(b, "order") else len(b)
+    scale = float(acoustic_scale)
+    if not (scale > 0.0 and np.isfinite(scale)):
+        raise ValueError(f"acoustic_scale must be a positive number, got {acoustic_scale!r}")
+    _refuse_mmi_family(network.family)
+    lmscore = _check_mmi_transcripts(transcripts, n_utts, network)  # (refused before a device is asked for)
+    feats, offs_dev, offs = _features(b)
+    total = int(offs[-1])
+    logb = emit_diag(feats, network)
+    if scale != 1.0:
+        logb = logb * scale
+    chain = copy.copy(network)  # the transcript's chain pays its word boundaries through lmscore
+    chain.word_penalty = 0.0
+    num = _run_embed(logb, feats, offs_dev, offs, transcripts, chain, True, False)
+    den_ll, _, _, post = _posteriors_device(logb, offs_dev, offs, network, False, True)
+    den_loglik = den_ll.cpu().numpy()
+    with np.errstate(invalid="ignore"):
+        num_loglik = num.loglik + lmscore
+    keep = np.isfinite(num_loglik) & np.isfinite(den_loglik)
+    if not keep.all() and np.isfinite(num.loglik[~keep]).any():
+        # an utterance that is dropped although its chain has a path: the numerator again, over the kept ones alone
+        kept = np.flatnonzero(keep)
+        if kept.size == 0:  # (nothing counts: a NaN in the language model makes every denominator NaN)
+            num = dataclasses.replace(num, stats=np.zeros_like(num.stats))
+        else:
+            rows = np.concatenate([np.arange(offs[u], offs[u + 1]) for u in kept])
+            idx = torch.from_numpy(rows.astype(np.int64)).to(logb.device)
+            _, offs_k = _offsets(np.diff(offs)[kept])
+            again = _run_embed(logb.index_select(0, idx), feats.index_select(0, idx),
+                               torch.from_numpy(offs_k).to(idx.device), offs_k, [transcripts[u] for u in kept], chain,
+                               True, False)
+            num = dataclasses.replace(num, stats=again.stats)
+    keep_dev = torch.from_numpy(keep.astype(np.uint8)).to(logb.device)
+    den_stats = _run_loop_stats(post, feats, offs_dev, n_utts, total, network, keep_dev).cpu().numpy()
+    objective = float((num_loglik[keep] - den_loglik[keep]).sum())
+    return MmiStats(num, den_stats, num_loglik, den_loglik, lmscore, keep, objective)
+
+
+def mmi_update(num, den, means, covars, covariance_type, E=2.0, tau=0.0, min_covar=1e-3):
+    """The extended Baum-Welch update of one word model's Gaussians (numpy float64): ``num`` / ``den`` are the
+    statistics dicts of :meth:`MmiStats.split`, ``means[S, D]``, ``covars`` ``[S, D]`` ("diag") or ``[S]``
+    ("spherical").  Per state, with I-smoothing ``tau`` on the numerator::
+
+        n = num * (1 + tau / num.post)      occ = n.post - den.post   th1 = n.obs - den.obs   th2 = n.obs2 - den.obs2
+        D_min = max(0, -occ, the larger real root over d of  var D^2 + (th2 + occ (var + mu^2) - 2 mu th1) D
+                                                             + occ th2 - th1^2)
+        D     = max(E den.post, 2 D_min)
+        mu'   = (th1 + D mu) / (occ + D)    var' = max((th2 + D (var + mu^2)) / (occ + D) - mu'^2, min_covar)
+
+    A state with ``occ + D == 0`` keeps its parameters; "spherical" takes the mean of ``var'`` over the features.
+    Returns ``(means, covars)`` as new arrays."""
+    if covariance_type not in ("diag", "spherical"):
+        raise NotImplementedError(f"mmi_update serves 'diag' and 'spherical' covariances, not {covariance_type!r} "
+                                  f"(the 'full' family)")
+    mu = np.array(means, dtype=np.float64)
+    cv = np.array(covars, dtype=np.float64)
+    var = np.broadcast_to(cv[:, None], mu.shape).copy() if covariance_type == "spherical" else cv.copy()
+    if var.shape != mu.shape:
+        raise ValueError(f"covars of shape {cv.shape} do not fit means of shape {mu.shape}")
+    n_post = np.asarray(num["post"], dtype=np.float64)
+    scale = np.ones_like(n_post)
+    if tau != 0.0:
+        live = n_post != 0.0
+        scale[live] = 1.0 + float(tau) / n_post[live]
+    occ = n_post * scale - np.asarray(den["post"], dtype=np.float64)
+    th1 = np.asarray(num["obs"], dtype=np.float64) * scale[:, None] - np.asarray(den["obs"], dtype=np.float64)
+    th2 = np.asarray(num["obs**2"], dtype=np.float64) * scale[:, None] - np.asarray(den["obs**2"], dtype=np.float64)
+    m2 = var + mu * mu
+    b = th2 + occ[:, None] * m2 - 2.0 * mu * th1
+    c = occ[:, None] * th2 - th1 * th1
+    disc = b * b - 4.0 * var * c
+    with np.errstate(invalid="ignore"):
+        root = np.where(disc >= 0.0, (-b + np.sqrt(np.maximum(disc, 0.0))) / (2.0 * var), 0.0)
+    d_min = np.maximum(np.maximum(root.max(axis=1), -occ), 0.0)
+    d_s = np.maximum(float(E) * np.asarray(den["post"], dtype=np.float64), 2.0 * d_min)
+    denom = occ + d_s
+    moved = denom != 0.0
+    safe = np.where(moved, denom, 1.0)[:, None]
+    mu_new = (th1 + d_s[:, None] * mu) / safe
+    var_new = np.maximum((th2 + d_s[:, None] * m2) / safe - mu_new * mu_new, float(min_covar))
+    mu_out = np.where(moved[:, None], mu_new, mu)
+    if covariance_type == "spherical":
+        return mu_out, np.where(moved, var_new.mean(axis=1), cv)
+    return mu_out, np.where(moved[:, None], var_new, cv)
+
+
+def mmi_fit(models, features, transcripts, bigram=None, n_iter=4, E=2.0, tau=0.0, acoustic_scale=1.0,
+            exit_states="last", word_penalty=0.0, names=None):
+    """Discriminative training of a "diag" / "spherical" ``GaussianHMM`` vocabulary IN PLACE by maximum mutual
+    information with the extended Baum-Welch update: ``features`` are frame-major ``(T, D)`` arrays, ``transcripts``
+    vocabulary indices.  ``bigram``: the :class:`WordBigram` (or grammar) the word loop runs under, as
+    ``bigram.scaled(1.0, word_penalty)``; without one the loop pays ``word_penalty`` per word boundary.  Each
+    iteration: the network of the current models, :func:`mmi_estep`, then :func:`mmi_update` per word with the model's
+    own covariance type and ``min_covar``; ``startprob_`` and ``transmat_`` are left as they are and a word that occurs
+    in no kept transcript is left untouched.  Returns the history of the objective F, one entry per iteration, each
+    evaluated before that iteration's update.  A ``GMMHMM`` vocabulary and one that holds a "full" or "tied" model are a
+    ``NotImplementedError`` that names the family."""
+    models = list(models)
+    _refuse_mmi_family(vocabulary_family(models, names, None))
+    if bigram is not None and not isinstance(bigram, WordBigram):
+        raise ValueError(f"bigram must be a WordBigram, got a {type(bigram).__name__}")
+
+    def network():
+        if bigram is None:
+            return ConnectedNetwork.from_models(models, exit_states, word_penalty, names, "hmmlearn")
+        return ConnectedNetwork.from_models(models, exit_states, 0.0, names, "hmmlearn",
+                                            bigram=bigram.scaled(1.0, word_penalty))
+
+    _check_mmi_transcripts(transcripts, len(features), network(), names)  # (refused before a device is asked for)
+    history = []
+    for _ in range(int(n_iter)):
+        st = mmi_estep(features, transcripts, network(), acoustic_scale)
+        history.append(st.objective)
+        for w, m in enumerate(models):
+            num, den = st.split(w)
+            if num["nobs"] == 0:
+                continue
+            m.means_, m._covars_ = mmi_update(num, den, m.means_, m._covars_, m.covariance_type, E, tau,
+                                              getattr(m, "min_covar", 1e-3))
+    return history

@@ -1,6 +1,7 @@
 // The lane layout behind the connected-word trellis units (connected.hip, connected_align.hip, connected_embed.hip,
 // connected_bigram.hip, connected_loop_fb.hip, connected_levels.hip).  Like lse_ops.h and gmm_ops.h this
-// header is included INSIDE the unit's `namespace sapr { namespace {`, after both of them.
+// header is included INSIDE the unit's `namespace sapr { namespace {`, after both of them.  connected_loop_stats.hip
+//  has no recursion; it takes the constants and the host helpers from here.
 //
 // The mapping every recursion kernel of these units uses:
 //   * One wavefront serves one utterance; a workgroup holds up to four of them, which share the tables in LDS.  The

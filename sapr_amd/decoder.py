@@ -310,6 +310,50 @@ class Decoder:
         self._pack = self._vocab = None  # (packed from the old parameters)
         return history
 
+    def train_discriminative(self, feature_list: List[np.ndarray], transcripts, bigram=None, n_iter: int = 4,
+                             E: float = 2.0, tau: float = 0.0, acoustic_scale: float = 1.0,
+                             word_penalty: float = 0.0, exit_states="last") -> List[float]:
+        """Discriminative (maximum mutual information) training over recordings of several words: the means and
+        variances of the loaded word models are re-estimated IN PLACE so that each recording's transcript gains
+        probability against every other word string the word loop allows (``sapr_amd.connected.mmi_fit``: the
+        numerator from ``sapr_connected_embed`` over the transcript's chain, the denominator from
+        ``sapr_connected_posteriors`` over the word loop reduced by ``sapr_connected_loop_stats``, then the extended
+        Baum-Welch update with the constant ``E`` and the I-smoothing weight ``tau``).  ``feature_list`` and
+        ``transcripts`` (word names) are as in ``train_embedded``; ``bigram`` as in ``decode_connected``.  Returns the
+        history of the objective, the summed log posterior of the transcripts, one entry per iteration (evaluated
+        before the iteration's update).  Start and transition probabilities stay as they are; a word that is in no
+        transcript keeps its parameters.
+
+        Served for ``implementation="hmmlearn"`` with "diag" / "spherical" models.  A ``GMMHMM`` vocabulary
+        (``implementation="gmmhmm"``) and one that holds a "full" or "tied" model are a ``NotImplementedError`` that
+        names the family; a transcript the grammar forbids is a ``ValueError`` that names the utterance, a word that
+        is not in the vocabulary one that names the word."""
+        if self.implementation == "gmmhmm":
+            raise NotImplementedError("MMI training is served for 'diag' and 'spherical' GaussianHMM word models; the "
+                                      "'gmm' family (implementation='gmmhmm') needs a denominator kernel of its own")
+        if self.implementation != "hmmlearn":
+            raise ValueError(f"discriminative training needs implementation='hmmlearn' (GaussianHMM word models): the "
+                             f"MMI E-step accumulates Gaussian statistics, not those of "
+                             f"implementation={self.implementation!r}")
+        from .connected import mmi_fit
+        if len(feature_list) == 0:
+            raise ValueError("empty utterance list")
+        words = list(self.models)
+        index = {w: i for i, w in enumerate(words)}
+        rows = []
+        for u, names in enumerate(transcripts):
+            for name in names:
+                if name not in index:
+                    raise ValueError(f"the transcript of utterance {u} names {name!r}, which is not in the vocabulary "
+                                     f"({', '.join(words)})")
+            rows.append([index[name] for name in names])
+        history = mmi_fit(self._model_list(), [np.asarray(f).T for f in feature_list], rows,
+                          bigram=None if bigram is None else self._word_bigram(bigram), n_iter=n_iter, E=E, tau=tau,
+                          acoustic_scale=acoustic_scale, exit_states=exit_states, word_penalty=word_penalty,
+                          names=words)
+        self._pack = self._vocab = None  # (packed from the old parameters)
+        return history
+
     def _decode_custom(self, features) -> List[Tuple[str, float, object]]:
         """The reference's from-scratch models: emission rows, trellis and the arg-max over the models
         (decoder.py:42-47, first strict maximum in load order) all on the device."""
