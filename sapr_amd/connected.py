@@ -71,6 +71,27 @@ def _workspace_bytes(entry, *sizes) -> int:
     return int(n.value)
 
 
+def _workspace(entry, dev, *sizes):
+    """``(workspace, bytes)``: the uninitialised device bytes one call at these sizes takes, as the library's size
+    function ``entry`` counts them (an empty workspace is one byte, so that it has an address)."""
+    torch = _torch()
+    ws_bytes = _workspace_bytes(entry, *sizes)
+    return torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev), ws_bytes
+
+
+def _stats_width(entry, *sizes) -> int:
+    """``entry(*sizes, &width)`` of the library: the doubles of one statistics row at these sizes."""
+    n = C.c_int32(0)
+    _lib.check(getattr(_lib.load(), entry)(*sizes, C.byref(n)), entry)
+    return int(n.value)
+
+
+def _n_utts(batch_or_feature_list) -> int:
+    """The utterances of a ``trellis.FeatureBatch`` or of a list of feature arrays, without touching a device."""
+    b = batch_or_feature_list
+    return len(b.lengths) if hasattr(b, "offsets") and hasattr(b, "order") else len(b)
+
+
 def workspace_bytes(total_frames, n_utts, W, S) -> int:
     return _workspace_bytes("sapr_connected_workspace_bytes", total_frames, n_utts, W, S)
 
@@ -509,12 +530,10 @@ def _path_tensors(n_utts, total, dev, want_paths=True):
 def _run_bigram(logb, offs_dev, n_utts, total, network, want_paths=True):
     """One ``sapr_connected_bigram`` -> device tensors (score, n_words, path_word, path_state, path_entry);
     ``want_paths=False``: the scores alone (the other four are ``None`` and no back-trace is launched)."""
-    torch = _torch()
     dev = logb.device
     ls, lt, lx, _ = network.device(dev)
     lm, lm_start, lm_end = network._dev_lm
-    ws_bytes = bigram_workspace_bytes(total, n_utts, network.W, network.S)
-    workspace = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    workspace, ws_bytes = _workspace("sapr_connected_bigram_workspace_bytes", dev, total, n_utts, network.W, network.S)
     score, n_words, path_word, path_state, path_entry = _path_tensors(n_utts, total, dev, want_paths)
     _lib.check(_lib.load().sapr_connected_bigram(
         _lib.ptr(logb), _lib.ptr(offs_dev), n_utts, total, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx), _lib.ptr(lm),
@@ -529,11 +548,9 @@ def _run_viterbi(logb, offs_dev, n_utts, total, network):
     tensors (score, n_words, path_word, path_state, path_entry)."""
     if network.bigram is not None:
         return _run_bigram(logb, offs_dev, n_utts, total, network)
-    torch = _torch()
     dev = logb.device
     ls, lt, lx, _ = network.device(dev)
-    ws_bytes = workspace_bytes(total, n_utts, network.W, network.S)
-    workspace = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    workspace, ws_bytes = _workspace("sapr_connected_workspace_bytes", dev, total, n_utts, network.W, network.S)
     score, n_words, path_word, path_state, path_entry = _path_tensors(n_utts, total, dev)
     _lib.check(_lib.load().sapr_connected_viterbi(
         _lib.ptr(logb), _lib.ptr(offs_dev), n_utts, total, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx),
@@ -548,23 +565,37 @@ def _result(tensors, offs) -> ConnectedResult:
     return ConnectedResult(*host, offsets=offs)
 
 
-def _flat_logb(logb, total, network, dev):
-    """A caller's ``logb`` (host array or device tensor, any of the three shapes) -> device ``[total_frames, R]``."""
+def _flat_states(x, total, network, dev, pad=float("-inf"), what="logb"):
+    """A caller's per-frame state array (host array or device tensor; ``[total_frames, W, S]``, ``[total_frames, W,
+    SP]`` or ``[total_frames, R]``) -> device ``[total_frames, R]``; the states from S to SP are filled with ``pad``
+    and the messages speak of ``what``."""
     torch = _torch()
-    if not torch.is_tensor(logb):
-        logb = torch.from_numpy(np.ascontiguousarray(logb, dtype=np.float64))
-    logb = logb.to(dev)
-    if logb.dtype != torch.float64 or int(logb.shape[0]) != total:
-        raise ValueError("logb must be float64 with sum(lengths) rows")
+    if not torch.is_tensor(x):
+        x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))
+    x = x.to(dev)
+    if x.dtype != torch.float64 or int(x.shape[0]) != total:
+        raise ValueError(f"{what} must be float64 with sum(lengths) rows")
     W, S, SP, R = network.W, network.S, network.SP, network.R
-    if tuple(logb.shape[1:]) == (W, S) and S != SP:
-        wide = torch.full((total, W, SP), float("-inf"), dtype=torch.float64, device=dev)
-        wide[:, :, :S] = logb
-        logb = wide
-    if tuple(logb.shape[1:]) not in ((W, SP), (R,)):
-        raise ValueError(f"logb must be [total_frames, {W}, {S}], [total_frames, {W}, {SP}] or [total_frames, {R}]; "
-                         f"got {tuple(logb.shape)}")
-    return logb.reshape(total, R).contiguous()
+    if tuple(x.shape[1:]) == (W, S) and S != SP:
+        wide = torch.full((total, W, SP), pad, dtype=torch.float64, device=dev)
+        wide[:, :, :S] = x
+        x = wide
+    if tuple(x.shape[1:]) not in ((W, SP), (R,)):
+        raise ValueError(f"{what} must be [total_frames, {W}, {S}], [total_frames, {W}, {SP}] or [total_frames, {R}]; "
+                         f"got {tuple(x.shape)}")
+    return x.reshape(total, R).contiguous()
+
+
+def _flat_feats(feats, total, dev, min_D=0):
+    """A caller's ``feats`` (host array or device tensor) -> device float32 ``[total_frames, D]`` with D >= ``min_D``."""
+    torch = _torch()
+    if not torch.is_tensor(feats):
+        feats = torch.from_numpy(np.ascontiguousarray(feats, dtype=np.float32))
+    feats = feats.to(dev).contiguous()
+    if feats.dtype != torch.float32 or feats.dim() != 2 or int(feats.shape[0]) != total \
+            or int(feats.shape[1]) < min_D:
+        raise ValueError("feats must be float32 [sum(lengths), D]" + (f" with D >= {min_D}" if min_D else ""))
+    return feats
 
 
 def connected_viterbi(logb, lengths, network: ConnectedNetwork) -> ConnectedResult:
@@ -575,7 +606,7 @@ def connected_viterbi(logb, lengths, network: ConnectedNetwork) -> ConnectedResu
     dev = _lib.require_gpu()
     lengths, offs = _offsets(lengths)
     total = int(offs[-1])
-    logb = _flat_logb(logb, total, network, dev)
+    logb = _flat_states(logb, total, network, dev)
     offs_dev = torch.from_numpy(offs).to(dev)
     return _result(_run_viterbi(logb, offs_dev, int(lengths.size), total, network), offs)
 
@@ -614,8 +645,8 @@ def _posteriors_device(logb, offs_dev, offs, network, want_words=True, want_post
     n_utts, total = int(offs.size - 1), int(offs[-1])
     ls, lt, lx, _ = network.device(dev)
     lm, lm_start, lm_end = network.device_lm(dev)
-    ws_bytes = posteriors_workspace_bytes(total, n_utts, network.W, network.S)
-    workspace = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    workspace, ws_bytes = _workspace("sapr_connected_posteriors_workspace_bytes", dev, total, n_utts, network.W,
+                                     network.S)
     loglik = torch.empty(n_utts, dtype=torch.float64, device=dev)
     word_post = torch.empty((total, network.W), dtype=torch.float64, device=dev) if want_words else None
     entry_post = torch.empty((total, network.W), dtype=torch.float64, device=dev) if want_words else None
@@ -641,7 +672,7 @@ def connected_posteriors(logb, lengths, network: ConnectedNetwork, want_post=Fal
     torch = _torch()
     dev = _lib.require_gpu()
     lengths, offs = _offsets(lengths)
-    logb = _flat_logb(logb, int(offs[-1]), network, dev)
+    logb = _flat_states(logb, int(offs[-1]), network, dev)
     return _run_posteriors(logb, torch.from_numpy(offs).to(dev), offs, network, want_post)
 
 
@@ -749,8 +780,8 @@ def _run_levels(logb, offs_dev, offs, network, max_words) -> LevelResult:
     L = int(max_words)
     ls, lt, lx, _ = network.device(dev)
     lm, lm_start, lm_end = network.device_lm(dev)
-    ws_bytes = levels_workspace_bytes(total, n_utts, network.W, network.S, L)
-    workspace = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    workspace, ws_bytes = _workspace("sapr_connected_levels_workspace_bytes", dev, total, n_utts, network.W, network.S,
+                                     L)
     level = torch.empty((n_utts, L), dtype=torch.float64, device=dev)
     _lib.check(_lib.load().sapr_connected_levels(
         _lib.ptr(logb), _lib.ptr(offs_dev), n_utts, total, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx), _lib.ptr(lm),
@@ -767,7 +798,7 @@ def connected_levels(logb, lengths, network: ConnectedNetwork, max_words) -> Lev
     L = _check_counts(None, max_words, 0)[1]
     dev = _lib.require_gpu()
     lengths, offs = _offsets(lengths)
-    logb = _flat_logb(logb, int(offs[-1]), network, dev)
+    logb = _flat_states(logb, int(offs[-1]), network, dev)
     return _run_levels(logb, torch.from_numpy(offs).to(dev), offs, network, L)
 
 
@@ -786,10 +817,9 @@ def connected_decode(batch_or_feature_list, network: ConnectedNetwork, posterior
         logb = _EMIT[network.family](feats, network)
         res = _result(_run_viterbi(logb, offs_dev, int(offs.size - 1), int(offs[-1]), network), offs)
     else:
-        b = batch_or_feature_list
-        n_utts = len(b.lengths) if hasattr(b, "offsets") and hasattr(b, "order") else len(b)
-        n_words, L = _check_counts(n_words, max_words, n_utts)  # (refused before a device is asked for)
-        feats, offs_dev, offs = _features(b)
+        # (refused before a device is asked for)
+        n_words, L = _check_counts(n_words, max_words, _n_utts(batch_or_feature_list))
+        feats, offs_dev, offs = _features(batch_or_feature_list)
         logb = _EMIT[network.family](feats, network)
         res = _run_levels(logb, offs_dev, offs, network, L).select(n_words)
     if posteriors:
@@ -894,8 +924,8 @@ def _optional(optional, transcripts):
 
 
 def _transcripts(transcripts, n_utts, network, optional=None):
-    """Validated transcripts -> ``(words[total_words] i32, word_offsets[N + 1] i64, max_words)``, and with
-    ``optional`` given a fourth entry, the validated flags ``[total_words] u8``."""
+    """Validated transcripts and flags -> ``(words[total_words] i32, word_offsets[N + 1] i64, max_words,
+    flags[total_words] u8)``; ``flags`` is ``None`` where no ``optional`` was given."""
     transcripts = [np.asarray(t, dtype=np.int64).reshape(-1) for t in transcripts]
     if len(transcripts) != n_utts:
         raise ValueError(f"{len(transcripts)} transcripts for {n_utts} utterances")
@@ -911,8 +941,6 @@ def _transcripts(transcripts, n_utts, network, optional=None):
     _, word_offs = _offsets([t.size for t in transcripts])
     words = np.concatenate(transcripts).astype(np.int32) if transcripts else np.zeros(0, np.int32)
     max_words = max((t.size for t in transcripts), default=1)
-    if optional is None:
-        return words, word_offs, max_words
     return words, word_offs, max_words, _optional(optional, transcripts)
 
 
@@ -920,8 +948,9 @@ def align_opt_workspace_bytes(total_frames, n_utts, max_words, S) -> int:
     return _workspace_bytes("sapr_connected_align_opt_workspace_bytes", total_frames, n_utts, max_words, S)
 
 
-def _run_align_opt(logb, offs_dev, offs, transcripts, network, optional) -> AlignResult:
-    """One ``sapr_connected_align_opt`` over device ``logb[total_frames, R]``."""
+def _run_align(logb, offs_dev, offs, transcripts, network, optional=None) -> AlignResult:
+    """One ``sapr_connected_align_opt`` over device ``logb[total_frames, R]``: with the flags of ``optional``, or
+    without flags (NULL), which is ``sapr_connected_align`` on its own, smaller workspace."""
     torch = _torch()
     dev = logb.device
     n_utts, total = int(offs.size - 1), int(offs[-1])
@@ -930,9 +959,9 @@ def _run_align_opt(logb, offs_dev, offs, transcripts, network, optional) -> Alig
     ls, lt, lx, _ = network.device(dev)
     words_dev = torch.from_numpy(words).to(dev)
     word_offs_dev = torch.from_numpy(word_offs).to(dev)
-    flags_dev = torch.from_numpy(flags).to(dev)
-    ws_bytes = align_opt_workspace_bytes(total, n_utts, max_words, network.S)
-    workspace = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    flags_dev = None if flags is None else torch.from_numpy(flags).to(dev)
+    name = "sapr_connected_align" if flags is None else "sapr_connected_align_opt"
+    workspace, ws_bytes = _workspace(name + "_workspace_bytes", dev, total, n_utts, max_words, network.S)
     score = torch.empty(n_utts, dtype=torch.float64, device=dev)
     path_word = torch.empty(total, dtype=torch.int32, device=dev)
     path_state = torch.empty(total, dtype=torch.int32, device=dev)
@@ -942,39 +971,9 @@ def _run_align_opt(logb, offs_dev, offs, transcripts, network, optional) -> Alig
         _lib.ptr(logb), _lib.ptr(offs_dev), n_utts, total, _lib.ptr(words_dev), _lib.ptr(word_offs_dev),
         _lib.ptr(flags_dev), total_words, max_words, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx), network.word_penalty,
         network.W, network.S, _lib.ptr(workspace), ws_bytes, _lib.ptr(score), _lib.ptr(path_word),
-        _lib.ptr(path_state), _lib.ptr(path_entry), _lib.ptr(word_start), _lib.current_stream()),
-        "sapr_connected_align_opt")
+        _lib.ptr(path_state), _lib.ptr(path_entry), _lib.ptr(word_start), _lib.current_stream()), name)
     host = [a.copy() for a in _lib.to_host(score, path_word, path_state, path_entry, word_start)]
     return AlignResult(*host, word_offsets=word_offs, offsets=offs, words=words, optional=flags)
-
-
-def _run_align(logb, offs_dev, offs, transcripts, network, optional=None) -> AlignResult:
-    """One ``sapr_connected_align`` over device ``logb[total_frames, R]`` (``optional``: one
-    ``sapr_connected_align_opt``)."""
-    if optional is not None:
-        return _run_align_opt(logb, offs_dev, offs, transcripts, network, optional)
-    torch = _torch()
-    dev = logb.device
-    n_utts, total = int(offs.size - 1), int(offs[-1])
-    words, word_offs, max_words = _transcripts(transcripts, n_utts, network)
-    total_words = int(word_offs[-1])
-    ls, lt, lx, _ = network.device(dev)
-    words_dev = torch.from_numpy(words).to(dev)
-    word_offs_dev = torch.from_numpy(word_offs).to(dev)
-    ws_bytes = align_workspace_bytes(total, n_utts, max_words, network.S)
-    workspace = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    score = torch.empty(n_utts, dtype=torch.float64, device=dev)
-    path_word = torch.empty(total, dtype=torch.int32, device=dev)
-    path_state = torch.empty(total, dtype=torch.int32, device=dev)
-    path_entry = torch.empty(total, dtype=torch.uint8, device=dev)
-    word_start = torch.empty(total_words, dtype=torch.int32, device=dev)
-    _lib.check(_lib.load().sapr_connected_align(
-        _lib.ptr(logb), _lib.ptr(offs_dev), n_utts, total, _lib.ptr(words_dev), _lib.ptr(word_offs_dev), total_words,
-        max_words, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx), network.word_penalty, network.W, network.S,
-        _lib.ptr(workspace), ws_bytes, _lib.ptr(score), _lib.ptr(path_word), _lib.ptr(path_state),
-        _lib.ptr(path_entry), _lib.ptr(word_start), _lib.current_stream()), "sapr_connected_align")
-    host = [a.copy() for a in _lib.to_host(score, path_word, path_state, path_entry, word_start)]
-    return AlignResult(*host, word_offsets=word_offs, offsets=offs, words=words)
 
 
 def align_viterbi(logb, lengths, transcripts, network: ConnectedNetwork, optional=None) -> AlignResult:
@@ -987,7 +986,7 @@ def align_viterbi(logb, lengths, transcripts, network: ConnectedNetwork, optiona
     lengths, offs = _offsets(lengths)
     _transcripts(transcripts, int(lengths.size), network, optional)  # (refused before a device is asked for)
     dev = _lib.require_gpu()
-    logb = _flat_logb(logb, int(offs[-1]), network, dev)
+    logb = _flat_states(logb, int(offs[-1]), network, dev)
     return _run_align(logb, torch.from_numpy(offs).to(dev), offs, transcripts, network, optional)
 
 
@@ -995,19 +994,16 @@ def connected_align(batch_or_feature_list, transcripts, network: ConnectedNetwor
     """Emission (by the network's family) and the alignment recursion: a ``trellis.FeatureBatch`` or a list of
     frame-major ``(T, D)`` feature arrays, with one transcript of vocabulary indices per utterance (and ``optional``
     as :func:`align_viterbi` takes it)."""
-    b = batch_or_feature_list
-    n_utts = len(b.lengths) if hasattr(b, "offsets") and hasattr(b, "order") else len(b)
-    _transcripts(transcripts, n_utts, network, optional)  # (refused before a device is asked for)
-    feats, offs_dev, offs = _features(b)
+    # (refused before a device is asked for)
+    _transcripts(transcripts, _n_utts(batch_or_feature_list), network, optional)
+    feats, offs_dev, offs = _features(batch_or_feature_list)
     logb = _EMIT[network.family](feats, network)
     return _run_align(logb, offs_dev, offs, transcripts, network, optional)
 
 
 # ---- embedded Baum-Welch --------------------------------------------------------------------------
 def embed_stats_width(S, D) -> int:
-    n = C.c_int32(0)
-    _lib.check(_lib.load().sapr_connected_embed_stats_width(S, D, C.byref(n)), "sapr_connected_embed_stats_width")
-    return int(n.value)
+    return _stats_width("sapr_connected_embed_stats_width", S, D)
 
 
 def embed_workspace_bytes(total_frames, n_utts, total_words, max_words, S, D) -> int:
@@ -1015,10 +1011,7 @@ def embed_workspace_bytes(total_frames, n_utts, total_words, max_words, S, D) ->
 
 
 def embed_full_stats_width(S, D) -> int:
-    n = C.c_int32(0)
-    _lib.check(_lib.load().sapr_connected_embed_full_stats_width(S, D, C.byref(n)),
-               "sapr_connected_embed_full_stats_width")
-    return int(n.value)
+    return _stats_width("sapr_connected_embed_full_stats_width", S, D)
 
 
 def embed_full_workspace_bytes(total_frames, n_utts, total_words, max_words, W, S, D) -> int:
@@ -1027,10 +1020,7 @@ def embed_full_workspace_bytes(total_frames, n_utts, total_words, max_words, W, 
 
 
 def embed_gmm_stats_width(S, M, D) -> int:
-    n = C.c_int32(0)
-    _lib.check(_lib.load().sapr_connected_embed_gmm_stats_width(S, M, D, C.byref(n)),
-               "sapr_connected_embed_gmm_stats_width")
-    return int(n.value)
+    return _stats_width("sapr_connected_embed_gmm_stats_width", S, M, D)
 
 
 def embed_gmm_workspace_bytes(total_frames, n_utts, total_words, max_words, W, S, M, D) -> int:
@@ -1078,106 +1068,50 @@ class EmbeddedStats:
         return self.post[lo:hi].reshape(hi - lo, -1, self.SP)[:, :K]
 
 
-def _flag_args(transcripts, n_utts, network, optional, dev):
-    """``(words, word_offsets, max_words, entry-point suffix, the extra pointer argument as a list, its tensor)``."""
-    if optional is None:
-        return (*_transcripts(transcripts, n_utts, network), "", [], None)
-    words, word_offs, max_words, flags = _transcripts(transcripts, n_utts, network, optional)
-    flags_dev = _torch().from_numpy(flags).to(dev)
-    return words, word_offs, max_words, "_opt", [_lib.ptr(flags_dev)], flags_dev
-
-
 def _run_embed(logb, feats, offs_dev, offs, transcripts, network, want_stats, want_post,
                second_moments=False, mixtures=False, optional=None) -> EmbeddedStats:
-    """One ``sapr_connected_embed`` over device ``logb[total_frames, R]`` (and device ``feats`` or ``None``);
-    ``second_moments``: one ``sapr_connected_embed_full`` instead, whose rows carry ``obs*obs.T``; ``mixtures``: one
-    ``sapr_connected_embed_gmm``, whose rows carry the statistics per mixture component."""
+    """One embedded E-step over device ``logb[total_frames, R]`` (and device ``feats`` or ``None``), by the ``_opt``
+    entry of the statistics' layout with the flags of ``optional`` or NULL: ``sapr_connected_embed``;
+    ``second_moments``: ``sapr_connected_embed_full``, whose rows carry ``obs*obs.T``; ``mixtures``:
+    ``sapr_connected_embed_gmm``, whose rows carry the statistics per mixture component of the network's ``GmmPack``
+    as the emission read it.  Without ``want_stats`` either switch is the plain entry without features."""
     torch = _torch()
-    if mixtures and want_stats:
-        if feats is None or int(feats.shape[1]) == 0:
-            raise ValueError("the mixture statistics need the frames: feats [total_frames, D] with D >= 1")
-        return _run_embed_gmm(logb, feats, offs_dev, offs, transcripts, network, want_post, optional)
-    if second_moments and want_stats:
-        if feats is None or int(feats.shape[1]) == 0:
-            raise ValueError("the second moments need the frames: feats [total_frames, D] with D >= 1")
-        return _run_embed_full(logb, feats, offs_dev, offs, transcripts, network, want_post, optional)
+    layout = "gmm" if mixtures and want_stats else "full" if second_moments and want_stats else "diag"
+    D = 0 if feats is None else int(feats.shape[1])
+    if layout != "diag" and D == 0:
+        raise ValueError(f"the {'mixture statistics' if layout == 'gmm' else 'second moments'} need the frames: feats "
+                         f"[total_frames, D] with D >= 1")
     dev = logb.device
     n_utts, total = int(offs.size - 1), int(offs[-1])
-    words, word_offs, max_words, sfx, flag, _keep = _flag_args(transcripts, n_utts, network, optional, dev)
+    words, word_offs, max_words, flags = _transcripts(transcripts, n_utts, network, optional)
     total_words = int(word_offs[-1])
-    D = 0 if feats is None else int(feats.shape[1])
-    ls, lt, lx, _ = network.device(dev)
+    if layout == "gmm" and D != network.D:
+        raise ValueError(f"the utterances have {D} features, the models {network.D}")
+    W, S, M = network.W, network.S, int(network.pack.M) if layout == "gmm" else 0
+    ls, lt, lx, pack = network.device(dev)
+    # per layout: the entry's stem, what its size and width functions take in front of D, its arguments behind D
+    entry, size_shape, width_shape, lead = {
+        "diag": ("sapr_connected_embed", (S,), (S,), ()),
+        "full": ("sapr_connected_embed_full", (W, S), (S,), ()),
+        "gmm": ("sapr_connected_embed_gmm", (W, S, M), (S, M), (_lib.ptr(pack), M)),
+    }[layout]
     words_dev = torch.from_numpy(words).to(dev)
     word_offs_dev = torch.from_numpy(word_offs).to(dev)
-    ws_bytes = embed_workspace_bytes(total, n_utts, total_words, max_words, network.S, D)
-    workspace = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    flags_dev = None if flags is None else torch.from_numpy(flags).to(dev)
+    workspace, ws_bytes = _workspace(entry + "_workspace_bytes", dev, total, n_utts, total_words, max_words,
+                                     *size_shape, D)
     loglik = torch.empty(n_utts, dtype=torch.float64, device=dev)
-    stats = torch.empty((network.W, embed_stats_width(network.S, D)), dtype=torch.float64, device=dev) \
+    stats = torch.empty((W, _stats_width(entry + "_stats_width", *width_shape, D)), dtype=torch.float64, device=dev) \
         if want_stats else None
     post = torch.zeros((total, max_words * network.SP), dtype=torch.float64, device=dev) if want_post else None
-    _lib.check(getattr(_lib.load(), "sapr_connected_embed" + sfx)(
-        _lib.ptr(logb), _lib.ptr(feats), D, _lib.ptr(offs_dev), n_utts, total, _lib.ptr(words_dev),
-        _lib.ptr(word_offs_dev), *flag, total_words, max_words, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx),
-        network.word_penalty, network.W, network.S, _lib.ptr(workspace), ws_bytes, _lib.ptr(loglik), _lib.ptr(stats),
-        _lib.ptr(post), _lib.current_stream()), "sapr_connected_embed" + sfx)
+    _lib.check(getattr(_lib.load(), entry + "_opt")(
+        _lib.ptr(logb), _lib.ptr(feats), D, *lead, _lib.ptr(offs_dev), n_utts, total, _lib.ptr(words_dev),
+        _lib.ptr(word_offs_dev), _lib.ptr(flags_dev), total_words, max_words, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx),
+        network.word_penalty, W, S, _lib.ptr(workspace), ws_bytes, _lib.ptr(loglik), _lib.ptr(stats), _lib.ptr(post),
+        _lib.current_stream()), entry + ("" if flags is None else "_opt"))
     host = [None if a is None else a.cpu().numpy() for a in (loglik, stats, post)]
-    return EmbeddedStats(*host, offsets=offs, word_offsets=word_offs, words=words, S=network.S, SP=network.SP, D=D,
-                         n_states=tuple(network.n_states))
-
-
-def _run_embed_full(logb, feats, offs_dev, offs, transcripts, network, want_post, optional=None) -> EmbeddedStats:
-    """One ``sapr_connected_embed_full`` over device ``logb[total_frames, R]`` and device ``feats``."""
-    torch = _torch()
-    dev = logb.device
-    n_utts, total = int(offs.size - 1), int(offs[-1])
-    words, word_offs, max_words, sfx, flag, _keep = _flag_args(transcripts, n_utts, network, optional, dev)
-    total_words = int(word_offs[-1])
-    D = int(feats.shape[1])
-    ls, lt, lx, _ = network.device(dev)
-    words_dev = torch.from_numpy(words).to(dev)
-    word_offs_dev = torch.from_numpy(word_offs).to(dev)
-    ws_bytes = embed_full_workspace_bytes(total, n_utts, total_words, max_words, network.W, network.S, D)
-    workspace = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    loglik = torch.empty(n_utts, dtype=torch.float64, device=dev)
-    stats = torch.empty((network.W, embed_full_stats_width(network.S, D)), dtype=torch.float64, device=dev)
-    post = torch.zeros((total, max_words * network.SP), dtype=torch.float64, device=dev) if want_post else None
-    _lib.check(getattr(_lib.load(), "sapr_connected_embed_full" + sfx)(
-        _lib.ptr(logb), _lib.ptr(feats), D, _lib.ptr(offs_dev), n_utts, total, _lib.ptr(words_dev),
-        _lib.ptr(word_offs_dev), *flag, total_words, max_words, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx),
-        network.word_penalty, network.W, network.S, _lib.ptr(workspace), ws_bytes, _lib.ptr(loglik), _lib.ptr(stats),
-        _lib.ptr(post), _lib.current_stream()), "sapr_connected_embed_full" + sfx)
-    host = [None if a is None else a.cpu().numpy() for a in (loglik, stats, post)]
-    return EmbeddedStats(*host, offsets=offs, word_offsets=word_offs, words=words, S=network.S, SP=network.SP, D=D,
-                         n_states=tuple(network.n_states), layout="full")
-
-
-def _run_embed_gmm(logb, feats, offs_dev, offs, transcripts, network, want_post, optional=None) -> EmbeddedStats:
-    """One ``sapr_connected_embed_gmm`` over device ``logb[total_frames, R]``, device ``feats`` and the network's
-    ``GmmPack`` as the emission read it."""
-    torch = _torch()
-    dev = logb.device
-    n_utts, total = int(offs.size - 1), int(offs[-1])
-    words, word_offs, max_words, sfx, flag, _keep = _flag_args(transcripts, n_utts, network, optional, dev)
-    total_words = int(word_offs[-1])
-    D, M = int(feats.shape[1]), int(network.pack.M)
-    if D != network.D:
-        raise ValueError(f"the utterances have {D} features, the models {network.D}")
-    ls, lt, lx, pack = network.device(dev)
-    words_dev = torch.from_numpy(words).to(dev)
-    word_offs_dev = torch.from_numpy(word_offs).to(dev)
-    ws_bytes = embed_gmm_workspace_bytes(total, n_utts, total_words, max_words, network.W, network.S, M, D)
-    workspace = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    loglik = torch.empty(n_utts, dtype=torch.float64, device=dev)
-    stats = torch.empty((network.W, embed_gmm_stats_width(network.S, M, D)), dtype=torch.float64, device=dev)
-    post = torch.zeros((total, max_words * network.SP), dtype=torch.float64, device=dev) if want_post else None
-    _lib.check(getattr(_lib.load(), "sapr_connected_embed_gmm" + sfx)(
-        _lib.ptr(logb), _lib.ptr(feats), D, _lib.ptr(pack), M, _lib.ptr(offs_dev), n_utts, total, _lib.ptr(words_dev),
-        _lib.ptr(word_offs_dev), *flag, total_words, max_words, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx),
-        network.word_penalty, network.W, network.S, _lib.ptr(workspace), ws_bytes, _lib.ptr(loglik), _lib.ptr(stats),
-        _lib.ptr(post), _lib.current_stream()), "sapr_connected_embed_gmm" + sfx)
-    host = [None if a is None else a.cpu().numpy() for a in (loglik, stats, post)]
-    return EmbeddedStats(*host, offsets=offs, word_offsets=word_offs, words=words, S=network.S, SP=network.SP, D=D,
-                         n_states=tuple(network.n_states), layout="gmm", M=M)
+    return EmbeddedStats(*host, offsets=offs, word_offsets=word_offs, words=words, S=S, SP=network.SP, D=D,
+                         n_states=tuple(network.n_states), layout=layout, M=M)
 
 
 def _refuse_stats(network, second_moments=False, mixtures=False):
@@ -1226,13 +1160,9 @@ def embedded_forward_backward(logb, lengths, transcripts, network: ConnectedNetw
                          f"[sum(lengths), D] with D >= 1")
     dev = _lib.require_gpu()
     total = int(offs[-1])
-    logb = _flat_logb(logb, total, network, dev)
+    logb = _flat_states(logb, total, network, dev)
     if feats is not None:
-        if not torch.is_tensor(feats):
-            feats = torch.from_numpy(np.ascontiguousarray(feats, dtype=np.float32))
-        feats = feats.to(dev).contiguous()
-        if feats.dtype != torch.float32 or feats.dim() != 2 or int(feats.shape[0]) != total:
-            raise ValueError("feats must be float32 [sum(lengths), D]")
+        feats = _flat_feats(feats, total, dev)
         if int(feats.shape[1]) == 0:
             feats = None
     return _run_embed(logb, feats, torch.from_numpy(offs).to(dev), offs, transcripts, network, True, want_post,
@@ -1249,12 +1179,11 @@ def embedded_estep(batch_or_feature_list, transcripts, network: ConnectedNetwork
     statistics of a "gmm" network carry ``post_mix`` and the per-component ``obs`` / ``obs**2``
     (``sapr_connected_embed_gmm``), what ``gmm_hmm.gmm_m_step`` reads; on another family, or together with
     ``second_moments=True``, the switch is a ``ValueError``.  ``optional``: the flags :func:`align_viterbi` takes."""
-    b = batch_or_feature_list
-    n_utts = len(b.lengths) if hasattr(b, "offsets") and hasattr(b, "order") else len(b)
-    _transcripts(transcripts, n_utts, network, optional)  # (refused before a device is asked for)
+    # (refused before a device is asked for)
+    _transcripts(transcripts, _n_utts(batch_or_feature_list), network, optional)
     if want_stats or mixtures:
         _refuse_stats(network, second_moments, mixtures)
-    feats, offs_dev, offs = _features(b)
+    feats, offs_dev, offs = _features(batch_or_feature_list)
     logb = _EMIT[network.family](feats, network)
     return _run_embed(logb, feats if want_stats else None, offs_dev, offs, transcripts, network, want_stats, want_post,
                       second_moments, mixtures, optional)
@@ -1268,38 +1197,6 @@ def _diag_of_moments(st, covariance_type):
         st = dict(st)
         st["obs**2"] = np.ascontiguousarray(np.diagonal(st["obs*obs.T"], axis1=1, axis2=2))
     return st
-
-
-def _embedded_fit_gmm(models, features, transcripts, n_iter, tol, exit_states, word_penalty, names, optional=None):
-    """:func:`embedded_fit` over ``GMMHMM`` word models."""
-    from .gmm_hmm import gmm_m_step
-    from .hmmlearn_hmm import ConvergenceMonitor
-
-    def network():
-        # (packing validates every model and notes the feature width on the object: done on shallow copies, so that a
-        # word that is never trained keeps its bytes)
-        return ConnectedNetwork.from_models([copy.copy(m) for m in models], exit_states, word_penalty, names, "gmmhmm")
-
-    net = network()
-    _transcripts(transcripts, len(features), net, optional)  # (refused before a device is asked for)
-    feats, offs_dev, offs = _features(features)
-    monitor = ConvergenceMonitor(tol, n_iter)
-    for _ in range(n_iter):
-        net = network()
-        res = _run_embed(emit_gmm(feats, net), feats, offs_dev, offs, transcripts, net, True, False, mixtures=True,
-                         optional=optional)
-        for w, m in enumerate(models):
-            st = res.split(w)
-            if st["nobs"] == 0:
-                continue
-            m.startprob_, m.transmat_, m.weights_, m.means_, m.covars_ = gmm_m_step(
-                st, m.startprob_, m.transmat_, m.weights_, m.means_, m.covars_, m.params, m.startprob_prior,
-                m.transmat_prior, m.weights_prior, m.means_prior, m.means_weight, m.covars_prior, m.covars_weight,
-                m.min_covar)
-        monitor.report(float(res.loglik[np.isfinite(res.loglik)].sum()))
-        if monitor.converged:
-            break
-    return list(monitor.history)
 
 
 def embedded_fit(models, features, transcripts, n_iter=10, tol=1e-2, exit_states="last", word_penalty=0.0,
@@ -1326,21 +1223,39 @@ def embedded_fit(models, features, transcripts, n_iter=10, tol=1e-2, exit_states
     family goes through its ``_opt`` entry point."""
     from .hmmlearn_hmm import ConvergenceMonitor, m_step_typed
     models = list(models)
-    if vocabulary_family(models, names, None) == "gmm":
+    family = vocabulary_family(models, names, None)
+    if family == "gmm":
         if second_moments:
             raise ValueError("second_moments=True serves GaussianHMM vocabularies; GMMHMM word models train on "
                              "mixture responsibilities")
-        return _embedded_fit_gmm(models, features, transcripts, n_iter, tol, exit_states, word_penalty, names,
-                                 optional)
-    family = vocabulary_family(models, names, "hmmlearn")
-    if family != "diag" and not second_moments:
-        raise ValueError("embedded_fit serves 'diag' and 'spherical' GaussianHMM vocabularies by default: a 'full' or "
-                         "'tied' model needs second-moment matrices, which second_moments=True accumulates")
+    else:
+        family = vocabulary_family(models, names, "hmmlearn")
+        if family != "diag" and not second_moments:
+            raise ValueError("embedded_fit serves 'diag' and 'spherical' GaussianHMM vocabularies by default: a 'full' "
+                             "or 'tied' model needs second-moment matrices, which second_moments=True accumulates")
+    gmm = family == "gmm"
+
     def network():
-        # (packing a 'full' vocabulary validates every model and notes what it found on the object: done on shallow
-        # copies, so that a word that is never trained keeps its bytes)
+        # (packing a 'gmm' or 'full' vocabulary validates every model and notes what it found on the object: done on
+        # shallow copies, so that a word that is never trained keeps its bytes)
         return ConnectedNetwork.from_models(models if family == "diag" else [copy.copy(m) for m in models],
-                                            exit_states, word_penalty, names, "hmmlearn")
+                                            exit_states, word_penalty, names, "gmmhmm" if gmm else "hmmlearn")
+
+    def m_step(m, st):
+        """The one family-specific piece: a model's new parameters from its statistics dict, by its own M-step."""
+        if gmm:
+            from .gmm_hmm import gmm_m_step
+            m.startprob_, m.transmat_, m.weights_, m.means_, m.covars_ = gmm_m_step(
+                st, m.startprob_, m.transmat_, m.weights_, m.means_, m.covars_, m.params, m.startprob_prior,
+                m.transmat_prior, m.weights_prior, m.means_prior, m.means_weight, m.covars_prior, m.covars_weight,
+                m.min_covar)
+            return
+        if second_moments:
+            st = _diag_of_moments(st, m.covariance_type)
+        m.startprob_, m.transmat_, m.means_, m._covars_ = m_step_typed(
+            st, m.covariance_type, m.startprob_, m.transmat_, m.params, m.startprob_prior, m.transmat_prior,
+            m.means_prior, m.means_weight, m.covars_prior, m.covars_weight, np.asarray(m.means_, dtype=np.float64),
+            np.asarray(m._covars_, dtype=np.float64))
 
     net = network()
     _transcripts(transcripts, len(features), net, optional)  # (refused before a device is asked for)
@@ -1349,17 +1264,11 @@ def embedded_fit(models, features, transcripts, n_iter=10, tol=1e-2, exit_states
     for _ in range(n_iter):
         net = network()
         res = _run_embed(_EMIT[net.family](feats, net), feats, offs_dev, offs, transcripts, net, True, False,
-                         second_moments, optional=optional)
+                         second_moments, gmm, optional)
         for w, m in enumerate(models):
             st = res.split(w)
-            if second_moments:
-                st = _diag_of_moments(st, m.covariance_type)
-            if st["nobs"] == 0:
-                continue
-            m.startprob_, m.transmat_, m.means_, m._covars_ = m_step_typed(
-                st, m.covariance_type, m.startprob_, m.transmat_, m.params, m.startprob_prior, m.transmat_prior,
-                m.means_prior, m.means_weight, m.covars_prior, m.covars_weight, np.asarray(m.means_, dtype=np.float64),
-                np.asarray(m._covars_, dtype=np.float64))
+            if st["nobs"] != 0:  # (a word that never occurs stays untouched)
+                m_step(m, st)
         monitor.report(float(res.loglik[np.isfinite(res.loglik)].sum()))
         if monitor.converged:
             break
@@ -1377,8 +1286,8 @@ def _run_loop_stats(post, feats, offs_dev, n_utts, total, network, keep_dev=None
     torch = _torch()
     dev = post.device
     D = int(feats.shape[1])
-    ws_bytes = loop_stats_workspace_bytes(total, n_utts, network.W, network.S, D)
-    workspace = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    workspace, ws_bytes = _workspace("sapr_connected_loop_stats_workspace_bytes", dev, total, n_utts, network.W,
+                                     network.S, D)
     stats = torch.empty((network.W, embed_stats_width(network.S, D)), dtype=torch.float64, device=dev)
     _lib.check(_lib.load().sapr_connected_loop_stats(
         _lib.ptr(post), _lib.ptr(feats), D, _lib.ptr(offs_dev), n_utts, total, _lib.ptr(keep_dev), network.W,
@@ -1408,25 +1317,8 @@ def loop_stats(post, feats, lengths, network: ConnectedNetwork, keep=None) -> np
     n_utts, total = int(lengths.size), int(offs[-1])
     keep = _keep_flags(keep, n_utts)
     dev = _lib.require_gpu()
-    if not torch.is_tensor(post):
-        post = torch.from_numpy(np.ascontiguousarray(post, dtype=np.float64))
-    post = post.to(dev)
-    W, S, SP, R = network.W, network.S, network.SP, network.R
-    if post.dtype != torch.float64 or int(post.shape[0]) != total:
-        raise ValueError("post must be float64 with sum(lengths) rows")
-    if tuple(post.shape[1:]) == (W, S) and S != SP:
-        wide = torch.zeros((total, W, SP), dtype=torch.float64, device=dev)
-        wide[:, :, :S] = post
-        post = wide
-    if tuple(post.shape[1:]) not in ((W, SP), (R,)):
-        raise ValueError(f"post must be [total_frames, {W}, {S}], [total_frames, {W}, {SP}] or [total_frames, {R}]; "
-                         f"got {tuple(post.shape)}")
-    post = post.reshape(total, R).contiguous()
-    if not torch.is_tensor(feats):
-        feats = torch.from_numpy(np.ascontiguousarray(feats, dtype=np.float32))
-    feats = feats.to(dev).contiguous()
-    if feats.dtype != torch.float32 or feats.dim() != 2 or int(feats.shape[0]) != total or int(feats.shape[1]) < 1:
-        raise ValueError("feats must be float32 [sum(lengths), D] with D >= 1")
+    post = _flat_states(post, total, network, dev, 0.0, "post")
+    feats = _flat_feats(feats, total, dev, 1)
     keep_dev = None if keep is None else torch.from_numpy(keep).to(dev)
     return _run_loop_stats(post, feats, torch.from_numpy(offs).to(dev), n_utts, total, network, keep_dev).cpu().numpy()
 
@@ -1501,14 +1393,13 @@ def mmi_estep(batch_or_feature_list, transcripts, network: ConnectedNetwork, aco
     offered (the transcript's language-model score would depend on the path)."""
     import dataclasses
     torch = _torch()
-    b = batch_or_feature_list
-    n_utts = len(b.lengths) if hasattr(b, "offsets") and hasattr(b, "order") else len(b)
+    n_utts = _n_utts(batch_or_feature_list)
     scale = float(acoustic_scale)
     if not (scale > 0.0 and np.isfinite(scale)):
         raise ValueError(f"acoustic_scale must be a positive number, got {acoustic_scale!r}")
     _refuse_mmi_family(network.family)
     lmscore = _check_mmi_transcripts(transcripts, n_utts, network)  # (refused before a device is asked for)
-    feats, offs_dev, offs = _features(b)
+    feats, offs_dev, offs = _features(batch_or_feature_list)
     total = int(offs[-1])
     logb = emit_diag(feats, network)
     if scale != 1.0:

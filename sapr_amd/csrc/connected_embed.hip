@@ -1067,6 +1067,45 @@ extern "C" int sapr_connected_embed_full_workspace_bytes(int64_t total_frames, i
   return 0;
 }
 
+// The host body the two entries with wider rows share ("full": obs*obs.T, "gmm": the per-component sums), after each
+// entry's own size and shape checks: the workspace and pointer checks, the carve, sapr_connected_embed itself on the
+// front of the workspace, one accumulation kernel over (groups, W) and the fold.  P: the doubles of a row behind its
+// head; what: the word for the D >= 1 message; missing: an entry's own NULL-pointer refusal, or NULL; launch(grid, st,
+// gamma, SP, per, part) launches the entry's accumulation kernel.
+template <typename Launch>
+static int embed_wide_rows(const double *logb, const float *feats, int32_t D, const int64_t *offsets, int64_t n_utts,
+                           int64_t total_frames, const int32_t *words, const int64_t *word_offsets,
+                           const uint8_t *optional, int64_t total_words, int32_t max_words, const double *log_start,
+                           const double *log_trans, const double *log_exit, double word_penalty, int32_t W, int32_t S,
+                           void *workspace, size_t workspace_bytes, double *loglik, double *stats, double *post,
+                           void *stream, size_t P, const char *what, const char *missing, Launch &&launch) {
+  const size_t need = em_full_carve(nullptr, total_frames, n_utts, total_words, max_words, W, S, P).bytes;
+  SAPR_REQUIRE(workspace_bytes >= need && (need == 0 || workspace), "workspace too small: %zu < %zu", workspace_bytes,
+               need);
+  SAPR_REQUIRE(!stats || D >= 1, "the %s need D >= 1 (got D=%d)", what, D);
+  SAPR_REQUIRE(!missing, "%s", missing);
+  SAPR_REQUIRE(!stats || n_utts == 0 || total_frames == 0 || feats, "NULL pointer argument");
+  const EmFullWorkspace ws = em_full_carve(workspace, total_frames, n_utts, total_words, max_words, W, S, P);
+  // the recursions, loglik, post and the head of the row: sapr_connected_embed itself on the front of the workspace,
+  // without features (the head does not depend on them); gamma stays behind in the workspace
+  if (int rc = sapr_connected_embed_opt(logb, nullptr, 0, offsets, n_utts, total_frames, words, word_offsets, optional,
+                                        total_words, max_words, log_start, log_trans, log_exit, word_penalty, W, S,
+                                        workspace, ws.base_bytes, loglik, stats ? ws.head : nullptr, post, stream))
+    return rc;
+  if (n_utts == 0 || !stats) return 0;
+  hipStream_t st = as_stream(stream);
+  const int64_t groups = em_full_groups(n_utts), per = em_full_group_utts(n_utts);
+  launch(dim3(static_cast<unsigned>(groups), static_cast<unsigned>(W)), st, static_cast<const double *>(workspace),
+         sp_of(S), per, ws.part);
+  SAPR_HIP_TRY(hipGetLastError());
+  const int32_t hw = static_cast<int32_t>(em_head_width(S));
+  const unsigned tiles = static_cast<unsigned>((hw + P + kXBlock - 1) / kXBlock);
+  SAPR_LAUNCH(embed_full_fold_kernel, dim3(tiles, static_cast<unsigned>(W)), dim3(kXBlock), 0, st, ws.head, ws.part,
+              groups, W, hw, static_cast<int32_t>(P), stats);
+  SAPR_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 extern "C" int sapr_connected_embed_full_opt(const double *logb, const float *feats, int32_t D,
                                              const int64_t *offsets, int64_t n_utts, int64_t total_frames,
                                              const int32_t *words, const int64_t *word_offsets,
@@ -1080,43 +1119,21 @@ extern "C" int sapr_connected_embed_full_opt(const double *logb, const float *fe
                (long long)n_utts, (long long)total_frames, (long long)total_words, max_words, W, S, D);
   if (int rc = em_check_shape(W, S, max_words)) return rc;
   if (int rc = em_check_dims(D)) return rc;
-  size_t need = 0;
-  if (int rc = sapr_connected_embed_full_workspace_bytes(total_frames, n_utts, total_words, max_words, W, S, D, &need))
-    return rc;
-  SAPR_REQUIRE(workspace_bytes >= need && (need == 0 || workspace), "workspace too small: %zu < %zu", workspace_bytes,
-               need);
-  SAPR_REQUIRE(!stats || D >= 1, "the second moments need D >= 1 (got D=%d)", D);
-  SAPR_REQUIRE(!stats || n_utts == 0 || total_frames == 0 || feats, "NULL pointer argument");
-  const EmFullWorkspace ws =
-      em_full_carve(workspace, total_frames, n_utts, total_words, max_words, W, S, em_full_p(S, D));
-  // the recursions, loglik, post and the head of the row: sapr_connected_embed itself on the front of the workspace,
-  // without features (the head does not depend on them); gamma stays behind in the workspace
-  if (int rc = sapr_connected_embed_opt(logb, nullptr, 0, offsets, n_utts, total_frames, words, word_offsets, optional,
-                                        total_words, max_words, log_start, log_trans, log_exit, word_penalty, W, S,
-                                        workspace, ws.base_bytes, loglik, stats ? ws.head : nullptr, post, stream))
-    return rc;
-  if (n_utts == 0 || !stats) return 0;
-  hipStream_t st = as_stream(stream);
-  const int32_t SP = sp_of(S);
-  const int64_t groups = em_full_groups(n_utts), per = em_full_group_utts(n_utts);
-  const double *gamma = static_cast<const double *>(workspace);
-  const dim3 grid(static_cast<unsigned>(groups), static_cast<unsigned>(W));
+  return embed_wide_rows(
+      logb, feats, D, offsets, n_utts, total_frames, words, word_offsets, optional, total_words, max_words, log_start,
+      log_trans, log_exit, word_penalty, W, S, workspace, workspace_bytes, loglik, stats, post, stream,
+      em_full_p(S, D), "second moments", nullptr,
+      [&](dim3 grid, hipStream_t st, const double *gamma, int32_t SP, int64_t per, double *part) {
 #define SAPR_EM_FULL_ACCUM(DP)                                                                                        \
   SAPR_LAUNCH(embed_full_accum_kernel<DP>, grid, dim3(kXBlock), 0, st, gamma, feats, D, offsets, n_utts,            \
-              total_frames, words, word_offsets, total_words, max_words, W, S, SP, per, loglik, ws.part)
-  switch (dp_of(D)) {
-    case 13: SAPR_EM_FULL_ACCUM(13); break;
-    case 26: SAPR_EM_FULL_ACCUM(26); break;
-    default: SAPR_EM_FULL_ACCUM(39); break;
-  }
+              total_frames, words, word_offsets, total_words, max_words, W, S, SP, per, loglik, part)
+        switch (dp_of(D)) {
+          case 13: SAPR_EM_FULL_ACCUM(13); break;
+          case 26: SAPR_EM_FULL_ACCUM(26); break;
+          default: SAPR_EM_FULL_ACCUM(39); break;
+        }
 #undef SAPR_EM_FULL_ACCUM
-  SAPR_HIP_TRY(hipGetLastError());
-  const int32_t hw = static_cast<int32_t>(em_head_width(S)), P = static_cast<int32_t>(em_full_p(S, D));
-  const unsigned tiles = static_cast<unsigned>((hw + P + kXBlock - 1) / kXBlock);
-  SAPR_LAUNCH(embed_full_fold_kernel, dim3(tiles, static_cast<unsigned>(W)), dim3(kXBlock), 0, st, ws.head, ws.part,
-              groups, W, hw, P, stats);
-  SAPR_HIP_TRY(hipGetLastError());
-  return 0;
+      });
 }
 
 extern "C" int sapr_connected_embed_full(const double *logb, const float *feats, int32_t D, const int64_t *offsets,
@@ -1169,55 +1186,31 @@ extern "C" int sapr_connected_embed_gmm_opt(const double *logb, const float *fea
   if (int rc = em_check_shape(W, S, max_words)) return rc;
   if (int rc = em_check_dims(D)) return rc;
   if (int rc = check_shape(S, M, D)) return rc;
-  size_t need = 0;
-  if (int rc =
-          sapr_connected_embed_gmm_workspace_bytes(total_frames, n_utts, total_words, max_words, W, S, M, D, &need))
-    return rc;
-  SAPR_REQUIRE(workspace_bytes >= need && (need == 0 || workspace), "workspace too small: %zu < %zu", workspace_bytes,
-               need);
-  SAPR_REQUIRE(!stats || D >= 1, "the mixture statistics need D >= 1 (got D=%d)", D);
-  SAPR_REQUIRE(!stats || n_utts == 0 || pack, "NULL pointer argument (pack)");
-  SAPR_REQUIRE(!stats || n_utts == 0 || total_frames == 0 || feats, "NULL pointer argument");
-  const size_t P = em_gmm_p(S, M, D);
-  const EmFullWorkspace ws = em_full_carve(workspace, total_frames, n_utts, total_words, max_words, W, S, P);
-  // as sapr_connected_embed_full: the recursions, loglik, post and the head of the row are sapr_connected_embed itself
-  // on the front of the workspace, without features; gamma stays behind in the workspace
-  if (int rc = sapr_connected_embed_opt(logb, nullptr, 0, offsets, n_utts, total_frames, words, word_offsets, optional,
-                                        total_words, max_words, log_start, log_trans, log_exit, word_penalty, W, S,
-                                        workspace, ws.base_bytes, loglik, stats ? ws.head : nullptr, post, stream))
-    return rc;
-  if (n_utts == 0 || !stats) return 0;
-  hipStream_t st = as_stream(stream);
-  const int32_t SP = sp_of(S);
-  const int64_t groups = em_full_groups(n_utts), per = em_full_group_utts(n_utts);
-  const int64_t stride = static_cast<int64_t>(model_doubles(SP, mp_of(M), dp_of(D)));
-  const double *gamma = static_cast<const double *>(workspace);
-  const dim3 grid(static_cast<unsigned>(groups), static_cast<unsigned>(W));
+  const char *missing = !stats || n_utts == 0 || pack ? nullptr : "NULL pointer argument (pack)";
+  const int64_t stride = static_cast<int64_t>(model_doubles(sp_of(S), mp_of(M), dp_of(D)));
+  return embed_wide_rows(
+      logb, feats, D, offsets, n_utts, total_frames, words, word_offsets, optional, total_words, max_words, log_start,
+      log_trans, log_exit, word_penalty, W, S, workspace, workspace_bytes, loglik, stats, post, stream,
+      em_gmm_p(S, M, D), "mixture statistics", missing,
+      [&](dim3 grid, hipStream_t st, const double *gamma, int32_t SP, int64_t per, double *part) {
 #define SAPR_EM_GMM_ACCUM(MP, DP)                                                                                     \
   SAPR_LAUNCH((embed_gmm_accum_kernel<MP, DP>), grid, dim3(kXBlock), 0, st, gamma, feats, D, pack, stride, M,        \
-              offsets, n_utts, total_frames, words, word_offsets, total_words, max_words, W, S, SP, per, loglik,      \
-              ws.part)
+              offsets, n_utts, total_frames, words, word_offsets, total_words, max_words, W, S, SP, per, loglik, part)
 #define SAPR_EM_GMM_ACCUM_DP(MP)                                                                                      \
   switch (dp_of(D)) {                                                                                                 \
     case 13: SAPR_EM_GMM_ACCUM(MP, 13); break;                                                                        \
     case 26: SAPR_EM_GMM_ACCUM(MP, 26); break;                                                                        \
     default: SAPR_EM_GMM_ACCUM(MP, 39); break;                                                                        \
   }
-  switch (mp_of(M)) {
-    case 1: SAPR_EM_GMM_ACCUM_DP(1); break;
-    case 2: SAPR_EM_GMM_ACCUM_DP(2); break;
-    case 4: SAPR_EM_GMM_ACCUM_DP(4); break;
-    default: SAPR_EM_GMM_ACCUM_DP(8); break;
-  }
+        switch (mp_of(M)) {
+          case 1: SAPR_EM_GMM_ACCUM_DP(1); break;
+          case 2: SAPR_EM_GMM_ACCUM_DP(2); break;
+          case 4: SAPR_EM_GMM_ACCUM_DP(4); break;
+          default: SAPR_EM_GMM_ACCUM_DP(8); break;
+        }
 #undef SAPR_EM_GMM_ACCUM_DP
 #undef SAPR_EM_GMM_ACCUM
-  SAPR_HIP_TRY(hipGetLastError());
-  const int32_t hw = static_cast<int32_t>(em_head_width(S));
-  const unsigned tiles = static_cast<unsigned>((hw + P + kXBlock - 1) / kXBlock);
-  SAPR_LAUNCH(embed_full_fold_kernel, dim3(tiles, static_cast<unsigned>(W)), dim3(kXBlock), 0, st, ws.head, ws.part,
-              groups, W, hw, static_cast<int32_t>(P), stats);
-  SAPR_HIP_TRY(hipGetLastError());
-  return 0;
+      });
 }
 
 extern "C" int sapr_connected_embed_gmm(const double *logb, const float *feats, int32_t D, const double *pack,

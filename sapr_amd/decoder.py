@@ -218,6 +218,24 @@ class Decoder:
                              f"({', '.join(words)})")
         return words.index(optional_silence)
 
+    def _transcript_rows(self, transcripts, optional_silence=None):
+        """Transcripts of word names -> ``(rows, flags, said)``: ``said`` is one row of vocabulary indices per
+        transcript, and without ``optional_silence`` ``rows`` is ``said`` and ``flags`` ``None``; with it they are
+        ``connected.with_optional(said, that word's index)``."""
+        words = list(self.models)
+        index = {w: i for i, w in enumerate(words)}
+        said = []
+        for u, names in enumerate(transcripts):
+            for name in names:
+                if name not in index:
+                    raise ValueError(f"the transcript of utterance {u} names {name!r}, which is not in the vocabulary "
+                                     f"({', '.join(words)})")
+            said.append([index[name] for name in names])
+        if optional_silence is None:
+            return said, None, said
+        from .connected import with_optional
+        return (*with_optional(said, self._silence_index(optional_silence)), said)
+
     def align(self, feature_list: List[np.ndarray], transcripts, word_penalty: float = 0.0,
               exit_states="last", optional_silence=None) -> List[Dict]:
         """Forced alignment: the words of every recording are known (``transcripts``: one list of word names per
@@ -243,19 +261,7 @@ class Decoder:
         if len(feature_list) == 0:
             raise ValueError("empty utterance list")
         words = list(self.models)
-        index = {w: i for i, w in enumerate(words)}
-        rows = []
-        for u, names in enumerate(transcripts):
-            for name in names:
-                if name not in index:
-                    raise ValueError(f"the transcript of utterance {u} names {name!r}, which is not in the vocabulary "
-                                     f"({', '.join(words)})")
-            rows.append([index[name] for name in names])
-        flags = None
-        if optional_silence is not None:
-            from .connected import with_optional
-            said = rows
-            rows, flags = with_optional(rows, self._silence_index(optional_silence))
+        rows, flags, said = self._transcript_rows(transcripts, optional_silence)
         net = self._connected_network(exit_states, word_penalty)
         res = connected_align([np.asarray(f).T for f in feature_list], rows, net, flags)
         out = []
@@ -292,18 +298,7 @@ class Decoder:
         if len(feature_list) == 0:
             raise ValueError("empty utterance list")
         words = list(self.models)
-        index = {w: i for i, w in enumerate(words)}
-        rows = []
-        for u, names in enumerate(transcripts):
-            for name in names:
-                if name not in index:
-                    raise ValueError(f"the transcript of utterance {u} names {name!r}, which is not in the vocabulary "
-                                     f"({', '.join(words)})")
-            rows.append([index[name] for name in names])
-        flags = None
-        if optional_silence is not None:
-            from .connected import with_optional
-            rows, flags = with_optional(rows, self._silence_index(optional_silence))
+        rows, flags, _ = self._transcript_rows(transcripts, optional_silence)
         history = embedded_fit(self._model_list(), [np.asarray(f).T for f in feature_list], rows, n_iter=n_iter,
                                tol=tol, exit_states=exit_states, word_penalty=word_penalty, names=words,
                                second_moments=self._is_full(), optional=flags)
@@ -339,14 +334,7 @@ class Decoder:
         if len(feature_list) == 0:
             raise ValueError("empty utterance list")
         words = list(self.models)
-        index = {w: i for i, w in enumerate(words)}
-        rows = []
-        for u, names in enumerate(transcripts):
-            for name in names:
-                if name not in index:
-                    raise ValueError(f"the transcript of utterance {u} names {name!r}, which is not in the vocabulary "
-                                     f"({', '.join(words)})")
-            rows.append([index[name] for name in names])
+        rows, _, _ = self._transcript_rows(transcripts)
         history = mmi_fit(self._model_list(), [np.asarray(f).T for f in feature_list], rows,
                           bigram=None if bigram is None else self._word_bigram(bigram), n_iter=n_iter, E=E, tau=tau,
                           acoustic_scale=acoustic_scale, exit_states=exit_states, word_penalty=word_penalty,
