@@ -595,6 +595,52 @@ int sapr_connected_levels_backtrace(const int64_t *offsets, int64_t n_utts, int6
                                     uint8_t *path_entry /* may be NULL */, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Connected-word N-best (csrc/connected_nbest.hip): the n_best <= 8 best DISTINCT word strings of every utterance with
+ * their Viterbi scores, in one recursion over the word loop of sapr_connected_bigram, without a back-pointer workspace.
+ * The definition is the CPU restatement tests/_nbest_ref.py.  A hypothesis is a pair (score: float64, code: uint64);
+ * code is the word string so far, the current word included: the string w_0 .. w_{k-1} has
+ * code = sum (w_i + 1) * B^(k-1-i) with B = W + 1, appending w is code * B + (w + 1), and cap(W) is the largest K with
+ * B^K <= 2^64 (sapr_connected_nbest_capacity: 17 at W = 11, 10 at W = 64, 40 at W = 2).  merge_n(cands) is a function
+ * of the candidates' values alone: 1. drop every candidate whose score is not > -inf (this drops -inf and NaN);
+ * 2. among candidates with equal code keep the largest score; 3. order by score descending, then code ascending;
+ * 4. keep the first n = n_best.  With b_t(w,j) = logb[t][w * SP + j], every + applying to each hypothesis's score and
+ * leaving its code alone unless said otherwise:
+ *     cell_0(w,j) = merge_n{ ((lm_start[w] + log_start[w][j]), w + 1) }                      then + b_0(w,j)
+ *     X_t(v)      = merge_n{ h + log_exit[v][s]        : s, h in cell_t(v,s) }
+ *     N_t(w)      = merge_n{ (h + lm[v][w], code * B + (w+1)) : v, h in X_t(v), code < B^(cap-1) }     t < T-1
+ *     cell_t(w,j) = merge_n( { h + log_trans[w][i][j] : i, h in cell_{t-1}(w,i) }
+ *                            U { h + log_start[w][j]  : h in N_{t-1}(w) } )                  then + b_t(w,j)
+ *     result      = merge_n{ h + lm_end[v]             : v, h in X_{T-1}(v) }
+ * A cell is the set AFTER b_t was added, with no re-sort and no drop; the next merge drops what became -inf.  overflow
+ * is 1 iff some candidate of an N_t had h + lm[v][w] > -inf and code >= B^(cap-1): that string would not fit and the
+ * candidate was dropped.  T = 0 gives an empty list.  Every addition is made in sapr_connected_bigram's order,
+ * ((delta + log_exit) + lm) + log_start, then + b, and adding a constant is monotone under rounding: rank 1 has
+ * sapr_connected_bigram's score bit for bit, and where no two of the top n_best + 1 string scores are equal and
+ * overflow is 0 the list is exactly the n_best best strings, each with the score of its own best path.
+ *   logb, offsets, log_start, log_trans, log_exit, lm, lm_start, lm_end, W, S: as for sapr_connected_bigram (same
+ *              layout, same limits)
+ *   n_best     1 .. 8
+ *   score      [n_utts][n_best]: best first, -inf padded
+ *   code       [n_utts][n_best]: the strings, 0 padded
+ *   n_found    [n_utts] int32, may be NULL: the strings found
+ *   overflow   [n_utts] uint8, may be NULL
+ * No workspace and no atomics: outputs are bit-identical from run to run, and an utterance's outputs are a function of
+ * its own frames and the tables alone; a NaN in logb drops hypotheses of its own utterance only.  Word boundaries of a
+ * returned string come from sapr_connected_align.
+ *
+ * Bad sizes and NULL required pointers (lm, lm_start, lm_end, score and code among them) return SAPR_ERR_ARG, S > 18,
+ * W * SP > 256 or n_best outside 1 .. 8 SAPR_ERR_UNSUPPORTED, all before any launch; n_utts == 0 returns 0 after the
+ * size, shape and language-model checks. */
+int sapr_connected_nbest(const double *logb, const int64_t *offsets, int64_t n_utts, int64_t total_frames,
+                         const double *log_start, const double *log_trans, const double *log_exit,
+                         const double *lm /* [W][W] */, const double *lm_start /* [W] */,
+                         const double *lm_end /* [W] */, int32_t W, int32_t S, int32_t n_best /* 1..8 */,
+                         double *score /* [n_utts][n_best], -inf padded */,
+                         uint64_t *code /* [n_utts][n_best], 0 padded */, int32_t *n_found /* may be NULL */,
+                         uint8_t *overflow /* may be NULL */, void *stream);
+int sapr_connected_nbest_capacity(int32_t W, int32_t *max_words); /* cap(W) */
+
+/* ------------------------------------------------------------------------------------
  * Connected-word confidence (csrc/connected_loop_fb.hip): forward-backward over the word loop under the word-pair
  * language model of sapr_connected_bigram — the sum over every word string the grammar allows where that function
  * takes the maximum.  The definition is the CPU restatement tests/_loop_fb_ref.py; with b_t(w,s) = logb[t][w * SP + s]

@@ -20,6 +20,12 @@ the best string of exactly k words for every k up to a bound of at most 8, and `
 walks back from a known count, a range of counts or each count in turn (:func:`connected_levels`,
 :class:`LevelResult`, ``connected_decode(..., n_words=, max_words=)``; the definition is ``tests/_levels_ref.py``).
 
+The alternatives a rescoring pass or a confirmation dialogue needs: ``sapr_connected_nbest``
+(``csrc/connected_nbest.hip``) returns the ``n_best <= 8`` best DISTINCT word strings of every utterance with their
+Viterbi scores, whatever their word counts, in one recursion over the same ``logb`` under the same language model and
+without a back-pointer workspace; forced alignment gives any of them its boundaries (:func:`connected_nbest`,
+:class:`NBestResult`, ``connected_decode(..., n_best=)``; the definition is ``tests/_nbest_ref.py``).
+
 How much to believe a decoded string: ``sapr_connected_posteriors`` (``csrc/connected_loop_fb.hip``) runs
 forward-backward over the same loop under the same language model — the sum over every word string where the search
 takes the best one — and returns the total log-likelihood, the per-frame word and word-boundary posteriors and, from
@@ -450,6 +456,7 @@ class ConnectedResult:
     posteriors: ConnectedPosteriors = None  # connected_decode(..., posteriors=True): over the same logb
     level_score: np.ndarray = None  # [N, L] f64: connected_decode(..., n_words= / max_words=): the best score per count
     levels: "LevelResult" = None    # ... and the recursion it was selected from (further back-traces, N-best strings)
+    nbest: "NBestResult" = None     # connected_decode(..., n_best=): the n best distinct strings over the same logb
 
     def segments(self, u):
         """``[(word_index, start, end_exclusive), ...]`` of utterance ``u``, frames counted from its own start."""
@@ -802,16 +809,136 @@ def connected_levels(logb, lengths, network: ConnectedNetwork, max_words) -> Lev
     return _run_levels(logb, torch.from_numpy(offs).to(dev), offs, network, L)
 
 
+# ---- the N best distinct word strings -------------------------------------------------------------
+MAX_NBEST = 8
+
+
+def _check_n_best(n_best) -> int:
+    if isinstance(n_best, bool) or not isinstance(n_best, (int, np.integer)) or not 1 <= int(n_best) <= MAX_NBEST:
+        raise ValueError(f"n_best must be an int inside 1..{MAX_NBEST} (the strings one list holds), got {n_best!r}")
+    return int(n_best)
+
+
+def nbest_capacity(W) -> int:
+    """``cap(W)``: the longest word string a 64-bit code holds, the largest K with ``(W + 1)**K <= 2**64``
+    (``sapr_connected_nbest_capacity``)."""
+    k = C.c_int32(0)
+    _lib.check(_lib.load().sapr_connected_nbest_capacity(int(W), C.byref(k)), "sapr_connected_nbest_capacity")
+    return int(k.value)
+
+
+class NBestResult:
+    """One N-best recursion (``sapr_connected_nbest``; the definition is ``tests/_nbest_ref.py``): per utterance the
+    ``n_best`` best distinct word strings with their Viterbi scores, best first.  The result keeps the device ``logb``
+    it was computed on: :meth:`align` gives any rank its word boundaries."""
+
+    def __init__(self, score, code, n_found, overflow, offsets, network, logb, offs_dev):
+        self.score = score        # [N, n] f64: best first, -inf padded
+        self.code = code          # [N, n] u64: the strings as base-(W + 1) numbers, 0 padded
+        self.n_found = n_found    # [N] i32: the strings found
+        self.overflow = overflow  # [N] bool: a string of nbest_capacity(W) words could not grow; the list may miss some
+        self.offsets = offsets    # [N + 1] i64
+        self._network, self._logb, self._offs_dev = network, logb, offs_dev
+        self._aligned = {}
+
+    def words(self, u, r):
+        """The word indices of rank ``r`` of utterance ``u``, first word first; ``[]`` where the list is shorter."""
+        code, B, out = int(self.code[u, r]), self._network.W + 1, []
+        while code:
+            out.append(code % B - 1)
+            code //= B
+        return out[::-1]
+
+    def strings(self, u):
+        """``[(score, words), ...]`` of utterance ``u``, best first."""
+        return [(float(self.score[u, r]), self.words(u, r)) for r in range(int(self.n_found[u]))]
+
+    def align(self, r) -> "RankAlignment":
+        """The word boundaries of rank ``r``, an :class:`AlignResult`: one forced alignment (:func:`align_viterbi`'s
+        kernel) over the kept ``logb`` for the utterances whose list has a rank ``r`` — ``result.utterances`` names
+        them, in order.  The
+        alignment's limit of ``max_words * SP <= 256`` chain positions applies here and only here.  The alignment's
+        score is the acoustic score of the string (with the network's ``word_penalty``); it does not read a bigram."""
+        r = int(r)
+        if not 0 <= r < self.score.shape[1]:
+            raise ValueError(f"rank {r} is outside 0..{self.score.shape[1] - 1}")
+        if r in self._aligned:
+            return self._aligned[r]
+        torch = _torch()
+        net = self._network
+        utts = np.flatnonzero(self.n_found > r)
+        transcripts = [self.words(int(u), r) for u in utts]
+        limit = MAX_FLAT // net.SP
+        for u, t in zip(utts, transcripts):
+            if len(t) > limit:
+                raise ValueError(f"rank {r} of utterance {int(u)} has {len(t)} words: alignment serves max_words * SP "
+                                 f"<= {MAX_FLAT} chain positions ({limit} words at SP = {net.SP})")
+        lengths = (self.offsets[1:] - self.offsets[:-1])[utts]
+        _, offs = _offsets(lengths)
+        if utts.size == self.n_found.size:
+            logb, offs_dev = self._logb, self._offs_dev
+        else:
+            rows = np.concatenate([np.arange(self.offsets[u], self.offsets[u + 1]) for u in utts]) if utts.size \
+                else np.zeros(0, np.int64)
+            logb = self._logb.index_select(0, torch.from_numpy(rows.astype(np.int64)).to(self._logb.device))
+            offs_dev = torch.from_numpy(offs).to(self._logb.device)
+        if utts.size == 0:
+            res = RankAlignment(np.zeros(0), np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.uint8),
+                                np.zeros(0, np.int32), word_offsets=np.zeros(1, np.int64), offsets=offs,
+                                words=np.zeros(0, np.int32), utterances=utts)
+        else:
+            res = RankAlignment(**vars(_run_align(logb, offs_dev, offs, transcripts, net)), utterances=utts)
+        self._aligned[r] = res
+        return res
+
+
+def _run_nbest(logb, offs_dev, offs, network, n_best) -> NBestResult:
+    """One ``sapr_connected_nbest`` over device ``logb[total_frames, R]``, under the network's bigram or, without one,
+    under ``lm == word_penalty``."""
+    torch = _torch()
+    dev = logb.device
+    n_utts, total = int(offs.size - 1), int(offs[-1])
+    ls, lt, lx, _ = network.device(dev)
+    lm, lm_start, lm_end = network.device_lm(dev)
+    score = torch.empty((n_utts, n_best), dtype=torch.float64, device=dev)
+    code = torch.empty((n_utts, n_best), dtype=torch.int64, device=dev)  # (the uint64 codes, bit for bit)
+    n_found = torch.empty(n_utts, dtype=torch.int32, device=dev)
+    overflow = torch.empty(n_utts, dtype=torch.uint8, device=dev)
+    _lib.check(_lib.load().sapr_connected_nbest(
+        _lib.ptr(logb), _lib.ptr(offs_dev), n_utts, total, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx), _lib.ptr(lm),
+        _lib.ptr(lm_start), _lib.ptr(lm_end), network.W, network.S, n_best, _lib.ptr(score), _lib.ptr(code),
+        _lib.ptr(n_found), _lib.ptr(overflow), _lib.current_stream()), "sapr_connected_nbest")
+    return NBestResult(score.cpu().numpy(), code.cpu().numpy().view(np.uint64), n_found.cpu().numpy(),
+                       overflow.cpu().numpy().astype(bool), offs, network, logb, offs_dev)
+
+
+def connected_nbest(logb, lengths, network: ConnectedNetwork, n_best) -> NBestResult:
+    """The ``n_best`` (1 .. 8) best distinct word strings of every utterance over a given ``logb`` (the shapes
+    :func:`connected_viterbi` takes), in one pass, under the network's bigram or, without one, under its
+    ``word_penalty``.  Rank 1 has the score of the one-pass search bit for bit; the list is exact unless two string
+    scores tie exactly or ``overflow`` is set (a string would exceed :func:`nbest_capacity` words)."""
+    torch = _torch()
+    n_best = _check_n_best(n_best)
+    dev = _lib.require_gpu()
+    lengths, offs = _offsets(lengths)
+    logb = _flat_states(logb, int(offs[-1]), network, dev)
+    return _run_nbest(logb, torch.from_numpy(offs).to(dev), offs, network, n_best)
+
+
 def connected_decode(batch_or_feature_list, network: ConnectedNetwork, posteriors=False, n_words=None,
-                     max_words=None) -> ConnectedResult:
+                     max_words=None, n_best=None) -> ConnectedResult:
     """Emission (by the network's family) and recursion: a ``trellis.FeatureBatch`` or a list of frame-major
     ``(T, D)`` feature arrays -> :class:`ConnectedResult`.  ``posteriors``: forward-backward over the same ``logb``
-    as well (one emission, both recursions); the result then carries its :class:`ConnectedPosteriors`.
+    as well (one emission, both recursions); the result then carries its :class:`ConnectedPosteriors`.  ``n_best``
+    (1 .. 8): the N-best recursion over the same ``logb`` as well; the result then carries its :class:`NBestResult`
+    as ``.nbest``.
 
     ``n_words`` (an int or one per utterance): the number of words is known; ``max_words``: it is at most this.  Either
     runs level building (``sapr_connected_levels``) instead of the free loop and the result carries ``level_score`` and
     its :class:`LevelResult`; ``n_words`` alone implies ``max_words`` = its largest count.  ``max_words`` above 8 or an
-    ``n_words`` outside 1 .. ``max_words`` is a ``ValueError``."""
+    ``n_words`` outside 1 .. ``max_words`` is a ``ValueError``, and so is an ``n_best`` outside 1 .. 8."""
+    if n_best is not None:
+        n_best = _check_n_best(n_best)  # (refused before a device is asked for)
     if n_words is None and max_words is None:
         feats, offs_dev, offs = _features(batch_or_feature_list)
         logb = _EMIT[network.family](feats, network)
@@ -824,6 +951,8 @@ def connected_decode(batch_or_feature_list, network: ConnectedNetwork, posterior
         res = _run_levels(logb, offs_dev, offs, network, L).select(n_words)
     if posteriors:
         res.posteriors = _run_posteriors(logb, offs_dev, offs, network)
+    if n_best is not None:
+        res.nbest = _run_nbest(logb, offs_dev, offs, network, n_best)
     return res
 
 
@@ -877,6 +1006,12 @@ class AlignResult:
             for w, a, b in self.segments(u):
                 out.setdefault(w, []).append(x[a:b])
         return out
+
+
+@dataclass
+class RankAlignment(AlignResult):
+    """:meth:`NBestResult.align`: the alignment of one rank's strings, over the utterances whose list has that rank."""
+    utterances: np.ndarray = None  # [n] the utterances of the list's batch this result covers, in order
 
 
 def with_optional(transcripts, word):

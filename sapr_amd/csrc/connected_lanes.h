@@ -1,5 +1,5 @@
 // The lane layout behind the connected-word trellis units (connected.hip, connected_align.hip, connected_embed.hip,
-// connected_bigram.hip, connected_loop_fb.hip, connected_levels.hip).  Like lse_ops.h and gmm_ops.h this
+// connected_bigram.hip, connected_loop_fb.hip, connected_levels.hip, connected_nbest.hip).  Like lse_ops.h and gmm_ops.h this
 // header is included INSIDE the unit's `namespace sapr { namespace {`, after both of them.  connected_loop_stats.hip
 //  has no recursion; it takes the constants and the host helpers from here.
 //

@@ -108,7 +108,7 @@ class Decoder:
     # ---- connected words ------------------------------------------------------------------------
     def decode_connected(self, feature_list: List[np.ndarray], word_penalty: float = 0.0,
                          exit_states="last", bigram=None, confidence=False, n_words=None, max_words=None,
-                         nbest=False) -> List[Dict]:
+                         nbest=False, alternatives=None) -> List[Dict]:
         """Recordings that hold several words in a row: one-pass Viterbi over the word loop (``sapr_amd.connected``:
         the emission stage of the vocabulary's family, then ``sapr_connected_viterbi``).  ``feature_list``: (D, T)
         arrays as in ``decode_batch``.  Per utterance ``{"words": [...], "log_likelihood": float, "segments": [(word,
@@ -137,6 +137,13 @@ class Decoder:
         ``"strings"``, a list of ``{"words", "log_likelihood", "segments"}``, one per count with a finite score, best
         first; its first entry is the result itself unless ``n_words`` asked for another count.
 
+        ``alternatives`` (an int 1 .. 8): that many of the best DISTINCT word strings of each recording, whatever their
+        word counts, from one more recursion over the same emission (``sapr_connected_nbest``).  Each dict gains
+        ``"alternatives"``, a list of ``{"words", "log_likelihood", "segments"}`` best first — the segments come from
+        a forced alignment of each string —, and ``"alternatives_complete"``: False where a string grew past what a
+        64-bit code holds (``sapr_amd.nbest_capacity``) and the list may miss strings.  A value outside 1 .. 8 is a
+        ``ValueError``.
+
         Served for ``implementation="hmmlearn"`` — "diag" / "spherical" vocabularies through
         ``sapr_connected_emit_diag``, a vocabulary with a "full" or "tied" model through ``sapr_connected_emit_full``
         over the decoder's ``FullPack`` — and for ``implementation="gmmhmm"`` through ``sapr_connected_emit_gmm`` over
@@ -156,7 +163,7 @@ class Decoder:
         if nbest and n_words is None and max_words is None:
             from .connected import MAX_LEVELS as max_words
         res = connected_decode([np.asarray(f).T for f in feature_list], net, posteriors=bool(confidence),
-                               n_words=n_words, max_words=max_words)
+                               n_words=n_words, max_words=max_words, n_best=alternatives)
         out = []
         for u in range(len(feature_list)):
             segs = res.segments(u)
@@ -171,6 +178,18 @@ class Decoder:
                     row["strings"] = [{"words": [words[w] for w in ws], "log_likelihood": sc,
                                        "segments": [(words[w], a, b) for w, a, b in segs]}
                                       for _, sc, ws, segs in res.levels.strings(u)]
+        if res.nbest is not None:
+            nb = res.nbest
+            for row in out:
+                row["alternatives"] = []
+            for r in range(int(nb.n_found.max()) if nb.n_found.size else 0):
+                al = nb.align(r)
+                for k, u in enumerate(al.utterances):
+                    out[u]["alternatives"].append({"words": [words[w] for w in nb.words(u, r)],
+                                                   "log_likelihood": float(nb.score[u, r]),
+                                                   "segments": [(words[w], a, b) for w, a, b in al.segments(k)]})
+            for u, row in enumerate(out):
+                row["alternatives_complete"] = not bool(nb.overflow[u])
         if confidence:
             log_post = res.posteriors.path_log_posterior(res)
             for u, row in enumerate(out):
