@@ -641,6 +641,64 @@ int sapr_connected_nbest(const double *logb, const int64_t *offsets, int64_t n_u
 int sapr_connected_nbest_capacity(int32_t W, int32_t *max_words); /* cap(W) */
 
 /* ------------------------------------------------------------------------------------
+ * Connected-word lattices (csrc/connected_lattice.hip): one pass over the word loop of sapr_connected_bigram leaves,
+ * for every (frame, word), the score of the best path that ends the word there and the frame at which that path
+ * entered the word.  That table is a word lattice: it is pruned to a beam around the best path and rescored under any
+ * other word-pair language model without emission or recursion.  The definition is the CPU restatement
+ * tests/_lattice_ref.py; with delta, X_t(w) and N_t(w) as for sapr_connected_bigram:
+ *     wend_score[t][w] = X_t(w)        wend_entry[t][w] = N_t(w)
+ *     wend_start[t][w] = B_t(w)        the utterance-relative frame at which the path that attains X_t(w) entered w:
+ *         b_0(w,j) = 0;  b_t(w,j) = t where entry won, else b_{t-1}(w,i*), i* the within-word predecessor that won;
+ *         B_t(w) = b_t(w, xarg_t(w)), and -1 where X_t(w) is not greater than -inf
+ * A record is a pair (w, t) with X_t(w) > -inf and tau = B_t(w) inside 0 .. t; in = lm_start[w] if tau = 0, else
+ * N_{tau-1}(w); ac = X_t(w) - in.  The record may follow any word that ends at tau - 1; tau = 0 starts the utterance.
+ * The backward pass under any tables (lm', lm_start', lm_end') — the forward pass's own give pruning margins, others
+ * rescore —: beta_{T-1}(w) = lm_end'[w], every other beta -inf, next = (-1, 255), root = -inf, first = (-1, 255);
+ * records are visited with t' from T - 1 down to 0 and, inside a frame, w' ascending:
+ *     g = ac + beta_{t'}(w')
+ *     tau > 0:  for every v: c = lm'[v][w'] + g;  where c > beta_{tau-1}(v): beta_{tau-1}(v) = c, next_{tau-1}(v) = (t', w')
+ *     tau = 0:               c = lm_start'[w'] + g; where c > root: root = c, first = (t', w')
+ * float64 adds, one subtract and strict compares in the order written: bit for bit numpy's.  The walk goes from first
+ * along next until a record ends at T - 1; next_end is clamped into (t, T - 1] and next_word below W.
+ *   logb, offsets, log_start, log_trans, log_exit, lm, lm_start, lm_end, W, S: as for sapr_connected_bigram (same
+ *              layout, same limits)
+ *   workspace  sapr_connected_lattice_workspace_bytes:  2 * a16(8 * total_frames * W) + a16(4 * total_frames * W)  bytes,
+ *              a16 rounding up to 16: the forward tables wend_score and wend_entry [total_frames][W] float64 and
+ *              wend_start [total_frames][W] int32, in this order.  The forward pass writes them, the backward pass reads
+ *              them; 20 W bytes per frame and no per-state back-pointer.
+ *   score      [n_utts]: sapr_connected_bigram's score bit for bit.  final_word [n_utts] int32, may be NULL
+ *   forward_lm_start  [W]: the lm_start the forward pass ran under (it defines `in` of a record with tau = 0)
+ *   beta       [total_frames][W] float64, next_end [total_frames][W] int32, next_word [total_frames][W] uint8
+ *   root       [n_utts] float64: the best complete lattice path under the tables of the backward pass
+ *   first      [n_utts][2] int32: (end frame, word) of that path's first record, (-1, 255) without one
+ *   n_words, path_word, path_entry: as for sapr_connected_viterbi (each may be NULL); where root is not finite the path
+ *              rows are -1, the entry flags 0 and n_words 0
+ * No atomics: outputs are bit-identical from run to run, and an utterance's outputs are a function of its own frames
+ * and the tables alone.  Non-finite values propagate; a NaN never wins a compare, and every index of the walk is
+ * clamped into its row.
+ *
+ * Bad sizes, NULL required pointers (the language-model tables among them) and a workspace that is too small return
+ * SAPR_ERR_ARG, S > 18 or W * SP > 256 SAPR_ERR_UNSUPPORTED (from the size function too), all before any launch;
+ * n_utts == 0 returns 0 after these checks. */
+int sapr_connected_lattice_workspace_bytes(int64_t total_frames, int64_t n_utts, int32_t W, int32_t S, size_t *bytes);
+int sapr_connected_lattice(const double *logb, const int64_t *offsets, int64_t n_utts, int64_t total_frames,
+                           const double *log_start, const double *log_trans, const double *log_exit,
+                           const double *lm /* [W][W] */, const double *lm_start /* [W] */,
+                           const double *lm_end /* [W] */, int32_t W, int32_t S, void *workspace,
+                           size_t workspace_bytes, double *score, int32_t *final_word /* may be NULL */, void *stream);
+int sapr_connected_lattice_backward(const int64_t *offsets, int64_t n_utts, int64_t total_frames, int32_t W, int32_t S,
+                                    const void *workspace, size_t workspace_bytes,
+                                    const double *forward_lm_start /* [W] */, const double *lm /* [W][W] */,
+                                    const double *lm_start /* [W] */, const double *lm_end /* [W] */, double *beta,
+                                    int32_t *next_end, uint8_t *next_word, double *root, int32_t *first /* [n_utts][2] */,
+                                    void *stream);
+int sapr_connected_lattice_walk(const int64_t *offsets, int64_t n_utts, int64_t total_frames, int32_t W, int32_t S,
+                                const int32_t *next_end, const uint8_t *next_word, const double *root,
+                                const int32_t *first, int32_t *n_words /* may be NULL */,
+                                int32_t *path_word /* may be NULL */, uint8_t *path_entry /* may be NULL */,
+                                void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Connected-word confidence (csrc/connected_loop_fb.hip): forward-backward over the word loop under the word-pair
  * language model of sapr_connected_bigram — the sum over every word string the grammar allows where that function
  * takes the maximum.  The definition is the CPU restatement tests/_loop_fb_ref.py; with b_t(w,s) = logb[t][w * SP + s]

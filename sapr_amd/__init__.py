@@ -13,7 +13,8 @@ behaviour) over hand-written HIP kernels in ``libsapr_hip.so``:
 * ``sapr_amd.connected``     connected-word recognition: one-pass Viterbi over the word loop (under a word bigram or a
                              word-pair grammar where one is given: ``WordBigram``; with a known or bounded number of
                              words by level building: ``connected_levels``; the N best distinct word strings
-                             in one pass: ``connected_nbest``), word and segment confidences
+                             in one pass: ``connected_nbest``; a word lattice that is pruned to a beam and rescored
+                             under another language model: ``connected_lattice``), word and segment confidences
                              from forward-backward over the same loop (``connected_posteriors``), forced alignment of
                              a recording to its known word string, embedded Baum-Welch training from such
                              recordings, and discriminative (MMI) training of the word models against the word loop
@@ -36,7 +37,9 @@ def __getattr__(name):
     ``sapr_amd.connected_levels`` / ``sapr_amd.levels_workspace_bytes`` / ``sapr_amd.with_optional`` /
     ``sapr_amd.align_opt_workspace_bytes`` / ``sapr_amd.loop_stats`` / ``sapr_amd.loop_stats_workspace_bytes`` /
     ``sapr_amd.MmiStats`` / ``sapr_amd.mmi_estep`` / ``sapr_amd.mmi_update`` / ``sapr_amd.mmi_fit`` /
-    ``sapr_amd.NBestResult`` / ``sapr_amd.connected_nbest`` / ``sapr_amd.nbest_capacity``
+    ``sapr_amd.NBestResult`` / ``sapr_amd.connected_nbest`` / ``sapr_amd.nbest_capacity`` / ``sapr_amd.WordLattice`` /
+    ``sapr_amd.LatticePath`` / ``sapr_amd.LatticeBackward`` / ``sapr_amd.connected_lattice`` /
+    ``sapr_amd.lattice_workspace_bytes``
     (resolved on first use: importing the package stays light)."""
     if name in ("GMMHMM", "fit_gmm_models", "vocab_scores"):
         from . import gmm_hmm
@@ -47,7 +50,8 @@ def __getattr__(name):
                 "embed_gmm_workspace_bytes", "ConnectedPosteriors", "connected_posteriors",
                 "posteriors_workspace_bytes", "LevelResult", "connected_levels", "levels_workspace_bytes",
                 "with_optional", "align_opt_workspace_bytes", "loop_stats", "loop_stats_workspace_bytes", "MmiStats",
-                "mmi_estep", "mmi_update", "mmi_fit", "NBestResult", "connected_nbest", "nbest_capacity"):
+                "mmi_estep", "mmi_update", "mmi_fit", "NBestResult", "connected_nbest", "nbest_capacity", "WordLattice",
+                "LatticePath", "LatticeBackward", "connected_lattice", "lattice_workspace_bytes"):
         from . import connected
         return getattr(connected, name)
     if name == "full_vocab_scores":

@@ -26,6 +26,13 @@ Viterbi scores, whatever their word counts, in one recursion over the same ``log
 without a back-pointer workspace; forced alignment gives any of them its boundaries (:func:`connected_nbest`,
 :class:`NBestResult`, ``connected_decode(..., n_best=)``; the definition is ``tests/_nbest_ref.py``).
 
+Rescoring and pruning: a word lattice keeps every alternative instead of the best few: ``sapr_connected_lattice``
+(``csrc/connected_lattice.hip``) leaves, for every (frame, word), the score of the best path that ends the word there and
+the frame at which that path entered it — 20 W bytes per frame —, and ``sapr_connected_lattice_backward`` /
+``sapr_connected_lattice_walk`` prune that table to a beam or return its best string under ANOTHER language model
+without emission or recursion (:func:`connected_lattice`, :class:`WordLattice`, ``connected_decode(..., lattice=True)``;
+the definition is ``tests/_lattice_ref.py``).
+
 How much to believe a decoded string: ``sapr_connected_posteriors`` (``csrc/connected_loop_fb.hip``) runs
 forward-backward over the same loop under the same language model — the sum over every word string where the search
 takes the best one — and returns the total log-likelihood, the per-frame word and word-boundary posteriors and, from
@@ -457,6 +464,7 @@ class ConnectedResult:
     level_score: np.ndarray = None  # [N, L] f64: connected_decode(..., n_words= / max_words=): the best score per count
     levels: "LevelResult" = None    # ... and the recursion it was selected from (further back-traces, N-best strings)
     nbest: "NBestResult" = None     # connected_decode(..., n_best=): the n best distinct strings over the same logb
+    lattice: "WordLattice" = None   # connected_decode(..., lattice=True): the word lattice over the same logb
 
     def segments(self, u):
         """``[(word_index, start, end_exclusive), ...]`` of utterance ``u``, frames counted from its own start."""
@@ -925,13 +933,256 @@ def connected_nbest(logb, lengths, network: ConnectedNetwork, n_best) -> NBestRe
     return _run_nbest(logb, torch.from_numpy(offs).to(dev), offs, network, n_best)
 
 
+# ---- word lattices ------------------------------------------------------------------------------
+def lattice_workspace_bytes(total_frames, n_utts, W, S) -> int:
+    return _workspace_bytes("sapr_connected_lattice_workspace_bytes", total_frames, n_utts, W, S)
+
+
+def _check_beam(beam) -> float:
+    if isinstance(beam, bool) or not isinstance(beam, (int, float, np.integer, np.floating)) or not float(beam) >= 0.0:
+        raise ValueError(f"beam must be a number >= 0 (inf keeps every record on a complete path), got {beam!r}")
+    return float(beam)
+
+
+@dataclass
+class LatticeBackward:
+    """One backward pass over a :class:`WordLattice` (``sapr_connected_lattice_backward``) under some tables."""
+    beta: np.ndarray       # [total_frames, W] f64: the best completion after word w ended at frame t; -inf without one
+    next_end: np.ndarray   # [total_frames, W] i32: the end frame of the record that attains it (-1 without one)
+    next_word: np.ndarray  # [total_frames, W] u8: ... and its word (255 without one)
+    root: np.ndarray       # [N] f64: the best complete lattice path
+    first: np.ndarray      # [N, 2] i32: (end frame, word) of its first record; (-1, 255) without one
+    device: tuple = None   # the same five on the device, for the walk
+
+
+@dataclass
+class LatticePath:
+    """The best string of every utterance through a lattice under some tables (:meth:`WordLattice.rescore`)."""
+    score: np.ndarray       # [N] f64: root — the best complete lattice path; -inf without one
+    n_words: np.ndarray     # [N] i32
+    path_word: np.ndarray   # [total_frames] i32 (-1 where the score is not finite)
+    path_entry: np.ndarray  # [total_frames] u8: 1 where a word begins
+    offsets: np.ndarray     # [N + 1] i64
+
+    segments = ConnectedResult.segments
+    words = ConnectedResult.words
+
+
+class WordLattice:
+    """The word-end tables one pass over the word loop leaves (``sapr_connected_lattice``; the definition is
+    ``tests/_lattice_ref.py``): for every (frame, word) the score ``X`` of the best path that ends the word there, the
+    entry score ``N`` and the frame ``B`` at which that path entered the word.  A record is a (word, end frame) with a
+    finite ``X``; it may follow any record that ends one frame before its start, so the table is a word lattice every
+    path of which is a real path of the network with its real within-word score.  It is pruned to a beam around the
+    best path (:meth:`prune`, :meth:`records`), rescored under another :class:`WordBigram` without emission or
+    recursion (:meth:`rescore`) and exported (:meth:`to_slf`).  The tables stay on the device (``wend_score``,
+    ``wend_entry``, ``wend_start``: views of one workspace); ``score`` and ``offsets`` are host arrays."""
+
+    def __init__(self, score, final_word, offsets, network, lm_host, lm_dev, workspace, ws_bytes, offs_dev):
+        self.score = score            # [N] f64: the one-pass search's score, bit for bit
+        self.final_word = final_word  # [N] i32: the word that attained it
+        self.offsets = offsets        # [N + 1] i64
+        self.W = int(network.W)
+        self._network, self._lm, self._lm_dev = network, lm_host, lm_dev
+        self._workspace, self._ws_bytes, self._offs_dev = workspace, ws_bytes, offs_dev
+        total, a16 = int(offsets[-1]), lambda n: (n + 15) // 16 * 16
+        x_bytes = a16(8 * total * self.W)
+        view = lambda lo, size, dt: workspace[lo:lo + size * total * self.W].view(dt).view(total, self.W)  # noqa: E731
+        torch = _torch()
+        self.wend_score = view(0, 8, torch.float64)
+        self.wend_entry = view(x_bytes, 8, torch.float64)
+        self.wend_start = view(2 * x_bytes, 4, torch.int32)
+        self._host, self._own, self._eps = None, None, None
+
+    def tables(self):
+        """``(X, N, B)`` on the host: ``[total_frames, W]`` float64, float64 and int32 (copied once)."""
+        if self._host is None:
+            self._host = tuple(a.copy() for a in _lib.to_host(self.wend_score, self.wend_entry, self.wend_start))
+        return self._host
+
+    def eps(self):
+        """``eps_u = 4 T_u 2^-52 M_u`` per utterance, M_u the largest finite ``|X|`` or ``|N|``: the rounding slack of
+        a lattice path's score against the state path it stands for."""
+        if self._eps is None:
+            X, N, _ = self.tables()
+            out = np.zeros(self.offsets.size - 1)
+            for u, (lo, hi) in enumerate(zip(self.offsets[:-1], self.offsets[1:])):
+                v = np.abs(np.concatenate([X[lo:hi].ravel(), N[lo:hi].ravel()]))
+                v = v[np.isfinite(v)]
+                out[u] = 4.0 * (hi - lo) * 2.0 ** -52 * (v.max() if v.size else 0.0)
+            self._eps = out
+        return self._eps
+
+    def backward(self, bigram=None) -> LatticeBackward:
+        """``beta`` / ``next`` / ``root`` / ``first`` under the tables of ``bigram`` (a :class:`WordBigram` over the
+        same W words), or under the tables the lattice was made under; that result is kept."""
+        if bigram is None and self._own is not None:
+            return self._own
+        torch = _torch()
+        dev = self._workspace.device
+        if bigram is None:
+            lm, lm_start, lm_end = self._lm_dev
+        else:
+            if not isinstance(bigram, WordBigram) or bigram.W != self.W:
+                raise ValueError(f"a lattice over {self.W} words is rescored under a WordBigram over {self.W} words, got "
+                                 f"{bigram!r}" + (f" over {bigram.W}" if isinstance(bigram, WordBigram) else ""))
+            lm, lm_start, lm_end = (torch.from_numpy(a).to(dev) for a in (bigram.lm, bigram.lm_start, bigram.lm_end))
+        n_utts, total = int(self.offsets.size - 1), int(self.offsets[-1])
+        beta = torch.empty((total, self.W), dtype=torch.float64, device=dev)
+        next_end = torch.empty((total, self.W), dtype=torch.int32, device=dev)
+        next_word = torch.empty((total, self.W), dtype=torch.uint8, device=dev)
+        root = torch.empty(n_utts, dtype=torch.float64, device=dev)
+        first = torch.empty((n_utts, 2), dtype=torch.int32, device=dev)
+        _lib.check(_lib.load().sapr_connected_lattice_backward(
+            _lib.ptr(self._offs_dev), n_utts, total, self.W, self._network.S, _lib.ptr(self._workspace), self._ws_bytes,
+            _lib.ptr(self._lm_dev[1]), _lib.ptr(lm), _lib.ptr(lm_start), _lib.ptr(lm_end), _lib.ptr(beta),
+            _lib.ptr(next_end), _lib.ptr(next_word), _lib.ptr(root), _lib.ptr(first), _lib.current_stream()),
+            "sapr_connected_lattice_backward")
+        tensors = (beta, next_end, next_word, root, first)
+        out = LatticeBackward(*[a.copy() for a in _lib.to_host(*tensors)], device=tensors)
+        if bigram is None:
+            self._own = out
+        return out
+
+    def rescore(self, bigram) -> LatticePath:
+        """The best string of every utterance through the lattice under another :class:`WordBigram` — for example
+        ``network.bigram.scaled(scale, word_penalty)`` — from one backward pass and one walk: no emission and no
+        recursion.  The score is never above a full decode under ``bigram`` by more than :meth:`eps`; it reaches it
+        where that decode's best path keeps the word boundaries this lattice recorded."""
+        torch = _torch()
+        back = self.backward(bigram)
+        _, next_end, next_word, root, first = back.device
+        n_utts, total = int(self.offsets.size - 1), int(self.offsets[-1])
+        dev = self._workspace.device
+        n_words = torch.empty(n_utts, dtype=torch.int32, device=dev)
+        path_word = torch.empty(total, dtype=torch.int32, device=dev)
+        path_entry = torch.empty(total, dtype=torch.uint8, device=dev)
+        _lib.check(_lib.load().sapr_connected_lattice_walk(
+            _lib.ptr(self._offs_dev), n_utts, total, self.W, self._network.S, _lib.ptr(next_end), _lib.ptr(next_word),
+            _lib.ptr(root), _lib.ptr(first), _lib.ptr(n_words), _lib.ptr(path_word), _lib.ptr(path_entry),
+            _lib.current_stream()), "sapr_connected_lattice_walk")
+        host = [a.copy() for a in _lib.to_host(n_words, path_word, path_entry)]
+        return LatticePath(back.root, *host, offsets=self.offsets)
+
+    def best(self) -> LatticePath:
+        """:meth:`rescore` under the tables the lattice was made under: the one-pass search's string."""
+        return self.rescore(None)
+
+    def margins(self):
+        """``[total_frames, W]`` float64: ``(X_t(w) + beta_t(w)) - score`` under the lattice's own tables — how far
+        the best complete path through the record (w, t) falls below the best path; -inf for a record on no complete
+        path."""
+        X = self.tables()[0]
+        lengths = self.offsets[1:] - self.offsets[:-1]
+        with np.errstate(invalid="ignore"):
+            m = X + self.backward().beta
+            return np.where(m > -np.inf, m - np.repeat(self.score, lengths)[:, None], -np.inf)
+
+    def prune(self, beam):
+        """A boolean mask ``[total_frames, W]``: the records kept at ``beam`` — on a complete path and with a margin
+        ``>= -(beam + eps_u)``.  ``beam=0`` keeps the best path's records, ``beam=inf`` every record on a complete
+        path; a negative beam is a ``ValueError``."""
+        beam = _check_beam(beam)
+        m = self.margins()
+        lengths = self.offsets[1:] - self.offsets[:-1]
+        return (m > -np.inf) & (m >= -(beam + np.repeat(self.eps(), lengths))[:, None])
+
+    def _records(self, u, keep):
+        """``[(t, w, tau, in, ac, margin), ...]`` of utterance ``u`` where ``keep[t, w]``, end ascending, then word."""
+        X, N, B = self.tables()
+        lo, hi = int(self.offsets[u]), int(self.offsets[u + 1])
+        X, N, B, m = X[lo:hi], N[lo:hi], B[lo:hi], self.margins()[lo:hi]
+        out = []
+        for t, w in zip(*np.nonzero((X > -np.inf) & (B >= 0) & (B <= np.arange(hi - lo)[:, None]) & keep[lo:hi])):
+            tau = int(B[t, w])
+            inc = self._lm[1][w] if tau == 0 else N[tau - 1, w]
+            with np.errstate(invalid="ignore"):
+                out.append((int(t), int(w), tau, float(inc), float(X[t, w] - inc), float(m[t, w])))
+        return out
+
+    def records(self, u, beam=None):
+        """The records of utterance ``u`` kept at ``beam`` (``None``: every record, on a complete path or not):
+        ``[(word, start, end_exclusive, acoustic, margin), ...]`` sorted by end and then by word, frames counted from
+        the utterance's own start.  ``acoustic`` is the within-word score ``X - in``: the language model is not in it."""
+        keep = np.ones((int(self.offsets[-1]), self.W), bool) if beam is None else self.prune(beam)
+        return [(w, tau, t + 1, ac, m) for t, w, tau, _, ac, m in self._records(u, keep)]
+
+    def to_slf(self, u, names, frame_shift=0.01, beam=None) -> str:
+        """The part of utterance ``u`` kept at ``beam`` (``None``: every record on a complete path) as HTK Standard
+        Lattice Format text.  One node per kept record — ``W=`` its word's name, ``t=`` its end time — plus a start and
+        an end node (``!NULL``).  The link from record (v, tau - 1) to record (w, t) carries ``a=`` the acoustic score
+        of (w, t) and ``l=`` ``lm[v][w]``; the start node links to the records with tau = 0 under ``lm_start`` and the
+        records that end the utterance link to the end node with ``a=0`` and ``l=lm_end``.  A link exists only where
+        both records are kept and its language-model score is finite.  Scores are printed with 17 significant digits.
+        Host code only."""
+        if len(names) != self.W:
+            raise ValueError(f"{len(names)} names for {self.W} words")
+        recs = self._records(u, self.prune(float("inf") if beam is None else beam))
+        lm, lm_start, lm_end = self._lm
+        T = int(self.offsets[u + 1] - self.offsets[u])
+        node = {(t, w): k + 1 for k, (t, w, *_) in enumerate(recs)}
+        end = len(recs) + 1
+        ends_at = {}
+        for t, w, *_ in recs:
+            ends_at.setdefault(t, []).append(w)
+        links = []
+        for t, w, tau, _, ac, _ in recs:
+            if tau == 0:
+                if lm_start[w] > -np.inf:
+                    links.append((0, node[t, w], ac, lm_start[w]))
+            else:
+                links += [(node[tau - 1, v], node[t, w], ac, lm[v, w]) for v in ends_at.get(tau - 1, [])
+                          if lm[v, w] > -np.inf]
+            if t == T - 1 and lm_end[w] > -np.inf:
+                links.append((node[t, w], end, 0.0, lm_end[w]))
+        num = lambda x: repr(float(x))  # noqa: E731
+        lines = ["VERSION=1.0", f"UTTERANCE={u}", "lmscale=1.00 wdpenalty=0.00", f"N={end + 1} L={len(links)}",
+                 "I=0 t=0.00 W=!NULL"]
+        lines += [f"I={node[t, w]} t={(t + 1) * frame_shift:.4f} W={names[w]}" for t, w, *_ in recs]
+        lines.append(f"I={end} t={T * frame_shift:.4f} W=!NULL")
+        lines += [f"J={j} S={a} E={b} a={num(ac)} l={num(l)}" for j, (a, b, ac, l) in enumerate(links)]
+        return "\n".join(lines) + "\n"
+
+
+def _run_lattice(logb, offs_dev, offs, network) -> WordLattice:
+    """One ``sapr_connected_lattice`` over device ``logb[total_frames, R]``, under the network's bigram or, without
+    one, under ``lm == word_penalty``."""
+    torch = _torch()
+    dev = logb.device
+    n_utts, total = int(offs.size - 1), int(offs[-1])
+    ls, lt, lx, _ = network.device(dev)
+    lm_dev = network.device_lm(dev)
+    workspace, ws_bytes = _workspace("sapr_connected_lattice_workspace_bytes", dev, total, n_utts, network.W,
+                                     network.S)
+    score = torch.empty(n_utts, dtype=torch.float64, device=dev)
+    final = torch.empty(n_utts, dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().sapr_connected_lattice(
+        _lib.ptr(logb), _lib.ptr(offs_dev), n_utts, total, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx),
+        _lib.ptr(lm_dev[0]), _lib.ptr(lm_dev[1]), _lib.ptr(lm_dev[2]), network.W, network.S, _lib.ptr(workspace),
+        ws_bytes, _lib.ptr(score), _lib.ptr(final), _lib.current_stream()), "sapr_connected_lattice")
+    return WordLattice(score.cpu().numpy(), final.cpu().numpy(), offs, network, network.loop_lm(), lm_dev, workspace,
+                       ws_bytes, offs_dev)
+
+
+def connected_lattice(logb, lengths, network: ConnectedNetwork) -> WordLattice:
+    """The word lattice of every utterance over a given ``logb`` (the shapes :func:`connected_viterbi` takes), in one
+    pass, under the network's bigram or, without one, under its ``word_penalty``.  ``score`` is the one-pass search's
+    bit for bit; the lattice costs 20 W bytes per frame and no per-state back-pointer."""
+    torch = _torch()
+    dev = _lib.require_gpu()
+    lengths, offs = _offsets(lengths)
+    logb = _flat_states(logb, int(offs[-1]), network, dev)
+    return _run_lattice(logb, torch.from_numpy(offs).to(dev), offs, network)
+
+
 def connected_decode(batch_or_feature_list, network: ConnectedNetwork, posteriors=False, n_words=None,
-                     max_words=None, n_best=None) -> ConnectedResult:
+                     max_words=None, n_best=None, lattice=False) -> ConnectedResult:
     """Emission (by the network's family) and recursion: a ``trellis.FeatureBatch`` or a list of frame-major
     ``(T, D)`` feature arrays -> :class:`ConnectedResult`.  ``posteriors``: forward-backward over the same ``logb``
     as well (one emission, both recursions); the result then carries its :class:`ConnectedPosteriors`.  ``n_best``
     (1 .. 8): the N-best recursion over the same ``logb`` as well; the result then carries its :class:`NBestResult`
-    as ``.nbest``.
+    as ``.nbest``.  ``lattice=True``: the lattice recursion over the same ``logb`` as well; the result then carries
+    its :class:`WordLattice` as ``.lattice``.
 
     ``n_words`` (an int or one per utterance): the number of words is known; ``max_words``: it is at most this.  Either
     runs level building (``sapr_connected_levels``) instead of the free loop and the result carries ``level_score`` and
@@ -953,6 +1204,8 @@ def connected_decode(batch_or_feature_list, network: ConnectedNetwork, posterior
         res.posteriors = _run_posteriors(logb, offs_dev, offs, network)
     if n_best is not None:
         res.nbest = _run_nbest(logb, offs_dev, offs, network, n_best)
+    if lattice:
+        res.lattice = _run_lattice(logb, offs_dev, offs, network)
     return res
 
 

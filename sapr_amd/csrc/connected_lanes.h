@@ -1,7 +1,8 @@
 // The lane layout behind the connected-word trellis units (connected.hip, connected_align.hip, connected_embed.hip,
-// connected_bigram.hip, connected_loop_fb.hip, connected_levels.hip, connected_nbest.hip).  Like lse_ops.h and gmm_ops.h this
-// header is included INSIDE the unit's `namespace sapr { namespace {`, after both of them.  connected_loop_stats.hip
-//  has no recursion; it takes the constants and the host helpers from here.
+// connected_bigram.hip, connected_loop_fb.hip, connected_levels.hip, connected_nbest.hip, connected_lattice.hip; DESIGN
+// 4.3o).  Like lse_ops.h and gmm_ops.h this header is included INSIDE the unit's `namespace sapr { namespace {`, after
+// both of them.  connected_loop_stats.hip has no recursion; it takes the constants and the host helpers
+// from here.
 //
 // The mapping every recursion kernel of these units uses:
 //   * One wavefront serves one utterance; a workgroup holds up to four of them, which share the tables in LDS.  The
@@ -183,6 +184,30 @@ __device__ __forceinline__ void x_rotate(const double (&val)[RL], int lane, int 
     const double below = k > 0 ? rot[k > 0 ? k - 1 : 0] : neg_inf();
     const double above = k + 1 < RL ? rot[k + 1 < RL ? k + 1 : k] : neg_inf();
     use(k, off < 0 ? below : (off >= kWave ? above : rot[k]));
+  }
+}
+
+// x_rotate with an int32 beside every value (the lattice's start frame, which moves with delta): use(k, value, tag) of
+// item r - shift; -inf and -1 where r - shift leaves 0 .. 64 RL - 1.  A second ds_bpermute per register.
+template <int RL, typename F>
+__device__ __forceinline__ void x_rotate_tagged(const double (&val)[RL], const int (&tag)[RL], int lane, int shift,
+                                                F &&use) {
+  const int off = lane - shift;
+  const int src = off & (kWave - 1);
+  double rot[RL];
+  int rtag[RL];
+#pragma unroll
+  for (int k = 0; k < RL; ++k) {
+    rot[k] = __shfl(val[k], src, kWave);
+    rtag[k] = __shfl(tag[k], src, kWave);
+  }
+#pragma unroll
+  for (int k = 0; k < RL; ++k) {
+    const double below = k > 0 ? rot[k > 0 ? k - 1 : 0] : neg_inf();
+    const double above = k + 1 < RL ? rot[k + 1 < RL ? k + 1 : k] : neg_inf();
+    const int tbelow = k > 0 ? rtag[k > 0 ? k - 1 : 0] : -1;
+    const int tabove = k + 1 < RL ? rtag[k + 1 < RL ? k + 1 : k] : -1;
+    use(k, off < 0 ? below : (off >= kWave ? above : rot[k]), off < 0 ? tbelow : (off >= kWave ? tabove : rtag[k]));
   }
 }
 

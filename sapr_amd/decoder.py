@@ -108,7 +108,7 @@ class Decoder:
     # ---- connected words ------------------------------------------------------------------------
     def decode_connected(self, feature_list: List[np.ndarray], word_penalty: float = 0.0,
                          exit_states="last", bigram=None, confidence=False, n_words=None, max_words=None,
-                         nbest=False, alternatives=None) -> List[Dict]:
+                         nbest=False, alternatives=None, lattice=None) -> List[Dict]:
         """Recordings that hold several words in a row: one-pass Viterbi over the word loop (``sapr_amd.connected``:
         the emission stage of the vocabulary's family, then ``sapr_connected_viterbi``).  ``feature_list``: (D, T)
         arrays as in ``decode_batch``.  Per utterance ``{"words": [...], "log_likelihood": float, "segments": [(word,
@@ -144,6 +144,13 @@ class Decoder:
         64-bit code holds (``sapr_amd.nbest_capacity``) and the list may miss strings.  A value outside 1 .. 8 is a
         ``ValueError``.
 
+        ``lattice`` (``True`` or a beam >= 0 in log score): the word lattice over the same emission under the same
+        language model (``sapr_connected_lattice``, ``sapr_amd.WordLattice``).  Each dict gains ``"lattice"``, a list
+        of ``(word, start, end_exclusive, acoustic, margin)`` sorted by end and then by word: the records whose best
+        complete path scores within the beam of the best path (``True``: every record on a complete path).  A
+        negative beam is a ``ValueError``.  With ``lattice=None`` the call makes exactly the launches it makes
+        without the argument.
+
         Served for ``implementation="hmmlearn"`` — "diag" / "spherical" vocabularies through
         ``sapr_connected_emit_diag``, a vocabulary with a "full" or "tied" model through ``sapr_connected_emit_full``
         over the decoder's ``FullPack`` — and for ``implementation="gmmhmm"`` through ``sapr_connected_emit_gmm`` over
@@ -152,7 +159,11 @@ class Decoder:
         if self.implementation not in ("hmmlearn", "gmmhmm"):
             raise ValueError(f"connected-word decoding needs implementation='hmmlearn' with 'diag' or 'spherical' "
                              f"models: it has no emission stage for implementation={self.implementation!r}")
-        from .connected import connected_decode
+        from .connected import _check_beam, connected_decode
+        if lattice is None or lattice is False:
+            beam = None
+        else:
+            beam = float("inf") if lattice is True else _check_beam(lattice)  # (refused before a device is asked for)
         if len(feature_list) == 0:
             raise ValueError("empty utterance list")
         words = list(self.models)
@@ -163,7 +174,7 @@ class Decoder:
         if nbest and n_words is None and max_words is None:
             from .connected import MAX_LEVELS as max_words
         res = connected_decode([np.asarray(f).T for f in feature_list], net, posteriors=bool(confidence),
-                               n_words=n_words, max_words=max_words, n_best=alternatives)
+                               n_words=n_words, max_words=max_words, n_best=alternatives, lattice=beam is not None)
         out = []
         for u in range(len(feature_list)):
             segs = res.segments(u)
@@ -190,6 +201,9 @@ class Decoder:
                                                    "segments": [(words[w], a, b) for w, a, b in al.segments(k)]})
             for u, row in enumerate(out):
                 row["alternatives_complete"] = not bool(nb.overflow[u])
+        if beam is not None:
+            for u, row in enumerate(out):
+                row["lattice"] = [(words[w], a, b, ac, m) for w, a, b, ac, m in res.lattice.records(u, beam)]
         if confidence:
             log_post = res.posteriors.path_log_posterior(res)
             for u, row in enumerate(out):
