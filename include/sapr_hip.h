@@ -699,6 +699,44 @@ int sapr_connected_lattice_walk(const int64_t *offsets, int64_t n_utts, int64_t 
                                 void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Lattice posteriors (csrc/connected_lattice.hip): forward-backward in the sum semiring over the records of a word
+ * lattice — link posteriors, word confidences and the likelihood of the lattice under any tables (lm', lm_start',
+ * lm_end') and any acoustic scale, without emission or recursion over states.  The definition is the CPU restatement
+ * tests/_lattice_post_ref.py over the records, tau, in and ac of tests/_lattice_ref.py.  With a = acoustic_scale * ac,
+ * lse the log-sum-exp (the maximum taken out, the exponentials added in ascending order) and alpha, Q, beta, H = -inf:
+ *     forward, t ascending:    for every record (w, t): alpha_t(w) = a + (lm_start'[w] if tau = 0 else Q_{tau-1}(w));
+ *                              then Q_t(w) = lse_v (alpha_t(v) + lm'[v][w])
+ *     backward, t descending:  beta_t(v) = lse_w (lm'[v][w] + H_{t+1}(w)), H_T = -inf; beta_{T-1}(v) = lm_end'[v];
+ *                              then for every record (w, t): H_tau(w) = logaddexp(H_tau(w), a + beta_t(w))
+ *     loglik[u]         = lse_w (alpha_{T-1}(w) + lm_end'[w]);  -inf for an utterance without frames
+ *     record_post[t][w] = exp(alpha_t(w) + beta_t(w) - loglik) for a record, 0 elsewhere
+ *     word_post[f][w]   = the sum of record_post[t][w] over the records of w with tau <= f <= t: the posterior that
+ *                         frame f lies inside word w.  It is formed as the mass that started at or before f,
+ *                         sum over tau <= f of exp(Q_{tau-1}(w) + H_tau(w) - loglik), minus the mass that ended before f
+ * A loglik that is not finite gives exact zeros in both tables of that utterance.
+ *   lattice_workspace  what sapr_connected_lattice wrote (sapr_connected_lattice_workspace_bytes), read only
+ *   forward_lm_start   [W]: the lm_start the lattice was made under (it defines ac)
+ *   keep       [total_frames][W] uint8, may be NULL (every record): a record with keep == 0 does not exist for this pass
+ *   workspace  sapr_connected_lattice_posteriors_workspace_bytes:  4 * a16(8 * total_frames * W)  bytes: alpha, Q, beta
+ *              and H [total_frames][W] float64, in this order (Q_{T-1} is not formed); 32 W bytes per frame
+ *   loglik [n_utts], record_post [total_frames][W], word_post [total_frames][W] (may be NULL): float64
+ * No atomics, a fixed order of every sum: outputs are bit-identical from run to run, and an utterance's outputs are a
+ * function of its own frames, the tables, acoustic_scale and keep alone.
+ *
+ * Bad sizes, NULL required pointers (the four tables among them), a workspace that is too small and an acoustic_scale
+ * that is not finite or not above 0 return SAPR_ERR_ARG, S > 18 or W * SP > 256 SAPR_ERR_UNSUPPORTED (from the size
+ * function too), all before any launch; n_utts == 0 returns 0 after these checks. */
+int sapr_connected_lattice_posteriors_workspace_bytes(int64_t total_frames, int64_t n_utts, int32_t W, int32_t S,
+                                                      size_t *bytes);
+int sapr_connected_lattice_posteriors(const int64_t *offsets, int64_t n_utts, int64_t total_frames, int32_t W, int32_t S,
+                                      const void *lattice_workspace, size_t lattice_workspace_bytes,
+                                      const double *forward_lm_start /* [W] */, const double *lm /* [W][W] */,
+                                      const double *lm_start /* [W] */, const double *lm_end /* [W] */,
+                                      double acoustic_scale, const uint8_t *keep /* may be NULL: every record */,
+                                      void *workspace, size_t workspace_bytes, double *loglik /* [n_utts] */,
+                                      double *record_post, double *word_post /* may be NULL */, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Connected-word confidence (csrc/connected_loop_fb.hip): forward-backward over the word loop under the word-pair
  * language model of sapr_connected_bigram — the sum over every word string the grammar allows where that function
  * takes the maximum.  The definition is the CPU restatement tests/_loop_fb_ref.py; with b_t(w,s) = logb[t][w * SP + s]

@@ -39,7 +39,8 @@ def __getattr__(name):
     ``sapr_amd.MmiStats`` / ``sapr_amd.mmi_estep`` / ``sapr_amd.mmi_update`` / ``sapr_amd.mmi_fit`` /
     ``sapr_amd.NBestResult`` / ``sapr_amd.connected_nbest`` / ``sapr_amd.nbest_capacity`` / ``sapr_amd.WordLattice`` /
     ``sapr_amd.LatticePath`` / ``sapr_amd.LatticeBackward`` / ``sapr_amd.connected_lattice`` /
-    ``sapr_amd.lattice_workspace_bytes``
+    ``sapr_amd.lattice_workspace_bytes`` / ``sapr_amd.LatticePosteriors`` /
+    ``sapr_amd.lattice_posteriors_workspace_bytes``
     (resolved on first use: importing the package stays light)."""
     if name in ("GMMHMM", "fit_gmm_models", "vocab_scores"):
         from . import gmm_hmm
@@ -51,7 +52,8 @@ def __getattr__(name):
                 "posteriors_workspace_bytes", "LevelResult", "connected_levels", "levels_workspace_bytes",
                 "with_optional", "align_opt_workspace_bytes", "loop_stats", "loop_stats_workspace_bytes", "MmiStats",
                 "mmi_estep", "mmi_update", "mmi_fit", "NBestResult", "connected_nbest", "nbest_capacity", "WordLattice",
-                "LatticePath", "LatticeBackward", "connected_lattice", "lattice_workspace_bytes"):
+                "LatticePath", "LatticeBackward", "connected_lattice", "lattice_workspace_bytes", "LatticePosteriors",
+                "lattice_posteriors_workspace_bytes"):
         from . import connected
         return getattr(connected, name)
     if name == "full_vocab_scores":

@@ -31,7 +31,9 @@ Rescoring and pruning: a word lattice keeps every alternative instead of the bes
 the frame at which that path entered it — 20 W bytes per frame —, and ``sapr_connected_lattice_backward`` /
 ``sapr_connected_lattice_walk`` prune that table to a beam or return its best string under ANOTHER language model
 without emission or recursion (:func:`connected_lattice`, :class:`WordLattice`, ``connected_decode(..., lattice=True)``;
-the definition is ``tests/_lattice_ref.py``).
+the definition is ``tests/_lattice_ref.py``).  ``sapr_connected_lattice_posteriors`` runs forward-backward in the sum
+semiring over the same records — link and word posteriors and the likelihood of the lattice under any tables and
+acoustic scale (:meth:`WordLattice.posteriors`, :class:`LatticePosteriors`; ``tests/_lattice_post_ref.py``).
 
 How much to believe a decoded string: ``sapr_connected_posteriors`` (``csrc/connected_loop_fb.hip``) runs
 forward-backward over the same loop under the same language model — the sum over every word string where the search
@@ -968,6 +970,48 @@ class LatticePath:
     words = ConnectedResult.words
 
 
+def lattice_posteriors_workspace_bytes(total_frames, n_utts, W, S) -> int:
+    return _workspace_bytes("sapr_connected_lattice_posteriors_workspace_bytes", total_frames, n_utts, W, S)
+
+
+def _check_acoustic_scale(acoustic_scale) -> float:
+    ok = not isinstance(acoustic_scale, bool) and isinstance(acoustic_scale, (int, float, np.integer, np.floating))
+    if not ok or not np.isfinite(acoustic_scale) or not float(acoustic_scale) > 0.0:
+        raise ValueError(f"acoustic_scale must be a finite number > 0, got {acoustic_scale!r}")
+    return float(acoustic_scale)
+
+
+@dataclass
+class LatticePosteriors:
+    """Forward-backward in the sum semiring over a :class:`WordLattice` (``sapr_connected_lattice_posteriors``; the
+    definition is ``tests/_lattice_post_ref.py``): the sum over every path of the lattice — Viterbi within words, the
+    recorded boundaries only — under some tables and an acoustic scale."""
+    loglik: np.ndarray       # [N] f64: the log-sum of every complete lattice path; -inf without one
+    record_post: np.ndarray  # [total_frames, W] f64: the posterior of the record (w, t), 0 where there is none
+    word_post: np.ndarray    # [total_frames, W] f64: the posterior that frame f lies inside word w
+    offsets: np.ndarray      # [N + 1] i64
+
+    def segment_confidence(self, path, u):
+        """One float per segment ``(w, a, b)`` of ``path.segments(u)`` (a :class:`LatticePath` or a
+        :class:`ConnectedResult`): the mean of ``word_post[a:b, w]`` over the segment's frames, as
+        :meth:`ConnectedPosteriors.segment_confidence` has it."""
+        lo = int(self.offsets[u])
+        return [float(self.word_post[lo + a:lo + b, w].mean()) for w, a, b in path.segments(u)]
+
+    def slots(self, path, u, top=None):
+        """Per segment of ``path.segments(u)`` the list ``[(word, posterior), ...]``, best first (``top``: at most that
+        many): the mean of ``word_post[a:b, v]`` over the segment's frames for every word v with a posterior above 0.
+        Each full slot sums to 1 where the utterance has a path.  This is a frame-based confusion network pivoted on
+        the given path — host code over the returned table —, not Mangu's clustering of the lattice's links."""
+        lo = int(self.offsets[u])
+        out = []
+        for _, a, b in path.segments(u):
+            mean = self.word_post[lo + a:lo + b].mean(axis=0)
+            order = sorted(np.flatnonzero(mean > 0.0).tolist(), key=lambda v: (-mean[v], v))
+            out.append([(int(v), float(mean[v])) for v in order[:top]])
+        return out
+
+
 class WordLattice:
     """The word-end tables one pass over the word loop leaves (``sapr_connected_lattice``; the definition is
     ``tests/_lattice_ref.py``): for every (frame, word) the score ``X`` of the best path that ends the word there, the
@@ -1013,20 +1057,28 @@ class WordLattice:
             self._eps = out
         return self._eps
 
+    def _check_bigram(self, bigram):
+        if bigram is not None and (not isinstance(bigram, WordBigram) or bigram.W != self.W):
+            raise ValueError(f"a lattice over {self.W} words is rescored under a WordBigram over {self.W} words, got "
+                             f"{bigram!r}" + (f" over {bigram.W}" if isinstance(bigram, WordBigram) else ""))
+
+    def _device_tables(self, bigram):
+        """``(lm, lm_start, lm_end)`` of ``bigram`` on the lattice's device; ``None``: the lattice's own."""
+        if bigram is None:
+            return self._lm_dev
+        torch = _torch()
+        dev = self._workspace.device
+        return tuple(torch.from_numpy(a).to(dev) for a in (bigram.lm, bigram.lm_start, bigram.lm_end))
+
     def backward(self, bigram=None) -> LatticeBackward:
         """``beta`` / ``next`` / ``root`` / ``first`` under the tables of ``bigram`` (a :class:`WordBigram` over the
         same W words), or under the tables the lattice was made under; that result is kept."""
         if bigram is None and self._own is not None:
             return self._own
         torch = _torch()
+        self._check_bigram(bigram)
         dev = self._workspace.device
-        if bigram is None:
-            lm, lm_start, lm_end = self._lm_dev
-        else:
-            if not isinstance(bigram, WordBigram) or bigram.W != self.W:
-                raise ValueError(f"a lattice over {self.W} words is rescored under a WordBigram over {self.W} words, got "
-                                 f"{bigram!r}" + (f" over {bigram.W}" if isinstance(bigram, WordBigram) else ""))
-            lm, lm_start, lm_end = (torch.from_numpy(a).to(dev) for a in (bigram.lm, bigram.lm_start, bigram.lm_end))
+        lm, lm_start, lm_end = self._device_tables(bigram)
         n_utts, total = int(self.offsets.size - 1), int(self.offsets[-1])
         beta = torch.empty((total, self.W), dtype=torch.float64, device=dev)
         next_end = torch.empty((total, self.W), dtype=torch.int32, device=dev)
@@ -1063,6 +1115,35 @@ class WordLattice:
             _lib.current_stream()), "sapr_connected_lattice_walk")
         host = [a.copy() for a in _lib.to_host(n_words, path_word, path_entry)]
         return LatticePath(back.root, *host, offsets=self.offsets)
+
+    def posteriors(self, bigram=None, acoustic_scale=1.0, beam=None) -> LatticePosteriors:
+        """Link and word posteriors over the lattice (``sapr_connected_lattice_posteriors``): forward-backward in the
+        sum semiring over the records under the tables of ``bigram`` (as for :meth:`backward`; ``None``: the tables
+        the lattice was made under) with every record's acoustic score multiplied by ``acoustic_scale`` — no
+        emission and no recursion over states, so another language-model weight, penalty or grammar costs one more
+        call.  ``beam``: ``None`` takes every record, otherwise only the records :meth:`prune` keeps at that beam.  A
+        bigram over another vocabulary, an ``acoustic_scale`` that is not a finite number above 0 and a negative beam
+        are a ``ValueError`` before any device call."""
+        self._check_bigram(bigram)
+        kappa = _check_acoustic_scale(acoustic_scale)
+        keep = None if beam is None else self.prune(_check_beam(beam))
+        torch = _torch()
+        dev = self._workspace.device
+        lm, lm_start, lm_end = self._device_tables(bigram)
+        n_utts, total = int(self.offsets.size - 1), int(self.offsets[-1])
+        keep_dev = None if keep is None else torch.from_numpy(np.ascontiguousarray(keep, dtype=np.uint8)).to(dev)
+        workspace, ws_bytes = _workspace("sapr_connected_lattice_posteriors_workspace_bytes", dev, total, n_utts,
+                                         self.W, self._network.S)
+        loglik = torch.empty(n_utts, dtype=torch.float64, device=dev)
+        record_post = torch.empty((total, self.W), dtype=torch.float64, device=dev)
+        word_post = torch.empty((total, self.W), dtype=torch.float64, device=dev)
+        _lib.check(_lib.load().sapr_connected_lattice_posteriors(
+            _lib.ptr(self._offs_dev), n_utts, total, self.W, self._network.S, _lib.ptr(self._workspace), self._ws_bytes,
+            _lib.ptr(self._lm_dev[1]), _lib.ptr(lm), _lib.ptr(lm_start), _lib.ptr(lm_end), kappa,
+            _lib.ptr(keep_dev), _lib.ptr(workspace), ws_bytes, _lib.ptr(loglik),
+            _lib.ptr(record_post), _lib.ptr(word_post), _lib.current_stream()), "sapr_connected_lattice_posteriors")
+        host = [a.copy() for a in _lib.to_host(loglik, record_post, word_post)]
+        return LatticePosteriors(*host, offsets=self.offsets)
 
     def best(self) -> LatticePath:
         """:meth:`rescore` under the tables the lattice was made under: the one-pass search's string."""

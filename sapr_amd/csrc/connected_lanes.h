@@ -26,7 +26,7 @@
 //     value to cbuf[r], lane q < n reduces the SP values of segment q (a word, or a slot of the chain) — the first
 //     maximum (x_first_max) or the log-sum-exp (x_segment_lse) — and, under a word-pair language model, lane w reduces
 //     the W values xbuf[v] + lm[v][w] (x_first_max_pair over a row of the transposed lm, rows of W | 1 doubles so that
-//     W lanes read W different banks while xbuf[v] is a broadcast).
+//     W lanes read W different banks while xbuf[v] is a broadcast; pair_lse is the same step in the sum semiring).
 // Which recursion step sits behind the rotation — max or lse2, what is stored, which workspace rows — is the unit's.
 
 // ---- constants and host helpers ----------------------------------------------------------------------------------
@@ -365,6 +365,49 @@ __device__ __forceinline__ double x_segment_lse(double *cbuf, double *mbuf, cons
     double acc = 0.0;
 #pragma unroll
     for (int s = 0; s < SP; ++s) acc += cbuf[lane * SP + s];
+    r = isinf(m) ? m : log(acc) + m;
+  }
+  return r;
+}
+
+// The W x W log-sum-exp against a table in LDS (the word loop's forward-backward and the lattice posteriors): lane
+// q < W returns lse_p (mat[q][p] + xbuf[p]), p ascending, in the three steps connected_loop_fb.hip writes out — the
+// row maxima, the W * W exponentials spread over the 64 lanes into ebuf[W][W | 1], the row sums.  xbuf[64] is
+// synchronised by the caller; mbuf[64] and ebuf are free again when this returns.
+__device__ __forceinline__ double pair_lse(const double *mat, const double *xbuf, double *mbuf, double *ebuf, int lane,
+                                           int W, int LS) {
+  double m = neg_inf();
+  if (lane < W) {
+    const double *__restrict__ row = mat + lane * LS;
+    m = row[0] + xbuf[0];
+#pragma unroll 4
+    for (int p = 1; p < W; ++p) {
+      const double c = row[p] + xbuf[p];
+      m = c > m ? c : m;
+    }
+    mbuf[lane] = m;
+  }
+  wave_lds_sync();
+  {
+    const int q64 = kWave / W, r64 = kWave - q64 * W;  // item n + 64 from item n without a division
+    int q = lane / W, p = lane - q * W;
+    for (int n = lane; n < W * W; n += kWave) {
+      ebuf[q * LS + p] = exp_unit((mat[q * LS + p] + xbuf[p]) - mbuf[q]);  // (an infinite maximum: selected away)
+      p += r64;
+      q += q64;
+      if (p >= W) {
+        p -= W;
+        ++q;
+      }
+    }
+  }
+  wave_lds_sync();
+  double r = m;
+  if (lane < W) {
+    const double *__restrict__ e = ebuf + lane * LS;
+    double acc = 0.0;
+#pragma unroll 4
+    for (int p = 0; p < W; ++p) acc += e[p];
     r = isinf(m) ? m : log(acc) + m;
   }
   return r;

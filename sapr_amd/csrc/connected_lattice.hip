@@ -24,6 +24,14 @@
 //
 // float64 adds, one subtract and strict compares in the order of the definition: bit for bit the restatement.  No
 // atomics; an utterance's outputs are a function of its own frames and the tables alone.  Non-finite values propagate.
+//
+// Lattice posteriors (the definition is tests/_lattice_post_ref.py): forward-backward in the sum semiring
+// over the same records under any tables and an acoustic scale.  lattice_post_forward_kernel and
+// lattice_post_backward_kernel keep the backward kernel's mapping — one wavefront per utterance, lane w owning column w
+// of alpha, Q, beta and H — and take one W x W log-sum-exp per frame (pair_lse, connected_lanes.h) where the
+// max-semiring pass does W read-modify-writes; lattice_post_kernel, one lane per (utterance, word), forms record_post
+// and word_post from two running sums per column.  These three match the restatement within the tolerances of the
+// word loop's forward-backward, not bit for bit; every sum has a fixed order, so two calls return the same bytes.
 #include "sapr_common.h"
 
 namespace sapr {
@@ -366,6 +374,239 @@ __global__ __launch_bounds__(kXBlock) void connected_lattice_walk_kernel(
   if (n_words) n_words[u] = nw;
 }
 
+// ---- lattice posteriors: forward-backward in the sum semiring over the records ------------------------
+// LDS of one workgroup in doubles: lm'[W][W | 1] (transposed forward, row-major backward), lm_end'[W], lm_start'[W];
+// per wavefront xbuf[64], mbuf[64] and the exponentials of pair_lse, ebuf[W][W | 1] — 33 KB at W = 64, where three
+// wavefronts share a workgroup (x_waves)
+constexpr size_t lp_shared_doubles(int W) { return static_cast<size_t>(W) * x_lm_stride(W) + 2 * W; }
+constexpr size_t lp_wave_doubles(int W) { return 2 * kWave + static_cast<size_t>(W) * x_lm_stride(W); }
+
+// the scratch of the posteriors: alpha, Q, beta and H, each [total_frames][W] f64
+struct LpTables {
+  double *alpha, *Q, *beta, *H;
+};
+
+inline LpTables lp_tables(void *workspace, int64_t total_frames, int32_t W) {
+  const size_t one = lt_table_bytes(static_cast<size_t>(total_frames), static_cast<size_t>(W), 8);
+  uint8_t *p = static_cast<uint8_t *>(workspace);
+  LpTables t;
+  t.alpha = reinterpret_cast<double *>(p);
+  t.Q = reinterpret_cast<double *>(p + one);
+  t.beta = reinterpret_cast<double *>(p + 2 * one);
+  t.H = reinterpret_cast<double *>(p + 3 * one);
+  return t;
+}
+
+// what lane w's record at frame t brings into either pass: a = kappa * ac and its start frame; tau = -1 without one
+// (X not above -inf, a start outside 0 .. t, or keep == 0).  t lies inside the utterance and lane < W.
+struct LpRecord {
+  double a;
+  int tau;
+};
+
+__device__ __forceinline__ LpRecord lp_record(const double *__restrict__ X, const double *__restrict__ N,
+                                              const int32_t *__restrict__ B, const uint8_t *__restrict__ keep,
+                                              int64_t beg, int64_t t, int W, int lane, double in0, double kappa) {
+  const int64_t at = (beg + t) * W + lane;
+  const double x = X[at];
+  const int b = B[at];
+  const bool kept = keep ? keep[at] != 0 : true;
+  LpRecord r;
+  r.a = neg_inf();
+  r.tau = -1;
+  if (x > neg_inf() && b >= 0 && b <= t && kept) {
+    const double in = b == 0 ? in0 : N[(beg + b - 1) * W + lane];
+    r.a = kappa * (x - in);
+    r.tau = b;
+  }
+  return r;
+}
+
+// Forward: lane w forms alpha_t(w) = a + Q_{tau-1}(w) from its own column of Q — written frames ago by this very lane,
+// loaded a frame ahead; Q_{t-1} is handed on in a register — and the wavefront takes Q_t = the W x W log-sum-exp of
+// alpha_t against lm'.  It also leaves H = -inf for the backward pass and loglik[u].
+__global__ __launch_bounds__(kXBlock) void lattice_post_forward_kernel(
+    const int64_t *__restrict__ offsets, int64_t n_utts, int64_t total_frames, int32_t W,
+    const double *__restrict__ wend_score, const double *__restrict__ wend_entry,
+    const int32_t *__restrict__ wend_start, const double *__restrict__ fwd_lm_start, const double *__restrict__ lm,
+    const double *__restrict__ lm_start, const double *__restrict__ lm_end, double kappa,
+    const uint8_t *__restrict__ keep, double *__restrict__ alpha, double *Q, double *__restrict__ H,
+    double *__restrict__ loglik) {
+  extern __shared__ double smem[];
+  const int LS = x_lm_stride(W);
+  double *lmt = smem;           // [W][LS]: lmt[w][v] = lm'[v][w]
+  double *lme = lmt + W * LS;   // [W]
+  double *lms = lme + W;        // [W]
+  x_load_lm(lmt, lme, lm, lm_end, W, true, blockDim.x);
+  for (int n = threadIdx.x; n < W; n += blockDim.x) lms[n] = lm_start[n];
+  __syncthreads();
+
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = threadIdx.x / kWave;
+  const int waves = blockDim.x / kWave;
+  double *xbuf = lms + W + static_cast<size_t>(wave) * lp_wave_doubles(W);  // [64]: alpha_t(v)
+  double *mbuf = xbuf + kWave;                                              // [64]: the maxima
+  double *ebuf = mbuf + kWave;                                              // [W][LS]
+  const int64_t u = static_cast<int64_t>(blockIdx.x) * waves + wave;
+  if (u >= n_utts) return;  // (after the only barrier; a whole wavefront leaves)
+  const XFrames fr = x_frames(offsets, total_frames, u);
+  const int64_t beg = fr.beg, T = fr.T;
+  if (T == 0) {
+    if (lane == 0) loglik[u] = neg_inf();
+    return;
+  }
+  const bool mine = lane < W;  // lane w owns column w of alpha, Q and H
+  const double in0 = mine ? fwd_lm_start[lane] : neg_inf();
+  const double q0 = mine ? lms[lane] : neg_inf();
+  LpRecord nx;
+  nx.a = neg_inf();
+  nx.tau = -1;
+  if (mine) nx = lp_record(wend_score, wend_entry, wend_start, keep, beg, 0, W, lane, in0, kappa);
+  double qn = q0;             // what the next record starts from, where it is in memory already
+  double qlast = neg_inf();   // Q_{t-1}(lane)
+  for (int64_t t = 0; t < T; ++t) {
+    const LpRecord rc = nx;
+    const double qp = (rc.tau > 0 && rc.tau == t) ? qlast : qn;
+    if (mine && t + 1 < T) {  // the next frame's record in flight under this frame's chain
+      nx = lp_record(wend_score, wend_entry, wend_start, keep, beg, t + 1, W, lane, in0, kappa);
+      // (tau = t + 1 starts from Q_t, which this frame forms: the register)
+      qn = nx.tau == 0 ? q0 : ((nx.tau > 0 && nx.tau <= t) ? Q[(beg + nx.tau - 1) * W + lane] : neg_inf());
+    }
+    const double al = rc.tau >= 0 ? rc.a + qp : neg_inf();
+    const int64_t at = (beg + t) * W + lane;
+    if (mine) {
+      alpha[at] = al;
+      H[at] = neg_inf();
+    }
+    xbuf[lane] = al;
+    wave_lds_sync();
+    if (t + 1 < T) {  // (uniform) Q_t(w) on lane w; nothing starts behind the last frame
+      const double qv = pair_lse(lmt, xbuf, mbuf, ebuf, lane, W, LS);
+      if (mine) Q[at] = qv;
+      qlast = qv;
+    }
+  }
+  if (lane == 0) {  // loglik = lse_w (alpha_{T-1}(w) + lm_end'[w]), w ascending
+    double m = xbuf[0] + lme[0];
+    for (int p = 1; p < W; ++p) {
+      const double c = xbuf[p] + lme[p];
+      m = c > m ? c : m;
+    }
+    double ll = m;
+    if (!isinf(m)) {
+      double acc = 0.0;
+      for (int p = 0; p < W; ++p) acc += exp_unit((xbuf[p] + lme[p]) - m);
+      ll = log(acc) + m;
+    }
+    loglik[u] = ll;
+  }
+}
+
+// Backward: beta_t = the W x W log-sum-exp of H_{t+1} against the rows of lm' (lm_end' at the last frame); lane w then
+// folds g = a + beta_t(w) into H[tau][w] with one lse2.  The row it folds into and the lane's own H_t are loaded
+// before pair_lse, the next frame's record with them; H_t is kept in a register beside the memory.
+__global__ __launch_bounds__(kXBlock) void lattice_post_backward_kernel(
+    const int64_t *__restrict__ offsets, int64_t n_utts, int64_t total_frames, int32_t W,
+    const double *__restrict__ wend_score, const double *__restrict__ wend_entry,
+    const int32_t *__restrict__ wend_start, const double *__restrict__ fwd_lm_start, const double *__restrict__ lm,
+    const double *__restrict__ lm_end, double kappa, const uint8_t *__restrict__ keep, double *__restrict__ beta,
+    double *H) {
+  extern __shared__ double smem[];
+  const int LS = x_lm_stride(W);
+  double *lmx = smem;           // [W][LS]: row v is what lane v reads
+  double *lme = lmx + W * LS;   // [W]
+  x_load_lm(lmx, lme, lm, lm_end, W, false, blockDim.x);
+  __syncthreads();
+
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = threadIdx.x / kWave;
+  const int waves = blockDim.x / kWave;
+  double *xbuf = lme + 2 * W + static_cast<size_t>(wave) * lp_wave_doubles(W);  // [64]: H_{t+1}(w)
+  double *mbuf = xbuf + kWave;
+  double *ebuf = mbuf + kWave;
+  const int64_t u = static_cast<int64_t>(blockIdx.x) * waves + wave;
+  if (u >= n_utts) return;  // (after the only barrier; a whole wavefront leaves)
+  const XFrames fr = x_frames(offsets, total_frames, u);
+  const int64_t beg = fr.beg, T = fr.T;
+  if (T == 0) return;
+  const bool mine = lane < W;  // lane w owns column w of beta and H
+  const double in0 = mine ? fwd_lm_start[lane] : neg_inf();
+  LpRecord nx;
+  nx.a = neg_inf();
+  nx.tau = -1;
+  if (mine) nx = lp_record(wend_score, wend_entry, wend_start, keep, beg, T - 1, W, lane, in0, kappa);
+  double hn = neg_inf();  // H_{t+1}(lane), complete: every record that starts at t + 1 ends there or later
+  for (int64_t t = T - 1; t >= 0; --t) {
+    const LpRecord rc = nx;
+    const int64_t at = (beg + t) * W + lane;
+    const int64_t to = (beg + (rc.tau >= 0 ? rc.tau : 0)) * W + lane;
+    double hs = neg_inf(), cur = neg_inf();
+    if (mine) {
+      hs = H[at];
+      if (rc.tau >= 0) cur = H[to];
+    }
+    if (mine && t > 0) nx = lp_record(wend_score, wend_entry, wend_start, keep, beg, t - 1, W, lane, in0, kappa);
+    double bv;
+    if (t == T - 1) {  // (uniform)
+      bv = mine ? lme[lane] : neg_inf();
+    } else {
+      xbuf[lane] = hn;
+      wave_lds_sync();
+      bv = pair_lse(lmx, xbuf, mbuf, ebuf, lane, W, LS);
+    }
+    if (mine) {
+      beta[at] = bv;
+      if (rc.tau >= 0) {
+        const double now = lse2(cur, rc.a + bv);
+        H[to] = now;
+        hs = rc.tau == t ? now : hs;
+      }
+    }
+    hn = hs;
+  }
+}
+
+// The posterior pass: one lane per (utterance, word), f ascending.  The mass of word w that has started at or before
+// f needs no walk over records: the records of w that start at tau share Q_{tau-1}(w), so their posteriors add up to
+// exp(Q_{tau-1}(w) + H_tau(w) - loglik).  word_post[f][w] is that running sum minus the running sum of the record
+// posteriors that ended before f — two non-decreasing sums per column, each added in frame order.
+__global__ __launch_bounds__(kXBlock) void lattice_post_kernel(
+    const int64_t *__restrict__ offsets, int64_t n_utts, int64_t total_frames, int32_t W,
+    const double *__restrict__ lm_start, const double *__restrict__ alpha, const double *__restrict__ Q,
+    const double *__restrict__ beta, const double *__restrict__ H, const double *__restrict__ loglik,
+    double *__restrict__ record_post, double *__restrict__ word_post) {
+  const int64_t gid = static_cast<int64_t>(blockIdx.x) * kXBlock + threadIdx.x;
+  if (gid >= n_utts * W) return;
+  const int64_t u = gid / W;
+  const int w = static_cast<int>(gid - u * W);
+  const XFrames fr = x_frames(offsets, total_frames, u);
+  const int64_t beg = fr.beg, T = fr.T;
+  const double ll = loglik[u];
+  if (!finite_f64(ll)) {  // no path, or a NaN on the way: exact zeros
+    for (int64_t f = 0; f < T; ++f) {
+      record_post[(beg + f) * W + w] = 0.0;
+      if (word_post) word_post[(beg + f) * W + w] = 0.0;
+    }
+    return;
+  }
+  double started = 0.0, ended = 0.0;
+  double qprev = lm_start[w];
+  for (int64_t f = 0; f < T; ++f) {
+    const int64_t at = (beg + f) * W + w;
+    const double al = alpha[at], be = beta[at], h = H[at];
+    const double qnext = f + 1 < T ? Q[at] : neg_inf();
+    started += exp_unit((qprev + h) - ll);
+    if (word_post) {
+      const double d = started - ended;
+      word_post[at] = d < 0.0 ? 0.0 : d;
+    }
+    const double rp = al == neg_inf() ? 0.0 : exp_unit((al + be) - ll);
+    record_post[at] = rp;
+    ended += rp;
+    qprev = qnext;
+  }
+}
+
 int lt_check(int64_t total_frames, int64_t n_utts, int32_t W, int32_t S) {
   SAPR_REQUIRE(total_frames >= 0 && n_utts >= 0 && W > 0 && S > 0,
                "bad sizes (total_frames=%lld n_utts=%lld W=%d S=%d)", (long long)total_frames, (long long)n_utts, W, S);
@@ -450,4 +691,58 @@ extern "C" int sapr_connected_lattice_walk(const int64_t *offsets, int64_t n_utt
   SAPR_REQUIRE(offsets && root && first && (total_frames == 0 || (next_end && next_word)), "NULL pointer argument");
   return x_launch(connected_lattice_walk_kernel, blocks, kXBlock, 0, as_stream(stream), offsets, n_utts, total_frames,
                   W, next_end, next_word, root, first, n_words, path_word, path_entry);
+}
+
+extern "C" int sapr_connected_lattice_posteriors_workspace_bytes(int64_t total_frames, int64_t n_utts, int32_t W,
+                                                                 int32_t S, size_t *bytes) {
+  SAPR_REQUIRE(bytes, "NULL pointer argument (bytes)");
+  if (int rc = lt_check(total_frames, n_utts, W, S)) return rc;
+  // alpha, Q, beta and H [total_frames][W] float64, each padded to 16
+  *bytes = 4 * lt_table_bytes(static_cast<size_t>(total_frames), static_cast<size_t>(W), 8);
+  return 0;
+}
+
+extern "C" int sapr_connected_lattice_posteriors(const int64_t *offsets, int64_t n_utts, int64_t total_frames,
+                                                 int32_t W, int32_t S, const void *lattice_workspace,
+                                                 size_t lattice_workspace_bytes, const double *forward_lm_start,
+                                                 const double *lm, const double *lm_start, const double *lm_end,
+                                                 double acoustic_scale, const uint8_t *keep, void *workspace,
+                                                 size_t workspace_bytes, double *loglik, double *record_post,
+                                                 double *word_post, void *stream) {
+  if (int rc = lt_check(total_frames, n_utts, W, S)) return rc;
+  SAPR_REQUIRE(forward_lm_start && lm && lm_start && lm_end,
+               "NULL language model (forward_lm_start, lm, lm_start, lm_end)");
+  SAPR_REQUIRE(acoustic_scale - acoustic_scale == 0.0 && acoustic_scale > 0.0,
+               "acoustic_scale must be finite and > 0, got %g", acoustic_scale);
+  size_t need = 0;
+  if (int rc = sapr_connected_lattice_workspace_bytes(total_frames, n_utts, W, S, &need)) return rc;
+  SAPR_REQUIRE(lattice_workspace_bytes >= need && (need == 0 || lattice_workspace),
+               "lattice workspace too small: %zu < %zu", lattice_workspace_bytes, need);
+  if (int rc = sapr_connected_lattice_posteriors_workspace_bytes(total_frames, n_utts, W, S, &need)) return rc;
+  SAPR_REQUIRE(workspace_bytes >= need && (need == 0 || workspace), "workspace too small: %zu < %zu", workspace_bytes,
+               need);
+  size_t lds = 0;
+  const int waves = x_waves(lp_shared_doubles(W) * sizeof(double), lp_wave_doubles(W) * sizeof(double), &lds);
+  if (lds > static_cast<size_t>(kXLdsMax))
+    return fail(SAPR_ERR_UNSUPPORTED, "the lattice posteriors need %zu bytes of LDS, the device offers %d", lds,
+                kXLdsMax);
+  const int64_t blocks = (n_utts + waves - 1) / waves;
+  const int64_t post_blocks = (n_utts * W + kXBlock - 1) / kXBlock;
+  SAPR_REQUIRE(blocks <= 0x7fffffffLL && post_blocks <= 0x7fffffffLL, "grid too large (%lld utterances)",
+               (long long)n_utts);
+  if (n_utts == 0) return 0;
+  SAPR_REQUIRE(offsets && loglik && (total_frames == 0 || record_post), "NULL pointer argument");
+  const LTables tb = lt_tables(const_cast<void *>(lattice_workspace), total_frames, W);
+  const LpTables pt = lp_tables(workspace, total_frames, W);
+  hipStream_t st = as_stream(stream);
+  if (int rc = x_launch(lattice_post_forward_kernel, blocks, waves * kWave, lds, st, offsets, n_utts, total_frames, W,
+                        tb.X, tb.N, tb.B, forward_lm_start, lm, lm_start, lm_end, acoustic_scale, keep, pt.alpha, pt.Q,
+                        pt.H, loglik))
+    return rc;
+  if (total_frames == 0) return 0;
+  if (int rc = x_launch(lattice_post_backward_kernel, blocks, waves * kWave, lds, st, offsets, n_utts, total_frames, W,
+                        tb.X, tb.N, tb.B, forward_lm_start, lm, lm_end, acoustic_scale, keep, pt.beta, pt.H))
+    return rc;
+  return x_launch(lattice_post_kernel, post_blocks, kXBlock, 0, st, offsets, n_utts, total_frames, W, lm_start,
+                  pt.alpha, pt.Q, pt.beta, pt.H, loglik, record_post, word_post);
 }

@@ -11,7 +11,8 @@
 // The arithmetic is the sum-product one: lse2 over the live distances, then the entry (exit) term; the per-word
 // log-sum-exp over a word's states is x_segment_lse.
 //
-// This unit's own is the W x W log-sum-exp against lm (pair_lse): N_t(w) = lse_v (X_t(v) + lm[v][w]) forward,
+// The W x W log-sum-exp against lm is pair_lse (connected_lanes.h: the lattice posteriors of connected_lattice.hip
+// share it): N_t(w) = lse_v (X_t(v) + lm[v][w]) forward,
 // F_t(v) = lse_w (lm[v][w] + E_t(w)) backward.  lm lies in LDS in rows of W | 1 doubles — transposed in the forward
 // kernel, row-major in the backward kernel — so that lane q walks its own row while the other operand is a broadcast:
 //   1. lane q < W takes the maximum of its W terms (adds and compares, pipelined LDS reads);
@@ -45,47 +46,6 @@ constexpr size_t lf_shared_doubles(int W, int SP, int RL) {
 }
 constexpr size_t lf_wave_doubles(int W, int RL) {
   return static_cast<size_t>(kWave) * RL + 3 * kWave + static_cast<size_t>(W) * x_lm_stride(W);
-}
-
-// The W x W log-sum-exp: lane q < W returns lse_p (mat[q][p] + xbuf[p]), p ascending (the three steps above).  xbuf is
-// synchronised by the caller; mbuf and ebuf are free again when this returns.
-__device__ __forceinline__ double pair_lse(const double *mat, const double *xbuf, double *mbuf, double *ebuf, int lane,
-                                           int W, int LS) {
-  double m = neg_inf();
-  if (lane < W) {
-    const double *__restrict__ row = mat + lane * LS;
-    m = row[0] + xbuf[0];
-#pragma unroll 4
-    for (int p = 1; p < W; ++p) {
-      const double c = row[p] + xbuf[p];
-      m = c > m ? c : m;
-    }
-    mbuf[lane] = m;
-  }
-  wave_lds_sync();
-  {
-    const int q64 = kWave / W, r64 = kWave - q64 * W;  // item n + 64 from item n without a division
-    int q = lane / W, p = lane - q * W;
-    for (int n = lane; n < W * W; n += kWave) {
-      ebuf[q * LS + p] = exp_unit((mat[q * LS + p] + xbuf[p]) - mbuf[q]);  // (an infinite maximum: selected away)
-      p += r64;
-      q += q64;
-      if (p >= W) {
-        p -= W;
-        ++q;
-      }
-    }
-  }
-  wave_lds_sync();
-  double r = m;
-  if (lane < W) {
-    const double *__restrict__ e = ebuf + lane * LS;
-    double acc = 0.0;
-#pragma unroll 4
-    for (int p = 0; p < W; ++p) acc += e[p];
-    r = isinf(m) ? m : log(acc) + m;
-  }
-  return r;
 }
 
 // tab[dd][r] = log_trans[w][i][s] with r = w * SP + s and i = (s - dd) mod SP; lmx[a][b] = lm[a][b], or lm[b][a] where

@@ -108,7 +108,7 @@ class Decoder:
     # ---- connected words ------------------------------------------------------------------------
     def decode_connected(self, feature_list: List[np.ndarray], word_penalty: float = 0.0,
                          exit_states="last", bigram=None, confidence=False, n_words=None, max_words=None,
-                         nbest=False, alternatives=None, lattice=None) -> List[Dict]:
+                         nbest=False, alternatives=None, lattice=None, acoustic_scale: float = 1.0) -> List[Dict]:
         """Recordings that hold several words in a row: one-pass Viterbi over the word loop (``sapr_amd.connected``:
         the emission stage of the vocabulary's family, then ``sapr_connected_viterbi``).  ``feature_list``: (D, T)
         arrays as in ``decode_batch``.  Per utterance ``{"words": [...], "log_likelihood": float, "segments": [(word,
@@ -128,6 +128,17 @@ class Decoder:
         posterior of the segment's word over its frames —, ``"total_log_likelihood"`` — the log-likelihood of the
         recording over every word string the language model allows — and ``"log_posterior"`` =
         ``log_likelihood - total_log_likelihood``, the log posterior of the decoded path among all paths.
+
+        ``confidence="lattice"``: the confidences come from the word lattice instead — the lattice recursion over the
+        same emission (``sapr_connected_lattice``), then forward-backward over its records under the search's own
+        tables with the acoustic scores multiplied by ``acoustic_scale`` (``sapr_connected_lattice_posteriors``,
+        ``sapr_amd.LatticePosteriors``); ``sapr_connected_posteriors`` is not launched.  Each dict gains
+        ``"confidence"`` — one float per segment —, ``"lattice_log_likelihood"`` — the log-sum over every path of the
+        lattice — and ``"slots"``, per segment the list of ``(word, posterior)`` of the words that compete for its
+        frames, best first (``LatticePosteriors.slots``).  It is a different quantity from ``confidence=True``: Viterbi
+        within words and the recorded boundaries only.  ``lattice=`` may be combined with it: one lattice recursion
+        serves both.  Any other string, or an ``acoustic_scale`` that is not a finite number above 0, is a
+        ``ValueError``.
 
         ``n_words`` (an int, or one per recording): the number of words is known; ``max_words``: it is at most this (up
         to 8).  The search then runs level building (``sapr_connected_levels``): one pass that returns the best string
@@ -159,7 +170,11 @@ class Decoder:
         if self.implementation not in ("hmmlearn", "gmmhmm"):
             raise ValueError(f"connected-word decoding needs implementation='hmmlearn' with 'diag' or 'spherical' "
                              f"models: it has no emission stage for implementation={self.implementation!r}")
-        from .connected import _check_beam, connected_decode
+        from .connected import _check_acoustic_scale, _check_beam, connected_decode
+        if isinstance(confidence, str) and confidence != "lattice":  # (refused before a device is asked for)
+            raise ValueError(f"confidence must be True, False or 'lattice', got {confidence!r}")
+        by_lattice = isinstance(confidence, str)
+        acoustic_scale = _check_acoustic_scale(acoustic_scale)
         if lattice is None or lattice is False:
             beam = None
         else:
@@ -173,8 +188,9 @@ class Decoder:
             net = self._connected_network(exit_states, 0.0, self._word_bigram(bigram).scaled(1.0, word_penalty))
         if nbest and n_words is None and max_words is None:
             from .connected import MAX_LEVELS as max_words
-        res = connected_decode([np.asarray(f).T for f in feature_list], net, posteriors=bool(confidence),
-                               n_words=n_words, max_words=max_words, n_best=alternatives, lattice=beam is not None)
+        res = connected_decode([np.asarray(f).T for f in feature_list], net,
+                               posteriors=bool(confidence) and not by_lattice, n_words=n_words, max_words=max_words,
+                               n_best=alternatives, lattice=beam is not None or by_lattice)
         out = []
         for u in range(len(feature_list)):
             segs = res.segments(u)
@@ -204,7 +220,13 @@ class Decoder:
         if beam is not None:
             for u, row in enumerate(out):
                 row["lattice"] = [(words[w], a, b, ac, m) for w, a, b, ac, m in res.lattice.records(u, beam)]
-        if confidence:
+        if by_lattice:
+            lp = res.lattice.posteriors(None, acoustic_scale)
+            for u, row in enumerate(out):
+                row["confidence"] = lp.segment_confidence(res, u)
+                row["lattice_log_likelihood"] = float(lp.loglik[u])
+                row["slots"] = [[(words[w], p) for w, p in slot] for slot in lp.slots(res, u)]
+        elif confidence:
             log_post = res.posteriors.path_log_posterior(res)
             for u, row in enumerate(out):
                 row["confidence"] = res.posteriors.segment_confidence(res, u)
