@@ -737,6 +737,66 @@ int sapr_connected_lattice_posteriors(const int64_t *offsets, int64_t n_utts, in
                                       double *record_post, double *word_post /* may be NULL */, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Online connected-word decoding (csrc/connected_online.hip): the recursion of sapr_connected_bigram over recordings
+ * that are still arriving.  A session holds n_streams streams over one network; a chunk of frames per stream is
+ * consumed by sapr_connected_online_step, and sapr_connected_online_commit hands out the part of the best path that
+ * can no longer change (partial traceback).  The definition is the CPU restatement tests/_online_ref.py.  Fixed for a
+ * session: window, the back-pointer rows a stream keeps, and max_chunk, the most frames one step consumes,
+ * 1 <= max_chunk < window.
+ *   state      sapr_connected_online_state_bytes: n_streams blocks of
+ *                  64 + a16(8 * (R + 2 W)) + a16(window * R) + 2 * a16(window * W)   bytes, a16 rounding up to 16:
+ *              a header (frames consumed, committed, forced, ...), delta[R], X[W] and N[W] float64, and the rows of
+ *              sapr_connected_bigram's workspace for the frames t mod window.  Opaque device memory; ALL ZERO is a
+ *              session of fresh streams.
+ * Step: stream u consumes the frames offsets[u] .. offsets[u+1] of logb — sapr_connected_bigram's recursion continued
+ * from the stream's delta and N; the stream's absolute frame 0 takes the lm_start branch.  After the step delta, X, N
+ * and the stored rows are bit for bit what the offline recursion has at those frames.  A chunk longer than max_chunk
+ * (or than the ring has free, if commit was not called after the step before) has only its first frames consumed and
+ * truncated[u] = 1.
+ *   logb, offsets, tables, lm, lm_start, lm_end, W, S: as for sapr_connected_bigram (n_streams in the place of n_utts)
+ *   reset      [n_streams] uint8, may be NULL: != 0 makes the stream fresh before its chunk
+ *   truncated  [n_streams] uint8, may be NULL
+ * Commit, with t = frames - 1, c = committed and live = the flat states with finite delta_t: stable is the largest
+ * frame tau in [c, t] at which the stored back-traces from every live state hold the same state.  If there is one, rows
+ * c .. tau of that back-trace are final and c = tau + 1.  If then frames - c > window - max_chunk, the oldest
+ * k = frames - c - (window - max_chunk) pending frames are committed by force along the back-trace from the first
+ * maximum of delta_t over the live states in flat order (-1 / -1 / 0 where nothing is live) and forced += k: the next
+ * chunk always fits the ring.  A forced commit gives up the continuity of the path across that boundary, never the
+ * score.  With flush[u] != 0 the stream is flushed instead: score = max_v (X(v) + lm_end[v]) (-inf without frames); a
+ * finite score commits every pending row along the walk from the word that attains it, a score that is not finite
+ * commits nothing more and n_words = 0 (rows handed out earlier stand); the stream is then fresh.
+ *   flush        [n_streams] uint8, may be NULL (no stream is flushed)
+ *   n_new        [n_streams] int32: rows handed out by this call;  first_frame [n_streams] int64: the absolute frame
+ *                of the first of them
+ *   out_word, out_state [n_streams][window] int32, out_entry [n_streams][window] uint8: row i is frame first_frame + i
+ *   score        [n_streams] float64, n_words [n_streams] int32: written where flush[u] != 0 (n_words counts every
+ *                entry flag handed out for the recording); required with flush
+ *   forced       [n_streams] int64: frames of the recording committed by force so far
+ *   hyp_len      [n_streams] int32, hyp_word, hyp_state [n_streams][window] int32, hyp_entry uint8, each may be NULL:
+ *                the rows a flush would write now over the frames still pending (0 where the score is not finite)
+ * With forced == 0 and a finite score the rows handed out over a recording, n_words and score are
+ * sapr_connected_bigram's bit for bit, whatever the chunking.  No atomics; a stream's outputs are a function of its own
+ * frames, its own state and the network alone.  Every index read from the ring is clamped into its row.
+ *
+ * Bad sizes (window < 2, max_chunk outside 1 .. window - 1), NULL required pointers and a state that is too small
+ * return SAPR_ERR_ARG, S > 18 or W * SP > 256 SAPR_ERR_UNSUPPORTED (from the size function too), all before any
+ * launch; n_streams == 0 returns 0 after these checks. */
+int sapr_connected_online_state_bytes(int64_t n_streams, int32_t W, int32_t S, int32_t window, size_t *bytes);
+int sapr_connected_online_step(const double *logb, const int64_t *offsets, int64_t n_streams, int64_t total_frames,
+                               const double *log_start, const double *log_trans, const double *log_exit,
+                               const double *lm /* [W][W] */, const double *lm_start /* [W] */,
+                               const double *lm_end /* [W] */, int32_t W, int32_t S, int32_t window, int32_t max_chunk,
+                               void *state, size_t state_bytes, const uint8_t *reset /* may be NULL */,
+                               uint8_t *truncated /* may be NULL */, void *stream);
+int sapr_connected_online_commit(int64_t n_streams, int32_t W, int32_t S, int32_t window, int32_t max_chunk,
+                                 void *state, size_t state_bytes, const uint8_t *flush /* may be NULL */,
+                                 int32_t *n_new, int64_t *first_frame, int32_t *out_word, int32_t *out_state,
+                                 uint8_t *out_entry, double *score, int32_t *n_words, int64_t *forced,
+                                 int32_t *hyp_len /* may be NULL */, int32_t *hyp_word /* may be NULL */,
+                                 int32_t *hyp_state /* may be NULL */, uint8_t *hyp_entry /* may be NULL */,
+                                 void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Connected-word confidence (csrc/connected_loop_fb.hip): forward-backward over the word loop under the word-pair
  * language model of sapr_connected_bigram — the sum over every word string the grammar allows where that function
  * takes the maximum.  The definition is the CPU restatement tests/_loop_fb_ref.py; with b_t(w,s) = logb[t][w * SP + s]

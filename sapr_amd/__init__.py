@@ -14,7 +14,8 @@ behaviour) over hand-written HIP kernels in ``libsapr_hip.so``:
                              word-pair grammar where one is given: ``WordBigram``; with a known or bounded number of
                              words by level building: ``connected_levels``; the N best distinct word strings
                              in one pass: ``connected_nbest``; a word lattice that is pruned to a beam and rescored
-                             under another language model: ``connected_lattice``), word and segment confidences
+                             under another language model: ``connected_lattice``; recordings that are still
+                             arriving, decoded chunk by chunk: ``ConnectedSession``), word and segment confidences
                              from forward-backward over the same loop (``connected_posteriors``), forced alignment of
                              a recording to its known word string, embedded Baum-Welch training from such
                              recordings, and discriminative (MMI) training of the word models against the word loop
@@ -40,7 +41,8 @@ def __getattr__(name):
     ``sapr_amd.NBestResult`` / ``sapr_amd.connected_nbest`` / ``sapr_amd.nbest_capacity`` / ``sapr_amd.WordLattice`` /
     ``sapr_amd.LatticePath`` / ``sapr_amd.LatticeBackward`` / ``sapr_amd.connected_lattice`` /
     ``sapr_amd.lattice_workspace_bytes`` / ``sapr_amd.LatticePosteriors`` /
-    ``sapr_amd.lattice_posteriors_workspace_bytes``
+    ``sapr_amd.lattice_posteriors_workspace_bytes`` / ``sapr_amd.ConnectedSession`` / ``sapr_amd.OnlineUpdate`` /
+    ``sapr_amd.OnlineResult`` / ``sapr_amd.online_state_bytes``
     (resolved on first use: importing the package stays light)."""
     if name in ("GMMHMM", "fit_gmm_models", "vocab_scores"):
         from . import gmm_hmm
@@ -53,7 +55,8 @@ def __getattr__(name):
                 "with_optional", "align_opt_workspace_bytes", "loop_stats", "loop_stats_workspace_bytes", "MmiStats",
                 "mmi_estep", "mmi_update", "mmi_fit", "NBestResult", "connected_nbest", "nbest_capacity", "WordLattice",
                 "LatticePath", "LatticeBackward", "connected_lattice", "lattice_workspace_bytes", "LatticePosteriors",
-                "lattice_posteriors_workspace_bytes"):
+                "lattice_posteriors_workspace_bytes", "ConnectedSession", "OnlineUpdate", "OnlineResult",
+                "online_state_bytes"):
         from . import connected
         return getattr(connected, name)
     if name == "full_vocab_scores":

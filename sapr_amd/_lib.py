@@ -122,6 +122,12 @@ SIGNATURES = {
     "sapr_connected_lattice_posteriors": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_size_t,
                                                   c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
                                                   c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sapr_connected_online_state_bytes": (c_int, [c_int64, c_int32, c_int32, c_int32, C.POINTER(c_size_t)]),
+    "sapr_connected_online_step": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_size_t,
+                                           c_void_p, c_void_p, c_void_p]),
+    "sapr_connected_online_commit": (c_int, [c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_size_t]
+                                     + [c_void_p] * 14),
     "sapr_connected_posteriors_workspace_bytes": (c_int, [c_int64, c_int64, c_int32, c_int32, C.POINTER(c_size_t)]),
     "sapr_connected_posteriors": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p, c_void_p,

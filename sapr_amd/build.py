@@ -25,7 +25,7 @@ SOURCES = ["viterbi_exact_39_18_t1s1.hip", "viterbi_exact_39_18_t1s0.hip", "vite
            "resample.hip", "kmeans.hip", "gmm_hmm.hip", "gmm_vocab.hip", "full_vocab.hip",
            "connected.hip", "connected_align.hip", "connected_embed.hip", "connected_bigram.hip",
            "connected_loop_fb.hip", "connected_levels.hip", "connected_loop_stats.hip", "connected_nbest.hip",
-           "connected_lattice.hip"]
+           "connected_lattice.hip", "connected_online.hip"]
 # -ffp-contract=off: the trellis kernels must perform the individually rounded IEEE
 # operations numpy performs (bit-identical Viterbi scores); kernels that want FMAs
 # call fma()/__builtin_fmaf explicitly.

@@ -35,6 +35,13 @@ the definition is ``tests/_lattice_ref.py``).  ``sapr_connected_lattice_posterio
 semiring over the same records — link and word posteriors and the likelihood of the lattice under any tables and
 acoustic scale (:meth:`WordLattice.posteriors`, :class:`LatticePosteriors`; ``tests/_lattice_post_ref.py``).
 
+Recordings that are still arriving: ``sapr_connected_online_step`` / ``sapr_connected_online_commit``
+(``csrc/connected_online.hip``) carry the bigram recursion's trellis column from chunk to chunk of B streams and hand
+the path out by partial traceback — everything before the frame at which the back-traces of all live hypotheses pass
+through one state is final —, over a ring of ``window`` back-pointer rows per stream; the final answer is the offline
+decoder's bit for bit (:class:`ConnectedSession`, ``Decoder.open_connected``; the definition is
+``tests/_online_ref.py``).
+
 How much to believe a decoded string: ``sapr_connected_posteriors`` (``csrc/connected_loop_fb.hip``) runs
 forward-backward over the same loop under the same language model — the sum over every word string where the search
 takes the best one — and returns the total log-likelihood, the per-frame word and word-boundary posteriors and, from
@@ -1288,6 +1295,210 @@ def connected_decode(batch_or_feature_list, network: ConnectedNetwork, posterior
     if lattice:
         res.lattice = _run_lattice(logb, offs_dev, offs, network)
     return res
+
+
+# ---- online decoding: recordings that are still arriving ----------------------------------------
+def online_state_bytes(n_streams, W, S, window) -> int:
+    return _workspace_bytes("sapr_connected_online_state_bytes", n_streams, W, S, window)
+
+
+@dataclass
+class OnlineUpdate:
+    """What one :meth:`ConnectedSession.push` hands out for one stream: the rows that became final."""
+    first_frame: int        # the absolute frame of the first new row
+    path_word: np.ndarray   # [n_new] i32
+    path_state: np.ndarray  # [n_new] i32
+    path_entry: np.ndarray  # [n_new] u8
+    segments: list          # newly complete (word_index, start, end_exclusive), absolute frames
+    frames: int             # frames of the recording consumed so far
+    stable_frames: int      # ... of which final
+    forced: int             # ... of which committed by force (the window was too small for the path to settle)
+    hypothesis: list = None  # push(..., hypothesis=True): the words of the best string over the pending frames
+    hypothesis_rows: tuple = None  # ... and its (path_word, path_state, path_entry) over them, as a flush would write
+
+
+@dataclass
+class OnlineResult:
+    """What :meth:`ConnectedSession.finish` returns for one stream: the fields of a :class:`ConnectedResult` for the
+    whole recording — the concatenation of every row handed out — and ``forced``.  With ``forced == 0`` and a finite
+    score they are the offline decoder's bit for bit; a score that is not finite leaves the rows handed out before the
+    flush as they are and ``n_words == 0``."""
+    score: float
+    n_words: int
+    path_word: np.ndarray
+    path_state: np.ndarray
+    path_entry: np.ndarray
+    forced: int
+    update: OnlineUpdate    # what the flush itself handed out
+
+    def segments(self):
+        if self.n_words == 0:
+            return []
+        starts = np.flatnonzero(self.path_entry).tolist()
+        return [(int(self.path_word[a]), a, b) for a, b in zip(starts, starts[1:] + [len(self.path_word)])]
+
+    def words(self):
+        return [w for w, _, _ in self.segments()]
+
+
+class ConnectedSession:
+    """Online connected-word decoding (``sapr_connected_online_step`` / ``sapr_connected_online_commit``,
+    ``csrc/connected_online.hip``; the definition is ``tests/_online_ref.py``): ``n_streams`` recordings that arrive in
+    chunks over one network.  The device keeps the trellis column and ``window`` back-pointer rows per stream; a path
+    prefix is handed out as soon as every live hypothesis agrees on it, and the final answer is the offline decoder's
+    bit for bit unless ``forced`` says that the window was too small.  A network without a bigram runs under
+    ``lm == word_penalty``.  ``1 <= max_chunk < window``."""
+
+    def __init__(self, network: ConnectedNetwork, n_streams, window=256, max_chunk=64):
+        torch = _torch()
+        self.network, self.n_streams = network, int(n_streams)
+        self.window, self.max_chunk = int(window), int(max_chunk)
+        if self.n_streams < 1:
+            raise ValueError(f"n_streams must be >= 1, got {n_streams!r}")
+        if not 1 <= self.max_chunk < self.window:
+            raise ValueError(f"1 <= max_chunk < window is required, got max_chunk={max_chunk!r} window={window!r}")
+        self._dev = dev = _lib.require_gpu()
+        self._state_bytes = online_state_bytes(self.n_streams, network.W, network.S, self.window)
+        self._state = torch.zeros(max(self._state_bytes, 1), dtype=torch.uint8, device=dev)  # all zero: fresh
+        B, win = self.n_streams, self.window
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+        u8 = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=dev)  # noqa: E731
+        self._n_new, self._first = i32(B), torch.empty(B, dtype=torch.int64, device=dev)
+        self._rows = (i32(B, win), i32(B, win), u8(B, win))
+        self._score, self._n_words = torch.empty(B, dtype=torch.float64, device=dev), i32(B)
+        self._forced = torch.empty(B, dtype=torch.int64, device=dev)
+        self._hyp = (i32(B), i32(B, win), i32(B, win), u8(B, win))
+        self._truncated = u8(B)
+        self.frames = [0] * B
+        self.stable_frames = [0] * B
+        self._open = [None] * B                      # (word, start) of the segment whose end is not final yet
+        self._kept = [[] for _ in range(B)]          # the rows handed out, for finish()
+
+    def _chunks(self, chunks, dtype):
+        """One host array per stream (``None``: no frames) -> ``(arrays, host offsets)``."""
+        if len(chunks) != self.n_streams:
+            raise ValueError(f"one chunk per stream: got {len(chunks)} for {self.n_streams} streams")
+        mats = []
+        for u, c in enumerate(chunks):
+            m = np.zeros(0, dtype) if c is None else np.asarray(c, dtype=dtype)
+            if m.shape[0] > self.max_chunk:
+                raise ValueError(f"the chunk of stream {u} has {m.shape[0]} frames, max_chunk is {self.max_chunk}")
+            mats.append(m)
+        _, offs = _offsets([m.shape[0] for m in mats])
+        return mats, offs
+
+    def push(self, feats=None, logb=None, hypothesis=False):
+        """One chunk per stream — ``feats``: frame-major ``(t, D)`` feature arrays for a network that carries its
+        emission parameters, or ``logb``: float64 ``[t, W, S]``, ``[t, W, SP]`` or ``[t, R]`` arrays; ``None`` or an
+        empty array for a stream without new frames, at most ``max_chunk`` frames each (a ``ValueError`` names the
+        stream otherwise).  Emission over the concatenated chunk frames, one step, one commit.  Returns one
+        :class:`OnlineUpdate` per stream."""
+        torch = _torch()
+        net, dev = self.network, self._dev
+        if (feats is None) == (logb is None):
+            raise ValueError("push takes either feats or logb")
+        if logb is None:
+            mats, offs = self._chunks(feats, np.float32)
+            total = int(offs[-1])
+            if any(m.ndim != 2 or m.shape[1] != net.D for m in mats if m.shape[0]):
+                raise ValueError(f"feature chunks must be (t, D = {net.D}) arrays")
+            packed = np.concatenate([m.reshape(-1, net.D) for m in mats]) if total else np.zeros((0, net.D), np.float32)
+            if total:
+                rows = _EMIT[net.family](torch.from_numpy(np.ascontiguousarray(packed, np.float32)).to(dev), net)
+            else:
+                rows = torch.empty((0, net.R), dtype=torch.float64, device=dev)
+        else:
+            mats, offs = self._chunks(logb, np.float64)
+            total = int(offs[-1])
+            live = [m for m in mats if m.shape[0]]
+            packed = np.concatenate(live) if live else np.zeros((0, net.R))
+            rows = _flat_states(packed, total, net, dev)
+        self._step(rows, offs, total)
+        return self._commit(None, hypothesis)
+
+    def _step(self, rows, offs, total, reset=None):
+        torch = _torch()
+        net, dev = self.network, self._dev
+        ls, lt, lx, _ = net.device(dev)
+        lm, lm_start, lm_end = net.device_lm(dev)
+        offs_dev = torch.from_numpy(offs).to(dev)
+        reset_dev = None if reset is None else torch.from_numpy(np.asarray(reset, np.uint8)).to(dev)
+        _lib.check(_lib.load().sapr_connected_online_step(
+            _lib.ptr(rows), _lib.ptr(offs_dev), self.n_streams, total, _lib.ptr(ls), _lib.ptr(lt), _lib.ptr(lx),
+            _lib.ptr(lm), _lib.ptr(lm_start), _lib.ptr(lm_end), net.W, net.S, self.window, self.max_chunk,
+            _lib.ptr(self._state), self._state_bytes, _lib.ptr(reset_dev), _lib.ptr(self._truncated),
+            _lib.current_stream()), "sapr_connected_online_step")
+        for u in range(self.n_streams):
+            if reset is not None and reset[u]:
+                self._forget(u)
+            self.frames[u] += int(offs[u + 1] - offs[u])
+
+    def _forget(self, u):
+        self.frames[u] = self.stable_frames[u] = 0
+        self._open[u] = None
+        self._kept[u] = []
+
+    def reset(self, streams=None):
+        """Abandon the recordings of ``streams`` (all by default): they start fresh, nothing is handed out."""
+        flags = np.zeros(self.n_streams, np.uint8)
+        flags[list(range(self.n_streams)) if streams is None else list(streams)] = 1
+        self._step(None, np.zeros(self.n_streams + 1, np.int64), 0, flags)
+
+    def _commit(self, flush, hypothesis):
+        torch = _torch()
+        net = self.network
+        flush_dev = None if flush is None else torch.from_numpy(flush).to(self._dev)
+        hyp = self._hyp if hypothesis else (None,) * 4
+        _lib.check(_lib.load().sapr_connected_online_commit(
+            self.n_streams, net.W, net.S, self.window, self.max_chunk, _lib.ptr(self._state), self._state_bytes,
+            _lib.ptr(flush_dev), _lib.ptr(self._n_new), _lib.ptr(self._first), *(_lib.ptr(t) for t in self._rows),
+            _lib.ptr(self._score), _lib.ptr(self._n_words), _lib.ptr(self._forced), *(_lib.ptr(t) for t in hyp),
+            _lib.current_stream()), "sapr_connected_online_commit")
+        host = _lib.to_host(self._n_new, self._first, *self._rows, self._score, self._n_words, self._forced,
+                            self._truncated, *(self._hyp if hypothesis else ()))
+        n_new, first, pw, ps, pe, score, n_words, forced, truncated = host[:9]
+        if truncated.any():  # (push refuses over-long chunks, so this is a session used against its contract)
+            raise _lib.SaprHipError(f"stream {int(np.flatnonzero(truncated)[0])}: the ring had no room for its chunk")
+        out = []
+        for u in range(self.n_streams):
+            n = int(n_new[u])
+            up = OnlineUpdate(int(first[u]), pw[u, :n].copy(), ps[u, :n].copy(), pe[u, :n].copy(), [],
+                              self.frames[u], int(first[u]) + n, int(forced[u]))
+            flushed = flush is not None and bool(flush[u])
+            for i in np.flatnonzero(up.path_entry).tolist():   # an entry closes the segment before it
+                if self._open[u] is not None:
+                    up.segments.append((*self._open[u], up.first_frame + i))
+                self._open[u] = (int(up.path_word[i]), up.first_frame + i)
+            if flushed and self._open[u] is not None and np.isfinite(score[u]):
+                up.segments.append((*self._open[u], self.frames[u]))
+            self.stable_frames[u] = up.stable_frames
+            self._kept[u].append((up.path_word, up.path_state, up.path_entry))
+            if hypothesis:
+                k = int(host[9][u])
+                ent = host[12][u, :k]
+                up.hypothesis_rows = (host[10][u, :k].copy(), host[11][u, :k].copy(), ent.copy())
+                up.hypothesis = [int(w) for w in host[10][u, :k][ent != 0]]
+                if k and not ent[0] and self._open[u] is not None:
+                    up.hypothesis.insert(0, self._open[u][0])  # (they begin inside the word whose start is final)
+            if flushed:
+                kept = self._kept[u]
+                cat = lambda j, dt: np.concatenate([r[j] for r in kept]).astype(dt)  # noqa: E731
+                out.append(OnlineResult(float(score[u]), int(n_words[u]), cat(0, np.int32), cat(1, np.int32),
+                                        cat(2, np.uint8), int(forced[u]), up))
+                self._forget(u)
+            else:
+                out.append(up)
+        return out
+
+    def finish(self, streams=None):
+        """End the recordings of ``streams`` (all by default): the pending frames are walked back from the best final
+        word and handed out, and the streams are fresh again.  One :class:`OnlineResult` per flushed stream, in the
+        order given."""
+        order = list(range(self.n_streams)) if streams is None else [int(u) for u in streams]
+        flags = np.zeros(self.n_streams, np.uint8)
+        flags[order] = 1
+        out = self._commit(flags, False)
+        return [out[u] for u in order]
 
 
 # ---- forced alignment ---------------------------------------------------------------------------

@@ -37,6 +37,43 @@ from . import _lib
 from .mfcc_extract import load_mfccs_by_word
 
 
+class DecoderSession:
+    """What ``Decoder.open_connected`` returns: a ``sapr_amd.ConnectedSession`` that speaks the decoder's language —
+    (D, t) feature chunks in, word names out."""
+
+    def __init__(self, session, words: List[str]):
+        self.session, self.words = session, words
+
+    def push(self, chunks, hypothesis: bool = False) -> List[Dict]:
+        """One (D, t) feature array per stream (``None``: no new frames; more than ``max_chunk`` frames is a
+        ``ValueError`` that names the stream).  Per stream ``{"segments": the newly complete (word, start,
+        end_exclusive) in frames of the recording, "state_sequence": the newly final states, "first_frame",
+        "frames", "stable_frames", "forced"}`` and, with ``hypothesis=True``, ``"hypothesis"``: the words of the best
+        string over the frames that are not final yet."""
+        ups = self.session.push(feats=[None if c is None else np.asarray(c).T for c in chunks],
+                                hypothesis=hypothesis)
+        out = []
+        for up in ups:
+            row = {"segments": [(self.words[w], a, b) for w, a, b in up.segments],
+                   "state_sequence": up.path_state.astype(np.int64), "first_frame": up.first_frame,
+                   "frames": up.frames, "stable_frames": up.stable_frames, "forced": up.forced}
+            if hypothesis:
+                row["hypothesis"] = [self.words[w] for w in up.hypothesis]
+            out.append(row)
+        return out
+
+    def finish(self, streams=None) -> List[Dict]:
+        """End the recordings of ``streams`` (all by default): per stream the dict of ``Decoder.decode_connected`` for
+        the whole recording plus ``"forced"``; the streams are fresh again."""
+        out = []
+        for res in self.session.finish(streams):
+            segs = res.segments()
+            out.append({"words": [self.words[w] for w, _, _ in segs], "log_likelihood": res.score,
+                        "segments": [(self.words[w], a, b) for w, a, b in segs],
+                        "state_sequence": res.path_state.astype(np.int64), "forced": res.forced})
+        return out
+
+
 class Decoder:
     def __init__(self, models_dir: str = "trained_models", implementation: str = "hmmlearn", n_iter: int = 15,
                  scoring: str = "viterbi"):
@@ -233,6 +270,27 @@ class Decoder:
                 row["total_log_likelihood"] = float(res.posteriors.loglik[u])
                 row["log_posterior"] = float(log_post[u])
         return out
+
+    def open_connected(self, n_streams: int, bigram=None, word_penalty: float = 0.0, exit_states="last",
+                       window: int = 256, max_chunk: int = 64) -> "DecoderSession":
+        """Online ``decode_connected``: ``n_streams`` recordings that are still arriving, decoded chunk by chunk over
+        the word loop under the same ``bigram`` / ``word_penalty`` / ``exit_states`` (``sapr_amd.ConnectedSession``:
+        the vocabulary's emission stage on each chunk, ``sapr_connected_online_step``, then
+        ``sapr_connected_online_commit``).  The returned :class:`DecoderSession` takes (D, t) feature chunks of at
+        most ``max_chunk`` frames; the device keeps ``window`` frames of back-pointers per stream.  Its ``finish``
+        returns the dicts of ``decode_connected`` — bit for bit where ``"forced"`` is 0.  The features are the
+        caller's: an MFCC front end that needs context across a chunk edge (deltas) must supply it itself.
+
+        Served for the implementations and families ``decode_connected`` serves."""
+        if self.implementation not in ("hmmlearn", "gmmhmm"):
+            raise ValueError(f"connected-word decoding needs implementation='hmmlearn' with 'diag' or 'spherical' "
+                             f"models: it has no emission stage for implementation={self.implementation!r}")
+        from .connected import ConnectedSession
+        if bigram is None:
+            net = self._connected_network(exit_states, word_penalty)
+        else:
+            net = self._connected_network(exit_states, 0.0, self._word_bigram(bigram).scaled(1.0, word_penalty))
+        return DecoderSession(ConnectedSession(net, n_streams, window, max_chunk), list(self.models))
 
     def _word_bigram(self, bigram):
         """``decode_connected``'s ``bigram`` as a ``WordBigram`` over the vocabulary in load order."""
