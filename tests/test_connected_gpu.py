@@ -15,7 +15,8 @@ pytestmark = pytest.mark.gpu
 
 NEG = -np.inf
 SHAPES = [(3, 4), (11, 10), (11, 18), (14, 18), (64, 4), (5, 7), (2, 1),
-          (3, 12), (17, 3), (4, 11)]   # RL = 1, 2, 2 at SP = 18, 4, 18: shapes the lists of the sibling decoders share
+          (3, 12), (17, 3), (4, 11),   # RL = 1, 2, 2 at SP = 18, 4, 18: shapes the lists of the sibling decoders share
+          (25, 10)]                    # ... and (RL, SP) = (4, 10)
 LENGTHS = [3, 64, 1, 300, 0, 65, 2, 63]   # mixed within one batch, an empty utterance in the middle
 
 

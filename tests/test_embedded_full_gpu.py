@@ -110,10 +110,12 @@ def _check_rows(rows, want, S, D, what="", n_states=None):
 
 
 # ---- 1. tile geometry ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("D", [1, 13, 14, 26, 27, 39])
+@pytest.mark.parametrize("D", [1, 13, 14, 26, 27, 39, 12, 15, 16, 17, 25, 31, 32, 33, 38])
 def test_tile_geometry(D):
     """The batch of ``test_observation_sums`` (repeated words in a transcript: the slot collapse; utterance 4 has
-    K > T) at every DP, on both sides of each padding boundary and with the ones column at every place it can sit."""
+    K > T) at every DP, on both sides of each padding boundary and with the ones column at every place it can sit;
+    D = 12, 15 .. 17, 25, 31 .. 33 and 38 cut a 16-wide matrix-core tile inside a padded width (the masks on rows and
+    columns and the ones column next to the last feature)."""
     W, S = 4, 5
     rng = np.random.default_rng(300)
     ls, lt, lx = aref.network(rng, W, S, "skip", "last", False)
@@ -142,8 +144,10 @@ def test_tile_geometry(D):
 # ---- 2. state groups and chain widths ---------------------------------------------------------------------------
 # (W, S, max_words, blocks of 64 chain positions): SP = 4, 10, 18 and the kernels with one, two and four positions per
 # lane; S = 3, 7, 10 and 18 are no multiple of the four states of a pass; (14, 18, 14) sits at the edge of the backward
-# kernel's LDS
-CHAIN_SHAPES = [(3, 3, 5, 1), (4, 4, 40, 3), (5, 7, 9, 2), (7, 10, 25, 4), (6, 18, 3, 1), (6, 18, 7, 2), (14, 18, 14, 4)]
+# kernel's LDS; S = 1 and S = 17 run the four-states-per-pass loop of the second-moment pass with one state and with one
+# state in its last round
+CHAIN_SHAPES = [(3, 3, 5, 1), (4, 4, 40, 3), (5, 7, 9, 2), (7, 10, 25, 4), (6, 18, 3, 1), (6, 18, 7, 2), (14, 18, 14, 4),
+                (2, 1, 6, 1), (3, 17, 3, 1)]
 CHAIN_LENGTHS = [40, 17, 1, 48, 23]
 
 
@@ -157,9 +161,10 @@ def test_state_groups_and_chain_widths(W, S, max_words, blocks):
     rng = np.random.default_rng(17 * W + S + max_words)
     ls, lt, lx = aref.network(rng, W, S, "dense", "any", False)
     logb = rng.normal(-40.0, 15.0, (sum(CHAIN_LENGTHS), W, S))
-    ls[0, S - 1] = lx[0, S - 1] = NEG                            # word 0: a model of S - 1 states, padded
-    lt[0, S - 1, :] = lt[0, :, S - 1] = NEG
-    logb[:, 0, S - 1] = NEG
+    if S > 1:
+        ls[0, S - 1] = lx[0, S - 1] = NEG                        # word 0: a model of S - 1 states, padded
+        lt[0, S - 1, :] = lt[0, :, S - 1] = NEG
+        logb[:, 0, S - 1] = NEG
     transcripts = []
     for T in CHAIN_LENGTHS:
         K = min(max_words, T) if T == 48 else int(rng.integers(1, min(max_words, T, 6) + 1))
@@ -172,6 +177,8 @@ def test_state_groups_and_chain_widths(W, S, max_words, blocks):
     what = f"(W, S, max_words) = {(W, S, max_words)}"
     _check_loglik(got[0], want["loglik"], what)
     _check_rows(got[1], want, S, D, what=what)
+    if S == 1:
+        return
     from sapr_amd.full_cov import split_stats
     whole = split_stats(got[1][0], S, D)
     for key in ("start", "post", "obs", "obs*obs.T"):
