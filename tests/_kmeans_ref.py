@@ -9,6 +9,10 @@ the summed squared centre shift is <= threshold, inertia from one more assignmen
 deviation: an empty cluster keeps its previous centre.  Like scikit-learn, :func:`lloyd` works on the data minus its column
 mean and adds the mean back to the centres (c0 sits near -300: coordinates near zero would otherwise carry the rounding
 of sums near -300 n, which an element-wise comparison against scikit-learn at rtol 1e-12 sees).
+
+:func:`seed_centres` and :func:`kmeans_seeded` restate the seeding of ``kmeans(init=None, seeds=...)`` for one rank from
+its documented rules (kmeans.py's docstring): ``default_rng(seed)``, a sorted uniform subsample of
+``min(n, 256 K)`` rows shared by the restarts, plain k-means++ on it.
 """
 from __future__ import annotations
 
@@ -128,3 +132,62 @@ def recipe_lloyd(D, K):
     """The reference Lloyd run of every (group, restart) problem of one shape: list over g of list over r."""
     groups, init = recipe_groups(D), recipe_init(D, K)
     return tuple(tuple(lloyd(X, init[g, r]) for r in range(R)) for g, X in enumerate(groups))
+
+
+# ---- kmeans(init=None, seeds=...): the seeding of ONE rank, restated from kmeans.py's docstring and DESIGN.md §8 ------
+SUBSAMPLE_PER_CLUSTER = 256
+
+
+def kmeans_pp(X, K, rng):
+    """Plain k-means++ -> indices of K rows of ``X[n, D]``: the first uniform (``rng.integers``), each further one
+    ``rng.choice`` in proportion to the squared distance to the nearest row chosen so far; when that total is zero (or
+    not finite) uniform among the rows not chosen yet."""
+    X = np.asarray(X, dtype=np.float64)
+    n = X.shape[0]
+    idx = [int(rng.integers(n))]
+    near = ((X - X[idx[0]]) ** 2).sum(axis=1)
+    for _ in range(1, K):
+        total = near.sum()
+        if np.isfinite(total) and total > 0:
+            i = int(rng.choice(n, p=near / total))
+        else:
+            free = np.setdiff1d(np.arange(n), idx)
+            i = int(free[rng.integers(free.size)])
+        idx.append(i)
+        near = np.minimum(near, ((X - X[i]) ** 2).sum(axis=1))
+    return np.array(idx, dtype=np.int64)
+
+
+def seed_centres(X, K, n_init, seed):
+    """-> (centres[n_init, K, D] float64, pick[m]): ``default_rng(seed)`` first draws the group's subsample — the sorted
+    ``choice(n, m, replace=False)`` with ``m = min(n, 256 K)``, every row when ``m == n`` (no draw) — which all restarts
+    share, then restart after restart one :func:`kmeans_pp` on it from the same stream."""
+    X = np.asarray(X, dtype=np.float64)
+    n = X.shape[0]
+    rng = np.random.default_rng(int(seed))
+    m = min(n, SUBSAMPLE_PER_CLUSTER * K)
+    pick = np.sort(rng.choice(n, m, replace=False)) if m < n else np.arange(n)
+    sub = X[pick]
+    return np.stack([sub[kmeans_pp(sub, K, rng)] for _ in range(n_init)]), pick
+
+
+def best_restart(runs):
+    """-> (index of the lowest inertia (first lowest), relative margin to the runner-up (inf for one run), indices of
+    the runs within 1e-9 of the best)."""
+    ri = np.array([run["inertia"] for run in runs])
+    order = np.argsort(ri, kind="stable")
+    if len(ri) < 2:
+        return int(order[0]), np.inf, [int(order[0])]
+    second = ri[order[1]]
+    margin = (second - ri[order[0]]) / second if second > 0 else 0.0
+    tied = [int(r) for r in range(len(ri)) if ri[r] - ri[order[0]] <= 1e-9 * ri[order[0]]]
+    return int(order[0]), float(margin), tied
+
+
+def kmeans_seeded(X, K, n_init, seed, tol=1e-4, max_iter=300):
+    """``kmeans(init=None, seeds=[seed])`` for one group -> dict(runs (one :func:`lloyd` per restart), best, margin,
+    tied, init, pick)."""
+    init, pick = seed_centres(X, K, n_init, seed)
+    runs = [lloyd(X, init[r], tol=tol, max_iter=max_iter) for r in range(n_init)]
+    best, margin, tied = best_restart(runs)
+    return dict(runs=runs, best=best, margin=margin, tied=tied, init=init, pick=pick)
