@@ -14,62 +14,28 @@ alignment, and the bytes per frame each recursion moves (from the shapes alone).
 --trace DIR: afterwards the script starts itself once more under rocprofv3 --kernel-trace --stats (a run of its own:
 one warm-up and one timed call of every route per shape) and writes DIR/align_rocprofv3_summary.txt."""
 import argparse
-import csv
-import glob
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 
 sys.path.insert(0, ".")
+from _timing import common_arguments, summary, timed_rounds, trace_run, warm, word_batch, write_summary
 
 REPEATS = 5
 WORDS = 5
 
-ap = argparse.ArgumentParser()
-ap.add_argument("N", nargs="?", type=int, default=10000)
-ap.add_argument("--frames", type=int, default=505)
-ap.add_argument("--shapes", nargs="+", default=["11,10,13", "11,18,39"], help="W,S,D")
-ap.add_argument("--trace", default=None, help="directory for the rocprofv3 summary (a second run of its own)")
-ap.add_argument("--child", action="store_true", help="(internal) the run under rocprofv3")
-args = ap.parse_args()
-N, T = args.N, args.frames
 
-
-def ev_time(fn):
-    import torch
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b)
-
-
-def summary(t):
-    return {"min": round(min(t), 3), "max": round(max(t), 3), "median": round(float(np.median(t)), 3)}
-
-
-def setup(W, S, D):
+def setup(args, W, S, D):
     import torch
     from sapr_amd import _lib, connected
     from tests._connected_ref import sample_case
+    N, T = args.N, args.frames
     model, _, _ = sample_case(7, W, S, D, 0)
     net = connected.ConnectedNetwork(model["log_start"], model["log_trans"], model["log_exit"], 0.0, None,
                                      model["means"], model["vars"], model["gconst"])
-    # five words in a row per utterance, the frames scattered about the means of the states they walk through
-    torch.manual_seed(0)
-    per = (T + WORDS - 1) // WORDS
-    t = torch.arange(T, device="cuda")
-    spoken = torch.randint(0, W, (N, WORDS), device="cuda")
-    word = spoken[:, (t // per).clamp(max=WORDS - 1)]                                          # [N, T]
-    state = ((t % per) * S // per).expand(N, T)
-    mu = torch.from_numpy(model["means"]).cuda()[word.reshape(-1), state.reshape(-1)]
-    sd = torch.from_numpy(np.sqrt(model["vars"])).cuda()[word.reshape(-1), state.reshape(-1)]
-    feats = (mu + torch.randn(N * T, D, device="cuda", dtype=torch.float64) * sd).float().contiguous()
-    del mu, sd, word, state
+    feats, spoken = word_batch(model["means"], np.sqrt(model["vars"]), N, T, WORDS)
     total, total_words = N * T, N * WORDS
     offs = torch.arange(N + 1, device="cuda", dtype=torch.int64) * T
     woffs = torch.arange(N + 1, device="cuda", dtype=torch.int64) * WORDS
@@ -116,24 +82,20 @@ def setup(W, S, D):
     return routes, facts, score, n_words
 
 
-def measure():
+def measure(args):
     import torch
+    N, T = args.N, args.frames
     for shape in args.shapes:
         W, S, D = (int(v) for v in shape.split(","))
-        routes, facts, score, n_words = setup(W, S, D)
+        routes, facts, score, n_words = setup(args, W, S, D)
         out = {"shape": {"N": N, "T": T, "W": W, "S": S, "D": D, "words": WORDS}, **facts}
-        for _ in range(1 if args.child else 2):
-            for fn in routes.values():
-                fn()
+        warm(routes, args.child)
         torch.cuda.synchronize()
         assert torch.isfinite(score["align"]).all() and torch.isfinite(score["loop"]).all()
         assert bool((score["align"] <= score["loop"]).all())
         out["aligned_score_equals_free_score"] = round(float((score["align"] == score["loop"]).float().mean()), 4)
         out["mean_words_found_by_the_loop"] = round(float(n_words.float().mean()), 2)
-        times = {k: [] for k in routes}
-        for _ in range(1 if args.child else REPEATS):
-            for k, fn in routes.items():
-                times[k].append(ev_time(fn))
+        times = timed_rounds(routes, REPEATS, args.child)
         for k, t in times.items():
             out[f"{k}_ms"] = summary(t)
         med = {k: float(np.median(t)) for k, t in times.items()}
@@ -148,30 +110,22 @@ def measure():
         torch.cuda.empty_cache()
 
 
-measure()
-if args.child or not args.trace:
-    sys.exit(0)
+def main():
+    ap = argparse.ArgumentParser()
+    common_arguments(ap)
+    args = ap.parse_args()
+    measure(args)
+    if args.child or not args.trace:
+        return
+    argv = [str(args.N), "--frames", str(args.frames), "--shapes", *args.shapes]
+    header = [
+        f"# rocprofv3 --kernel-trace --stats of: python scripts/time_align.py {' '.join(argv)} --child",
+        "# one warm-up and one timed call of every route (emission; alignment recursion alone and with its back-trace;",
+        "# word-loop recursion alone and with its back-trace) per shape; sapr kernels only",
+    ]
+    write_summary(os.path.join(args.trace, "align_rocprofv3_summary.txt"), header,
+                  trace_run(__file__, argv, args.trace, 900))
 
-os.makedirs(args.trace, exist_ok=True)
-trace = os.path.join(args.trace, "trace")
-cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", trace, "--", sys.executable,
-       os.path.abspath(__file__), str(N), "--frames", str(T), "--shapes", *args.shapes, "--child"]
-with open(os.path.join(args.trace, "child.log"), "w") as log:
-    subprocess.run(cmd, check=True, stdout=log, stderr=subprocess.STDOUT, stdin=subprocess.DEVNULL, timeout=900)
-rows = []
-for f in glob.glob(os.path.join(trace, "**", "*kernel_stats.csv"), recursive=True):
-    with open(f) as fh:
-        rows += [r for r in csv.DictReader(fh) if "sapr" in r["Name"]]
-rows.sort(key=lambda r: -float(r["TotalDurationNs"]))
-lines = [f"# rocprofv3 --kernel-trace --stats of: python scripts/time_align.py {N} --frames {T} --shapes "
-         f"{' '.join(args.shapes)} --child",
-         "# one warm-up and one timed call of every route (emission; alignment recursion alone and with its back-trace;",
-         "# word-loop recursion alone and with its back-trace) per shape; sapr kernels only",
-         "# calls  total_ms  avg_ms  min_ms  max_ms  name"]
-for r in rows:
-    lines.append("%5s %9.3f %8.3f %8.3f %8.3f  %s" % (r["Calls"], float(r["TotalDurationNs"]) / 1e6,
-                                                     float(r["AverageNs"]) / 1e6, float(r["MinNs"]) / 1e6,
-                                                     float(r["MaxNs"]) / 1e6, r["Name"]))
-with open(os.path.join(args.trace, "align_rocprofv3_summary.txt"), "w") as fh:
-    fh.write("\n".join(lines) + "\n")
-print("\n".join(lines))
+
+if __name__ == "__main__":
+    main()

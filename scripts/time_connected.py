@@ -22,52 +22,25 @@ per finite transition distance one add and one compare in the recursion.
 one warm-up and one timed call of every route per shape) and writes DIR/connected_rocprofv3_summary.txt, which ends
 with the yardstick comparison: connected emission kernel against W x the per-model emission kernel."""
 import argparse
-import csv
-import glob
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 
 sys.path.insert(0, ".")
+from _timing import common_arguments, summary, timed_rounds, trace_run, warm, word_batch, write_summary
 
 REPEATS = 5
 
-ap = argparse.ArgumentParser()
-ap.add_argument("N", nargs="?", type=int, default=10000)
-ap.add_argument("--frames", type=int, default=505)
-ap.add_argument("--families", nargs="+", default=["diag", "gmm", "full"], choices=["diag", "gmm", "full"])
-ap.add_argument("--shapes", nargs="+", default=["11,10,13", "11,18,39"], help="W,S,D of the diagonal family")
-ap.add_argument("--gmm-shapes", nargs="+", default=["11,10,2,13", "11,18,2,39"], help="W,S,M,D")
-ap.add_argument("--full-shapes", nargs="+", default=["11,10,13", "11,18,39"], help="W,S,D")
-ap.add_argument("--trace", default=None, help="directory for the rocprofv3 summary (a second run of its own)")
-ap.add_argument("--child", action="store_true", help="(internal) the run under rocprofv3")
-args = ap.parse_args()
-N, T = args.N, args.frames
 
-
-def ev_time(fn):
-    import torch
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b)
-
-
-def summary(t):
-    return {"min": round(min(t), 3), "max": round(max(t), 3), "median": round(float(np.median(t)), 3)}
-
-
-def setup(family, shape):
+def setup(args, family, shape):
     import torch
     from sapr_amd import _lib, connected
     from sapr_amd.trellis import DiagModelPack, FeatureBatch, viterbi_decode
     from tests import _connected_family_cases as cases
     from tests._connected_ref import sample_case
+    N, T = args.N, args.frames
     W, S, D = shape[0], shape[1], shape[-1]
     if family == "diag":
         model, _, _ = sample_case(7, W, S, D, 0)
@@ -80,16 +53,7 @@ def setup(family, shape):
         # (timing only: the frames lie about the first component's mean / the state's mean, a few units wide)
         centres = model["means"][:, :, 0] if family == "gmm" else model["means"]
         spread = np.sqrt(model["covars"][:, :, 0]) if family == "gmm" else np.full(centres.shape, 3.0)
-    # five words in a row per utterance, the frames scattered about the means of the states they walk through
-    torch.manual_seed(0)
-    per = (T + 4) // 5
-    t = torch.arange(T, device="cuda")
-    word = (torch.randint(0, W, (N, 5), device="cuda"))[:, (t // per).clamp(max=4)]          # [N, T]
-    state = ((t % per) * S // per).expand(N, T)
-    mu = torch.from_numpy(centres).cuda()[word.reshape(-1), state.reshape(-1)]
-    sd = torch.from_numpy(spread).cuda()[word.reshape(-1), state.reshape(-1)]
-    feats = (mu + torch.randn(N * T, D, device="cuda", dtype=torch.float64) * sd).float().contiguous()
-    del mu, sd, word, state
+    feats = word_batch(centres, spread, N, T)[0]
     lengths = np.full(N, T)
     offs = torch.from_numpy(np.r_[0, np.cumsum(lengths)].astype(np.int64)).cuda()
     total = N * T
@@ -136,27 +100,23 @@ def setup(family, shape):
     return routes, facts, (n_words, score)
 
 
-def family_shapes():
+def family_shapes(args):
     given = {"diag": args.shapes, "gmm": args.gmm_shapes, "full": args.full_shapes}
     return [(f, tuple(int(v) for v in s.split(","))) for f in args.families for s in given[f]]
 
 
-def measure():
+def measure(args):
     import torch
-    for family, shape in family_shapes():
-        routes, facts, (n_words, score) = setup(family, shape)
+    N, T = args.N, args.frames
+    for family, shape in family_shapes(args):
+        routes, facts, (n_words, score) = setup(args, family, shape)
         names = ("W", "S", "M", "D") if family == "gmm" else ("W", "S", "D")
         out = {"family": family, "shape": {"N": N, "T": T, **dict(zip(names, shape))}, **facts}
-        for _ in range(1 if args.child else 2):
-            for fn in routes.values():
-                fn()
+        warm(routes, args.child)
         torch.cuda.synchronize()
         assert torch.isfinite(score).all()
         out["mean_words_found"] = round(float(n_words.float().mean()), 2)
-        times = {k: [] for k in routes}
-        for _ in range(1 if args.child else REPEATS):
-            for k, fn in routes.items():
-                times[k].append(ev_time(fn))
+        times = timed_rounds(routes, REPEATS, args.child)
         for k, t in times.items():
             out[f"{k}_ms"] = summary(t)
         med = {k: float(np.median(t)) for k, t in times.items()}
@@ -171,36 +131,7 @@ def measure():
         torch.cuda.empty_cache()
 
 
-measure()
-if args.child or not args.trace:
-    sys.exit(0)
-
-os.makedirs(args.trace, exist_ok=True)
-trace = os.path.join(args.trace, "trace")
-shape_args = ["--families", *args.families, "--shapes", *args.shapes, "--gmm-shapes", *args.gmm_shapes,
-              "--full-shapes", *args.full_shapes]
-cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", trace, "--", sys.executable,
-       os.path.abspath(__file__), str(N), "--frames", str(T), *shape_args, "--child"]
-with open(os.path.join(args.trace, "child.log"), "w") as log:
-    subprocess.run(cmd, check=True, stdout=log, stderr=subprocess.STDOUT, stdin=subprocess.DEVNULL, timeout=900)
-rows = []
-for f in glob.glob(os.path.join(trace, "**", "*kernel_stats.csv"), recursive=True):
-    with open(f) as fh:
-        rows += [r for r in csv.DictReader(fh) if "sapr" in r["Name"]]
-rows.sort(key=lambda r: -float(r["TotalDurationNs"]))
-lines = [f"# rocprofv3 --kernel-trace --stats of: python scripts/time_connected.py {N} --frames {T} "
-         f"{' '.join(shape_args)} --child",
-         "# one warm-up and one timed call of every route (emission; recursion alone; recursion + back-trace; the",
-         "# yardstick on the same frames: the all-vocabulary isolated-word scorer (diag), the per-model decoder under",
-         "# one word (gmm, full)) per family and shape; sapr kernels only",
-         "# calls  total_ms  avg_ms  min_ms  max_ms  name"]
-for r in rows:
-    lines.append("%5s %9.3f %8.3f %8.3f %8.3f  %s" % (r["Calls"], float(r["TotalDurationNs"]) / 1e6,
-                                                     float(r["AverageNs"]) / 1e6, float(r["MinNs"]) / 1e6,
-                                                     float(r["MaxNs"]) / 1e6, r["Name"]))
-
-
-def kernel_avg_ms(kernel, targs):
+def kernel_avg_ms(rows, kernel, targs):
     """Average duration of the instantiation ``kernel<targs>`` (the name without its namespace and arguments)."""
     for r in rows:
         if f"{kernel}<{targs}>".replace(" ", "") in r["Name"].replace(" ", ""):
@@ -208,18 +139,45 @@ def kernel_avg_ms(kernel, targs):
     return None
 
 
-lines.append("# yardstick: connected emission kernel against W x the per-model emission kernel of the same arithmetic")
-for family, shape in family_shapes():
-    if family == "diag":
-        continue
-    DP = 13 if shape[-1] <= 13 else (26 if shape[-1] <= 26 else 39)
-    targs = f"{ {1: 1, 2: 2, 3: 4, 4: 4}.get(shape[2], 8)}, {DP}" if family == "gmm" else f"{DP}"
-    new, old = kernel_avg_ms(f"connected_emit_{family}_kernel", targs), kernel_avg_ms(f"{family}_emit_kernel", targs)
-    if new is None or old is None:
-        lines.append(f"# {family} {shape}: kernels not found in the trace")
-        continue
-    lines.append(f"# {family} {shape}: connected_emit_{family}_kernel<{targs}> {new:.3f} ms, {family}_emit_kernel<{targs}> "
-                 f"{old:.3f} ms x W = {old * shape[0]:.3f} ms, ratio {new / (old * shape[0]):.3f}")
-with open(os.path.join(args.trace, "connected_rocprofv3_summary.txt"), "w") as fh:
-    fh.write("\n".join(lines) + "\n")
-print("\n".join(lines))
+def yardstick_lines(args, rows):
+    lines = ["# yardstick: connected emission kernel against W x the per-model emission kernel of the same arithmetic"]
+    for family, shape in family_shapes(args):
+        if family == "diag":
+            continue
+        DP = 13 if shape[-1] <= 13 else (26 if shape[-1] <= 26 else 39)
+        targs = f"{ {1: 1, 2: 2, 3: 4, 4: 4}.get(shape[2], 8)}, {DP}" if family == "gmm" else f"{DP}"
+        new = kernel_avg_ms(rows, f"connected_emit_{family}_kernel", targs)
+        old = kernel_avg_ms(rows, f"{family}_emit_kernel", targs)
+        if new is None or old is None:
+            lines.append(f"# {family} {shape}: kernels not found in the trace")
+            continue
+        lines.append(f"# {family} {shape}: connected_emit_{family}_kernel<{targs}> {new:.3f} ms, "
+                     f"{family}_emit_kernel<{targs}> {old:.3f} ms x W = {old * shape[0]:.3f} ms, "
+                     f"ratio {new / (old * shape[0]):.3f}")
+    return lines
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    common_arguments(ap, shapes_help="W,S,D of the diagonal family")
+    ap.add_argument("--families", nargs="+", default=["diag", "gmm", "full"], choices=["diag", "gmm", "full"])
+    ap.add_argument("--gmm-shapes", nargs="+", default=["11,10,2,13", "11,18,2,39"], help="W,S,M,D")
+    ap.add_argument("--full-shapes", nargs="+", default=["11,10,13", "11,18,39"], help="W,S,D")
+    args = ap.parse_args()
+    measure(args)
+    if args.child or not args.trace:
+        return
+    argv = [str(args.N), "--frames", str(args.frames), "--families", *args.families, "--shapes", *args.shapes,
+            "--gmm-shapes", *args.gmm_shapes, "--full-shapes", *args.full_shapes]
+    header = [
+        f"# rocprofv3 --kernel-trace --stats of: python scripts/time_connected.py {' '.join(argv)} --child",
+        "# one warm-up and one timed call of every route (emission; recursion alone; recursion + back-trace; the",
+        "# yardstick on the same frames: the all-vocabulary isolated-word scorer (diag), the per-model decoder under",
+        "# one word (gmm, full)) per family and shape; sapr kernels only",
+    ]
+    rows = trace_run(__file__, argv, args.trace, 900)
+    write_summary(os.path.join(args.trace, "connected_rocprofv3_summary.txt"), header, rows, yardstick_lines(args, rows))
+
+
+if __name__ == "__main__":
+    main()

@@ -17,50 +17,21 @@ import sys
 import numpy as np
 
 sys.path.insert(0, ".")
+from _timing import common_arguments, summary, timed_rounds, warm, word_batch
 
 REPEATS = 5
 WORDS = 5
 
-ap = argparse.ArgumentParser()
-ap.add_argument("N", nargs="?", type=int, default=10000)
-ap.add_argument("--frames", type=int, default=505)
-ap.add_argument("--shapes", nargs="+", default=["11,10,13", "11,18,39"], help="W,S,D")
-args = ap.parse_args()
-N, T = args.N, args.frames
 
-
-def ev_time(fn):
-    import torch
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b)
-
-
-def summary(t):
-    return {"min": round(min(t), 3), "max": round(max(t), 3), "median": round(float(np.median(t)), 3)}
-
-
-def setup(W, S, D):
+def setup(args, W, S, D):
     import torch
     from sapr_amd import _lib, connected
     from tests._connected_ref import sample_case
+    N, T = args.N, args.frames
     model, _, _ = sample_case(7, W, S, D, 0)
     net = connected.ConnectedNetwork(model["log_start"], model["log_trans"], model["log_exit"], 0.0, None,
                                      model["means"], model["vars"], model["gconst"])
-    # five words in a row per utterance, the frames scattered about the means of the states they walk through
-    torch.manual_seed(0)
-    per = (T + WORDS - 1) // WORDS
-    t = torch.arange(T, device="cuda")
-    spoken = torch.randint(0, W, (N, WORDS), device="cuda")
-    word = spoken[:, (t // per).clamp(max=WORDS - 1)]                                          # [N, T]
-    state = ((t % per) * S // per).expand(N, T)
-    mu = torch.from_numpy(model["means"]).cuda()[word.reshape(-1), state.reshape(-1)]
-    sd = torch.from_numpy(np.sqrt(model["vars"])).cuda()[word.reshape(-1), state.reshape(-1)]
-    feats = (mu + torch.randn(N * T, D, device="cuda", dtype=torch.float64) * sd).float().contiguous()
-    del mu, sd, word, state
+    feats, spoken = word_batch(model["means"], np.sqrt(model["vars"]), N, T, WORDS)
     total, total_words = N * T, N * WORDS
     offs = torch.arange(N + 1, device="cuda", dtype=torch.int64) * T
     woffs = torch.arange(N + 1, device="cuda", dtype=torch.int64) * WORDS
@@ -103,23 +74,19 @@ def setup(W, S, D):
     return routes, facts, score, loglik, stats[D]
 
 
-def measure():
+def measure(args):
     import torch
+    N, T = args.N, args.frames
     for shape in args.shapes:
         W, S, D = (int(v) for v in shape.split(","))
-        routes, facts, score, loglik, stats = setup(W, S, D)
+        routes, facts, score, loglik, stats = setup(args, W, S, D)
         out = {"shape": {"N": N, "T": T, "W": W, "S": S, "D": D, "words": WORDS}, **facts}
-        for _ in range(2):
-            for fn in routes.values():
-                fn()
+        warm(routes)
         torch.cuda.synchronize()
         assert torch.isfinite(score).all() and torch.isfinite(loglik).all() and bool((score <= loglik).all())
         assert float(stats[:, 0].sum()) == N * WORDS
         out["mean_loglik_minus_viterbi_score"] = round(float((loglik - score).mean()), 4)
-        times = {k: [] for k in routes}
-        for _ in range(REPEATS):
-            for k, fn in routes.items():
-                times[k].append(ev_time(fn))
+        times = timed_rounds(routes, REPEATS)
         for k, t in times.items():
             out[f"{k}_ms"] = summary(t)
         med = {k: float(np.median(t)) for k, t in times.items()}
@@ -135,4 +102,11 @@ def measure():
         torch.cuda.empty_cache()
 
 
-measure()
+def main():
+    ap = argparse.ArgumentParser()
+    common_arguments(ap, trace=False)
+    measure(ap.parse_args())
+
+
+if __name__ == "__main__":
+    main()

@@ -16,62 +16,28 @@ byte.
 --trace DIR: afterwards the script starts itself once more under rocprofv3 --kernel-trace --stats (a run of its own:
 one warm-up and one timed call of every route per shape) and writes DIR/embedded_full_rocprofv3_summary.txt."""
 import argparse
-import csv
-import glob
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 
 sys.path.insert(0, ".")
+from _timing import common_arguments, summary, timed_rounds, trace_run, warm, word_batch, write_summary
 
 REPEATS = 5
 WORDS = 5
 
-ap = argparse.ArgumentParser()
-ap.add_argument("N", nargs="?", type=int, default=10000)
-ap.add_argument("--frames", type=int, default=505)
-ap.add_argument("--shapes", nargs="+", default=["11,10,13", "11,18,39"], help="W,S,D")
-ap.add_argument("--trace", default=None, help="directory for the rocprofv3 summary (a second run of its own)")
-ap.add_argument("--child", action="store_true", help="(internal) the run under rocprofv3")
-args = ap.parse_args()
-N, T = args.N, args.frames
 
-
-def ev_time(fn):
-    import torch
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b)
-
-
-def summary(t):
-    return {"min": round(min(t), 3), "max": round(max(t), 3), "median": round(float(np.median(t)), 3)}
-
-
-def setup(W, S, D):
+def setup(args, W, S, D):
     import torch
     from sapr_amd import _lib, connected, full_cov
     from tests._connected_ref import sample_case
+    N, T = args.N, args.frames
     model, _, _ = sample_case(7, W, S, D, 0)
     net = connected.ConnectedNetwork(model["log_start"], model["log_trans"], model["log_exit"], 0.0, None,
                                      model["means"], model["vars"], model["gconst"])
-    # five words in a row per utterance, the frames scattered about the means of the states they walk through
-    torch.manual_seed(0)
-    per = (T + WORDS - 1) // WORDS
-    t = torch.arange(T, device="cuda")
-    spoken = torch.randint(0, W, (N, WORDS), device="cuda")
-    word = spoken[:, (t // per).clamp(max=WORDS - 1)]                                          # [N, T]
-    state = ((t % per) * S // per).expand(N, T)
-    mu = torch.from_numpy(model["means"]).cuda()[word.reshape(-1), state.reshape(-1)]
-    sd = torch.from_numpy(np.sqrt(model["vars"])).cuda()[word.reshape(-1), state.reshape(-1)]
-    feats = (mu + torch.randn(N * T, D, device="cuda", dtype=torch.float64) * sd).float().contiguous()
-    del mu, sd, word, state
+    feats, spoken = word_batch(model["means"], np.sqrt(model["vars"]), N, T, WORDS)
     total, total_words = N * T, N * WORDS
     offs = torch.arange(N + 1, device="cuda", dtype=torch.int64) * T
     woffs = torch.arange(N + 1, device="cuda", dtype=torch.int64) * WORDS
@@ -107,7 +73,7 @@ def setup(W, S, D):
         params = [(np.exp(model["log_start"][w]), np.exp(model["log_trans"][w]), model["means"][w],
                    np.array([np.diag(v) for v in model["vars"][w]])) for w in range(W)]
     pack = full_cov.FullPack.from_params(params)
-    seg = np.diff(np.minimum(np.arange(WORDS + 1) * per, T))
+    seg = np.diff(np.minimum(np.arange(WORDS + 1) * ((T + WORDS - 1) // WORDS), T))
     iso = pack.batch(feats, np.tile(seg, N), spoken.reshape(-1).cpu().numpy())
     routes = {"fb": lambda: embed(0, True), "diag": lambda: embed(D, True), "full": full,
               "iso": lambda: iso.estep(pack, want_stats=True), "iso_ll": lambda: iso.estep(pack, want_stats=False)}
@@ -117,15 +83,14 @@ def setup(W, S, D):
     return routes, facts, loglik, stats[D], stats_full
 
 
-def measure():
+def measure(args):
     import torch
+    N, T = args.N, args.frames
     for shape in args.shapes:
         W, S, D = (int(v) for v in shape.split(","))
-        routes, facts, loglik, stats, stats_full = setup(W, S, D)
+        routes, facts, loglik, stats, stats_full = setup(args, W, S, D)
         out = {"shape": {"N": N, "T": T, "W": W, "S": S, "D": D, "words": WORDS}, **facts}
-        for _ in range(1 if args.child else 2):
-            for fn in routes.values():
-                fn()
+        warm(routes, args.child)
         torch.cuda.synchronize()
         assert torch.isfinite(loglik).all() and torch.isfinite(stats_full).all()
         assert float(stats[:, 0].sum()) == float(stats_full[:, 0].sum()) == N * WORDS
@@ -133,10 +98,7 @@ def measure():
         assert torch.equal(stats[:, :head], stats_full[:, :head])
         obs_err = float((stats[:, head:head + S * D] - stats_full[:, head:head + S * D]).abs().max())
         out["obs_max_abs_difference_diag_vs_full"] = obs_err
-        times = {k: [] for k in routes}
-        for _ in range(1 if args.child else REPEATS):
-            for k, fn in routes.items():
-                times[k].append(ev_time(fn))
+        times = timed_rounds(routes, REPEATS, args.child)
         for k, t in times.items():
             out[f"{k}_ms"] = summary(t)
         med = {k: float(np.median(t)) for k, t in times.items()}
@@ -152,31 +114,23 @@ def measure():
         torch.cuda.empty_cache()
 
 
-measure()
-if args.child or not args.trace:
-    sys.exit(0)
+def main():
+    ap = argparse.ArgumentParser()
+    common_arguments(ap)
+    args = ap.parse_args()
+    measure(args)
+    if args.child or not args.trace:
+        return
+    argv = [str(args.N), "--frames", str(args.frames), "--shapes", *args.shapes]
+    header = [
+        f"# rocprofv3 --kernel-trace --stats of: python scripts/time_embedded_full.py {' '.join(argv)} --child",
+        "# one warm-up and one timed call of every route (sapr_connected_embed at D = 0 and with the features,",
+        "# sapr_connected_embed_full, sapr_full_estep with and without statistics over the same frames) per shape;",
+        "# sapr kernels only",
+    ]
+    write_summary(os.path.join(args.trace, "embedded_full_rocprofv3_summary.txt"), header,
+                  trace_run(__file__, argv, args.trace, 900))
 
-os.makedirs(args.trace, exist_ok=True)
-trace = os.path.join(args.trace, "trace")
-cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", trace, "--", sys.executable,
-       os.path.abspath(__file__), str(N), "--frames", str(T), "--shapes", *args.shapes, "--child"]
-with open(os.path.join(args.trace, "child.log"), "w") as log:
-    subprocess.run(cmd, check=True, stdout=log, stderr=subprocess.STDOUT, stdin=subprocess.DEVNULL, timeout=900)
-rows = []
-for f in glob.glob(os.path.join(trace, "**", "*kernel_stats.csv"), recursive=True):
-    with open(f) as fh:
-        rows += [r for r in csv.DictReader(fh) if "sapr" in r["Name"]]
-rows.sort(key=lambda r: -float(r["TotalDurationNs"]))
-lines = [f"# rocprofv3 --kernel-trace --stats of: python scripts/time_embedded_full.py {N} --frames {T} --shapes "
-         f"{' '.join(args.shapes)} --child",
-         "# one warm-up and one timed call of every route (sapr_connected_embed at D = 0 and with the features,",
-         "# sapr_connected_embed_full, sapr_full_estep with and without statistics over the same frames) per shape;",
-         "# sapr kernels only",
-         "# calls  total_ms  avg_ms  min_ms  max_ms  name"]
-for r in rows:
-    lines.append("%5s %9.3f %8.3f %8.3f %8.3f  %s" % (r["Calls"], float(r["TotalDurationNs"]) / 1e6,
-                                                     float(r["AverageNs"]) / 1e6, float(r["MinNs"]) / 1e6,
-                                                     float(r["MaxNs"]) / 1e6, r["Name"]))
-with open(os.path.join(args.trace, "embedded_full_rocprofv3_summary.txt"), "w") as fh:
-    fh.write("\n".join(lines) + "\n")
-print("\n".join(lines))
+
+if __name__ == "__main__":
+    main()

@@ -16,48 +16,24 @@ gmm_accum_kernel on its own is a line of the kernel trace below).
 --trace DIR: afterwards the script starts itself once more under rocprofv3 --kernel-trace --stats (a run of its own:
 one warm-up and one timed call of every route per shape) and writes DIR/embedded_gmm_rocprofv3_summary.txt."""
 import argparse
-import csv
-import glob
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 
 sys.path.insert(0, ".")
+from _timing import common_arguments, summary, timed_rounds, trace_run, warm, write_summary
 
 REPEATS = 5
 WORDS = 5
 
-ap = argparse.ArgumentParser()
-ap.add_argument("N", nargs="?", type=int, default=10000)
-ap.add_argument("--frames", type=int, default=505)
-ap.add_argument("--shapes", nargs="+", default=["11,10,2,13", "11,18,2,39"], help="W,S,M,D")
-ap.add_argument("--trace", default=None, help="directory for the rocprofv3 summary (a second run of its own)")
-ap.add_argument("--child", action="store_true", help="(internal) the run under rocprofv3")
-args = ap.parse_args()
-N, T = args.N, args.frames
 
-
-def ev_time(fn):
-    import torch
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b)
-
-
-def summary(t):
-    return {"min": round(min(t), 3), "max": round(max(t), 3), "median": round(float(np.median(t)), 3)}
-
-
-def setup(W, S, M, D):
+def setup(args, W, S, M, D):
     import torch
     from sapr_amd import _lib, connected, gmm_hmm
     from tests._connected_family_cases import gmm_case
+    N, T = args.N, args.frames
     model, _, _ = gmm_case(7, W, S, M, D, 0)
     pack = gmm_hmm.GmmPack.from_params([(model["startprob"][w], model["transmat"][w], model["weights"][w],
                                          model["means"][w], model["covars"][w]) for w in range(W)])
@@ -114,15 +90,14 @@ def setup(W, S, M, D):
     return routes, facts, loglik, stats[D], stats_gmm
 
 
-def measure():
+def measure(args):
     import torch
+    N, T = args.N, args.frames
     for shape in args.shapes:
         W, S, M, D = (int(v) for v in shape.split(","))
-        routes, facts, loglik, stats, stats_gmm = setup(W, S, M, D)
+        routes, facts, loglik, stats, stats_gmm = setup(args, W, S, M, D)
         out = {"shape": {"N": N, "T": T, "W": W, "S": S, "M": M, "D": D, "words": WORDS}, **facts}
-        for _ in range(1 if args.child else 2):
-            for fn in routes.values():
-                fn()
+        warm(routes, args.child)
         torch.cuda.synchronize()
         assert torch.isfinite(loglik).all() and torch.isfinite(stats_gmm).all()
         assert float(stats[:, 0].sum()) == float(stats_gmm[:, 0].sum()) == N * WORDS
@@ -132,10 +107,7 @@ def measure():
         mixed = stats_gmm[:, head + S * M:].reshape(W, 2, S, M, D).sum(dim=3).reshape(W, -1)
         rel = (mixed - stats[:, head:]).abs() / (1.0 + stats[:, head:].abs())
         out["obs_max_scaled_difference_summed_components_vs_diag"] = float(rel.max())
-        times = {k: [] for k in routes}
-        for _ in range(1 if args.child else REPEATS):
-            for k, fn in routes.items():
-                times[k].append(ev_time(fn))
+        times = timed_rounds(routes, REPEATS, args.child)
         for k, t in times.items():
             out[f"{k}_ms"] = summary(t)
         med = {k: float(np.median(t)) for k, t in times.items()}
@@ -150,31 +122,23 @@ def measure():
         torch.cuda.empty_cache()
 
 
-measure()
-if args.child or not args.trace:
-    sys.exit(0)
+def main():
+    ap = argparse.ArgumentParser()
+    common_arguments(ap, ("11,10,2,13", "11,18,2,39"), "W,S,M,D")
+    args = ap.parse_args()
+    measure(args)
+    if args.child or not args.trace:
+        return
+    argv = [str(args.N), "--frames", str(args.frames), "--shapes", *args.shapes]
+    header = [
+        f"# rocprofv3 --kernel-trace --stats of: python scripts/time_embedded_gmm.py {' '.join(argv)} --child",
+        "# one warm-up and one timed call of every route (sapr_connected_embed at D = 0 and with the features,",
+        "# sapr_connected_embed_gmm, sapr_gmm_estep_diag with and without statistics over the same frames) per shape;",
+        "# sapr kernels only",
+    ]
+    write_summary(os.path.join(args.trace, "embedded_gmm_rocprofv3_summary.txt"), header,
+                  trace_run(__file__, argv, args.trace, 900))
 
-os.makedirs(args.trace, exist_ok=True)
-trace = os.path.join(args.trace, "trace")
-cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", trace, "--", sys.executable,
-       os.path.abspath(__file__), str(N), "--frames", str(T), "--shapes", *args.shapes, "--child"]
-with open(os.path.join(args.trace, "child.log"), "w") as log:
-    subprocess.run(cmd, check=True, stdout=log, stderr=subprocess.STDOUT, stdin=subprocess.DEVNULL, timeout=900)
-rows = []
-for f in glob.glob(os.path.join(trace, "**", "*kernel_stats.csv"), recursive=True):
-    with open(f) as fh:
-        rows += [r for r in csv.DictReader(fh) if "sapr" in r["Name"]]
-rows.sort(key=lambda r: -float(r["TotalDurationNs"]))
-lines = [f"# rocprofv3 --kernel-trace --stats of: python scripts/time_embedded_gmm.py {N} --frames {T} --shapes "
-         f"{' '.join(args.shapes)} --child",
-         "# one warm-up and one timed call of every route (sapr_connected_embed at D = 0 and with the features,",
-         "# sapr_connected_embed_gmm, sapr_gmm_estep_diag with and without statistics over the same frames) per shape;",
-         "# sapr kernels only",
-         "# calls  total_ms  avg_ms  min_ms  max_ms  name"]
-for r in rows:
-    lines.append("%5s %9.3f %8.3f %8.3f %8.3f  %s" % (r["Calls"], float(r["TotalDurationNs"]) / 1e6,
-                                                     float(r["AverageNs"]) / 1e6, float(r["MinNs"]) / 1e6,
-                                                     float(r["MaxNs"]) / 1e6, r["Name"]))
-with open(os.path.join(args.trace, "embedded_gmm_rocprofv3_summary.txt"), "w") as fh:
-    fh.write("\n".join(lines) + "\n")
-print("\n".join(lines))
+
+if __name__ == "__main__":
+    main()

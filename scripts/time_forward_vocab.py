@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, ".")
+from _timing import ev_time
 import bench
 from sapr_amd.frontend import BENCH, MfccPlan
 from sapr_amd.trellis import DiagModelPack, FeatureBatch, TileLayout, forward_loglik, forward_scores
@@ -37,15 +38,6 @@ def vocab():
 
 def per_word():
     return torch.stack([forward_loglik(batch, pack, None, layout=layouts[w]) for w in range(W)], dim=1)
-
-
-def ev_time(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b)
 
 
 for _ in range(2):

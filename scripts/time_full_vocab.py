@@ -14,44 +14,20 @@ mode) per finite transition.
 --trace DIR: afterwards the script starts itself once more under rocprofv3 --kernel-trace --stats (a run of its own:
 one warm-up and one timed call of every route per shape) and writes DIR/full_vocab_rocprofv3_summary.txt."""
 import argparse
-import csv
-import glob
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 
 sys.path.insert(0, ".")
+from _timing import summary, timed_rounds, trace_run, write_summary
 
 F64_VECTOR_FLOPS = 78.6e12
 T, W, REPEATS = 101, 11, 5
 
-ap = argparse.ArgumentParser()
-ap.add_argument("N", nargs="?", type=int, default=100000)
-ap.add_argument("--shapes", nargs="+", default=["13,10", "39,18"])
-ap.add_argument("--trace", default=None, help="directory for the rocprofv3 summary (a second run of its own)")
-ap.add_argument("--child", action="store_true", help="(internal) the run under rocprofv3")
-args = ap.parse_args()
-N = args.N
 
-
-def ev_time(fn):
-    import torch
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b)
-
-
-def summary(t):
-    return {"min": round(min(t), 3), "max": round(max(t), 3), "median": round(float(np.median(t)), 3)}
-
-
-def setup(D, S):
+def setup(N, D, S):
     import torch
     from sapr_amd import full_cov
     from sapr_amd.trellis import FeatureBatch
@@ -90,11 +66,12 @@ def setup(D, S):
     return routes, per_word, flops, full_cov.pack_layout(S, D)[0]
 
 
-def measure():
+def measure(args):
     import torch
+    N = args.N
     for shape in args.shapes:
         D, S = (int(v) for v in shape.split(","))
-        routes, per_word, flops, SP = setup(D, S)
+        routes, per_word, flops, SP = setup(N, D, S)
         out = {"shape": {"N": N, "T": T, "D": D, "S": S, "W": W},
                "per_word_workspace_GB_each": round(per_word[0].ws_bytes / 1e9, 3),
                "per_word_workspace_GB_all_W": round(sum(b.ws_bytes for b in per_word) / 1e9, 3),
@@ -105,10 +82,7 @@ def measure():
                 new, old = vocab(), words()
             torch.cuda.synchronize()
             assert torch.isfinite(old).all() and torch.equal(new, old), f"{mode}: the two matrices differ"
-            t_new, t_old = [], []
-            for _ in range(1 if args.child else REPEATS):
-                t_new.append(ev_time(vocab))
-                t_old.append(ev_time(words))
+            t_new, t_old = timed_rounds({"vocab": vocab, "per_word": words}, REPEATS, args.child).values()
             med_new, med_old = float(np.median(t_new)), float(np.median(t_old))
             out[f"{mode}_vocab_ms"] = summary(t_new)
             out[f"{mode}_per_word_ms"] = summary(t_old)
@@ -120,29 +94,25 @@ def measure():
         torch.cuda.empty_cache()
 
 
-measure()
-if args.child or not args.trace:
-    sys.exit(0)
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("N", nargs="?", type=int, default=100000)
+    ap.add_argument("--shapes", nargs="+", default=["13,10", "39,18"])
+    ap.add_argument("--trace", default=None, help="directory for the rocprofv3 summary (a second run of its own)")
+    ap.add_argument("--child", action="store_true", help="(internal) the run under rocprofv3")
+    args = ap.parse_args()
+    measure(args)
+    if args.child or not args.trace:
+        return
+    argv = [str(args.N), "--shapes", *args.shapes]
+    header = [
+        f"# rocprofv3 --kernel-trace --stats of: python scripts/time_full_vocab.py {' '.join(argv)} --child",
+        "# one warm-up and one timed call of every route (one call over the vocabulary; W per-word calls) per shape and",
+        "# mode; sapr kernels only",
+    ]
+    write_summary(os.path.join(args.trace, "full_vocab_rocprofv3_summary.txt"), header,
+                  trace_run(__file__, argv, args.trace, 900))
 
-os.makedirs(args.trace, exist_ok=True)
-trace = os.path.join(args.trace, "trace")
-cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", trace, "--", sys.executable,
-       os.path.abspath(__file__), str(N), "--shapes", *args.shapes, "--child"]
-with open(os.path.join(args.trace, "child.log"), "w") as log:
-    subprocess.run(cmd, check=True, stdout=log, stderr=subprocess.STDOUT, stdin=subprocess.DEVNULL, timeout=900)
-rows = []
-for f in glob.glob(os.path.join(trace, "**", "*kernel_stats.csv"), recursive=True):
-    with open(f) as fh:
-        rows += [r for r in csv.DictReader(fh) if "sapr" in r["Name"]]
-rows.sort(key=lambda r: -float(r["TotalDurationNs"]))
-lines = [f"# rocprofv3 --kernel-trace --stats of: python scripts/time_full_vocab.py {N} --shapes {' '.join(args.shapes)} --child",
-         "# one warm-up and one timed call of every route (one call over the vocabulary; W per-word calls) per shape and",
-         "# mode; sapr kernels only",
-         "# calls  total_ms  avg_ms  min_ms  max_ms  name"]
-for r in rows:
-    lines.append("%5s %9.3f %8.3f %8.3f %8.3f  %s" % (r["Calls"], float(r["TotalDurationNs"]) / 1e6,
-                                                     float(r["AverageNs"]) / 1e6, float(r["MinNs"]) / 1e6,
-                                                     float(r["MaxNs"]) / 1e6, r["Name"]))
-with open(os.path.join(args.trace, "full_vocab_rocprofv3_summary.txt"), "w") as fh:
-    fh.write("\n".join(lines) + "\n")
-print("\n".join(lines))
+
+if __name__ == "__main__":
+    main()

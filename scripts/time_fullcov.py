@@ -14,30 +14,20 @@ full_accum_kernel against the float64 matrix-core peak: the kernel issues S * NT
 16 * 16 * 4 FMAs (NTU = 1, 3, 6 tiles on or above the diagonal at DP = 13, 26, 39); `mfma_flops` counts what it issues,
 `useful_flops` the 2 * S * D * (D + 1) / 2 + 2 * S * D per frame a symmetric update needs."""
 import argparse
-import csv
-import glob
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 
 sys.path.insert(0, ".")
+from _timing import summary, timed_rounds, trace_run, write_summary
 
 F64_MATRIX_FLOPS = 78.6e12   # MI355X float64 matrix peak (equal to the vector peak)
 T, W, REPEATS = 101, 11, 5
 
-ap = argparse.ArgumentParser()
-ap.add_argument("N", nargs="?", type=int, default=100000)
-ap.add_argument("--shapes", nargs="+", default=["13,10", "39,18"])
-ap.add_argument("--out", default="build/fullcov")
-ap.add_argument("--child", action="store_true", help="(internal) the run under rocprofv3")
-args = ap.parse_args()
-N = args.N
 
-
-def setup(D, S):
+def setup(N, D, S):
     import torch
     from sapr_amd import full_cov, gmm_hmm as gh
     from sapr_amd.trellis import DiagModelPack, EStep, FeatureBatch
@@ -73,40 +63,23 @@ def setup(D, S):
     return runs, fbatch
 
 
-def ev_time(fn):
-    import torch
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b)
-
-
-def summary(t):
-    return {"min": round(min(t), 3), "max": round(max(t), 3), "median": round(float(np.median(t)), 3)}
-
-
 def accum_flops(frames, S, D):
     ntu = {13: 1, 26: 3, 39: 6}[13 if D <= 13 else (26 if D <= 26 else 39)]
     return {"mfma_flops": 2.0 * 16 * 16 * 4 * S * ntu * frames / 4, "useful_flops": frames * (S * D * (D + 1) + 2.0 * S * D)}
 
 
-def measure():
+def measure(args):
     import torch
+    N = args.N
     for shape in args.shapes:
         D, S = (int(v) for v in shape.split(","))
-        runs, fbatch = setup(D, S)
-        reps = 1 if args.child else REPEATS
+        runs, fbatch = setup(N, D, S)
         for fn in runs.values():
             fn()
             if not args.child:
                 fn()
         torch.cuda.synchronize()
-        times = {k: [] for k in runs}
-        for _ in range(reps):                                            # alternating
-            for k, fn in runs.items():
-                times[k].append(ev_time(fn))
+        times = timed_rounds(runs, REPEATS, args.child)                  # alternating
         ll, stats, _, _ = fbatch.estep(None)
         assert torch.isfinite(ll).all() and torch.isfinite(stats).all()
         assert abs(stats[:, 0].sum().item() - N) < 0.5
@@ -118,40 +91,40 @@ def measure():
         torch.cuda.empty_cache()
 
 
-if args.child:
-    measure()
-    sys.exit(0)
+def accum_lines(args, rows):
+    """The accumulation kernel against the float64 matrix-core peak, from its traced time."""
+    lines = []
+    for shape in args.shapes:
+        D, S = (int(v) for v in shape.split(","))
+        dp = 13 if D <= 13 else (26 if D <= 26 else 39)
+        for r in rows:
+            if f"full_accum_kernel<{dp}>" in r["Name"]:
+                fl, sec = accum_flops(args.N * T, S, D), float(r["AverageNs"]) / 1e9
+                lines.append("# full_accum_kernel<%d> at (D, S) = (%d, %d): %.3f ms, issued %.1f%% and useful %.1f%% of the "
+                             "%.1f TFLOP/s float64 matrix peak" % (dp, D, S, sec * 1e3, 100 * fl["mfma_flops"] / sec /
+                                                                    F64_MATRIX_FLOPS, 100 * fl["useful_flops"] / sec /
+                                                                    F64_MATRIX_FLOPS, F64_MATRIX_FLOPS / 1e12))
+    return lines
 
-os.makedirs(args.out, exist_ok=True)
-measure()
-trace = os.path.join(args.out, "trace")
-cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", trace, "--", sys.executable,
-       os.path.abspath(__file__), str(N), "--shapes", *args.shapes, "--child"]
-with open(os.path.join(args.out, "child.log"), "w") as log:
-    subprocess.run(cmd, check=True, stdout=log, stderr=subprocess.STDOUT, stdin=subprocess.DEVNULL, timeout=600)
-rows = []
-for f in glob.glob(os.path.join(trace, "**", "*kernel_stats.csv"), recursive=True):
-    with open(f) as fh:
-        rows += [r for r in csv.DictReader(fh) if "sapr" in r["Name"]]
-rows.sort(key=lambda r: -float(r["TotalDurationNs"]))
-lines = [f"# rocprofv3 --kernel-trace --stats of: python scripts/time_fullcov.py {N} --shapes {' '.join(args.shapes)} --child",
-         "# one warm-up and one timed launch of each entry point per shape; sapr kernels only",
-         "# calls  total_ms  avg_ms  min_ms  max_ms  name"]
-for r in rows:
-    lines.append("%5s %9.3f %8.3f %8.3f %8.3f  %s" % (r["Calls"], float(r["TotalDurationNs"]) / 1e6,
-                                                     float(r["AverageNs"]) / 1e6, float(r["MinNs"]) / 1e6,
-                                                     float(r["MaxNs"]) / 1e6, r["Name"]))
-# the accumulation kernel against the float64 matrix-core peak, from its traced time
-for shape in args.shapes:
-    D, S = (int(v) for v in shape.split(","))
-    dp = 13 if D <= 13 else (26 if D <= 26 else 39)
-    for r in rows:
-        if f"full_accum_kernel<{dp}>" in r["Name"]:
-            fl, sec = accum_flops(N * T, S, D), float(r["AverageNs"]) / 1e9
-            lines.append("# full_accum_kernel<%d> at (D, S) = (%d, %d): %.3f ms, issued %.1f%% and useful %.1f%% of the "
-                         "%.1f TFLOP/s float64 matrix peak" % (dp, D, S, sec * 1e3, 100 * fl["mfma_flops"] / sec /
-                                                                F64_MATRIX_FLOPS, 100 * fl["useful_flops"] / sec /
-                                                                F64_MATRIX_FLOPS, F64_MATRIX_FLOPS / 1e12))
-with open(os.path.join(args.out, "fullcov_rocprofv3_summary.txt"), "w") as fh:
-    fh.write("\n".join(lines) + "\n")
-print("\n".join(lines))
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("N", nargs="?", type=int, default=100000)
+    ap.add_argument("--shapes", nargs="+", default=["13,10", "39,18"])
+    ap.add_argument("--out", default="build/fullcov")
+    ap.add_argument("--child", action="store_true", help="(internal) the run under rocprofv3")
+    args = ap.parse_args()
+    measure(args)
+    if args.child:
+        return
+    argv = [str(args.N), "--shapes", *args.shapes]
+    header = [
+        f"# rocprofv3 --kernel-trace --stats of: python scripts/time_fullcov.py {' '.join(argv)} --child",
+        "# one warm-up and one timed launch of each entry point per shape; sapr kernels only",
+    ]
+    rows = trace_run(__file__, argv, args.out, 600)
+    write_summary(os.path.join(args.out, "fullcov_rocprofv3_summary.txt"), header, rows, accum_lines(args, rows))
+
+
+if __name__ == "__main__":
+    main()

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, ".")
+from _timing import ev_time, summary
 from sapr_amd import gmm_hmm as gh
 from sapr_amd.trellis import DiagModelPack, EStep, FeatureBatch
 from tests._synth import trained_like_models
@@ -38,19 +39,6 @@ ap.add_argument("--shapes", nargs="+", default=["13,10", "39,18"])
 ap.add_argument("--mix", nargs="+", type=int, default=[1, 2, 4, 8])
 args = ap.parse_args()
 N, T, W, REPEATS = args.N, 101, 11, 5
-
-
-def ev_time(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b)
-
-
-def summary(t):
-    return {"min": round(min(t), 3), "max": round(max(t), 3), "median": round(float(np.median(t)), 3)}
 
 
 def bounds_ms(frames, S, M, D, SP, nnz):

@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, ".")
+from _timing import ev_time
 from sapr_amd import _lib
 from sapr_amd.kmeans import FrameTiles
 from sapr_amd.trellis import DiagModelPack, EStep, FeatureBatch, kernel_states
@@ -44,15 +45,6 @@ ap.add_argument("--no-sklearn", action="store_true")
 args = ap.parse_args()
 N, T, W, REPEATS = args.N, 101, 11, 5
 lib = _lib.load()
-
-
-def ev_time(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b)
 
 
 def summary(t):

@@ -18,8 +18,6 @@ of word_post over a segment's frames) lies from the word loop's: max and mean ab
 no counters: one warm-up and one timed call of every route per shape) and writes
 DIR/lattice_posteriors_rocprofv3_summary.txt — the only place the three kernels behind lat_post are timed apart."""
 import argparse
-import csv
-import glob
 import json
 import os
 import subprocess
@@ -28,45 +26,19 @@ import sys
 import numpy as np
 
 sys.path.insert(0, ".")
+from _timing import COLUMNS, common_arguments, kernel_rows, row_lines, timed_rounds, trace_command, word_batch
 
 REPEATS = 2
 WORDS = 5
 
-ap = argparse.ArgumentParser()
-ap.add_argument("N", nargs="?", type=int, default=10000)
-ap.add_argument("--frames", type=int, default=505)
-ap.add_argument("--shapes", nargs="+", default=["11,10,13", "11,18,39"], help="W,S,D")
-ap.add_argument("--trace", default=None, help="directory for the rocprofv3 summary (a second run of its own)")
-ap.add_argument("--child", action="store_true", help="(internal) the run under rocprofv3")
-args = ap.parse_args()
-N, T = args.N, args.frames
 
-
-def ev_time(fn):
-    import torch
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b)
-
-
-def setup(W, S, D):
+def setup(args, W, S, D):
     import torch
     from sapr_amd import _lib, connected
     from tests._connected_ref import sample_case
+    N, T = args.N, args.frames
     model, _, _ = sample_case(7, W, S, D, 0)
-    torch.manual_seed(0)
-    per = (T + WORDS - 1) // WORDS
-    t = torch.arange(T, device="cuda")
-    spoken = torch.randint(0, W, (N, WORDS), device="cuda")
-    word = spoken[:, (t // per).clamp(max=WORDS - 1)]                                          # [N, T]
-    state = ((t % per) * S // per).expand(N, T)
-    mu = torch.from_numpy(model["means"]).cuda()[word.reshape(-1), state.reshape(-1)]
-    sd = torch.from_numpy(np.sqrt(model["vars"])).cuda()[word.reshape(-1), state.reshape(-1)]
-    feats = (mu + torch.randn(N * T, D, device="cuda", dtype=torch.float64) * sd).float().contiguous()
-    del mu, sd, word, state
+    feats, spoken = word_batch(model["means"], np.sqrt(model["vars"]), N, T, WORDS)
     bigram = connected.WordBigram.from_transcripts(spoken.cpu().numpy(), W)
     second = bigram.scaled(1.5, -2.0)
     net = connected.ConnectedNetwork(model["log_start"], model["log_trans"], model["log_exit"], 0.0, None,
@@ -154,11 +126,12 @@ def segment_confidences(word_post, pw, pe):
     return total / count
 
 
-def measure():
+def measure(args):
     import torch
+    N, T = args.N, args.frames
     for shape in args.shapes:
         W, S, D = (int(v) for v in shape.split(","))
-        routes, facts, s = setup(W, S, D)
+        routes, facts, s = setup(args, W, S, D)
         out = {"shape": {"N": N, "T": T, "W": W, "S": S, "D": D, "words": WORDS}, **facts}
         for fn in routes.values():
             fn()
@@ -180,10 +153,7 @@ def measure():
         out["segments"] = int(diff.numel())
         out["confidence_abs_difference"] = {"max": round(float(diff.max()), 6), "mean": round(float(diff.mean()), 6)}
         out["mean_confidence"] = {"lattice": round(float(c_lat.mean()), 6), "loop": round(float(c_loop.mean()), 6)}
-        times = {k: [] for k in routes}
-        for _ in range(1 if args.child else REPEATS):
-            for k, fn in routes.items():
-                times[k].append(ev_time(fn))
+        times = timed_rounds(routes, REPEATS, args.child)
         for k, t in times.items():
             out[f"{k}_ms"] = {"min": round(min(t), 3), "max": round(max(t), 3)}
         best = {k: min(t) for k, t in times.items()}
@@ -195,32 +165,30 @@ def measure():
         torch.cuda.empty_cache()
 
 
-measure()
-if args.child or not args.trace:
-    sys.exit(0)
+def main():
+    ap = argparse.ArgumentParser()
+    common_arguments(ap)
+    args = ap.parse_args()
+    measure(args)
+    if args.child or not args.trace:
+        return
+    # (one run under rocprofv3 per shape, so that the tables of the two shapes stay apart)
+    os.makedirs(args.trace, exist_ok=True)
+    lines = ["# rocprofv3 --kernel-trace --stats (no counters), one run per shape of:",
+             f"#   python scripts/time_lattice_posteriors.py {args.N} --frames {args.frames} --shapes W,S,D --child",
+             "# one warm-up and one timed call of every route (emission; bigram search; the lattice's forward tables; its",
+             "# max-semiring backward pass; the lattice posteriors under two bigrams; the word loop's forward-backward under",
+             "# two bigrams); sapr kernels only"]
+    for shape in args.shapes:
+        trace = os.path.join(args.trace, "trace_" + shape.replace(",", "_"))
+        cmd = trace_command(__file__, [str(args.N), "--frames", str(args.frames), "--shapes", shape], trace)
+        with open(os.path.join(args.trace, "child.log"), "a") as log:
+            subprocess.run(cmd, check=True, stdout=log, stderr=subprocess.STDOUT, stdin=subprocess.DEVNULL, timeout=600)
+        lines += [f"# (W, S, D) = ({shape})", COLUMNS, *row_lines(kernel_rows(trace))]
+    with open(os.path.join(args.trace, "lattice_posteriors_rocprofv3_summary.txt"), "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
 
-os.makedirs(args.trace, exist_ok=True)
-lines = ["# rocprofv3 --kernel-trace --stats (no counters), one run per shape of:",
-         f"#   python scripts/time_lattice_posteriors.py {N} --frames {T} --shapes W,S,D --child",
-         "# one warm-up and one timed call of every route (emission; bigram search; the lattice's forward tables; its",
-         "# max-semiring backward pass; the lattice posteriors under two bigrams; the word loop's forward-backward under",
-         "# two bigrams); sapr kernels only"]
-for shape in args.shapes:
-    trace = os.path.join(args.trace, "trace_" + shape.replace(",", "_"))
-    cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", trace, "--", sys.executable,
-           os.path.abspath(__file__), str(N), "--frames", str(T), "--shapes", shape, "--child"]
-    with open(os.path.join(args.trace, "child.log"), "a") as log:
-        subprocess.run(cmd, check=True, stdout=log, stderr=subprocess.STDOUT, stdin=subprocess.DEVNULL, timeout=600)
-    rows = []
-    for f in glob.glob(os.path.join(trace, "**", "*kernel_stats.csv"), recursive=True):
-        with open(f) as fh:
-            rows += [r for r in csv.DictReader(fh) if "sapr" in r["Name"]]
-    rows.sort(key=lambda r: -float(r["TotalDurationNs"]))
-    lines += [f"# (W, S, D) = ({shape})", "# calls  total_ms  avg_ms  min_ms  max_ms  name"]
-    for r in rows:
-        lines.append("%5s %9.3f %8.3f %8.3f %8.3f  %s" % (r["Calls"], float(r["TotalDurationNs"]) / 1e6,
-                                                         float(r["AverageNs"]) / 1e6, float(r["MinNs"]) / 1e6,
-                                                         float(r["MaxNs"]) / 1e6, r["Name"]))
-with open(os.path.join(args.trace, "lattice_posteriors_rocprofv3_summary.txt"), "w") as fh:
-    fh.write("\n".join(lines) + "\n")
-print("\n".join(lines))
+
+if __name__ == "__main__":
+    main()

@@ -17,68 +17,34 @@ online scores against the offline ones by bytes and the concatenated word path w
 --trace DIR: afterwards the script starts itself once more under rocprofv3 --kernel-trace --stats (a run of its own,
 one pass) and writes DIR/online_rocprofv3_summary.txt."""
 import argparse
-import csv
-import glob
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 
 sys.path.insert(0, ".")
+from _timing import common_arguments, ev_time, span, trace_run, word_batch, write_summary
 
 RUNS = 2
 WORDS = 5
 
-ap = argparse.ArgumentParser()
-ap.add_argument("N", nargs="?", type=int, default=10000)
-ap.add_argument("--frames", type=int, default=505)
-ap.add_argument("--shapes", nargs="+", default=["11,10,13", "11,18,39"], help="W,S,D")
-ap.add_argument("--chunks", nargs="+", type=int, default=[10, 50, 505])
-ap.add_argument("--trace", default=None, help="directory for the rocprofv3 summary (a second run of its own)")
-ap.add_argument("--child", action="store_true", help="(internal) the run under rocprofv3")
-args = ap.parse_args()
-N, T = args.N, args.frames
 
-
-def ev_time(fn):
-    import torch
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b)
-
-
-def span(t):
-    return [round(min(t), 3), round(max(t), 3)]
-
-
-def setup(W, S, D):
+def setup(args, W, S, D):
     """The batch of scripts/time_bigram.py and its emitted logb."""
     import torch
     from sapr_amd import connected
     from tests._connected_ref import sample_case
+    N, T = args.N, args.frames
     model, _, _ = sample_case(7, W, S, D, 0)
-    torch.manual_seed(0)
-    per = (T + WORDS - 1) // WORDS
-    t = torch.arange(T, device="cuda")
-    spoken = torch.randint(0, W, (N, WORDS), device="cuda")
-    word = spoken[:, (t // per).clamp(max=WORDS - 1)]
-    state = ((t % per) * S // per).expand(N, T)
-    mu = torch.from_numpy(model["means"]).cuda()[word.reshape(-1), state.reshape(-1)]
-    sd = torch.from_numpy(np.sqrt(model["vars"])).cuda()[word.reshape(-1), state.reshape(-1)]
-    feats = (mu + torch.randn(N * T, D, device="cuda", dtype=torch.float64) * sd).float().contiguous()
-    del mu, sd, word, state
+    feats, spoken = word_batch(model["means"], np.sqrt(model["vars"]), N, T, WORDS)
     bigram = connected.WordBigram.from_transcripts(spoken.cpu().numpy(), W)
     net = connected.ConnectedNetwork(model["log_start"], model["log_trans"], model["log_exit"], 0.0, None,
                                      model["means"], model["vars"], model["gconst"], bigram=bigram)
     return net, connected.emit_diag(feats, net)
 
 
-def offline(net, logb):
+def offline(net, logb, N, T):
     """``(run, outputs)``: one sapr_connected_bigram with every output over the whole batch."""
     import torch
     from sapr_amd import _lib, connected
@@ -102,7 +68,7 @@ def offline(net, logb):
     return run, (score, n_words, pw)
 
 
-def online(net, logb, chunk, want=None):
+def online(net, logb, N, T, chunk, want=None):
     """One pass over the batch in chunks of ``chunk`` frames: ``(step_ms, commit_ms, latency mean, max, forced)``;
     ``want``: the offline ``(score, n_words, path_word)`` to check against."""
     import torch
@@ -162,12 +128,13 @@ def online(net, logb, chunk, want=None):
     return step_ms, commit_ms, lat_sum / pushes, lat_max, int(forced.sum())
 
 
-def measure():
+def measure(args):
     import torch
+    N, T = args.N, args.frames
     for shape in args.shapes:
         W, S, D = (int(v) for v in shape.split(","))
-        net, logb = setup(W, S, D)
-        run, want = offline(net, logb)
+        net, logb = setup(args, W, S, D)
+        run, want = offline(net, logb, N, T)
         run()
         torch.cuda.synchronize()
         out = {"shape": {"N": N, "T": T, "W": W, "S": S, "D": D, "words": WORDS}, "R": net.R}
@@ -175,7 +142,7 @@ def measure():
         off = [ev_time(run) for _ in range(runs)]
         out["offline_ms"] = span(off)
         for chunk in args.chunks:
-            res = [online(net, logb, chunk, want if k == 0 else None) for k in range(runs)]
+            res = [online(net, logb, N, T, chunk, want if k == 0 else None) for k in range(runs)]
             step, com = [r[0] for r in res], [r[1] for r in res]
             out[f"chunk_{chunk}"] = {
                 "window": 256 if chunk <= 64 else chunk + 256, "pushes": (T + chunk - 1) // chunk,
@@ -187,31 +154,24 @@ def measure():
         torch.cuda.empty_cache()
 
 
-measure()
-if args.child or not args.trace:
-    sys.exit(0)
+def main():
+    ap = argparse.ArgumentParser()
+    common_arguments(ap)
+    ap.add_argument("--chunks", nargs="+", type=int, default=[10, 50, 505])
+    args = ap.parse_args()
+    measure(args)
+    if args.child or not args.trace:
+        return
+    argv = [str(args.N), "--frames", str(args.frames), "--shapes", *args.shapes,
+            "--chunks", *(str(c) for c in args.chunks)]
+    header = [
+        f"# rocprofv3 --kernel-trace --stats of: python scripts/time_online.py {' '.join(argv)} --child",
+        "# one pass: emission, one offline decode (recursion + back-trace) and, per chunk size, the step and the commit of",
+        "# every chunk and the flush, per shape; sapr kernels only (no counters are collected in this run)",
+    ]
+    write_summary(os.path.join(args.trace, "online_rocprofv3_summary.txt"), header,
+                  trace_run(__file__, argv, args.trace, 900))
 
-os.makedirs(args.trace, exist_ok=True)
-trace = os.path.join(args.trace, "trace")
-cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", trace, "--", sys.executable,
-       os.path.abspath(__file__), str(N), "--frames", str(T), "--shapes", *args.shapes, "--chunks",
-       *(str(c) for c in args.chunks), "--child"]
-with open(os.path.join(args.trace, "child.log"), "w") as log:
-    subprocess.run(cmd, check=True, stdout=log, stderr=subprocess.STDOUT, stdin=subprocess.DEVNULL, timeout=900)
-rows = []
-for f in glob.glob(os.path.join(trace, "**", "*kernel_stats.csv"), recursive=True):
-    with open(f) as fh:
-        rows += [r for r in csv.DictReader(fh) if "sapr" in r["Name"]]
-rows.sort(key=lambda r: -float(r["TotalDurationNs"]))
-lines = [f"# rocprofv3 --kernel-trace --stats of: python scripts/time_online.py {N} --frames {T} --shapes "
-         f"{' '.join(args.shapes)} --chunks {' '.join(str(c) for c in args.chunks)} --child",
-         "# one pass: emission, one offline decode (recursion + back-trace) and, per chunk size, the step and the commit of",
-         "# every chunk and the flush, per shape; sapr kernels only (no counters are collected in this run)",
-         "# calls  total_ms  avg_ms  min_ms  max_ms  name"]
-for r in rows:
-    lines.append("%5s %9.3f %8.3f %8.3f %8.3f  %s" % (r["Calls"], float(r["TotalDurationNs"]) / 1e6,
-                                                     float(r["AverageNs"]) / 1e6, float(r["MinNs"]) / 1e6,
-                                                     float(r["MaxNs"]) / 1e6, r["Name"]))
-with open(os.path.join(args.trace, "online_rocprofv3_summary.txt"), "w") as fh:
-    fh.write("\n".join(lines) + "\n")
-print("\n".join(lines))
+
+if __name__ == "__main__":
+    main()

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, ".")
+from _timing import ev_time
 from sapr_amd import _lib
 from sapr_amd.trellis import DiagModelPack, EStep, FeatureBatch, TileLayout
 from tests._synth import trained_like_models
@@ -32,15 +33,6 @@ ap.add_argument("--yardstick", action="store_true")
 args = ap.parse_args()
 N, T, W, REPEATS = args.N, 101, 11, 5
 lib = _lib.load()
-
-
-def ev_time(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b)
 
 
 for shape in args.shapes:
